@@ -10,9 +10,16 @@ clamp -> uint8 frame in a device ring.  Frames are independent units: rank r ren
 (weak scaling, no data-path collective) and ONE gather to rank 0 re-assembles the clip inside the timed region.
 Synthetic tri-planes / decoder / SR weights / cameras (no checkpoints offline).
 
-Prints ONE JSON line on rank 0 (see README of the task): metric, value (whole-job frames/s), roofline of the
-dominant kernel (conv_mfma_kernel, MFMA-bound) from HIP events recorded on the launch stream inside the timed
-region, and the CPU oracle timed on this box's host cores (a baseline, not the target).
+Prints ONE JSON line on rank 0: metric, value (whole-job frames/s), ms_per_step, dtype and the run's configuration.
+A plain run does only that: set-up, warm-up, the K timed steps, the outputs (--dump-outputs DIR) and the line.
+--full adds everything else to the same line: four more timed regions (`repeats`), the roofline of the dominant kernel
+(conv_mfma_kernel, MFMA-bound) from HIP events recorded on the launch stream, its HBM traffic re-measured by rocprofv3
+child passes, the single-stream rate, the extras (other precision, API path, torso frame, configs 3 / 5, power) and
+the CPU oracle timed on this box's host cores (a baseline, not the target).
+
+--dump-outputs DIR writes what the timed path computed in its last step: DIR/frames_last_step.npy, float32
+[ranks, 512, 512, 3] = the uint8 frame of each rank's last timed step (rank 0 holds them all after the gather).
+The inputs are seeded, so the same arguments give the same frames from run to run and from build to build.
 """
 import argparse
 import json
@@ -39,6 +46,20 @@ def conv_flops_per_frame(r=128):
     return [t0, c1, t2, c3]
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every tensor as path/<name>.npy in float32 (a uint8 frame keeps its 0..255 values exactly), at most 64 MB in all."""
+    import numpy as np
+    host = {k: v.detach().cpu().numpy().astype(np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    assert total <= DUMP_LIMIT_BYTES, "--dump-outputs: %d bytes exceed the %d-byte limit" % (total, DUMP_LIMIT_BYTES)
+    os.makedirs(path, exist_ok=True)
+    for k, a in host.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+
+
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -46,8 +67,13 @@ def parse():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--device-warmup-ms", type=float, default=500.0,
                     help="untimed frames rendered for this long before the W warm-up steps (brings the GPU's clocks to their sustained state; 0 = off)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and report everything beyond the headline figure (repeats, roofline, traffic, single stream, extras, "
+                         "CPU baselines); a plain run does only the set-up, the warm-up, the K timed steps and the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the uint8 frame of the last timed step (of every rank) to DIR/frames_last_step.npy as float32")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) no CPU baselines")
+    ap.add_argument("--no-extras", action="store_true", help="(--full) no extras")
     ap.add_argument("--streams", type=int, default=int(os.environ.get("R3D_BENCH_STREAMS", "3")),
                     help="HIP streams that consecutive frames are issued on (frames are independent)")
     ap.add_argument("--sr-precision", default=None, choices=["f16mx", "f16x3", "f32"],
@@ -55,7 +81,7 @@ def parse():
                          "or R3D_SR_PRECISION): the cross products of each SR conv on the block-scaled 8-bit MFMA, e5m2 activation records -- inside the "
                          "2e-4 of SURVEY 8(d) on every reference golden and heavy-tail sweep (tests/test_gpu_mx.py, tests/test_gpu_pinned_config.py). "
                          "The fp32-class 'f16x3' is reported as alt_f16x3 in the same line")
-    ap.add_argument("--no-traffic", action="store_true", help="do not re-measure roofline.traffic with rocprofv3 --pmc child runs")
+    ap.add_argument("--no-traffic", action="store_true", help="(--full) do not re-measure roofline.traffic with rocprofv3 --pmc child runs")
     ap.add_argument("--traffic-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--clip", type=int, default=0,
                     help="strong-scaling mode (BASELINE config 3): render ONE clip of this many frames, frame-sharded over the ranks "
@@ -460,6 +486,33 @@ def cfg5_stress(torch, dev, lib, precision="f16mx"):
                               "note": "gather-bound view (SURVEY 8d): S * 1536 B of taps, served by L1 / L2"}}
 
 
+def headline_line(args, prec, world, total_frames, K, W, elapsed, warm_frames):
+    """The fields of the result line that a plain run reports (--full adds its measurements to the same dict)."""
+    fps = total_frames / elapsed
+    return {"metric": "rendered frames/sec @ 512x512, 48 depth samples", "value": round(fps, 2), "unit": "frames/s",
+            "n_gpus": world, "steps": K, "warmup": W, "ms_per_step": round(elapsed / K * 1e3, 4),
+            "higher_is_better": True, "scaling": "strong" if args.clip > 0 else "weak", "vs_baseline": None,
+            "dtype": {"f32": "f32",
+                      "f16x3": "f32 (f16x3 split: fp32 operands as two fp16 terms, 3 MFMA products per MAC, fp32 accumulate)",
+                      "f16mx": "f32 operands as fp16 hi + lo, fp32 accumulate (SR precision 'f16mx' = the library default, superresolution.DEFAULT_SR_PRECISION; the fp32-class "
+                               "f16x3 is `alt_f16x3`): in block0.conv1, block1.conv0 and block1.conv1 hi*hi runs on the f16 MFMA and the two cross products "
+                               "on the block-scaled 8-bit MFMA, e5m2 activation x e4m3 weight records (<= 5e-5 * max|ref| on every reference golden, 3.6e-5 on "
+                               "the benchmarked frame vs the oracle; heavy-tail sweeps, spikes of 2^6 / 2^10 / 2^14 sigma: <= 6.3e-5 near field, 2e-5 far field "
+                               "against the 2e-4 of SURVEY 8(d), tests/test_gpu_pinned_config.py); block0.conv0 and the renderer: f16x3"}[prec],
+            "data": "synthetic",
+            "config": {"workload": "ref_frame_512: TriPlaneGenerator.synthesis path, 1 frame/step/GPU: "
+                                   "planes cano+residual [1,3,32,256,256] -> 128^2 rays x (48 coarse + 48 importance) "
+                                   "-> SuperresolutionHybrid8XDC -> 512^2 uint8; clip gathered to rank 0",
+                       "neural_rendering_resolution": 128, "depth_samples": "48+48", "final_resolution": 512,
+                       "frames_total": total_frames, "streams_per_gpu": args.streams, "parallelism": "frame-sharded dp%d + gather" % world,
+                       "device_warmup": "%d untimed frames (%.0f ms) rendered before the %d warm-up steps: the GPU reaches its sustained clocks only after "
+                                        "~20 ms of load and drops them within 50 ms of idle (scripts/gpu_warm_probe.py, profiles/r02/warm_probe.txt); "
+                                        "--device-warmup-ms 0 gives the cold-start rate" % (warm_frames, args.device_warmup_ms, W),
+                       "clip_constants": "weight prepack and the SR style / demodulation vectors (functions of ws = ones and the parameters only, "
+                                         "triplane.py:131-132) are computed once per clip; every per-frame input (planes = cano + residual_t, camera, "
+                                         "sampling noise) is processed inside the timed region"}}
+
+
 def main():
     args = parse()
     if args.gpus > 1 and "RANK" not in os.environ:      # convenience: self-launch one process per GPU
@@ -552,6 +605,8 @@ def main():
         clip_out = gatherer.gather(ring, total_frames)
     import ctypes
     lib.r3d_profile_configure(1 << 1); lib.r3d_profile_reset()      # event pairs around the dominant kernel, on its launch stream
+    gathered = {}
+
     def timed_region():
         barrier()
         t0 = time.perf_counter()
@@ -563,6 +618,7 @@ def main():
             clip_out = gatherer.gather(ring, total_frames)
             if rank == 0:
                 assert clip_out.shape == (total_frames, 512, 512, 3)
+                gathered["clip"] = clip_out
         barrier()
         return time.perf_counter() - t0
 
@@ -575,6 +631,21 @@ def main():
     if use_dist:
         dist.all_reduce(el, op=dist.ReduceOp.MAX)
     elapsed = float(el.item())
+    if args.dump_outputs and rank == 0:                  # before anything else writes the ring or the clip buffer
+        if use_dist:                                     # each rank's last timed frame, out of the gathered clip
+            spans = [shard_frames(args.clip, world, r) if args.clip > 0 else (r * K, r * K + K) for r in range(world)]
+            last = gathered["clip"][[hi - 1 for lo, hi in spans if hi > lo]]
+        else:
+            last = ring[K_mine - 1:K_mine]
+        dump_outputs(args.dump_outputs, {"frames_last_step": last})
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(headline_line(args, prec, world, total_frames, K, W, elapsed, warm_frames)))
+        if use_dist:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+    # ---- --full: everything below is reported beside the headline figure, nothing of it changes `value` ----
     # the same K-step region four more times, back to back (run-to-run spread of a 15 ms measurement; `value` stays the first one)
     rep_s = [elapsed]
     for _ in range(4):
@@ -683,29 +754,8 @@ def main():
     out = None
     if rank == 0:
         fps = total_frames / elapsed
-        out = {"metric": "rendered frames/sec @ 512x512, 48 depth samples", "value": round(fps, 2), "unit": "frames/s",
-               "n_gpus": world, "steps": K, "warmup": W, "ms_per_step": round(elapsed / K * 1e3, 4),
-               "higher_is_better": True, "scaling": "strong" if args.clip > 0 else "weak", "vs_baseline": None,
-               "dtype": {"f32": "f32",
-                         "f16x3": "f32 (f16x3 split: fp32 operands as two fp16 terms, 3 MFMA products per MAC, fp32 accumulate)",
-                         "f16mx": "f32 operands as fp16 hi + lo, fp32 accumulate (SR precision 'f16mx' = the library default, superresolution.DEFAULT_SR_PRECISION; the fp32-class "
-                                  "f16x3 is `alt_f16x3`): in block0.conv1, block1.conv0 and block1.conv1 hi*hi runs on the f16 MFMA and the two cross products "
-                                  "on the block-scaled 8-bit MFMA, e5m2 activation x e4m3 weight records (<= 5e-5 * max|ref| on every reference golden, 3.6e-5 on "
-                                  "the benchmarked frame vs the oracle; heavy-tail sweeps, spikes of 2^6 / 2^10 / 2^14 sigma: <= 6.3e-5 near field, 2e-5 far field "
-                                  "against the 2e-4 of SURVEY 8(d), tests/test_gpu_pinned_config.py); block0.conv0 and the renderer: f16x3"}[prec],
-               "data": "synthetic",
-               "config": {"workload": "ref_frame_512: TriPlaneGenerator.synthesis path, 1 frame/step/GPU: "
-                                      "planes cano+residual [1,3,32,256,256] -> 128^2 rays x (48 coarse + 48 importance) "
-                                      "-> SuperresolutionHybrid8XDC -> 512^2 uint8; clip gathered to rank 0",
-                          "neural_rendering_resolution": 128, "depth_samples": "48+48", "final_resolution": 512,
-                          "frames_total": total_frames, "streams_per_gpu": args.streams, "parallelism": "frame-sharded dp%d + gather" % world,
-                          "device_warmup": "%d untimed frames (%.0f ms) rendered before the %d warm-up steps: the GPU reaches its sustained clocks only after "
-                                           "~20 ms of load and drops them within 50 ms of idle (scripts/gpu_warm_probe.py, profiles/r02/warm_probe.txt); "
-                                           "--device-warmup-ms 0 gives the cold-start rate" % (warm_frames, args.device_warmup_ms, W),
-                          "clip_constants": "weight prepack and the SR style / demodulation vectors (functions of ws = ones and the parameters only, "
-                                            "triplane.py:131-132) are computed once per clip; every per-frame input (planes = cano + residual_t, camera, "
-                                            "sampling noise) is processed inside the timed region"},
-               "roofline": roofline}
+        out = headline_line(args, prec, world, total_frames, K, W, elapsed, warm_frames)
+        out["roofline"] = roofline
         rep_fps = sorted(total_frames / t for t in rep_s)
         out["repeats"] = {"n": len(rep_s), "what": "the timed region run 5 times back to back (the first one is `value`)",
                           "fps": [round(total_frames / t, 1) for t in rep_s], "median": round(rep_fps[len(rep_fps) // 2], 1),

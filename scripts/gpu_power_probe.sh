@@ -2,7 +2,8 @@
 # what the power management reports while the bench loop runs: average socket power, sclk, temperature (rocm-smi samples every 0.5 s)
 cd "$(dirname "$0")/.." || exit 1
 rocm-smi --showmaxpower --showpowercap 2>/dev/null | grep -v "^=\|^$" | head -8
-(python bench.py --steps 2400 --warmup 24 --no-extras --no-cpu-baseline --no-traffic > /tmp/b.json 2>/dev/null) &
+BJ=$(mktemp)
+(python bench.py --steps 2400 --warmup 24 --full --no-extras --no-cpu-baseline --no-traffic > "$BJ" 2>/dev/null) &
 BP=$!
 sleep 6
 for i in 1 2 3 4 5 6 7 8; do
@@ -11,4 +12,4 @@ for i in 1 2 3 4 5 6 7 8; do
 done
 wait $BP
 python -c "
-import json; d=json.loads([l for l in open('/tmp/b.json') if l.startswith('{')][0]); print('bench', d['value'], d['roofline']['shader_clock_ghz'], d['roofline']['shader_clock_ghz_other_kernels'])"
+import json; d=json.loads([l for l in open('$BJ') if l.startswith('{')][0]); print('bench', d['value'], d['roofline']['shader_clock_ghz'], d['roofline']['shader_clock_ghz_other_kernels'])"

@@ -7,7 +7,7 @@
 # its SQ counters next to the direct kernel's (scripts/gpu_r6_pmc_conv.sh) and its phase stamps (instrumented build libr3d_hip_stamps.so, if present).
 # Writes gpurun_out/profile_r06/; the summaries are copied to profiles/r06/ by hand (tracked).
 cd $GRAFT_REPO_ROOT; export R=$PWD; O=$R/gpurun_out/profile_r06; rm -rf $O; mkdir -p $O; cd /tmp; export TMPDIR=/tmp
-python $R/bench.py --steps 40 --warmup 5 > $O/bench_n1.json 2> $O/bench.err
+python $R/bench.py --steps 40 --warmup 5 --full > $O/bench_n1.json 2> $O/bench.err
 B="python $R/bench.py --steps 10 --warmup 2 --streams 1 --no-cpu-baseline --no-extras --no-traffic"
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o p -- $B > $O/stats.log 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_f16x3 -o p -- $B --sr-precision f16x3 > $O/stats_f16x3.log 2>&1

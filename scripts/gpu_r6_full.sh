@@ -2,7 +2,7 @@
 mkdir -p gpurun_out/r6full; O=gpurun_out/r6full
 timeout 1500 python -m pytest tests -m gpu -q -rP > $O/pytest_full.log 2>&1; echo "pytest rc $?"; tail -5 $O/pytest_full.log
 grep -E "heavy tail|dense heavy|f16mx|synthesis golden|FAILED|Error" $O/pytest_full.log | head -150 > $O/pytest_lines.txt
-timeout 900 python bench.py > $O/bench.log 2> $O/bench.err; echo "bench rc $?"; tail -2 $O/bench.err; cut -c1-600 $O/bench.log
+timeout 900 python bench.py --full > $O/bench.log 2> $O/bench.err; echo "bench rc $?"; tail -2 $O/bench.err; cut -c1-600 $O/bench.log
 python - <<'PY'
 import json
 d = json.load(open("gpurun_out/r6full/bench.log"))

@@ -27,7 +27,7 @@ def _run(args, torchrun):
 
 
 def test_bench_weak_scaling_line_under_torchrun():
-    d = _run(["--gpus", "1", "--steps", "6", "--warmup", "2", "--no-extras", "--no-cpu-baseline"], torchrun=True)
+    d = _run(["--gpus", "1", "--steps", "6", "--warmup", "2", "--full", "--no-extras", "--no-cpu-baseline"], torchrun=True)
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config", "roofline", "repeats"):
         assert k in d, k
     assert d["n_gpus"] == 1 and d["steps"] == 6 and d["warmup"] == 2 and d["scaling"] == "weak" and d["higher_is_better"] is True
@@ -48,6 +48,27 @@ def test_bench_weak_scaling_line_under_torchrun():
     assert r["peak_clock_ghz"] == 2.4 and 0.8 < r["shader_clock_ghz"] <= 2.45, r["shader_clock_ghz"]
     assert abs(r["frac_at_measured_clock"] - r["frac"] * r["peak_clock_ghz"] / r["shader_clock_ghz"]) < 2e-3 and r["frac_at_measured_clock"] < 1
     assert set(r["shader_clock_ghz_other_kernels"]) == {"render_kernel", "upconv_fir"} and all(0.8 < v < 2.45 for v in r["shader_clock_ghz_other_kernels"].values())
+
+
+def test_bench_plain_line_and_dump_outputs(tmp_path):
+    """A plain run (no --full) times exactly --steps steps, reports the headline fields only, and --dump-outputs writes the frame of the last
+    timed step: the same frame on every run with the same arguments."""
+    import numpy as np
+    frames = []
+    for rep in range(2):
+        out = tmp_path / ("run%d" % rep)
+        d = _run(["--gpus", "1", "--steps", "5", "--warmup", "2", "--dump-outputs", str(out)], torchrun=False)
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "config"):
+            assert k in d, k
+        for k in ("roofline", "repeats", "value_single_stream", "cpu_baseline", "cpu_baseline_reference", "torso_frame", "alt_f16x3"):
+            assert k not in d, k
+        assert d["steps"] == 5 and d["warmup"] == 2 and d["config"]["frames_total"] == 5 and d["higher_is_better"] is True
+        assert abs(d["value"] - 5 / (d["ms_per_step"] * 5e-3)) / d["value"] < 1e-3 and d["value"] > 100
+        f = np.load(out / "frames_last_step.npy")
+        assert f.dtype == np.float32 and f.shape == (1, 512, 512, 3)
+        assert f.min() >= 0 and f.max() <= 255 and np.array_equal(f, np.round(f)) and f.std() > 1.0
+        frames.append(f)
+    assert np.array_equal(frames[0], frames[1])
 
 
 def test_profile_clock_is_zero_until_a_profiled_launch_and_plausible_after():
