@@ -7,14 +7,15 @@ import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _SO = os.path.join(_HERE, "_build", "libr3d_oracle.so")
+_SO64 = os.path.join(_HERE, "_build", "libr3d_oracle_f64.so")     # the render path in double (-DR3D_ORACLE_F64)
 
 
-def build_oracle(force=False):
-    """Compile r3d_oracle.c with gcc (seconds).  Returns the .so path."""
+def build_oracle(force=False, precision="f32"):
+    """Compile r3d_oracle.c with gcc (seconds), both builds.  Returns the .so path of `precision`."""
     src = os.path.join(_HERE, "r3d_oracle.c")
-    if force or not os.path.exists(_SO) or os.path.getmtime(_SO) < os.path.getmtime(src):
+    if force or any(not os.path.exists(so) or os.path.getmtime(so) < os.path.getmtime(src) for so in (_SO, _SO64)):
         subprocess.check_call(["make", "-s", "-C", _HERE, "-B"])
-    return _SO
+    return {"f32": _SO, "f64": _SO64}[precision]
 
 
 def _f(a):
@@ -26,8 +27,19 @@ def _p(a):
 
 
 class Oracle:
-    def __init__(self):
-        self.lib = ctypes.CDLL(build_oracle())
+    """precision="f32": the fp32 restatement (outputs float32).  precision="f64": the same code with the render path
+    (ray limits, sampling, decoder, marcher, importance sampler, merge, clamp) in double, outputs float64 -- the truth
+    the fp32 implementations are measured against.  Inputs are float32 arrays for both; raygen and the SR part are
+    fp32 in both libraries."""
+
+    def __init__(self, precision="f32"):
+        assert precision in ("f32", "f64"), precision
+        self.precision = precision
+        self.lib = ctypes.CDLL(build_oracle(precision=precision))
+        self.lib.r3d_oracle_real_bytes.restype = ctypes.c_int
+        self.real = np.float64 if precision == "f64" else np.float32
+        self._c_real = ctypes.c_double if precision == "f64" else ctypes.c_float
+        assert self.lib.r3d_oracle_real_bytes() == np.dtype(self.real).itemsize, "stale oracle build"
         self.lib.r3d_oracle_version.restype = ctypes.c_int
         self.lib.r3d_oracle_num_threads.restype = ctypes.c_int
         self.lib.r3d_oracle_render.restype = ctypes.c_int
@@ -48,9 +60,9 @@ class Oracle:
     def ray_limits(self, origins, dirs, box_warp):
         o, d = _f(origins), _f(dirs)
         n = o.size // 3
-        rs, re = np.empty(n, np.float32), np.empty(n, np.float32)
+        rs, re = np.empty(n, self.real), np.empty(n, self.real)
         v = np.empty(n, np.uint8)
-        self.lib.r3d_oracle_ray_limits(_p(o), _p(d), n, ctypes.c_float(box_warp), _p(rs), _p(re), _p(v))
+        self.lib.r3d_oracle_ray_limits(_p(o), _p(d), n, self._c_real(box_warp), _p(rs), _p(re), _p(v))
         shp = o.shape[:-1]
         return rs.reshape(shp), re.reshape(shp), v.reshape(shp).astype(bool)
 
@@ -67,10 +79,10 @@ class Oracle:
         npts = coords.shape[1]
         w1, b1, w2, b2 = (_f(x) for x in dec)
         HID, OUT = w1.shape[0], w2.shape[0]
-        rgb = np.empty((N, npts, OUT - 1), np.float32)
-        sig = np.empty((N, npts, 1), np.float32)
+        rgb = np.empty((N, npts, OUT - 1), self.real)
+        sig = np.empty((N, npts, 1), self.real)
         self.lib.r3d_oracle_run_model(_p(planes), N, C, H, W, _p(w1), _p(b1), _p(w2), _p(b2), HID, OUT,
-                                      ctypes.c_float(box_warp), _p(coords), npts, _p(rgb), _p(sig))
+                                      self._c_real(box_warp), _p(coords), npts, _p(rgb), _p(sig))
         self.lib.r3d_oracle_set_triplane_depth(1)
         return rgb, sig
 
@@ -85,15 +97,15 @@ class Oracle:
         noise_c = _f(noise_c).reshape(-1)
         u_f = _f(u_f).reshape(-1) if Nf > 0 else np.zeros(1, np.float32)
         assert noise_c.size == N * M * Nc
-        rgb = np.empty((N, M, OUT - 1), np.float32)
-        depth = np.empty((N, M, 1), np.float32)
-        wsum = np.empty((N, M, 1), np.float32)
+        rgb = np.empty((N, M, OUT - 1), self.real)
+        depth = np.empty((N, M, 1), self.real)
+        wsum = np.empty((N, M, 1), self.real)
         valid = np.empty((N, M, 1), np.uint8)
-        dc = np.empty((N, M, Nc), np.float32) if debug else None
-        df = np.empty((N, M, max(Nf, 1)), np.float32) if debug else None
-        sc = np.empty((N, M, Nc), np.float32) if debug else None
+        dc = np.empty((N, M, Nc), self.real) if debug else None
+        df = np.empty((N, M, max(Nf, 1)), self.real) if debug else None
+        sc = np.empty((N, M, Nc), self.real) if debug else None
         rc = self.lib.r3d_oracle_render(_p(planes), N, C, H, W, _p(w1), _p(b1), _p(w2), _p(b2), HID, OUT,
-                                        _p(o), _p(d), M, Nc, Nf, ctypes.c_float(box_warp), int(white_back),
+                                        _p(o), _p(d), M, Nc, Nf, self._c_real(box_warp), int(white_back),
                                         _p(noise_c), _p(u_f), _p(rgb), _p(depth), _p(wsum), _p(valid),
                                         _p(dc), _p(df), _p(sc))
         self.lib.r3d_oracle_set_triplane_depth(1)

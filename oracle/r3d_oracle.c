@@ -16,8 +16,9 @@
  * whose behaviour it restates.  Nothing here is copied: the reference is Python/PyTorch,
  * this is scalar C written from the behavioural spec.
  *
- * Build: see oracle/Makefile  (gcc -O2 -fopenmp -shared -fPIC).
+ * Build: see oracle/Makefile  (gcc -O3 -fopenmp -shared -fPIC; once as is, once with -DR3D_ORACLE_F64).
  */
+#include <float.h>
 #include <math.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -29,7 +30,34 @@
 
 #define R3D_API __attribute__((visibility("default")))
 
+/* Real type of the render path (A2, A4-A8, A10; run_model).  Default float: the fp32 restatement that the
+ * golden tests pin.  -DR3D_ORACLE_F64 compiles the same code in double (oracle/Makefile builds both,
+ * _build/libr3d_oracle_f64.so): the precision reference of the surface-scene tests.  Array inputs stay fp32 in
+ * both builds (planes, decoder weights, rays and sampling noise ARE fp32 data); scalars, intermediates and
+ * outputs are `real`.  The one fp32 step the double build keeps is the reference's own: linspace's fp32 steps
+ * (math_utils.py:107).  Ray generation (A1) and the SR part (A9) are fp32 in both builds. */
+#ifdef R3D_ORACLE_F64
+typedef double real;
+#define RE_EXP exp
+#define RE_LOG1P log1p
+#define RE_FLOOR floor
+#define RE_FMAX fmax
+#define RE_FMIN fmin
+#define RE_MAX_FINITE DBL_MAX
+#else
+typedef float real;
+#define RE_EXP expf
+#define RE_LOG1P log1pf
+#define RE_FLOOR floorf
+#define RE_FMAX fmaxf
+#define RE_FMIN fminf
+#define RE_MAX_FINITE 3.4028234663852886e38f
+#endif
+
 R3D_API int r3d_oracle_version(void) { return 1; }
+
+/* sizeof(real): 4 for the fp32 build, 8 for the fp64 one (oracle.py checks which library it loaded). */
+R3D_API int r3d_oracle_real_bytes(void) { return (int)sizeof(real); }
 
 R3D_API int r3d_oracle_num_threads(void) {
 #ifdef _OPENMP
@@ -86,34 +114,34 @@ R3D_API void r3d_oracle_raygen(const float* c2w, const float* K, int N, int R,
  *   get start = min(valid starts), end = max(valid STARTS) -- sic, both from ray_start)
  * nrays = N*M.  valid_out: 1 byte per ray.
  * ---------------------------------------------------------------------------------- */
-static void ray_box(const float* o, const float* d, float half, float* tmin_o, float* tmax_o)
+static void ray_box(const float* o, const float* d, real half, real* tmin_o, real* tmax_o)
 {
-    float inv[3], lo[3], hi[3];
+    real inv[3], lo[3], hi[3];
     for (int a = 0; a < 3; ++a) {
-        inv[a] = 1.0f / d[a];
-        const int sgn = inv[a] < 0.0f;
-        const float bmin = -half, bmax = half;
-        lo[a] = ((sgn ? bmax : bmin) - o[a]) * inv[a];
-        hi[a] = ((sgn ? bmin : bmax) - o[a]) * inv[a];
+        inv[a] = (real)1 / (real)d[a];
+        const int sgn = inv[a] < (real)0;
+        const real bmin = -half, bmax = half;
+        lo[a] = ((sgn ? bmax : bmin) - (real)o[a]) * inv[a];
+        hi[a] = ((sgn ? bmin : bmax) - (real)o[a]) * inv[a];
     }
     int valid = 1;
-    float tmin = lo[0], tmax = hi[0];
+    real tmin = lo[0], tmax = hi[0];
     if (tmin > hi[1] || lo[1] > tmax) valid = 0;
-    tmin = fmaxf(tmin, lo[1]);   /* torch.max propagates NaN; fmaxf does not -- NaN only for d==0 & o on slab */
-    tmax = fminf(tmax, hi[1]);
+    tmin = RE_FMAX(tmin, lo[1]);   /* torch.max propagates NaN; fmaxf does not -- NaN only for d==0 & o on slab */
+    tmax = RE_FMIN(tmax, hi[1]);
     if (tmin > hi[2] || lo[2] > tmax) valid = 0;
-    tmin = fmaxf(tmin, lo[2]);
-    tmax = fminf(tmax, hi[2]);
-    if (!valid) { tmin = -1.0f; tmax = -2.0f; }
+    tmin = RE_FMAX(tmin, lo[2]);
+    tmax = RE_FMIN(tmax, hi[2]);
+    if (!valid) { tmin = (real)-1; tmax = (real)-2; }
     *tmin_o = tmin; *tmax_o = tmax;
 }
 
-R3D_API void r3d_oracle_ray_limits(const float* origins, const float* dirs, int nrays, float box_warp,
-                                   float* ray_start, float* ray_end, uint8_t* valid_out)
+R3D_API void r3d_oracle_ray_limits(const float* origins, const float* dirs, int nrays, real box_warp,
+                                   real* ray_start, real* ray_end, uint8_t* valid_out)
 {
-    const float half = box_warp / 2.0f;
+    const real half = box_warp / (real)2;
     int any = 0;
-    float gmin = INFINITY, gmax = -INFINITY;
+    real gmin = INFINITY, gmax = -INFINITY;
     for (int r = 0; r < nrays; ++r) {
         ray_box(origins + 3 * (size_t)r, dirs + 3 * (size_t)r, half, &ray_start[r], &ray_end[r]);
         const int v = ray_end[r] > ray_start[r];
@@ -145,70 +173,70 @@ R3D_API void r3d_oracle_set_triplane_depth(int d) { g_triplane_depth = d < 1 ? 1
 /* sample_from_trigrids (renderer.py:78-89): planes [3][C*D][H][W] viewed as [3][C][D][H][W] (channel c*D + d), 5-D
  * F.grid_sample (tri-linear, zeros padding, align_corners=False) at the projected coordinates: (u, v) as for tri-planes,
  * third coordinate = z, y, y (coordinates . inv(plane_axes), renderer.py:29-45,60-62); grid x -> W, y -> H, z -> D. */
-static void sample_trigrids(const float* planes, int C, int D, int H, int W, const float* us, const float* vs, const float* ws,
-                            float* feat_out)
+static void sample_trigrids(const float* planes, int C, int D, int H, int W, const real* us, const real* vs, const real* ws,
+                            real* feat_out)
 {
     for (int p = 0; p < 3; ++p) {
-        const float ix = ((us[p] + 1.0f) * (float)W - 1.0f) / 2.0f;
-        const float iy = ((vs[p] + 1.0f) * (float)H - 1.0f) / 2.0f;
-        const float iz = ((ws[p] + 1.0f) * (float)D - 1.0f) / 2.0f;
-        const float x0f = floorf(ix), y0f = floorf(iy), z0f = floorf(iz);
-        const int x0 = (x0f >= -2.0f && x0f <= (float)W + 1.0f) ? (int)x0f : -5;
-        const int y0 = (y0f >= -2.0f && y0f <= (float)H + 1.0f) ? (int)y0f : -5;
-        const int z0 = (z0f >= -2.0f && z0f <= (float)D + 1.0f) ? (int)z0f : -5;
+        const real ix = ((us[p] + (real)1) * (real)W - (real)1) / (real)2;
+        const real iy = ((vs[p] + (real)1) * (real)H - (real)1) / (real)2;
+        const real iz = ((ws[p] + (real)1) * (real)D - (real)1) / (real)2;
+        const real x0f = RE_FLOOR(ix), y0f = RE_FLOOR(iy), z0f = RE_FLOOR(iz);
+        const int x0 = (x0f >= (real)-2 && x0f <= (real)W + (real)1) ? (int)x0f : -5;
+        const int y0 = (y0f >= (real)-2 && y0f <= (real)H + (real)1) ? (int)y0f : -5;
+        const int z0 = (z0f >= (real)-2 && z0f <= (real)D + (real)1) ? (int)z0f : -5;
         const float* P = planes + (size_t)p * C * D * H * W;
         for (int c = 0; c < C; ++c) {
-            float acc = 0.0f;
+            real acc = 0;
             for (int dz = 0; dz < 2; ++dz)
                 for (int dy = 0; dy < 2; ++dy)
                     for (int dx = 0; dx < 2; ++dx) {
                         const int x = x0 + dx, y = y0 + dy, z = z0 + dz;
                         if (x < 0 || x >= W || y < 0 || y >= H || z < 0 || z >= D) continue;
-                        const float wx = dx ? ix - x0f : (x0f + 1.0f) - ix;
-                        const float wy = dy ? iy - y0f : (y0f + 1.0f) - iy;
-                        const float wz = dz ? iz - z0f : (z0f + 1.0f) - iz;
-                        acc += P[(((size_t)c * D + z) * H + y) * W + x] * (wx * wy * wz);
+                        const real wx = dx ? ix - x0f : (x0f + (real)1) - ix;
+                        const real wy = dy ? iy - y0f : (y0f + (real)1) - iy;
+                        const real wz = dz ? iz - z0f : (z0f + (real)1) - iz;
+                        acc += (real)P[(((size_t)c * D + z) * H + y) * W + x] * (wx * wy * wz);
                     }
             feat_out[p * C + c] = acc;
         }
     }
 }
 
-static void sample_planes(const float* planes, int C, int H, int W, float box_warp,
-                          const float* xyz, float* feat_out /* [3*C] */)
+static void sample_planes(const float* planes, int C, int H, int W, real box_warp,
+                          const real* xyz, real* feat_out /* [3*C] */)
 {
-    const float s = (float)(2.0 / (double)box_warp);
-    const float q[3] = { xyz[0] * s, xyz[1] * s, xyz[2] * s };
-    const float us[3] = { q[0], q[0], q[2] };
-    const float vs[3] = { q[1], q[2], q[0] };
+    const real s = (real)(2.0 / (double)box_warp);
+    const real q[3] = { xyz[0] * s, xyz[1] * s, xyz[2] * s };
+    const real us[3] = { q[0], q[0], q[2] };
+    const real vs[3] = { q[1], q[2], q[0] };
     if (g_triplane_depth > 1) {
-        const float ws[3] = { q[2], q[1], q[1] };
+        const real ws[3] = { q[2], q[1], q[1] };
         sample_trigrids(planes, C, g_triplane_depth, H, W, us, vs, ws, feat_out);
         return;
     }
     for (int p = 0; p < 3; ++p) {
-        const float ix = ((us[p] + 1.0f) * (float)W - 1.0f) / 2.0f;
-        const float iy = ((vs[p] + 1.0f) * (float)H - 1.0f) / 2.0f;
-        const float x0f = floorf(ix), y0f = floorf(iy);
-        const float x1f = x0f + 1.0f, y1f = y0f + 1.0f;
-        const float wnw = (x1f - ix) * (y1f - iy);
-        const float wne = (ix - x0f) * (y1f - iy);
-        const float wsw = (x1f - ix) * (iy - y0f);
-        const float wse = (ix - x0f) * (iy - y0f);
+        const real ix = ((us[p] + (real)1) * (real)W - (real)1) / (real)2;
+        const real iy = ((vs[p] + (real)1) * (real)H - (real)1) / (real)2;
+        const real x0f = RE_FLOOR(ix), y0f = RE_FLOOR(iy);
+        const real x1f = x0f + (real)1, y1f = y0f + (real)1;
+        const real wnw = (x1f - ix) * (y1f - iy);
+        const real wne = (ix - x0f) * (y1f - iy);
+        const real wsw = (x1f - ix) * (iy - y0f);
+        const real wse = (ix - x0f) * (iy - y0f);
         /* out-of-range coordinates (incl. NaN/inf) contribute nothing */
-        const int x0 = (x0f >= -2.0f && x0f <= (float)W + 1.0f) ? (int)x0f : -5;
-        const int y0 = (y0f >= -2.0f && y0f <= (float)H + 1.0f) ? (int)y0f : -5;
+        const int x0 = (x0f >= (real)-2 && x0f <= (real)W + (real)1) ? (int)x0f : -5;
+        const int y0 = (y0f >= (real)-2 && y0f <= (real)H + (real)1) ? (int)y0f : -5;
         const int x1 = x0 + 1, y1 = y0 + 1;
         const int vx0 = x0 >= 0 && x0 < W, vx1 = x1 >= 0 && x1 < W;
         const int vy0 = y0 >= 0 && y0 < H, vy1 = y1 >= 0 && y1 < H;
         const float* P = planes + (size_t)p * C * H * W;
         for (int c = 0; c < C; ++c) {
             const float* Pc = P + (size_t)c * H * W;
-            float acc = 0.0f;
-            if (vx0 && vy0) acc += Pc[(size_t)y0 * W + x0] * wnw;
-            if (vx1 && vy0) acc += Pc[(size_t)y0 * W + x1] * wne;
-            if (vx0 && vy1) acc += Pc[(size_t)y1 * W + x0] * wsw;
-            if (vx1 && vy1) acc += Pc[(size_t)y1 * W + x1] * wse;
+            real acc = 0;
+            if (vx0 && vy0) acc += (real)Pc[(size_t)y0 * W + x0] * wnw;
+            if (vx1 && vy0) acc += (real)Pc[(size_t)y0 * W + x1] * wne;
+            if (vx0 && vy1) acc += (real)Pc[(size_t)y1 * W + x0] * wsw;
+            if (vx1 && vy1) acc += (real)Pc[(size_t)y1 * W + x1] * wse;
             feat_out[p * C + c] = acc;
         }
     }
@@ -223,26 +251,26 @@ static void sample_planes(const float* planes, int C, int H, int W, float box_wa
  * w1 [HID, C], b1 [HID], w2 [OUT, HID], b2 [OUT] are the RAW module parameters
  * (decoder.net.0.weight etc.); gains are applied here like the reference does at call time.
  * ---------------------------------------------------------------------------------- */
-static inline float softplus20(float x) { return x > 20.0f ? x : log1pf(expf(x)); }
+static inline real softplus20(real x) { return x > (real)20 ? x : RE_LOG1P(RE_EXP(x)); }
 
-static void decode(const float* feat3 /*[3*C]*/, int C, int HID, int OUT,
+static void decode(const real* feat3 /*[3*C]*/, int C, int HID, int OUT,
                    const float* w1, const float* b1, const float* w2, const float* b2,
-                   float* sigma, float* rgb /* [OUT-1] */)
+                   real* sigma, real* rgb /* [OUT-1] */)
 {
-    float x[64], h[128];
-    const float g1 = (float)(1.0 / sqrt((double)C));
-    const float g2 = (float)(1.0 / sqrt((double)HID));
-    for (int c = 0; c < C; ++c) x[c] = (feat3[c] + feat3[C + c] + feat3[2 * C + c]) / 3.0f;
+    real x[64], h[128];
+    const real g1 = (real)(1.0 / sqrt((double)C));
+    const real g2 = (real)(1.0 / sqrt((double)HID));
+    for (int c = 0; c < C; ++c) x[c] = (feat3[c] + feat3[C + c] + feat3[2 * C + c]) / (real)3;
     for (int j = 0; j < HID; ++j) {
-        float acc = b1[j];
-        for (int c = 0; c < C; ++c) acc += x[c] * (w1[j * C + c] * g1);
+        real acc = (real)b1[j];
+        for (int c = 0; c < C; ++c) acc += x[c] * ((real)w1[j * C + c] * g1);
         h[j] = softplus20(acc);
     }
     for (int o = 0; o < OUT; ++o) {
-        float acc = b2[o];
-        for (int j = 0; j < HID; ++j) acc += h[j] * (w2[o * HID + j] * g2);
+        real acc = (real)b2[o];
+        for (int j = 0; j < HID; ++j) acc += h[j] * ((real)w2[o * HID + j] * g2);
         if (o == 0) *sigma = acc;
-        else rgb[o - 1] = (1.0f / (1.0f + expf(-acc))) * 1.002f - 0.001f;
+        else rgb[o - 1] = ((real)1 / ((real)1 + RE_EXP(-acc))) * (real)1.002 - (real)0.001;
     }
 }
 
@@ -251,16 +279,17 @@ static void decode(const float* feat3 /*[3*C]*/, int C, int HID, int OUT,
  * planes [N,3,C,H,W]; coords [N, npts, 3]; rgb_out [N,npts,OUT-1]; sigma_out [N,npts]. */
 R3D_API void r3d_oracle_run_model(const float* planes, int N, int C, int H, int W,
                                   const float* w1, const float* b1, const float* w2, const float* b2,
-                                  int HID, int OUT, float box_warp,
-                                  const float* coords, int npts, float* rgb_out, float* sigma_out)
+                                  int HID, int OUT, real box_warp,
+                                  const float* coords, int npts, real* rgb_out, real* sigma_out)
 {
     for (int n = 0; n < N; ++n) {
         const float* Pn = planes + (size_t)n * 3 * C * g_triplane_depth * H * W;
 #pragma omp parallel for schedule(static)
         for (int i = 0; i < npts; ++i) {
-            float feat[3 * 64];
+            real feat[3 * 64];
             const size_t idx = (size_t)n * npts + i;
-            sample_planes(Pn, C, H, W, box_warp, coords + 3 * idx, feat);
+            const real xyz[3] = { coords[3 * idx], coords[3 * idx + 1], coords[3 * idx + 2] };
+            sample_planes(Pn, C, H, W, box_warp, xyz, feat);
             decode(feat, C, HID, OUT, w1, b1, w2, b2, &sigma_out[idx], rgb_out + idx * (OUT - 1));
         }
     }
@@ -273,36 +302,36 @@ R3D_API void r3d_oracle_run_model(const float* planes, int N, int C, int H, int 
  * [min(depths), max(depths)] (:50) is applied by the caller over the whole call.
  * weights_out: S-1 values.  rgb_out: CO channels, already scaled to (-1,1) (:55).
  * ---------------------------------------------------------------------------------- */
-static void march_ray(const float* colors /*[S][CO]*/, const float* dens /*[S]*/, const float* depths /*[S]*/,
+static void march_ray(const real* colors /*[S][CO]*/, const real* dens /*[S]*/, const real* depths /*[S]*/,
                       int S, int CO, int white_back,
-                      float* rgb_out, float* depth_out, float* wsum_out, float* weights_out)
+                      real* rgb_out, real* depth_out, real* wsum_out, real* weights_out)
 {
-    float T = 1.0f;           /* cumprod of [1, 1-alpha+1e-10][: -1] */
-    float wsum = 0.0f, dsum = 0.0f;
-    for (int c = 0; c < CO; ++c) rgb_out[c] = 0.0f;
+    real T = 1;               /* cumprod of [1, 1-alpha+1e-10][: -1] */
+    real wsum = 0, dsum = 0;
+    for (int c = 0; c < CO; ++c) rgb_out[c] = 0;
     for (int k = 0; k < S - 1; ++k) {
-        const float delta = depths[k + 1] - depths[k];
-        const float dmid = (dens[k] + dens[k + 1]) / 2.0f;
-        const float tmid = (depths[k] + depths[k + 1]) / 2.0f;
-        const float sp = softplus20(dmid - 1.0f);
-        const float alpha = 1.0f - expf(-(sp * delta));
-        const float w = alpha * T;
-        T = T * (1.0f - alpha + 1e-10f);
+        const real delta = depths[k + 1] - depths[k];
+        const real dmid = (dens[k] + dens[k + 1]) / (real)2;
+        const real tmid = (depths[k] + depths[k + 1]) / (real)2;
+        const real sp = softplus20(dmid - (real)1);
+        const real alpha = (real)1 - RE_EXP(-(sp * delta));
+        const real w = alpha * T;
+        T = T * ((real)1 - alpha + (real)1e-10);
         weights_out[k] = w;
         wsum += w;
         dsum += w * tmid;
         for (int c = 0; c < CO; ++c)
-            rgb_out[c] += w * ((colors[(size_t)k * CO + c] + colors[(size_t)(k + 1) * CO + c]) / 2.0f);
+            rgb_out[c] += w * ((colors[(size_t)k * CO + c] + colors[(size_t)(k + 1) * CO + c]) / (real)2);
     }
-    float dep = dsum / wsum;
+    real dep = dsum / wsum;
     if (isnan(dep)) dep = INFINITY;       /* torch.nan_to_num(x, float('inf')) */
-    if (isinf(dep)) dep = dep > 0 ? 3.4028234663852886e38f : -3.4028234663852886e38f; /* posinf/neginf default */
+    if (isinf(dep)) dep = dep > 0 ? RE_MAX_FINITE : -RE_MAX_FINITE; /* posinf/neginf default: the dtype's largest finite */
     *depth_out = dep;
     *wsum_out = wsum;
     for (int c = 0; c < CO; ++c) {
-        float v = rgb_out[c];
-        if (white_back) v = v + 1.0f - wsum;
-        rgb_out[c] = v * 2.0f - 1.0f;
+        real v = rgb_out[c];
+        if (white_back) v = v + (real)1 - wsum;
+        rgb_out[c] = v * (real)2 - (real)1;
     }
 }
 
@@ -312,38 +341,38 @@ static void march_ray(const float* colors /*[S][CO]*/, const float* dens /*[S]*/
  *   sample_pdf over weights[1:-1] (+1e-5), cdf with leading 0, searchsorted(right=True),
  *   below/above clamps, denom<eps -> 1, linear interpolation (:271-296).
  * ---------------------------------------------------------------------------------- */
-static void importance_ray(const float* z /*[Nc]*/, const float* w /*[Nc-1]*/, int Nc,
-                           const float* u /*[Nf]*/, int Nf, float* out /*[Nf]*/)
+static void importance_ray(const real* z /*[Nc]*/, const real* w /*[Nc-1]*/, int Nc,
+                           const float* u /*[Nf]*/, int Nf, real* out /*[Nf]*/)
 {
-    float a[512], s[512], bins[512], cdf[512];
+    real a[512], s[512], bins[512], cdf[512];
     const int nw = Nc - 1;
     for (int i = 0; i < Nc; ++i) {            /* max_pool1d, -inf padding */
-        const float l = (i - 1 >= 0) ? w[i - 1] : -INFINITY;
-        const float r = (i < nw) ? w[i] : -INFINITY;
+        const real l = (i - 1 >= 0) ? w[i - 1] : -INFINITY;
+        const real r = (i < nw) ? w[i] : -INFINITY;
         a[i] = l > r ? l : r;
     }
-    for (int i = 0; i < nw; ++i) s[i] = (a[i] + a[i + 1]) / 2.0f + 0.01f;   /* avg_pool1d + 0.01 */
-    for (int i = 0; i < nw; ++i) bins[i] = 0.5f * (z[i] + z[i + 1]);
+    for (int i = 0; i < nw; ++i) s[i] = (a[i] + a[i + 1]) / (real)2 + (real)0.01;   /* avg_pool1d + 0.01 */
+    for (int i = 0; i < nw; ++i) bins[i] = (real)0.5 * (z[i] + z[i + 1]);
     const int ns = Nc - 3;                   /* weights[:, 1:-1] */
-    float tot = 0.0f;
-    for (int i = 0; i < ns; ++i) tot += (s[i + 1] + 1e-5f);
-    cdf[0] = 0.0f;
-    float run = 0.0f;
-    for (int i = 0; i < ns; ++i) { run += (s[i + 1] + 1e-5f) / tot; cdf[i + 1] = run; }
+    real tot = 0;
+    for (int i = 0; i < ns; ++i) tot += (s[i + 1] + (real)1e-5);
+    cdf[0] = 0;
+    real run = 0;
+    for (int i = 0; i < ns; ++i) { run += (s[i + 1] + (real)1e-5) / tot; cdf[i + 1] = run; }
     const int ncdf = ns + 1;
     for (int j = 0; j < Nf; ++j) {
         int ind = 0;                          /* searchsorted right: #cdf <= u */
-        while (ind < ncdf && cdf[ind] <= u[j]) ++ind;
+        while (ind < ncdf && cdf[ind] <= (real)u[j]) ++ind;
         const int below = ind - 1 > 0 ? ind - 1 : 0;
         const int above = ind < ns ? ind : ns;
-        float denom = cdf[above] - cdf[below];
-        if (denom < 1e-5f) denom = 1.0f;
-        out[j] = bins[below] + (u[j] - cdf[below]) / denom * (bins[above] - bins[below]);
+        real denom = cdf[above] - cdf[below];
+        if (denom < (real)1e-5) denom = 1;
+        out[j] = bins[below] + ((real)u[j] - cdf[below]) / denom * (bins[above] - bins[below]);
     }
 }
 
 /* stable insertion ordering of indices by depth (torch.sort ascending, renderer.py:202) */
-static void argsort_depth(const float* t, int n, int* idx)
+static void argsort_depth(const real* t, int n, int* idx)
 {
     for (int i = 0; i < n; ++i) idx[i] = i;
     for (int i = 1; i < n; ++i) {
@@ -368,60 +397,60 @@ R3D_API int r3d_oracle_render(const float* planes, int N, int C, int H, int W,
                               const float* w1, const float* b1, const float* w2, const float* b2,
                               int HID, int OUT,
                               const float* origins, const float* dirs, int M,
-                              int Nc, int Nf, float box_warp, int white_back,
+                              int Nc, int Nf, real box_warp, int white_back,
                               const float* noise_c, const float* u_f,
-                              float* rgb, float* depth, float* wsum, uint8_t* valid,
-                              float* dbg_depths_c, float* dbg_depths_f, float* dbg_sigma_c)
+                              real* rgb, real* depth, real* wsum, uint8_t* valid,
+                              real* dbg_depths_c, real* dbg_depths_f, real* dbg_sigma_c)
 {
     const int CO = OUT - 1;
     const int nrays = N * M;
     if (Nc < 4 || Nc > 256 || Nf < 0 || Nf > 256 || C > 64 || HID > 128) return -1;
-    float* rs = (float*)malloc(sizeof(float) * nrays);
-    float* re = (float*)malloc(sizeof(float) * nrays);
+    real* rs = (real*)malloc(sizeof(real) * nrays);
+    real* re = (real*)malloc(sizeof(real) * nrays);
     r3d_oracle_ray_limits(origins, dirs, nrays, box_warp, rs, re, valid);
 
     const int S = Nc + Nf;
-    float gmin = INFINITY, gmax = -INFINITY;   /* global depth range of the FINAL marcher call */
+    real gmin = INFINITY, gmax = -INFINITY;    /* global depth range of the FINAL marcher call */
 
 #pragma omp parallel
     {
-        float* col = (float*)malloc(sizeof(float) * (size_t)S * CO);
-        float* den = (float*)malloc(sizeof(float) * S);
-        float* t = (float*)malloc(sizeof(float) * S);
-        float* col2 = (float*)malloc(sizeof(float) * (size_t)S * CO);
-        float* den2 = (float*)malloc(sizeof(float) * S);
-        float* t2 = (float*)malloc(sizeof(float) * S);
-        float* wts = (float*)malloc(sizeof(float) * S);
+        real* col = (real*)malloc(sizeof(real) * (size_t)S * CO);
+        real* den = (real*)malloc(sizeof(real) * S);
+        real* t = (real*)malloc(sizeof(real) * S);
+        real* col2 = (real*)malloc(sizeof(real) * (size_t)S * CO);
+        real* den2 = (real*)malloc(sizeof(real) * S);
+        real* t2 = (real*)malloc(sizeof(real) * S);
+        real* wts = (real*)malloc(sizeof(real) * S);
         int* order = (int*)malloc(sizeof(int) * S);
-        float feat[3 * 64];
-        float lmin = INFINITY, lmax = -INFINITY;
+        real feat[3 * 64];
+        real lmin = INFINITY, lmax = -INFINITY;
 #pragma omp for schedule(dynamic, 64)
         for (int r = 0; r < nrays; ++r) {
             const int n = r / M;
             const float* Pn = planes + (size_t)n * 3 * C * g_triplane_depth * H * W;
             const float* o = origins + 3 * (size_t)r;
             const float* d = dirs + 3 * (size_t)r;
-            const float start = rs[r], end = re[r];
+            const real start = rs[r], end = re[r];
             /* stratified depths: linspace + jitter */
-            const float delta = (end - start) / (float)(Nc - 1);
+            const real delta = (end - start) / (real)(Nc - 1);
             for (int k = 0; k < Nc; ++k) {
-                const float step = (float)k / (float)(Nc - 1);
-                float tk = start + step * (end - start);
-                tk += noise_c[(size_t)r * Nc + k] * delta;
+                const float step = (float)k / (float)(Nc - 1);    /* fp32 steps in both builds (math_utils.py:107) */
+                real tk = start + (real)step * (end - start);
+                tk += (real)noise_c[(size_t)r * Nc + k] * delta;
                 t[k] = tk;
-                float xyz[3] = { o[0] + tk * d[0], o[1] + tk * d[1], o[2] + tk * d[2] };
+                const real xyz[3] = { (real)o[0] + tk * (real)d[0], (real)o[1] + tk * (real)d[1], (real)o[2] + tk * (real)d[2] };
                 sample_planes(Pn, C, H, W, box_warp, xyz, feat);
                 decode(feat, C, HID, OUT, w1, b1, w2, b2, &den[k], col + (size_t)k * CO);
             }
-            if (dbg_depths_c) memcpy(dbg_depths_c + (size_t)r * Nc, t, sizeof(float) * Nc);
-            if (dbg_sigma_c) memcpy(dbg_sigma_c + (size_t)r * Nc, den, sizeof(float) * Nc);
-            float rgb_r[64], dep_r, ws_r;
+            if (dbg_depths_c) memcpy(dbg_depths_c + (size_t)r * Nc, t, sizeof(real) * Nc);
+            if (dbg_sigma_c) memcpy(dbg_sigma_c + (size_t)r * Nc, den, sizeof(real) * Nc);
+            real rgb_r[64], dep_r, ws_r;
             if (Nf > 0) {
                 march_ray(col, den, t, Nc, CO, white_back, rgb_r, &dep_r, &ws_r, wts);
                 importance_ray(t, wts, Nc, u_f + (size_t)r * Nf, Nf, t + Nc);
-                if (dbg_depths_f) memcpy(dbg_depths_f + (size_t)r * Nf, t + Nc, sizeof(float) * Nf);
+                if (dbg_depths_f) memcpy(dbg_depths_f + (size_t)r * Nf, t + Nc, sizeof(real) * Nf);
                 for (int k = Nc; k < S; ++k) {
-                    float xyz[3] = { o[0] + t[k] * d[0], o[1] + t[k] * d[1], o[2] + t[k] * d[2] };
+                    const real xyz[3] = { (real)o[0] + t[k] * (real)d[0], (real)o[1] + t[k] * (real)d[1], (real)o[2] + t[k] * (real)d[2] };
                     sample_planes(Pn, C, H, W, box_warp, xyz, feat);
                     decode(feat, C, HID, OUT, w1, b1, w2, b2, &den[k], col + (size_t)k * CO);
                 }
@@ -429,7 +458,7 @@ R3D_API int r3d_oracle_render(const float* planes, int N, int C, int H, int W,
                 for (int k = 0; k < S; ++k) {
                     t2[k] = t[order[k]];
                     den2[k] = den[order[k]];
-                    memcpy(col2 + (size_t)k * CO, col + (size_t)order[k] * CO, sizeof(float) * CO);
+                    memcpy(col2 + (size_t)k * CO, col + (size_t)order[k] * CO, sizeof(real) * CO);
                 }
                 march_ray(col2, den2, t2, S, CO, white_back, rgb_r, &dep_r, &ws_r, wts);
                 for (int k = 0; k < S; ++k) { if (t2[k] < lmin) lmin = t2[k]; if (t2[k] > lmax) lmax = t2[k]; }
@@ -437,7 +466,7 @@ R3D_API int r3d_oracle_render(const float* planes, int N, int C, int H, int W,
                 march_ray(col, den, t, Nc, CO, white_back, rgb_r, &dep_r, &ws_r, wts);
                 for (int k = 0; k < Nc; ++k) { if (t[k] < lmin) lmin = t[k]; if (t[k] > lmax) lmax = t[k]; }
             }
-            memcpy(rgb + (size_t)r * CO, rgb_r, sizeof(float) * CO);
+            memcpy(rgb + (size_t)r * CO, rgb_r, sizeof(real) * CO);
             depth[r] = dep_r;
             wsum[r] = ws_r;
         }
@@ -447,7 +476,7 @@ R3D_API int r3d_oracle_render(const float* planes, int N, int C, int H, int W,
     }
     /* ray_marcher.py:50  clamp to the global [min, max] of all depths in the call */
     for (int r = 0; r < nrays; ++r) {
-        float v = depth[r];
+        real v = depth[r];
         if (v < gmin) v = gmin;
         if (v > gmax) v = gmax;
         depth[r] = v;

@@ -70,6 +70,12 @@ SIGNATURES = {
 }
 
 
+# test hooks outside the C ABI of include/r3d_hip.h: bound when the library exports them, absent otherwise (nothing in the product calls
+# them, and a library built from older sources -- the packed-f32 A/B partner of an earlier tree, say -- must keep loading)
+OPTIONAL_SIGNATURES = {
+    "r3d_debug_merge_fallbacks": (c_int, [ctypes.POINTER(ctypes.c_ulonglong), c_int]),
+}
+
 
 class ChainOp(ctypes.Structure):
     """r3d_chain_op of include/r3d_hip.h (one layer of an r3d_chain_fold chain)."""
@@ -112,6 +118,10 @@ def load():
     for name, (res, args) in SIGNATURES.items():
         fn = getattr(lib, name)      # AttributeError if the ABI and this table drift apart
         fn.restype, fn.argtypes = res, args
+    for name, (res, args) in OPTIONAL_SIGNATURES.items():
+        fn = getattr(lib, name, None)
+        if fn is not None:
+            fn.restype, fn.argtypes = res, args
     if lib.r3d_version() != ABI_VERSION:      # a stale in-tree build (real3dportrait_amd/lib/ is not tracked): arguments would be shifted silently
         raise RuntimeError("real3dportrait_amd: %s reports ABI %d, this package binds ABI %d -- rebuild it (`make -C %s`)"
                            % (LIB_PATH, lib.r3d_version(), ABI_VERSION, CSRC))

@@ -183,6 +183,10 @@ __global__ void raygen_kernel(const float* __restrict__ c2w, const float* __rest
     dirs[o] = d3[0]; dirs[o + 1] = d3[1]; dirs[o + 2] = d3[2];
 }
 
+// Rays whose A8 merge (render_kernel) left the rank fast path for the exact counting sort since the last r3d_debug_merge_fallbacks(.., 1):
+// exact fine-sample ties, a non-monotone coarse list.  Per device; read by the tests to prove that path ran.
+__device__ unsigned int g_merge_fallbacks;
+
 // ray_marcher.py:46-50: nan_to_num(inf) then clamp to the global [min, max] of all depths of the call
 __global__ void depth_clamp_kernel(float* __restrict__ depth, int nrays, const int* __restrict__ gstate)
 {
@@ -960,7 +964,10 @@ __device__ __forceinline__ void march(const float* T, const float* S, float* wv,
         const float dmid = (s0 + s1) * 0.5f;
         const float tmid = (t0 + t1) * 0.5f;
         const float sp = softplus20(dmid - 1.0f);
-        const float alpha = 1.0f - fexp(-(sp * delta));
+        // 1 - exp(-sigma delta) without the cancellation: in near-empty space sigma delta ~ 1e-5 and 1 - exp() keeps only ~2 digits
+        // of alpha (the fp32 reference's own error there; the hardware exp's ~1 ulp doubled it), which is what the depth of an empty ray
+        // is a weighted mean of
+        const float alpha = -expm1f(-(sp * delta));
         const float om1 = act ? (1.0f - alpha + 1e-10f) : 1.0f;
         const float incl = wave_incl_mul(om1, lane);
         const float excl = wave_shift_up1(incl, 1.0f);
@@ -1293,6 +1300,7 @@ __global__ __launch_bounds__(256, OCC) void render_kernel(RenderArgs a, int R)
                 }
             }
             if (!fast) {
+                if (lane == 0) atomicAdd(&g_merge_fallbacks, 1u);       // test hook (r3d_debug_merge_fallbacks): rare path, one atomic per ray
 #pragma unroll
                 for (int sl = 0; sl < SLOTS; ++sl) {
                     const int i = sl * 64 + lane;
@@ -1615,6 +1623,19 @@ extern "C" size_t r3d_render_workspace_bytes(int N, int M, int Nc, int Nf)
 {
     const size_t nrays = (size_t)N * M;
     return render_state_bytes(nrays) + 2 * nrays * sizeof(float) + 64 + kFoldBytes + render_park_bytes(nrays, Nc, Nf);
+}
+
+// Test hook, not part of the C ABI of include/r3d_hip.h (like the stamp readers of experiment builds): *count = rays of the current device
+// whose merge left the rank fast path since the last call with reset != 0.  Synchronises the device.  real3dportrait_amd/_lib.py binds it
+// when the library exports it (OPTIONAL_SIGNATURES); tests/test_gpu_surface.py reads it.
+extern "C" int r3d_debug_merge_fallbacks(unsigned long long* count, int reset)
+{
+    unsigned int v = 0;
+    if (hipDeviceSynchronize() != hipSuccess || hipMemcpyFromSymbol(&v, HIP_SYMBOL(g_merge_fallbacks), sizeof(v)) != hipSuccess) return R3D_ERR_LAUNCH;
+    if (count) *count = v;
+    const unsigned int z = 0;
+    if (reset && hipMemcpyToSymbol(HIP_SYMBOL(g_merge_fallbacks), &z, sizeof(z)) != hipSuccess) return R3D_ERR_LAUNCH;
+    return R3D_OK;
 }
 
 extern "C" size_t r3d_run_model_workspace_bytes(void) { return kFoldBytes; }

@@ -159,3 +159,54 @@ def render_hash_noise(seed, rays, Nc, Nf):
     nc = device_hash_uniform(seed, 0, rays * np.uint64(Nc) + np.arange(Nc, dtype=np.uint64)[None, :])
     uf = device_hash_uniform(seed, 1, rays * np.uint64(max(Nf, 1)) + np.arange(max(Nf, 1), dtype=np.uint64)[None, :])[:, :Nf]
     return nc, uf
+
+
+# ---- surface-like scenes for the ray kernel (what a trained checkpoint looks like to the renderer) --------------------------------
+def surface_scene(seed, N=1, H=64, W=64, centre=(0.15, 0.1, 0.05), radius=0.3, a=100.0, c=None, bg_bias=-5.0, box_warp=1.0,
+                  triplane_depth=1, dense=False, texture=0.3):
+    """(planes [N,3,32*D,H,W], (w1, b1, w2, b2)) of an opaque textured sphere in near-empty space.
+
+    The random planes of synth_planes give every ray a weight sum of 0.3-1 spread along its whole length.  A trained model
+    packs density onto a surface instead: transmittance falls to ~0 at the hit, the space around it is near-empty, and the
+    importance samples crowd into one or two coarse bins.  This scene has that shape with a closed-form surface:
+
+    * Feature channel 0 is a quadratic sampled at the texel centres (grid_sample, align_corners=False: texel i of n sits at
+      (2i+1)/n - 1).  With the plane axes of renderer.py:37-63 (plane 0 reads (x, y), plane 1 (x, z), plane 2 (z, x), in
+      coordinates scaled by 2/box_warp, renderer.py:71), plane 0 holds (u-qx)^2 + (v-qy)^2, plane 1 holds (v-qz)^2 and
+      plane 2 holds 0, so the decoder's plane mean (triplane.py:179) is s = |q - qc|^2 / 3 for q = 2p/box_warp.  Tri-grids
+      (triplane_depth D > 1) hold the same value at every depth slice.
+    * The other 31 channels are `texture` * hash_unitvar noise (the colour texture).
+    * Hidden unit 0 of the decoder is softplus(a (s0 - s)) with s0 = (2 radius / box_warp)^2 / 3: w1[0] = e0 * (-a sqrt(C))
+      and b1[0] = a s0 undo FullyConnectedLayer's weight gain 1/sqrt(C) (networks_stylegan2.py:99-131).  No other hidden
+      unit reads channel 0.  The surface is a steep softplus, not a large bias cancelled in layer 2 (that would measure
+      fp32 rounding of the bias, not the renderer).
+    * The density row reads only that unit: w2[0] = e0 * c sqrt(HID) (gain 1/sqrt(HID)), b2[0] = bg_bias; so sigma =
+      c softplus(a (s0 - s)) + bg_bias, and MipRayMarcher2's softplus(sigma - 1) (ray_marcher.py:25-57) gives ~e^(bg_bias-1)
+      outside the sphere and ~c a (s0 - s) inside.  The rgb rows are synth_decoder's.
+    * dense=True raises c from 30 to 600: sigma * delta > 20 inside at 48 coarse samples, so 1 - exp(-sigma delta) rounds
+      to 1 in fp32 and the transmittance products underflow.
+
+    `centre` (world units) is off the box centre so that the silhouette crosses the image of look_at_camera.  Everything is
+    computed in float64 numpy from the parameters and rounded once to float32: bit-reproducible on every machine."""
+    C, HID, OUT = 32, 64, 33
+    D = int(triplane_depth)
+    if c is None:
+        c = 600.0 if dense else 30.0
+    qc = [2.0 * float(x) / float(box_warp) for x in centre]
+    s0 = (2.0 * float(radius) / float(box_warp)) ** 2 / 3.0
+    planes = hash_unitvar(seed, (N, 3, C * D, H, W), stream=41) * np.float32(texture)
+    u = (2.0 * np.arange(W, dtype=np.float64) + 1.0) / W - 1.0        # texel centres along the width axis (first coordinate)
+    v = (2.0 * np.arange(H, dtype=np.float64) + 1.0) / H - 1.0        # ... along the height axis (second coordinate)
+    ch0 = np.zeros((3, H, W), np.float64)
+    ch0[0] = (u[None, :] - qc[0]) ** 2 + (v[:, None] - qc[1]) ** 2   # plane 0: (x, y)
+    ch0[1] = np.broadcast_to((v[:, None] - qc[2]) ** 2, (H, W))       # plane 1: (x, z) -> z is the second coordinate
+    planes[:, :, 0:D] = ch0.astype(np.float32)[None, :, None]         # channel 0 = channels 0..D-1 of the [C*D] layout
+    w1, b1, w2, b2 = synth_decoder(seed, C, HID, OUT)
+    w1[:, 0] = 0.0
+    w1[0, :] = 0.0
+    w1[0, 0] = np.float32(-float(a) * math.sqrt(C))
+    b1[0] = np.float32(float(a) * s0)
+    w2[0, :] = 0.0
+    w2[0, 0] = np.float32(float(c) * math.sqrt(HID))
+    b2[0] = np.float32(bg_bias)
+    return planes.astype(np.float32), (w1, b1, w2, b2)

@@ -14,6 +14,7 @@ renderer.py:281) are replaced, for the duration of the call, by functions return
 that are stored with the outputs, so every implementation sees identical sampling noise.
 """
 import contextlib
+import json
 import os
 import sys
 
@@ -36,7 +37,7 @@ from modules.eg3ds.volumetric_rendering.ray_sampler import RaySampler  # noqa: E
 from modules.eg3ds.volumetric_rendering.renderer import ImportanceRenderer  # noqa: E402
 from modules.eg3ds.volumetric_rendering import math_utils  # noqa: E402
 
-OUT = os.path.dirname(os.path.abspath(__file__))
+OUT = os.environ.get("R3D_GOLDEN_OUT") or os.path.dirname(os.path.abspath(__file__))     # R3D_GOLDEN_OUT: regenerate elsewhere to compare
 torch.set_num_threads(8)
 
 
@@ -122,6 +123,103 @@ def render_case(name, planes, cams, R, Nc, Nf, dec_seed, noise_seed, box_warp=1.
         out["planes_spec"] = np.asarray(planes_spec, np.float64)   # (seed, N, C, H, W, scale)
     np.savez_compressed(os.path.join(OUT, name + ".npz"), **out)
     print(name, "rgb", rgb.shape, "valid frac", float(valid.float().mean()), "wsum mean", float(wsum.mean()))
+
+
+# ---- surface-like scenes (synth.surface_scene) with an fp64 truth --------------------------------------------------------------------
+SURFACE_CLASSES = ("opaque", "silhouette", "empty")      # by the fp64 weight sum: > 0.99, otherwise >= 0.01, < 0.01
+
+
+def surface_classes(wsum64):
+    w = np.asarray(wsum64, np.float64)[..., 0]
+    return {"opaque": w > 0.99, "silhouette": (w >= 0.01) & (w <= 0.99), "empty": w < 0.01}
+
+
+@contextlib.contextmanager
+def reference_in_float64(ren):
+    """Run the reference renderer in float64 (inputs cast by the caller): its plane axes become float64 and Tensor.float() leaves
+    float64 tensors as they are.  The reference casts with .float() in three places of the render path: the grid_sample grids
+    (renderer.py:74, :88) and the coarse weights entering the importance sampler (:245); nothing else in the path calls it.
+    Restored afterwards, like injected_noise."""
+    real_float = torch.Tensor.float
+    axes = ren.plane_axes
+
+    def keep_double(t, *a, **k):
+        return t if t.dtype == torch.float64 else real_float(t, *a, **k)
+
+    ren.plane_axes = axes.double()
+    torch.Tensor.float = keep_double
+    try:
+        yield
+    finally:
+        torch.Tensor.float = real_float
+        ren.plane_axes = axes
+
+
+def surface_case(name, scene, cams, R, Nc, Nf, noise_seed, white_back=False):
+    """One surface scene rendered by the reference twice: in fp32 (as every other render golden) and in float64 (the
+    truth).  Stored: the fp32 and fp64 outputs, the fp32 reference's per-class max error against fp64, rays, and the scene
+    and noise as specs (tests regenerate them with synth.surface_scene / synth.synth_noise)."""
+    scene = dict(scene)
+    box_warp, D = float(scene.get("box_warp", 1.0)), int(scene.get("triplane_depth", 1))
+    cams = np.asarray(cams, np.float32).reshape(-1, 25)
+    N, M = cams.shape[0], R * R
+    planes, dec_np = synth.surface_scene(N=N, **scene)
+    dec = make_decoder(dec_np)
+    noise_c = synth.synth_noise(noise_seed, (N, M, Nc, 1), stream=7)
+    u_f = synth.synth_noise(noise_seed, (N * M, Nf), stream=8)
+    cam_t = torch.from_numpy(cams)
+    hp = {"enable_rescale_plane_regulation": False, "triplane_feature_type": "triplane"}
+    if D > 1:
+        hp = {"enable_rescale_plane_regulation": False, "triplane_feature_type": "trigrid", "triplane_depth": D}
+    outs = {}
+    with torch.no_grad():
+        o, d = RaySampler()(cam_t[:, :16].view(-1, 4, 4), cam_t[:, 16:].view(-1, 3, 3), R)
+        for tag, dt in (("32", torch.float32), ("64", torch.float64)):
+            ren = ImportanceRenderer(hp=hp).eval()
+            cast = np.float32 if dt == torch.float32 else np.float64
+            ctx = reference_in_float64(ren) if dt == torch.float64 else contextlib.nullcontext()
+            with ctx, injected_noise(noise_c.astype(cast), u_f.astype(cast)) as st:
+                out = ren(torch.from_numpy(planes).to(dt), dec, o.to(dt), d.to(dt), opts(Nc, Nf, box_warp, white_back))
+            assert st["c"] == 1 and st["f"] == (1 if Nf > 0 else 0)
+            assert all(t.dtype == (torch.bool if i == 3 else dt) for i, t in enumerate(out)), [t.dtype for t in out]
+            outs[tag] = [t.numpy() for t in out]
+    rgb, depth, wsum, valid = outs["32"]
+    rgb64, depth64, wsum64, valid64 = outs["64"]
+    assert np.array_equal(valid, valid64)
+    cls = surface_classes(wsum64)
+    err = np.zeros((3, 3), np.float64)          # [output rgb / depth / wsum][class]
+    for j, c in enumerate(SURFACE_CLASSES):
+        m = cls[c]
+        if m.any():
+            for i, (a, b) in enumerate(((rgb, rgb64), (depth, depth64), (wsum, wsum64))):
+                err[i, j] = np.abs(a.astype(np.float64) - b)[m].max()
+    # the two [N, M, 32] colour arrays are stored byte-shuffled ([4, n] uint8: byte k of every value, then k + 1, ...; zlib packs the
+    # exponent bytes far better) so that the R = 64 case stays under 1 MB; tests/surface_common.py undoes it
+    shuffle = lambda a: np.ascontiguousarray(np.ascontiguousarray(a, np.float32).view(np.uint8).reshape(-1, 4).T)
+    out = dict(cams=cams, R=R, Nc=Nc, Nf=Nf, box_warp=np.float32(box_warp), white_back=int(white_back), triplane_depth=D,
+               noise_seed=noise_seed, origins=o.numpy(), dirs=d.numpy(),
+               rgb_shuffled=shuffle(rgb), depth=depth, wsum=wsum, valid=valid,
+               # fp64 outputs as the fp32 reference's value plus a float32 residual: half the bytes of float64 and ~1e-13 from the
+               # float64 value, far below any bound the tests apply
+               rgb64_res_shuffled=shuffle(rgb64 - rgb), depth64_res=(depth64 - depth).astype(np.float32),
+               wsum64_res=(wsum64 - wsum).astype(np.float32),
+               err_fp32_ref=err, classes=np.array(SURFACE_CLASSES), outputs=np.array(["rgb", "depth", "wsum"]),
+               scene=np.array(json.dumps(scene, sort_keys=True)))            # synth.surface_scene(N=len(cams), **json.loads(scene))
+    np.savez_compressed(os.path.join(OUT, name + ".npz"), **out)
+    print(name, "rays", N * M, "classes", {c: int(cls[c].sum()) for c in SURFACE_CLASSES})
+    for j, c in enumerate(SURFACE_CLASSES):
+        print("   %-10s fp32 reference vs fp64: rgb %.2e depth %.2e wsum %.2e" % (c, err[0, j], err[1, j], err[2, j]))
+
+
+def surface_cases():
+    cam = synth.look_at_camera(0.1, 0.05)
+    surface_case("surface_a_r64_48p48", dict(seed=301), [cam], 64, 48, 48, 311)
+    surface_case("surface_b_n2_r32_96p96", dict(seed=302), synth.camera_sweep(2, -0.3, 0.3), 32, 96, 96, 312)
+    surface_case("surface_c_white_bw_r32_32p16", dict(seed=303, box_warp=1.2), [synth.look_at_camera(-0.2, 0.15)], 32, 32, 16, 313,
+                 white_back=True)
+    surface_case("surface_d_dense_r48_48p48", dict(seed=304, dense=True), [cam], 48, 48, 48, 314)
+    surface_case("surface_e_trigrid_d3_r16_20p12", dict(seed=305, H=24, W=24, triplane_depth=3), [synth.look_at_camera(0.15, -0.1)],
+                 16, 20, 12, 315)
 
 
 def run_model_case(name, trigrid_depth=1):
@@ -553,7 +651,10 @@ def sr_resize_case(name):
 
 def main():
     which = sys.argv[1:] or ["render", "run_model", "sr_small", "sr_full", "synthesis", "fusion", "toplane", "sr_cfg5", "fusion_full",
-                             "toplane_full", "synthesis_mask", "warp_sr", "warp_sr_two_stage", "warp_sr_v1", "render_r512", "sr_resize"]
+                             "toplane_full", "synthesis_mask", "warp_sr", "warp_sr_two_stage", "warp_sr_v1", "render_r512", "sr_resize",
+                             "surface"]
+    if "surface" in which:
+        surface_cases()
     if "render_r512" in which:
         render_r512_case("render_g_r512_48p0", 0)
         render_r512_case("render_h_r512_48p48_sr", 48)
