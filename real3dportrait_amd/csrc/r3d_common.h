@@ -51,10 +51,24 @@ __device__ __forceinline__ float ord2f(int k) {
 // ---- fast transcendentals on the hardware exp2/log2 (<= ~1 ulp of the result scale) ---------------
 __device__ __forceinline__ float fexp(float x) { return __builtin_amdgcn_exp2f(x * 1.4426950408889634f); }
 __device__ __forceinline__ float flog(float x) { return __builtin_amdgcn_logf(x) * 0.6931471805599453f; }
+// log1p(y), y >= 0, branch-free on the hardware log2: log(u) y / (u - 1) with u = 1 + y (u - 1 is exact, and the ratio undoes the rounding
+// of u to first order; <= 3e-7 relative).  ocml's log1pf is a call full of branches and constants, and in the ray kernel it cost scratch.
+__device__ __forceinline__ float flog1p(float y) {
+    const float u = 1.0f + y, d = u - 1.0f;
+    return d == 0.0f ? y : flog(u) * (y * __builtin_amdgcn_rcpf(d));
+}
+// -expm1(-x) = 1 - e^-x, branch-free: the Taylor series x (1 - x/2 (1 - x/3 (1 - ...))) to x^8 below 0.5 (where 1 - e^-x cancels; the
+// truncation is < 2e-8 relative there), 1 - fexp(-x) above.  <= 2e-7 relative against fp64 in fp32 emulation.
+__device__ __forceinline__ float one_minus_exp_neg(float x) {
+    float p = 1.0f;
+#pragma unroll
+    for (int k = 8; k >= 2; --k) p = 1.0f - (x * (1.0f / (float)k)) * p;
+    return x < 0.5f ? x * p : 1.0f - fexp(-x);
+}
 // torch.nn.Softplus(beta=1, threshold=20) of the marcher's densities.  log1p, not log(1 + e): in near-empty space (x ~ -6) rounding
 // 1 + e^x loses up to ~2e-5 of the result, and the loss differs from sample to sample (tests/test_gpu_surface.py)
 __device__ __forceinline__ float softplus20(float x) {
-    const float r = fmaxf(x, 0.0f) + log1pf(fexp(-fabsf(x)));
+    const float r = fmaxf(x, 0.0f) + flog1p(fexp(-fabsf(x)));
     return x > 20.0f ? x : r;
 }
 __device__ __forceinline__ float sigmoidf(float x) { return __builtin_amdgcn_rcpf(1.0f + fexp(-x)); }

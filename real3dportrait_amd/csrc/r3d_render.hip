@@ -868,10 +868,11 @@ struct TileGather {                               // one lane quad = one sample;
 };
 
 // One pass over NT tiles.  depth_of(t): depth of the sample this lane gathers for in tile t.  col0 / col1 / sig: the per-tile outputs.
-template <int NT, int GPF, bool TRI, int NB = 2, typename DepthFn>
+// first_done(): called once the open first tile is in its staging slot (R3D_STAMPS builds time the exposed gather with it; else empty).
+template <int NT, int GPF, bool TRI, int NB = 2, typename DepthFn, typename FirstFn>
 __device__ __forceinline__ void decode_pass(FeatLds& F, const DecoderLds& dec, const float4* __restrict__ P, int H, int W, int D, int lane,
                                             float ox, float oy, float oz, float dx, float dy, float dz, float scale, float xs3,
-                                            DepthFn depth_of, f32x4 (&col0)[NT], f32x4 (&col1)[NT], float (&sig)[NT], f32x4* gp = nullptr)
+                                            DepthFn depth_of, FirstFn first_done, f32x4 (&col0)[NT], f32x4 (&col1)[NT], float (&sig)[NT], f32x4* gp = nullptr)
 {
     const int gq = lane & 3, gs = lane >> 2, q = lane >> 4, s = lane & 15;
     // Staging slots: slot(sample, k-slot q) = 16 q + (sample ^ 2 q).  A ds_read_b128 is served in the lane groups {0-3, 12-15, 20-27}, {4-11, 16-19,
@@ -915,6 +916,7 @@ __device__ __forceinline__ void decode_pass(FeatLds& F, const DecoderLds& dec, c
         }
     };
     gather_whole(0);
+    first_done();
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
         wave_lds_sync();
@@ -966,8 +968,8 @@ __device__ __forceinline__ void march(const float* T, const float* S, float* wv,
         const float sp = softplus20(dmid - 1.0f);
         // 1 - exp(-sigma delta) without the cancellation: in near-empty space sigma delta ~ 1e-5 and 1 - exp() keeps only ~2 digits
         // of alpha (the fp32 reference's own error there; the hardware exp's ~1 ulp doubled it), which is what the depth of an empty ray
-        // is a weighted mean of
-        const float alpha = -expm1f(-(sp * delta));
+        // is a weighted mean of (one_minus_exp_neg: r3d_common.h, the series below 0.5)
+        const float alpha = one_minus_exp_neg(sp * delta);
         const float om1 = act ? (1.0f - alpha + 1e-10f) : 1.0f;
         const float incl = wave_incl_mul(om1, lane);
         const float excl = wave_shift_up1(incl, 1.0f);
@@ -1071,7 +1073,6 @@ __global__ __launch_bounds__(256, OCC) void render_kernel(RenderArgs a, int R)
     const int gs = gather_s(lane);                        // gather mapping: lane = 4 * sample + q
     RayL& L = rl[wave];
     FeatLds& F = feat[wave];
-    const int Nc = a.Nc, Nf = a.Nf, S = Nc + Nf;
     // min / max of the valid rays' starts (renderer.py:123-126): reduce the per-block partials of ray_limits_kernel
     int pmin = 0x7fffffff, pmax = (int)0x80000000, pany = 0;
     for (int b = lane; b < a.nlimit_blocks; b += 64) {
@@ -1082,6 +1083,7 @@ __global__ __launch_bounds__(256, OCC) void render_kernel(RenderArgs a, int R)
     for (int d = 32; d >= 1; d >>= 1) { pmin = min(pmin, __shfl_xor(pmin, d)); pmax = max(pmax, __shfl_xor(pmax, d)); pany |= __shfl_xor(pany, d); }
     const float gmin_start = ord2f(pmin), gmax_start = ord2f(pmax);
     const bool any_valid = pany != 0;
+    const int Nc_all = a.Nc;
     float run_min = INFINITY, run_max = -INFINITY;
     R3D_STAMP_DECL;
     int st_rays_ = 0; (void)st_rays_;
@@ -1096,6 +1098,9 @@ __global__ __launch_bounds__(256, OCC) void render_kernel(RenderArgs a, int R)
         KArgs ap = (KArgs)__builtin_amdgcn_kernarg_segment_ptr();
         asm volatile("" : "+s"(ap));
         const auto& A = *ap;
+        // (Nc, Nf re-read per ray like the rest: held across the loop they were 53 SGPR spills of the REF shape; the coarse-only shapes
+        // keep Nc, which there the allocator places better -- re-read, <6, 0> spilled 2 VGPRs)
+        const int Nc = NTF > 0 ? A.Nc : Nc_all, Nf = A.Nf, S = Nc + Nf;
         int ray, n;
         if (!it.get(ray, n)) break;
         ++st_rays_;
@@ -1145,7 +1150,8 @@ __global__ __launch_bounds__(256, OCC) void render_kernel(RenderArgs a, int R)
             }
             wave_lds_sync();
             auto dof = [&](int t) { const int k = 16 * t + gs; return k < Nc ? L.t[k] : start; };
-            decode_pass<NTC, GPF, TRI, (OCC >= 3 ? 1 : 2)>(F, dec, P, A.H, A.W, A.D, lane, ox, oy, oz, dx, dy, dz, A.scale, xs3, dof, colc[0], colc[1], sigc, gpark);
+            decode_pass<NTC, GPF, TRI, (OCC >= 3 ? 1 : 2)>(F, dec, P, A.H, A.W, A.D, lane, ox, oy, oz, dx, dy, dz, A.scale, xs3, dof,
+                                                           [&]() { R3D_STAMP(8); }, colc[0], colc[1], sigc, gpark);
         }
         constexpr bool parked = PARK;                  // (an instantiation with NTF > 0 is only launched with Nf > 0)
         if (parked) {
@@ -1217,7 +1223,8 @@ __global__ __launch_bounds__(256, OCC) void render_kernel(RenderArgs a, int R)
             float sigf[NTF > 0 ? NTF : 1];
             {
                 auto dof = [&](int t) { const int k = 16 * t + gs; return L.t[Nc + (k < Nf ? k : 0)]; };
-                decode_pass<(NTF > 0 ? NTF : 1), GPF, TRI, (OCC >= 3 ? 1 : 2)>(F, dec, P, A.H, A.W, A.D, lane, ox, oy, oz, dx, dy, dz, A.scale, xs3, dof, colf[0], colf[1], sigf, GPARK ? gpark + 2 * NTC * 64 : nullptr);
+                decode_pass<(NTF > 0 ? NTF : 1), GPF, TRI, (OCC >= 3 ? 1 : 2)>(F, dec, P, A.H, A.W, A.D, lane, ox, oy, oz, dx, dy, dz, A.scale, xs3, dof,
+                                                                             [&]() { R3D_STAMP(9); }, colf[0], colf[1], sigf, GPARK ? gpark + 2 * NTC * 64 : nullptr);
             }
             if (q == 0) {
 #pragma unroll
