@@ -5,6 +5,7 @@ Operators keep the reference's names and signatures (see each module's docstring
     SynthesisBlock, SuperresolutionHybrid8XDC           (superresolution.py)
     SynthesisBlockNoUp, Conv2d, ConvStack                (superresolution.py: torso/background fusion convs)
     TriPlaneGenerator (.synthesis contract), patch_model (triplane.py)
+    SegFormerSECC2PlaneBackbone                          (segformer.py: the per-frame SECC encoder, mode b0)
     render_clip_sharded                                  (frames.py: frame sharding + RCCL gather)
 All compute goes through libr3d_hip.so (include/r3d_hip.h); there is no eager/CPU fallback.
 """
@@ -20,6 +21,9 @@ def __getattr__(name):      # lazy: importing the package (e.g. for synth) must 
         return getattr(m, name)
     if name in ("TriPlaneGenerator", "patch_model"):
         from . import triplane as m
+        return getattr(m, name)
+    if name == "SegFormerSECC2PlaneBackbone":
+        from . import segformer as m
         return getattr(m, name)
     if name in ("render_clip_sharded", "shard_frames"):
         from . import frames as m

@@ -1,0 +1,268 @@
+"""SegFormerSECC2PlaneBackbone (modules/real3d/segformer.py:672-731) in mode b0 on the HIP SECC encoder (r3d_secc_* of
+include/r3d_hip.h): prenet, the MiT-b0 encoder and the SegFormerHead in exact fp32, then to_plane_cnn as a ConvStack.
+
+The module keeps the reference's parameter names, so a reference checkpoint loads with strict=True.  INFERENCE ONLY (eval semantics:
+DropPath / Dropout are identity, BatchNorm uses its running statistics); inputs are detached and no autograd graph is built.
+
+    forward(x)          [B, in_dim, H, W] -> the reference's flipped planes [B, 3, 32, H/2, W/2]
+    forward_features(x) -> the head output [B, 256, H/4, W/4]
+    forward_raw(x)      -> the unflipped to_plane_cnn output [B, 96, H/2, W/2], for
+                           ImportanceRenderer.prepare_planes(cano, add=raw, add_flip=SECC_PLANE_FLIPS)
+"""
+import torch
+import torch.nn as nn
+
+from . import _lib
+from .superresolution import Conv2d, ConvStack
+from .synth import SECC_DIMS, SECC_HEADS, SECC_SR
+
+MAX_KEYS = 1024          # r3d_secc_attention's limit on L = (H/32)(W/32): inputs up to 1024^2
+
+
+class _Prenet(nn.Module):
+    """Conv2dLayer(in_dim, 3, 1) (modules/eg3ds/models/networks_stylegan2.py:139-190): parameters and the resample_filter buffer."""
+
+    def __init__(self, in_dim):
+        super().__init__()
+        self.weight = nn.Parameter(torch.randn(3, in_dim, 1, 1))
+        self.bias = nn.Parameter(torch.zeros(3))
+        f = torch.tensor([1.0, 3.0, 3.0, 1.0])
+        self.register_buffer("resample_filter", torch.outer(f, f) / 64.0)
+
+
+class _PatchEmbed(nn.Module):
+    def __init__(self, cin, cout, k, stride):
+        super().__init__()
+        self.proj = nn.Conv2d(cin, cout, k, stride, k // 2)
+        self.norm = nn.LayerNorm(cout)
+
+
+class _Attention(nn.Module):
+    def __init__(self, C, sr):
+        super().__init__()
+        self.q, self.kv, self.proj = nn.Linear(C, C), nn.Linear(C, 2 * C), nn.Linear(C, C)
+        if sr > 1:
+            self.sr = nn.Conv2d(C, C, sr, sr)
+            self.norm = nn.LayerNorm(C)
+
+
+class _DWConv(nn.Module):
+    def __init__(self, C):
+        super().__init__()
+        self.dwconv = nn.Conv2d(C, C, 3, 1, 1, groups=C)
+
+
+class _Mlp(nn.Module):
+    def __init__(self, C):
+        super().__init__()
+        self.fc1, self.dwconv, self.fc2 = nn.Linear(C, 4 * C), _DWConv(4 * C), nn.Linear(4 * C, C)
+
+
+class _Block(nn.Module):
+    def __init__(self, C, sr):
+        super().__init__()
+        self.norm1, self.attn, self.norm2, self.mlp = nn.LayerNorm(C), _Attention(C, sr), nn.LayerNorm(C), _Mlp(C)
+
+
+class _MixVisionTransformer(nn.Module):
+    """mit_b0's parameters (segformer.py:244-310, 407-413)."""
+
+    def __init__(self):
+        super().__init__()
+        cin = 3
+        for s, (C, sr) in enumerate(zip(SECC_DIMS, SECC_SR), 1):
+            setattr(self, "patch_embed%d" % s, _PatchEmbed(cin, C, 7 if s == 1 else 3, 4 if s == 1 else 2))
+            setattr(self, "block%d" % s, nn.ModuleList([_Block(C, sr) for _ in range(2)]))
+            setattr(self, "norm%d" % s, nn.LayerNorm(C))
+            cin = C
+
+
+class _HeadMLP(nn.Module):
+    def __init__(self, cin):
+        super().__init__()
+        self.proj = nn.Linear(cin, 256)
+
+
+class _ConvModule(nn.Module):
+    """mmcv ConvModule(1024, 256, 1, norm_cfg=BN): conv without bias, BatchNorm2d, ReLU."""
+
+    def __init__(self):
+        super().__init__()
+        self.conv = nn.Conv2d(1024, 256, 1, bias=False)
+        self.bn = nn.BatchNorm2d(256)
+
+
+class _SegFormerHead(nn.Module):
+    def __init__(self):
+        super().__init__()
+        for s, C in enumerate(SECC_DIMS, 1):
+            setattr(self, "linear_c%d" % s, _HeadMLP(C))
+        self.linear_fuse = _ConvModule()
+
+
+class SegFormerSECC2PlaneBackbone(nn.Module):
+    def __init__(self, mode="b0", out_channels=96, pncc_cond_mode="cano_src_tgt"):
+        super().__init__()
+        if mode != "b0":
+            raise NotImplementedError("SegFormerSECC2PlaneBackbone: only mode 'b0' has a HIP encoder (got %r)" % (mode,))
+        self.mode, self.pncc_cond_mode = mode, pncc_cond_mode
+        self.in_dim = 9 if pncc_cond_mode == "cano_src_tgt" else 6
+        self.prenet = _Prenet(self.in_dim)
+        self.mix_vit = _MixVisionTransformer()
+        self.fuse_head = _SegFormerHead()
+        self.to_plane_cnn = ConvStack(Conv2d(256, 256, 3, 1, 1), nn.LeakyReLU(0.01), Conv2d(256, 256, 3, 1, 1), nn.LeakyReLU(0.01),
+                                      Conv2d(256, 256, 3, 1, 1), nn.LeakyReLU(0.01), nn.UpsamplingBilinear2d(scale_factor=2.0),
+                                      Conv2d(256, out_channels, 3, 1, 1))
+        self._derived_key = None
+        self._derived = None
+        self._work = {}          # (device, stream, B, H, W) -> activation buffers: two streams in flight never share one
+
+    # ---- parameters in the kernels' layouts (once per parameter version) ----------------------------------------------------------
+    def _params_key(self):
+        return tuple((p.data_ptr(), p._version) for p in self.parameters()) + tuple((b.data_ptr(), b._version) for b in self.buffers())
+
+    def _prepare(self):
+        key = self._params_key()
+        if key == self._derived_key:
+            return self._derived
+        mv, fh = self.mix_vit, self.fuse_head
+        d = {"conv": {}}
+        with torch.no_grad():
+            for s in range(1, 5):
+                pe = getattr(mv, "patch_embed%d" % s)
+                d["conv"]["pe%d" % s] = pe.proj.weight.detach().permute(0, 2, 3, 1).contiguous().float()
+                for j, blk in enumerate(getattr(mv, "block%d" % s)):
+                    if hasattr(blk.attn, "sr"):
+                        d["conv"]["sr%d.%d" % (s, j)] = blk.attn.sr.weight.detach().permute(0, 2, 3, 1).contiguous().float()
+            # the head fold, in fp64: W'_i = W_fuse[:, block(i)] W_ci, const = sum_i W_fuse[:, block(i)] b_ci, BN -> scale, shift
+            wf = fh.linear_fuse.conv.weight.detach().double()[:, :, 0, 0]
+            const = torch.zeros(256, dtype=torch.float64, device=wf.device)
+            for blk, s in enumerate((4, 3, 2, 1)):
+                part = wf[:, 256 * blk:256 * (blk + 1)]
+                lin = getattr(fh, "linear_c%d" % s).proj
+                d["wfold%d" % s] = (part @ lin.weight.detach().double()).float().contiguous()
+                const = const + part @ lin.bias.detach().double()
+            bn = fh.linear_fuse.bn
+            scale = bn.weight.detach().double() / torch.sqrt(bn.running_var.detach().double() + bn.eps)
+            d["hconst"] = const.float().contiguous()
+            d["bn_scale"] = scale.float().contiguous()
+            d["bn_shift"] = (bn.bias.detach().double() - bn.running_mean.detach().double() * scale).float().contiguous()
+        self._derived_key, self._derived = key, d
+        return d
+
+    def _buffers_for(self, B, H, W, dev):
+        key = (dev, _lib.stream_ptr(), B, H, W)
+        w = self._work.get(key)
+        if w is None:
+            n1 = B * (H // 4) * (W // 4)
+            L = B * (H // 32) * (W // 32) * 64       # spatial-reduction output rows x C, the largest stage (C sr^2 = 2048 ... 256)
+            e = lambda n: torch.empty(n, device=dev, dtype=torch.float32)
+            w = {"x": e(n1 * 32), "t": e(n1 * 32), "q": e(n1 * 32), "o": e(n1 * 32), "h1": e(n1 * 128), "h2": e(n1 * 128),
+                 "sr": e(L * 4), "kv": e(L * 8),
+                 "c": [e(n1 * 32), e(n1 // 4 * 64), e(n1 // 16 * 160), e(n1 // 64 * 256)],
+                 "f": [None, e(n1 // 4 * 256), e(n1 // 16 * 256), e(n1 // 64 * 256)]}
+            self._work[key] = w
+        return w
+
+    # ---- the encoder ---------------------------------------------------------------------------------------------------------------
+    def _check_input(self, x):
+        if x.dim() != 4 or x.shape[1] != self.in_dim:
+            raise ValueError("SegFormerSECC2PlaneBackbone: expected [B, %d, H, W], got %s" % (self.in_dim, tuple(x.shape)))
+        B, _, H, W = x.shape
+        if H % 32 or W % 32:
+            raise NotImplementedError("SegFormerSECC2PlaneBackbone: H and W must be multiples of 32 (got %d x %d)" % (H, W))
+        if (H // 32) * (W // 32) > MAX_KEYS:
+            raise NotImplementedError("SegFormerSECC2PlaneBackbone: (H/32)(W/32) = %d keys > %d" % ((H // 32) * (W // 32), MAX_KEYS))
+        return B, H, W
+
+    def _encode(self, x):
+        """Runs prenet + mix_vit; returns (buffers, B, H, W, params).  Stage outputs c1..c4 stay in the stream's buffers [B, h, w, C]."""
+        B, H, W = self._check_input(x)
+        x = x.detach().float().contiguous()
+        lib, P, st = _lib.load(), _lib.ptr, _lib.stream_ptr()
+        d = self._prepare()
+        w = self._buffers_for(B, H, W, x.device)
+        mv = self.mix_vit
+        X, T, Q, O, H1, H2, SR, KV = w["x"], w["t"], w["q"], w["o"], w["h1"], w["h2"], w["sr"], w["kv"]
+        h, wd = H // 4, W // 4
+        pe = mv.patch_embed1
+        _lib.check(lib.r3d_secc_embed1(P(x), B, self.in_dim, H, W, P(self.prenet.weight), P(self.prenet.bias), P(d["conv"]["pe1"]),
+                                       P(pe.proj.bias), P(pe.norm.weight), P(pe.norm.bias), P(X), st), "secc_embed1")
+        for s, (C, heads, sr) in enumerate(zip(SECC_DIMS, SECC_HEADS, SECC_SR), 1):
+            if s > 1:
+                pe, prev = getattr(mv, "patch_embed%d" % s), w["c"][s - 2]
+                _lib.check(lib.r3d_secc_conv(P(prev), B, h, wd, SECC_DIMS[s - 2], P(d["conv"]["pe%d" % s]), P(pe.proj.bias), C, 3, 2, 1,
+                                             P(pe.norm.weight), P(pe.norm.bias), pe.norm.eps, P(X), st), "secc_conv")
+                h, wd = h // 2, wd // 2
+            M, L = B * h * wd, (h // sr) * (wd // sr)
+            for j, blk in enumerate(getattr(mv, "block%d" % s)):
+                a, n1 = blk.attn, blk.norm1
+                if sr > 1:
+                    _lib.check(lib.r3d_secc_layernorm(P(X), M, C, P(n1.weight), P(n1.bias), n1.eps, P(T), st), "secc_layernorm")
+                    _lib.check(lib.r3d_secc_linear(P(T), M, C, None, None, 0.0, P(a.q.weight), P(a.q.bias), C, 0, None, P(Q), st), "secc_linear")
+                    _lib.check(lib.r3d_secc_conv(P(T), B, h, wd, C, P(d["conv"]["sr%d.%d" % (s, j)]), P(a.sr.bias), C, sr, sr, 0,
+                                                 None, None, 0.0, P(SR), st), "secc_conv")
+                    _lib.check(lib.r3d_secc_linear(P(SR), B * L, C, P(a.norm.weight), P(a.norm.bias), a.norm.eps, P(a.kv.weight),
+                                                   P(a.kv.bias), 2 * C, 0, None, P(KV), st), "secc_linear")
+                else:
+                    _lib.check(lib.r3d_secc_linear(P(X), M, C, P(n1.weight), P(n1.bias), n1.eps, P(a.q.weight), P(a.q.bias), C, 0, None,
+                                                   P(Q), st), "secc_linear")
+                    _lib.check(lib.r3d_secc_linear(P(X), M, C, P(n1.weight), P(n1.bias), n1.eps, P(a.kv.weight), P(a.kv.bias), 2 * C, 0,
+                                                   None, P(KV), st), "secc_linear")
+                _lib.check(lib.r3d_secc_attention(P(Q), P(KV), B, h * wd, L, C, heads, (C // heads) ** -0.5, P(O), st), "secc_attention")
+                _lib.check(lib.r3d_secc_linear(P(O), M, C, None, None, 0.0, P(a.proj.weight), P(a.proj.bias), C, 0, P(X), P(X), st),
+                           "secc_linear")
+                mlp, n2 = blk.mlp, blk.norm2
+                _lib.check(lib.r3d_secc_linear(P(X), M, C, P(n2.weight), P(n2.bias), n2.eps, P(mlp.fc1.weight), P(mlp.fc1.bias), 4 * C, 0,
+                                               None, P(H1), st), "secc_linear")
+                dw = mlp.dwconv.dwconv
+                _lib.check(lib.r3d_secc_dwconv_gelu(P(H1), B, h, wd, 4 * C, P(dw.weight), P(dw.bias), P(H2), st), "secc_dwconv_gelu")
+                _lib.check(lib.r3d_secc_linear(P(H2), M, 4 * C, None, None, 0.0, P(mlp.fc2.weight), P(mlp.fc2.bias), C, 0, P(X), P(X), st),
+                           "secc_linear")
+            nrm = getattr(mv, "norm%d" % s)
+            _lib.check(lib.r3d_secc_layernorm(P(X), M, C, P(nrm.weight), P(nrm.bias), nrm.eps, P(w["c"][s - 1]), st), "secc_layernorm")
+        return w, B, H, W, d
+
+    @torch.no_grad()
+    def forward_stages(self, x):
+        """[c1, c2, c3, c4] NCHW (MixVisionTransformer.forward_features, segformer.py:377-410), as new tensors."""
+        w, B, H, W, _ = self._encode(x)
+        out = []
+        for s, C in enumerate(SECC_DIMS, 1):
+            h, wd = H // (2 ** (s + 1)), W // (2 ** (s + 1))
+            out.append(w["c"][s - 1][:B * h * wd * C].view(B, h, wd, C).permute(0, 3, 1, 2).contiguous())
+        return out
+
+    @torch.no_grad()
+    def forward_features(self, x):
+        """fuse_head(mix_vit(prenet(x))): [B, 256, H/4, W/4] NCHW fp32."""
+        w, B, H, W, d = self._encode(x)
+        lib, P, st = _lib.load(), _lib.ptr, _lib.stream_ptr()
+        for s in (2, 3, 4):
+            n = B * (H // 2 ** (s + 1)) * (W // 2 ** (s + 1))
+            _lib.check(lib.r3d_secc_linear(P(w["c"][s - 1]), n, SECC_DIMS[s - 1], None, None, 0.0, P(d["wfold%d" % s]), None, 256, 0, None,
+                                           P(w["f"][s - 1]), st), "secc_linear")
+        out = torch.empty(B, 256, H // 4, W // 4, device=x.device, dtype=torch.float32)
+        _lib.check(lib.r3d_secc_head(P(w["c"][0]), B, H // 4, W // 4, P(d["wfold1"]), P(w["f"][1]), P(w["f"][2]), P(w["f"][3]),
+                                     P(d["hconst"]), P(d["bn_scale"]), P(d["bn_shift"]), P(out), st), "secc_head")
+        return out
+
+    @torch.no_grad()
+    def forward_raw(self, x):
+        """to_plane_cnn(forward_features(x)): [B, out_channels, H/2, W/2], before the flips of segformer.py:721-729."""
+        return self.to_plane_cnn(self.forward_features(x))
+
+    @torch.no_grad()
+    def forward(self, x):
+        planes = self.forward_raw(x)
+        planes = planes.view(len(planes), 3, -1, planes.shape[-2], planes.shape[-1])
+        return torch.stack([torch.flip(planes[:, 0], [2]), torch.flip(planes[:, 1], [2]), torch.flip(planes[:, 2], [2, 3])], dim=1)
+
+    @classmethod
+    def from_reference(cls, ref):
+        """A HIP copy of a constructed reference SegFormerSECC2PlaneBackbone in mode b0 (strict key copy)."""
+        out_channels = ref.to_plane_cnn[-1].out_channels
+        m = cls(mode=ref.mode, out_channels=out_channels, pncc_cond_mode=ref.pncc_cond_mode)
+        m.load_state_dict(ref.state_dict(), strict=True)
+        dev = next(ref.parameters()).device
+        return m.to(dev).eval()

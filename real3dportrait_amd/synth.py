@@ -210,3 +210,69 @@ def surface_scene(seed, N=1, H=64, W=64, centre=(0.15, 0.1, 0.05), radius=0.3, a
     w2[0, 0] = np.float32(float(c) * math.sqrt(HID))
     b2[0] = np.float32(bg_bias)
     return planes.astype(np.float32), (w1, b1, w2, b2)
+
+
+SECC_DIMS, SECC_HEADS, SECC_SR = (32, 64, 160, 256), (1, 2, 5, 8), (8, 4, 2, 1)     # mit_b0 (modules/real3d/segformer.py:407-413)
+
+
+def secc_backbone_shapes(pncc_cond_mode="cano_src_tgt", out_channels=96):
+    """[(state_dict key, shape)] of SegFormerSECC2PlaneBackbone('b0', out_channels, pncc_cond_mode) (modules/real3d/segformer.py:672-700)."""
+    in_dim = 9 if pncc_cond_mode == "cano_src_tgt" else 6
+    out = [("prenet.weight", (3, in_dim, 1, 1)), ("prenet.bias", (3,)), ("prenet.resample_filter", (4, 4))]
+    cin = 3
+    for s, (C, sr) in enumerate(zip(SECC_DIMS, SECC_SR), 1):
+        k = 7 if s == 1 else 3
+        p = "mix_vit.patch_embed%d." % s
+        out += [(p + "proj.weight", (C, cin, k, k)), (p + "proj.bias", (C,)), (p + "norm.weight", (C,)), (p + "norm.bias", (C,))]
+        for j in range(2):
+            p = "mix_vit.block%d.%d." % (s, j)
+            out += [(p + "norm1.weight", (C,)), (p + "norm1.bias", (C,)), (p + "attn.q.weight", (C, C)), (p + "attn.q.bias", (C,)),
+                    (p + "attn.kv.weight", (2 * C, C)), (p + "attn.kv.bias", (2 * C,)), (p + "attn.proj.weight", (C, C)),
+                    (p + "attn.proj.bias", (C,))]
+            if sr > 1:
+                out += [(p + "attn.sr.weight", (C, C, sr, sr)), (p + "attn.sr.bias", (C,)), (p + "attn.norm.weight", (C,)),
+                        (p + "attn.norm.bias", (C,))]
+            out += [(p + "norm2.weight", (C,)), (p + "norm2.bias", (C,)), (p + "mlp.fc1.weight", (4 * C, C)), (p + "mlp.fc1.bias", (4 * C,)),
+                    (p + "mlp.dwconv.dwconv.weight", (4 * C, 1, 3, 3)), (p + "mlp.dwconv.dwconv.bias", (4 * C,)),
+                    (p + "mlp.fc2.weight", (C, 4 * C)), (p + "mlp.fc2.bias", (C,))]
+        out += [("mix_vit.norm%d.weight" % s, (C,)), ("mix_vit.norm%d.bias" % s, (C,))]
+        cin = C
+    for s, C in enumerate(SECC_DIMS, 1):
+        out += [("fuse_head.linear_c%d.proj.weight" % s, (256, C)), ("fuse_head.linear_c%d.proj.bias" % s, (256,))]
+    out += [("fuse_head.linear_fuse.conv.weight", (256, 1024, 1, 1))]
+    out += [("fuse_head.linear_fuse.bn." + n, (256,)) for n in ("weight", "bias", "running_mean", "running_var")]
+    out += [("fuse_head.linear_fuse.bn.num_batches_tracked", ())]
+    for i, co in ((0, 256), (2, 256), (4, 256), (7, out_channels)):
+        out += [("to_plane_cnn.%d.weight" % i, (co, 256, 3, 3)), ("to_plane_cnn.%d.bias" % i, (co,))]
+    return out
+
+
+def synth_secc_backbone(seed, pncc_cond_mode="cano_src_tgt", out_channels=96, qk_gain=2.5):
+    """A full state_dict (numpy) of SegFormerSECC2PlaneBackbone('b0') from hash_unitvar streams, scaled so that activations stay O(1)
+    through every stage: weights ~ N(0, 1/fan_in) (the prenet's raw weight unit variance: Conv2dLayer applies 1/sqrt(fan_in) itself),
+    biases 0.1 n, LayerNorm / BatchNorm weights 1 + 0.1 n, BN running_var in [0.5, 2].  The q weights and the key half of the kv weights
+    carry `qk_gain`, so that the attention logits reach about +-20 (a peaked softmax, not a uniform one)."""
+    sd = {}
+    for i, (key, shape) in enumerate(secc_backbone_shapes(pncc_cond_mode, out_channels)):
+        st = 1000 + i
+        last = key.rsplit(".", 1)[-1]
+        if key == "prenet.resample_filter":
+            f = np.array([1.0, 3.0, 3.0, 1.0], np.float32)
+            v = np.outer(f, f) / np.float32(64.0)                  # upfirdn2d.setup_filter([1, 3, 3, 1])
+        elif last == "num_batches_tracked":
+            v = np.array(0, dtype=np.int64)
+        elif last == "running_var":
+            v = np.float32(0.5) + np.float32(1.5) * hash_uniform(seed, shape[0], st)
+        elif last in ("bias", "running_mean"):
+            v = hash_unitvar(seed, shape, st) * np.float32(0.1)
+        elif len(shape) == 1:                                        # LayerNorm / BatchNorm weight
+            v = np.float32(1.0) + hash_unitvar(seed, shape, st) * np.float32(0.1)
+        else:
+            fan_in = int(np.prod(shape[1:]))
+            v = hash_unitvar(seed, shape, st) * np.float32(1.0 if key == "prenet.weight" else 1.0 / math.sqrt(fan_in))
+            if key.endswith("attn.q.weight"):
+                v = v * np.float32(qk_gain)
+            elif key.endswith("attn.kv.weight"):
+                v[: shape[0] // 2] *= np.float32(qk_gain)
+        sd[key] = np.asarray(v, dtype=np.int64 if last == "num_batches_tracked" else np.float32)
+    return sd

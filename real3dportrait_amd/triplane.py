@@ -180,7 +180,7 @@ def _reference_hparams(model):
     return hp
 
 
-def patch_model(model, fuse_warp_sr=True, precision=None):
+def patch_model(model, fuse_warp_sr=True, precision=None, secc_encoder=False):
     """Swap the hot-path operators of a constructed reference model for the HIP ones (in place).  INFERENCE ONLY: the HIP modules
     detach their inputs and build no autograd graph (the reference runs this path under torch.no_grad(), real3d_infer.py:435,479).
     precision: SR precision of the installed blocks (None = the library default 'f16mx': inside the 2e-4 of SURVEY 8(d) on every golden and heavy-tail sweep,
@@ -196,6 +196,9 @@ def patch_model(model, fuse_warp_sr=True, precision=None):
       With hparams weight_fuse=False the reference calls block1(x, None, ws) (sr_with_ref.py:161), which the HIP block does not
       cover: block1 is then left untouched.
     * <backbone>.to_plane_cnn (segformer.py:691-700) -> ConvStack.
+    * secc_encoder=True (opt-in): model.secc_img2plane_backbone, when it is the reference's SegFormerSECC2PlaneBackbone in mode b0
+      (segformer.py:672-731), -> the HIP SegFormerSECC2PlaneBackbone (segformer.py of this package: prenet, MiT-b0 and the head in
+      exact fp32, to_plane_cnn as a ConvStack).  Other backbones are left as they are.
     Parameters are copied with strict key matching; the decoder module is left untouched (the renderer reads
     decoder.net[0|2].{weight,bias} directly)."""
     import types
@@ -236,6 +239,12 @@ def patch_model(model, fuse_warp_sr=True, precision=None):
             sr._r3d_reference_forward = sr.forward           # the exact-f32 precision runs the reference forward over the patched sub-modules
             sr.forward = types.MethodType(sr_with_ref.forward_v2, sr)
             sr.split_input_spec = types.MethodType(sr_with_ref.warp_split_input_spec, sr)
+    if secc_encoder:
+        bb = getattr(model, "secc_img2plane_backbone", None)
+        if (type(bb).__name__ == "SegFormerSECC2PlaneBackbone" and not type(bb).__module__.startswith("real3dportrait_amd")
+                and getattr(bb, "mode", None) == "b0"):
+            from .segformer import SegFormerSECC2PlaneBackbone as HipSECC
+            model.secc_img2plane_backbone = HipSECC.from_reference(bb)
     for owner in (getattr(model, "secc_img2plane_backbone", None), getattr(model, "img2plane_backbone", None)):
         _patch_sequential(owner, "to_plane_cnn", dev)       # per-frame plane producer tail (segformer.py:691-700)
     from .superresolution import set_sr_precision

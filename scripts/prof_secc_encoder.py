@@ -1,0 +1,81 @@
+"""Time the per-frame SECC encoder (SegFormerSECC2PlaneBackbone, mode b0) at B = 1, 512^2, cano_src_tgt, and print one JSON
+line: the HIP encoder (prenet + MiT-b0 + head, forward_features) and the HIP backbone including to_plane_cnn, in ms/frame from HIP events
+after warm-up; the same math as eager fp32 torch on the same GPU (tests/segformer_ref64.py in float32, what the reference pays); and the
+encoder's kernel launches per frame (counted at the C entry points).
+    python scripts/prof_secc_encoder.py [iters]"""
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+import segformer_ref64 as R  # noqa: E402
+from real3dportrait_amd import _lib, synth  # noqa: E402
+from real3dportrait_amd.segformer import SegFormerSECC2PlaneBackbone  # noqa: E402
+
+
+def timed(fn, iters, warm=5):
+    for _ in range(warm):
+        fn()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(iters):
+        fn()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b) / iters
+
+
+def count_launches(m, x):
+    """Kernel launches of one forward_features, counted by wrapping the r3d_secc_* entry points (embed1 and a conv with a LayerNorm
+    epilogue are two launches each)."""
+    lib = _lib.load()
+    names = [n for n in _lib.SIGNATURES if n.startswith("r3d_secc_")]
+    orig = {n: getattr(lib, n) for n in names}
+    count = [0]
+
+    def wrap(n, f):
+        def g(*a):
+            count[0] += 2 if n == "r3d_secc_embed1" or (n == "r3d_secc_conv" and a[11] is not None) else 1
+            return f(*a)
+        return g
+
+    for n in names:
+        setattr(lib, n, wrap(n, orig[n]))
+    try:
+        m.forward_features(x)
+    finally:
+        for n in names:
+            setattr(lib, n, orig[n])
+    return count[0]
+
+
+def main():
+    iters = int(sys.argv[1]) if len(sys.argv) > 1 else 50
+    dev = "cuda:0"
+    sd = synth.synth_secc_backbone(11)
+    m = SegFormerSECC2PlaneBackbone()
+    m.load_state_dict({k: torch.from_numpy(np.ascontiguousarray(v)) for k, v in sd.items()}, strict=True)
+    m = m.to(dev).eval()
+    x = (torch.from_numpy(synth.hash_uniform(13, 9 * 512 * 512, stream=5)).view(1, 9, 512, 512) * 2 - 1).to(dev)
+    sd_dev = {k: torch.from_numpy(np.ascontiguousarray(v)).to(dev) for k, v in sd.items()}
+    with torch.no_grad():
+        enc = timed(lambda: m.forward_features(x), iters)
+        full = timed(lambda: m(x), iters)
+        eager = timed(lambda: R.head(sd_dev, R.encoder(sd_dev, x, torch.float32), torch.float32), iters)
+        launches = count_launches(m, x)
+        e = R.head(sd_dev, R.encoder(sd_dev, x, torch.float32), torch.float32)
+        h = m.forward_features(x)
+        diff = float((e - h).abs().max() / e.abs().max())
+    print(json.dumps({"metric": "secc_encoder_b0_512", "B": 1, "H": 512, "W": 512, "hip_encoder_ms": round(enc, 4),
+                      "hip_backbone_with_to_plane_cnn_ms": round(full, 4), "eager_fp32_torch_encoder_ms": round(eager, 4),
+                      "speedup_vs_eager": round(eager / enc, 2), "encoder_launches_per_frame": launches,
+                      "hip_vs_eager_max_rel_diff": diff, "iters": iters}))
+
+
+if __name__ == "__main__":
+    main()

@@ -1,0 +1,212 @@
+"""CPU: the SECC encoder's host side (real3dportrait_amd/segformer.py, r3d_secc_* of include/r3d_hip.h).
+
+The fp64 restatement (tests/segformer_ref64.py) against the reference's goldens, the head fold, argument validation of the C entry points
+(which runs before any HIP call), the patch_model swap and the kernels' scratch use."""
+import ctypes
+import sys
+import types
+
+import numpy as np
+import pytest
+import torch
+
+from conftest import GOLDEN, load_golden
+import segformer_ref64 as R64
+from real3dportrait_amd import synth
+
+
+def secc_input(seed, B, in_dim, H, W):
+    """tests/golden/make_golden_secc.py's input (hash uniform in [-1, 1])."""
+    return synth.hash_uniform(seed, B * in_dim * H * W, stream=5).reshape(B, in_dim, H, W) * np.float32(2.0) - np.float32(1.0)
+
+
+def golden_case(name):
+    g = load_golden(name)
+    sw, sx, B, in_dim, H, W = (int(v) for v in g["spec"])
+    sd = synth.synth_secc_backbone(sw, str(g["mode"]))
+    return g, sd, secc_input(sx, B, in_dim, H, W)
+
+
+def rel(a, ref):
+    a, ref = np.asarray(a, np.float64), np.asarray(ref, np.float64)
+    return float(np.abs(a - ref).max() / np.abs(ref).max())
+
+
+@pytest.mark.parametrize("name", ["secc_a_r64", "secc_b_r64"])
+def test_fp64_restatement_matches_reference_goldens(name):
+    g, sd, x = golden_case(name)
+    feats, head, planes = R64.backbone(sd, torch.from_numpy(x))
+    for i in range(4):
+        assert rel(feats[i].numpy(), g["c%d" % (i + 1)]) <= 1e-5, i
+    assert rel(head.numpy(), g["head"]) <= 1e-5
+    assert rel(planes.numpy(), g["planes"]) <= 1e-5
+
+
+def test_fp64_restatement_matches_512_golden():
+    torch.set_num_threads(8)
+    g, sd, x = golden_case("secc_c_r512")
+    feats = R64.encoder(sd, torch.from_numpy(x))
+    head = R64.head(sd, feats)
+    # at 512^2 the golden's own fp32 rounding (the reference runs in fp32) reaches 3.6e-5 of max|c4| against this fp64 evaluation
+    assert rel(feats[3].numpy(), g["c4"]) <= 1e-4
+    assert rel(head[:, :, ::8, ::8].numpy(), g["head_s8"]) <= 1e-4
+
+
+def test_head_fold_equals_unfolded_head():
+    g, sd, x = golden_case("secc_a_r64")
+    feats = [torch.from_numpy(g["c%d" % i]).double() for i in range(1, 5)]
+    a, b = R64.head(sd, feats), R64.head_folded(sd, feats)
+    assert float((a - b).abs().max()) <= 1e-12 * float(a.abs().max())
+
+
+def test_synth_weights_give_a_peaked_softmax():
+    """The q / k gains of synth_secc_backbone put the stage-1 attention logits around +-20 (the issue's 'peaked, not uniform')."""
+    g, sd, x = golden_case("secc_a_r64")
+    import torch.nn.functional as F
+    t = lambda k: torch.from_numpy(sd[k]).double()
+    xx = torch.from_numpy(x).double()
+    y = F.conv2d(xx, t("prenet.weight") / 3.0, t("prenet.bias"))
+    y = F.conv2d(y, t("mix_vit.patch_embed1.proj.weight"), t("mix_vit.patch_embed1.proj.bias"), stride=4, padding=3)
+    tok = F.layer_norm(y.flatten(2).transpose(1, 2), (32,), t("mix_vit.patch_embed1.norm.weight"), t("mix_vit.patch_embed1.norm.bias"), 1e-5)
+    n = F.layer_norm(tok, (32,), t("mix_vit.block1.0.norm1.weight"), t("mix_vit.block1.0.norm1.bias"), 1e-6)
+    q = n @ t("mix_vit.block1.0.attn.q.weight").T + t("mix_vit.block1.0.attn.q.bias")
+    r = F.conv2d(n.transpose(1, 2).reshape(1, 32, 16, 16), t("mix_vit.block1.0.attn.sr.weight"), t("mix_vit.block1.0.attn.sr.bias"), stride=8)
+    r = F.layer_norm(r.flatten(2).transpose(1, 2), (32,), t("mix_vit.block1.0.attn.norm.weight"), t("mix_vit.block1.0.attn.norm.bias"), 1e-5)
+    k = (r @ t("mix_vit.block1.0.attn.kv.weight").T + t("mix_vit.block1.0.attn.kv.bias"))[..., :32]
+    s = (q @ k.transpose(1, 2)) * 32 ** -0.5
+    assert 8.0 <= float(s.abs().max()) <= 60.0
+
+
+def test_state_dict_keys_match_the_reference_layout():
+    from real3dportrait_amd.segformer import SegFormerSECC2PlaneBackbone
+    for mode in ("cano_src_tgt", "cano_tgt"):
+        m = SegFormerSECC2PlaneBackbone(pncc_cond_mode=mode)
+        ref = synth.secc_backbone_shapes(mode)
+        sd = m.state_dict()
+        assert sorted(sd) == sorted(k for k, _ in ref)
+        for k, shape in ref:
+            assert tuple(sd[k].shape) == tuple(shape), k
+        m.load_state_dict({k: torch.from_numpy(v) for k, v in synth.synth_secc_backbone(3, mode).items()}, strict=True)
+
+
+def test_unsupported_configurations_raise():
+    from real3dportrait_amd.segformer import SegFormerSECC2PlaneBackbone
+    with pytest.raises(NotImplementedError):
+        SegFormerSECC2PlaneBackbone(mode="b3")
+    m = SegFormerSECC2PlaneBackbone()
+    with pytest.raises(NotImplementedError):
+        m._check_input(torch.zeros(1, 9, 80, 64))
+    with pytest.raises(NotImplementedError):
+        m._check_input(torch.zeros(1, 9, 32 * 33, 32 * 32))      # 1056 keys
+
+
+def test_c_entry_points_reject_bad_arguments_without_a_gpu():
+    from real3dportrait_amd import _lib
+    lib = _lib.load()
+    one = ctypes.c_void_p(64)      # never dereferenced: validation fails first
+    rc = lib.r3d_secc_embed1(None, 1, 9, 64, 64, one, one, one, one, one, one, one, None)
+    assert rc == -1 and b"NULL" in lib.r3d_last_error()
+    rc = lib.r3d_secc_embed1(one, 1, 9, 80, 64, one, one, one, one, one, one, one, None)
+    assert rc == -1 and b"multiples of 32" in lib.r3d_last_error()
+    rc = lib.r3d_secc_embed1(one, 1, 9, 32 * 33, 32 * 32, one, one, one, one, one, one, one, None)
+    assert rc == -1 and b"1024" in lib.r3d_last_error()
+    rc = lib.r3d_secc_embed1(one, 1, 7, 64, 64, one, one, one, one, one, one, one, None)
+    assert rc == -1 and b"in_dim" in lib.r3d_last_error()
+    rc = lib.r3d_secc_attention(one, one, 1, 256, 1025, 64, 2, 0.17, one, None)
+    assert rc == -1 and b"1025" in lib.r3d_last_error()
+    rc = lib.r3d_secc_attention(one, one, 1, 256, 256, 64, 1, 0.17, one, None)
+    assert rc == -1 and b"C = 32 heads" in lib.r3d_last_error()
+    rc = lib.r3d_secc_attention(None, one, 1, 256, 256, 64, 2, 0.17, one, None)
+    assert rc == -1 and b"NULL" in lib.r3d_last_error()
+    rc = lib.r3d_secc_head(one, 1, 20, 16, one, one, one, one, one, one, one, one, None)
+    assert rc == -1 and b"multiples of 8" in lib.r3d_last_error()
+    rc = lib.r3d_secc_head(one, 1, 16, 16, None, one, one, one, one, one, one, one, None)
+    assert rc == -1 and b"NULL" in lib.r3d_last_error()
+    rc = lib.r3d_secc_linear(None, 64, 32, None, None, 0.0, one, None, 32, 0, None, one, None)
+    assert rc == -1 and b"NULL" in lib.r3d_last_error()
+    rc = lib.r3d_secc_linear(one, 64, 32, one, None, 1e-6, one, None, 32, 0, None, ctypes.c_void_p(1 << 30), None)
+    assert rc == -1 and b"NULL" in lib.r3d_last_error()      # LayerNorm weight without its bias
+    rc = lib.r3d_secc_linear(one, 64, 32, None, None, 0.0, one, None, 32, 0, None, one, None)
+    assert rc == -1 and b"overlap" in lib.r3d_last_error()
+    rc = lib.r3d_secc_conv(one, 1, 16, 16, 32, one, one, 64, 3, 2, 3, None, None, 0.0, one, None)
+    assert rc == -1 and b"bad argument" in lib.r3d_last_error()
+    rc = lib.r3d_secc_dwconv_gelu(one, 1, 16, 16, 128, one, one, one, None)
+    assert rc == -1 and b"bad argument" in lib.r3d_last_error()      # in place is not supported
+    rc = lib.r3d_secc_layernorm(one, 16, 32, one, one, 0.0, one, None)
+    assert rc == -1 and b"bad argument" in lib.r3d_last_error()
+
+
+def _reference_like_backbone(mode="b0", pncc_cond_mode="cano_src_tgt"):
+    """A CPU stand-in with the reference's class name, attributes and state_dict (the reference module needs timm / mmcv)."""
+    from real3dportrait_amd.segformer import SegFormerSECC2PlaneBackbone as Hip
+    import torch.nn as nn
+
+    class SegFormerSECC2PlaneBackbone(nn.Module):
+        pass
+
+    m = SegFormerSECC2PlaneBackbone()
+    h = Hip(pncc_cond_mode=pncc_cond_mode)
+    for name in ("prenet", "mix_vit", "fuse_head"):
+        setattr(m, name, getattr(h, name))
+    m.to_plane_cnn = nn.Sequential(nn.Conv2d(256, 256, 3, 1, 1), nn.LeakyReLU(0.01, inplace=True), nn.Conv2d(256, 256, 3, 1, 1),
+                                   nn.LeakyReLU(0.01, inplace=True), nn.Conv2d(256, 256, 3, 1, 1), nn.LeakyReLU(0.01, inplace=True),
+                                   nn.UpsamplingBilinear2d(scale_factor=2.0), nn.Conv2d(256, 96, 3, 1, 1))
+    m.mode, m.pncc_cond_mode = mode, pncc_cond_mode
+    m.load_state_dict({k: torch.from_numpy(v) for k, v in synth.synth_secc_backbone(5, pncc_cond_mode).items()}, strict=True)
+    return m
+
+
+def _model_shell(backbone):
+    """The smallest model patch_model accepts (renderer, superresolution, the SECC backbone)."""
+    import torch.nn as nn
+
+    class SR(nn.Module):
+        def __init__(self):
+            super().__init__()
+            self.block0 = nn.Linear(1, 1)
+
+    class Model(nn.Module):
+        def __init__(self):
+            super().__init__()
+            self.renderer = nn.Module()
+            self.superresolution = SR()
+            self.secc_img2plane_backbone = backbone
+
+    return Model()
+
+
+@pytest.mark.parametrize("pncc", ["cano_src_tgt", "cano_tgt"])
+def test_patch_model_swaps_the_reference_backbone_with_identical_keys(pncc):
+    from real3dportrait_amd import patch_model
+    from real3dportrait_amd.segformer import SegFormerSECC2PlaneBackbone as Hip
+    ref = _reference_like_backbone(pncc_cond_mode=pncc)
+    before = {k: v.clone() for k, v in ref.state_dict().items()}
+    model = patch_model(_model_shell(ref), secc_encoder=True)
+    new = model.secc_img2plane_backbone
+    assert isinstance(new, Hip) and new.pncc_cond_mode == pncc
+    sd = new.state_dict()
+    assert sorted(sd) == sorted(before)
+    for k, v in before.items():
+        assert sd[k].dtype == v.dtype and torch.equal(sd[k], v), k
+
+
+def test_patch_model_leaves_the_backbone_without_the_flag_or_outside_b0():
+    from real3dportrait_amd import patch_model
+    from real3dportrait_amd.superresolution import ConvStack
+    ref = _reference_like_backbone()
+    model = patch_model(_model_shell(ref))
+    assert model.secc_img2plane_backbone is ref and isinstance(ref.to_plane_cnn, ConvStack)       # only the existing tail swap
+    ref = _reference_like_backbone(mode="b1")
+    model = patch_model(_model_shell(ref), secc_encoder=True)
+    assert model.secc_img2plane_backbone is ref
+
+
+def test_secc_kernels_do_not_use_scratch():
+    from test_render_kernel_resources import _kernel_metadata
+    from real3dportrait_amd import _lib
+    meta = _kernel_metadata(_lib.LIB_PATH)
+    names = [k for k in meta if "3seg" in k]
+    assert len(names) >= 7, names          # seg_gemm x 4 variants, seg_layernorm, seg_attention, seg_dwconv_gelu
+    for k in names:
+        assert int(meta[k]["private_segment_fixed_size"]) == 0, (k, meta[k])
+        assert int(meta[k]["vgpr_spill_count"]) == 0, (k, meta[k])
