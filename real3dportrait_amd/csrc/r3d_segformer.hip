@@ -8,7 +8,7 @@
 //                          input, k = (ky, kx, ci)),  PRENET  (stage 1: the 7x7/s4 conv whose taps are the prenet's 1x1 conv of the raw
 //                          NCHW image, zero outside the image).  Epilogue: + bias, exact GELU, + residual;  HEAD: + bilinear samples of
 //                          the three folded low-resolution maps + constant, BatchNorm scale/shift, ReLU, NCHW store.
-//   seg_layernorm          one wave per token row, two-pass statistics.
+//   seg_layernorm          one wave per token row, two-pass statistics of the row shifted by its first entry.
 //   seg_attention          one block per (batch, head, 64 queries): keys / values staged in LDS 64 at a time, S = QK^T and O = PV on the
 //                          MFMA, online max-subtracted softmax (d = 32 for every MiT-b0 stage).
 //   seg_dwconv_gelu        depthwise 3x3 + bias + exact GELU on [B, H, W, C].
@@ -42,12 +42,12 @@ __device__ __forceinline__ float gelu_erf(float v) { return 0.5f * v * (1.0f + e
 
 // one element of A (zero outside [M, K] and outside the zero-padded input)
 template <int AMODE>
-__device__ __forceinline__ float load_a(const GemmArgs& g, int m, int k, float mu, float rs)
+__device__ __forceinline__ float load_a(const GemmArgs& g, int m, int k, float sh, float mu, float rs)
 {
     if (m >= g.M || k >= g.K) return 0.0f;
     if (AMODE == A_ROW) {
         float v = g.a[(size_t)m * g.lda + k];
-        if (g.ln_g) v = (v - mu) * rs * g.ln_g[k] + g.ln_b[k];
+        if (g.ln_g) v = ((v - sh) - mu) * rs * g.ln_g[k] + g.ln_b[k];
         return v;
     } else {
         const int hw = g.Ho * g.Wo, b = m / hw, r = m - b * hw, oy = r / g.Wo, ox = r - oy * g.Wo;
@@ -83,25 +83,28 @@ __global__ void __launch_bounds__(256) seg_gemm(GemmArgs g)
 {
     __shared__ float As[BK * LDA];
     __shared__ float Ws[BK * LDW];
-    __shared__ float s_mu[BM], s_rs[BM];
+    __shared__ float s_sh[BM], s_mu[BM], s_rs[BM];
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int m0 = blockIdx.x * BM, n0 = blockIdx.y * BN;
     const int lr = t >> 2, lk = (t & 3) * 4;          // loader: row / column lr of the tile, k entries lk .. lk + 3
 
-    float mu = 0.0f, rs = 0.0f;
+    float sh = 0.0f, mu = 0.0f, rs = 0.0f;
     if (AMODE == A_ROW && g.ln_g) {
-        // statistics of row m0 + lr by the 4 lanes t & ~3 (two passes: mean, then the mean squared deviation)
+        // statistics of row m0 + lr by the 4 lanes t & ~3, as seg_layernorm: shifted by the row's first entry x0, two passes (the mean of
+        // x - x0, then the mean squared deviation)
         const int m = m0 + lr;
+        const float* row = g.a + (size_t)m * g.lda;
+        const float x0 = m < g.M ? row[0] : 0.0f;
         float s = 0.0f;
-        if (m < g.M) for (int k = t & 3; k < g.K; k += 4) s += g.a[(size_t)m * g.lda + k];
+        if (m < g.M) for (int k = t & 3; k < g.K; k += 4) s += row[k] - x0;
         s += __shfl_xor(s, 1); s += __shfl_xor(s, 2);
         const float mean = s / (float)g.K;
         float q = 0.0f;
-        if (m < g.M) for (int k = t & 3; k < g.K; k += 4) { const float d = g.a[(size_t)m * g.lda + k] - mean; q = fmaf(d, d, q); }
+        if (m < g.M) for (int k = t & 3; k < g.K; k += 4) { const float d = (row[k] - x0) - mean; q = fmaf(d, d, q); }
         q += __shfl_xor(q, 1); q += __shfl_xor(q, 2);
-        if ((t & 3) == 0) { s_mu[lr] = mean; s_rs[lr] = 1.0f / sqrtf(q / (float)g.K + g.ln_eps); }
+        if ((t & 3) == 0) { s_sh[lr] = x0; s_mu[lr] = mean; s_rs[lr] = 1.0f / sqrtf(q / (float)g.K + g.ln_eps); }
         __syncthreads();
-        mu = s_mu[lr]; rs = s_rs[lr];
+        sh = s_sh[lr]; mu = s_mu[lr]; rs = s_rs[lr];
     }
 
     const int wm = (wave >> 1) * 32, wn = (wave & 1) * 32;     // the wave's 32 x 32 sub-tile: 2 x 2 MFMA tiles of 16 x 16
@@ -115,7 +118,7 @@ __global__ void __launch_bounds__(256) seg_gemm(GemmArgs g)
         float av[4], wv[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            av[j] = load_a<AMODE>(g, m0 + lr, k0 + lk + j, mu, rs);
+            av[j] = load_a<AMODE>(g, m0 + lr, k0 + lk + j, sh, mu, rs);
             const int n = n0 + lr, k = k0 + lk + j;
             wv[j] = (n < g.N && k < g.K) ? g.w[(size_t)n * g.K + k] : 0.0f;
         }
@@ -165,23 +168,26 @@ __global__ void __launch_bounds__(256) seg_gemm(GemmArgs g)
             }
 }
 
-// nn.LayerNorm over the C entries of each of M rows; one wave per row
+// nn.LayerNorm over the C entries of each of M rows; one wave per row.  The statistics are those of the row shifted by its first entry x0
+// (x - x0 is exact for entries within a factor 2 of x0): a constant row normalises to exactly 0, and a row whose mean is large next to its
+// spread keeps the accuracy of its deviations (an unshifted fp32 mean of such a row is off by a rounding of the mean itself).
 __global__ void __launch_bounds__(256) seg_layernorm(const float* x, int M, int C, const float* gam, const float* bet, float eps, float* y)
 {
     const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= M) return;
     const float* xr = x + (size_t)row * C;
+    const float x0 = xr[0];
     float s = 0.0f;
-    for (int c = lane; c < C; c += 64) s += xr[c];
+    for (int c = lane; c < C; c += 64) s += xr[c] - x0;
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) s += __shfl_xor(s, o);
-    const float mean = s / (float)C;
+    const float mean = s / (float)C;          // of x - x0
     float q = 0.0f;
-    for (int c = lane; c < C; c += 64) { const float d = xr[c] - mean; q = fmaf(d, d, q); }
+    for (int c = lane; c < C; c += 64) { const float d = (xr[c] - x0) - mean; q = fmaf(d, d, q); }
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) q += __shfl_xor(q, o);
     const float rs = 1.0f / sqrtf(q / (float)C + eps);
-    for (int c = lane; c < C; c += 64) y[(size_t)row * C + c] = (xr[c] - mean) * rs * gam[c] + bet[c];
+    for (int c = lane; c < C; c += 64) y[(size_t)row * C + c] = ((xr[c] - x0) - mean) * rs * gam[c] + bet[c];
 }
 
 // depthwise 3x3 (padding 1, bias) + exact GELU on [B, H, W, C] (DWConv, segformer.py:394-404; Mlp.act, :92)
@@ -323,6 +329,9 @@ static int launch_layernorm(const float* x, int M, int C, const float* gam, cons
 using namespace r3d;
 using namespace r3d::seg;
 
+// [a, a + na) and [b, b + nb) (counts of floats) share an element
+static bool overlap(const float* a, size_t na, const float* b, size_t nb) { return a < b + nb && b < a + na; }
+
 extern "C" int r3d_secc_embed1(const float* x, int B, int in_dim, int H, int W, const float* prenet_w, const float* prenet_b,
                                const float* w, const float* bias, const float* ln_g, const float* ln_b, float* y, r3d_stream_t stream)
 {
@@ -330,6 +339,7 @@ extern "C" int r3d_secc_embed1(const float* x, int B, int in_dim, int H, int W, 
     if (B <= 0 || (in_dim != 6 && in_dim != 9)) { set_error("secc_embed1: bad argument (B > 0, in_dim 6 or 9)"); return R3D_ERR_INVALID_ARG; }
     if (H <= 0 || W <= 0 || H % 32 || W % 32) { set_error("secc_embed1: H and W must be positive multiples of 32"); return R3D_ERR_INVALID_ARG; }
     if ((size_t)(H / 32) * (W / 32) > 1024) { set_error("secc_embed1: L = (H/32)(W/32) > 1024 keys"); return R3D_ERR_INVALID_ARG; }
+    if (overlap(x, (size_t)B * in_dim * H * W, y, (size_t)B * (H / 4) * (W / 4) * 32)) { set_error("secc_embed1: x and y overlap"); return R3D_ERR_INVALID_ARG; }
     hipStream_t st = (hipStream_t)stream;
     GemmArgs g = {};
     g.a = x; g.Hin = H; g.Win = W; g.Cin = 3; g.Ho = H / 4; g.Wo = W / 4; g.ks = 7; g.stride = 4; g.pad = 3;
@@ -346,8 +356,10 @@ extern "C" int r3d_secc_conv(const float* x, int B, int Hin, int Win, int Cin, c
     if (!x || !w || !bias || !y || (!ln_g) != (!ln_b)) { set_error("secc_conv: NULL pointer"); return R3D_ERR_INVALID_ARG; }
     if (B <= 0 || Hin <= 0 || Win <= 0 || Cin <= 0 || Cout <= 0 || ksize <= 0 || stride <= 0 || pad < 0 || pad >= ksize ||
         Cout > 1024 || Cin > 1024 || ksize > 8) { set_error("secc_conv: bad argument"); return R3D_ERR_INVALID_ARG; }
+    // the padded input holds at least one window (C division truncates: without this, -stride < Hin + 2 pad - ksize < 0 gave Ho = 1)
+    if (Hin + 2 * pad < ksize || Win + 2 * pad < ksize) { set_error("secc_conv: empty output (Hin or Win + 2 pad < ksize)"); return R3D_ERR_INVALID_ARG; }
     const int Ho = (Hin + 2 * pad - ksize) / stride + 1, Wo = (Win + 2 * pad - ksize) / stride + 1;
-    if (Ho <= 0 || Wo <= 0) { set_error("secc_conv: empty output"); return R3D_ERR_INVALID_ARG; }
+    if (overlap(x, (size_t)B * Hin * Win * Cin, y, (size_t)B * Ho * Wo * Cout)) { set_error("secc_conv: x and y overlap"); return R3D_ERR_INVALID_ARG; }
     hipStream_t st = (hipStream_t)stream;
     GemmArgs g = {};
     g.a = x; g.Hin = Hin; g.Win = Win; g.Cin = Cin; g.Ho = Ho; g.Wo = Wo; g.ks = ksize; g.stride = stride; g.pad = pad;
@@ -374,6 +386,7 @@ extern "C" int r3d_secc_layernorm(const float* x, int M, int C, const float* ln_
 {
     if (!x || !ln_g || !ln_b || !y) { set_error("secc_layernorm: NULL pointer"); return R3D_ERR_INVALID_ARG; }
     if (M <= 0 || C <= 0 || !(eps > 0.0f)) { set_error("secc_layernorm: bad argument"); return R3D_ERR_INVALID_ARG; }
+    if (x != y && overlap(x, (size_t)M * C, y, (size_t)M * C)) { set_error("secc_layernorm: x and y overlap (y may be x itself)"); return R3D_ERR_INVALID_ARG; }
     return launch_layernorm(x, M, C, ln_g, ln_b, eps, y, (hipStream_t)stream);
 }
 
@@ -383,6 +396,9 @@ extern "C" int r3d_secc_attention(const float* q, const float* kv, int B, int N,
     if (!q || !kv || !out) { set_error("secc_attention: NULL pointer"); return R3D_ERR_INVALID_ARG; }
     if (B <= 0 || N <= 0 || heads <= 0 || C != 32 * heads) { set_error("secc_attention: bad argument (C = 32 heads)"); return R3D_ERR_INVALID_ARG; }
     if (L <= 0 || L > 1024) { set_error("secc_attention: L = %d keys outside 1 .. 1024", L); return R3D_ERR_INVALID_ARG; }
+    const size_t nout = (size_t)B * N * C;
+    if (overlap(out, nout, kv, (size_t)B * L * 2 * C) || (out != q && overlap(out, nout, q, nout)))
+        { set_error("secc_attention: out overlaps kv, or q without being q"); return R3D_ERR_INVALID_ARG; }
     hipLaunchKernelGGL(seg_attention, dim3((N + AQ - 1) / AQ, heads, B), dim3(256), 0, (hipStream_t)stream, q, kv, N, L, C, scale, out);
     return check_launch("secc_attention");
 }
@@ -390,8 +406,9 @@ extern "C" int r3d_secc_attention(const float* q, const float* kv, int B, int N,
 extern "C" int r3d_secc_dwconv_gelu(const float* x, int B, int H, int W, int C, const float* w, const float* bias, float* y, r3d_stream_t stream)
 {
     if (!x || !w || !bias || !y) { set_error("secc_dwconv_gelu: NULL pointer"); return R3D_ERR_INVALID_ARG; }
-    if (B <= 0 || H <= 0 || W <= 0 || C <= 0 || x == y) { set_error("secc_dwconv_gelu: bad argument"); return R3D_ERR_INVALID_ARG; }
+    if (B <= 0 || H <= 0 || W <= 0 || C <= 0) { set_error("secc_dwconv_gelu: bad argument"); return R3D_ERR_INVALID_ARG; }
     const size_t total = (size_t)B * H * W * C;
+    if (overlap(x, total, y, total)) { set_error("secc_dwconv_gelu: bad argument (x and y overlap)"); return R3D_ERR_INVALID_ARG; }
     hipLaunchKernelGGL(seg_dwconv_gelu, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, B, H, W, C, w, bias, y);
     return check_launch("secc_dwconv_gelu");
 }
@@ -401,6 +418,11 @@ extern "C" int r3d_secc_head(const float* c1, int B, int H1, int W1, const float
 {
     if (!c1 || !w1f || !f2 || !f3 || !f4 || !hconst || !bn_scale || !bn_shift || !out) { set_error("secc_head: NULL pointer"); return R3D_ERR_INVALID_ARG; }
     if (B <= 0 || H1 <= 0 || W1 <= 0 || H1 % 8 || W1 % 8) { set_error("secc_head: H1, W1 (= H/4, W/4) must be positive multiples of 8"); return R3D_ERR_INVALID_ARG; }
+    const size_t hw = (size_t)H1 * W1, nout = (size_t)B * 256 * hw;
+    if (overlap(out, nout, c1, (size_t)B * hw * 32) || overlap(out, nout, f2, (size_t)B * hw / 4 * 256) ||
+        overlap(out, nout, f3, (size_t)B * hw / 16 * 256) || overlap(out, nout, f4, (size_t)B * hw / 64 * 256) ||
+        overlap(out, nout, w1f, 256 * 32) || overlap(out, nout, hconst, 256) || overlap(out, nout, bn_scale, 256) ||
+        overlap(out, nout, bn_shift, 256)) { set_error("secc_head: out overlaps an input"); return R3D_ERR_INVALID_ARG; }
     GemmArgs g = {};
     g.a = c1; g.M = B * H1 * W1; g.K = 32; g.lda = 32; g.w = w1f; g.N = 256;
     g.f2 = f2; g.f3 = f3; g.f4 = f4; g.hconst = hconst; g.bn_s = bn_scale; g.bn_t = bn_shift; g.H1 = H1; g.W1 = W1; g.y = out;

@@ -117,6 +117,15 @@ def main():
     np.savez_compressed(os.path.join(HERE, "secc_c_r512.npz"), spec=np.array([SEED_W, SEED_X + 1, 1, 9, 512, 512], np.int64),
                         mode=np.array("cano_src_tgt"), c4=feats[3].numpy(), head_s8=head[:, :, ::8, ::8].numpy())
     print("secc_c_r512: max|c4| %.3g max|head| %.3g" % (float(feats[3].abs().max()), float(head.abs().max())))
+    # non-square (H 288, W 256): L = 9 x 8 = 72 keys (one full chunk of 64 plus 8), 72 stage-4 queries, a 72 x 64 head; subsampled to stay
+    # under 1 MB
+    x = secc_input(SEED_X + 2, 1, 9, 288, 256)
+    feats, head, planes = run(m, x)
+    np.savez_compressed(os.path.join(HERE, "secc_d_r288x256.npz"), spec=np.array([SEED_W, SEED_X + 2, 1, 9, 288, 256], np.int64),
+                        mode=np.array("cano_src_tgt"), c1_s2=feats[0][..., ::2, ::2].numpy(), c2=feats[1].numpy(), c3=feats[2].numpy(),
+                        c4=feats[3].numpy(), head_s8=head[..., ::8, ::8].numpy(), planes_s8=planes[..., ::8, ::8].numpy())
+    print("secc_d_r288x256: max|c4| %.3g max|head| %.3g max|planes| %.3g" % (float(feats[3].abs().max()), float(head.abs().max()),
+                                                                            float(planes.abs().max())))
 
 
 if __name__ == "__main__":

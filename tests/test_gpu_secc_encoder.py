@@ -52,6 +52,52 @@ def test_512_against_fp64_and_golden_subset():
     assert all(e <= TOL for e in errs.values()), errs
 
 
+@pytest.mark.parametrize("B,H,W", [(2, 32, 32), (1, 32, 1024), (1, 1024, 32), (1, 1024, 1024)])
+def test_sizes_at_the_edges_against_fp64(B, H, W):
+    """32^2 (every L = 1, stage 4 is 1 x 1), a 1 x 32 and a 32 x 1 grid of keys, and 1024^2 (L = 1024, the key limit); the planes
+    except at 1024^2 (the fp64 to_plane_cnn costs too much there)."""
+    sd = synth.synth_secc_backbone(51)
+    m = hip_backbone(sd)
+    x = torch.from_numpy(secc_input(52, B, 9, H, W)).to(DEV)
+    feats = m.forward_stages(x)
+    head = m.forward_features(x)
+    ref = R64.encoder(sd, x.double())
+    href = R64.head(sd, ref)
+    errs = {"c%d" % (i + 1): rel(feats[i].cpu().numpy(), ref[i].cpu().numpy()) for i in range(4)}
+    errs["head"] = rel(head.cpu().numpy(), href.cpu().numpy())
+    if H * W < 1024 * 1024:
+        errs["planes"] = rel(m(x).cpu().numpy(), R64.flip_planes(R64.to_plane_cnn(sd, href)).cpu().numpy())
+    print("%dx%dx%d:" % (B, H, W), errs)
+    assert all(e <= TOL for e in errs.values()), errs
+
+
+def test_non_square_golden():
+    g, sd, x = golden_case("secc_d_r288x256")
+    m = hip_backbone(sd, str(g["mode"]))
+    xt = torch.from_numpy(x).to(DEV)
+    feats = m.forward_stages(xt)
+    errs = {"c1_s2": rel(feats[0][..., ::2, ::2].cpu().numpy(), g["c1_s2"])}
+    for i in (2, 3, 4):
+        errs["c%d" % i] = rel(feats[i - 1].cpu().numpy(), g["c%d" % i])
+    errs["head_s8"] = rel(m.forward_features(xt)[..., ::8, ::8].cpu().numpy(), g["head_s8"])
+    errs["planes_s8"] = rel(m(xt)[..., ::8, ::8].cpu().numpy(), g["planes_s8"])
+    print("288x256:", errs)
+    assert all(e <= TOL for e in errs.values()), errs
+
+
+def test_batch_of_three_at_a_ragged_non_square_size_equals_single_calls():
+    """160 x 96: 15 keys at stage 1, 240 stage-2 tokens per sample (its 64-row tiles straddle samples)."""
+    sd = synth.synth_secc_backbone(61)
+    m = hip_backbone(sd)
+    x = torch.from_numpy(secc_input(62, 3, 9, 160, 96)).to(DEV)
+    feats, head = m.forward_stages(x), m.forward_features(x)
+    for i in range(3):
+        xi = x[i:i + 1].contiguous()
+        fi, hi = m.forward_stages(xi), m.forward_features(xi)
+        assert all(torch.equal(a[i:i + 1], b) for a, b in zip(feats, fi)), i
+        assert torch.equal(head[i:i + 1], hi), i
+
+
 def test_batch_repeat_and_side_stream_are_bit_identical():
     sd = synth.synth_secc_backbone(21)
     m = hip_backbone(sd)

@@ -52,6 +52,18 @@ def test_fp64_restatement_matches_512_golden():
     assert rel(head[:, :, ::8, ::8].numpy(), g["head_s8"]) <= 1e-4
 
 
+def test_fp64_restatement_matches_non_square_golden():
+    """288 x 256 (H != W): an H / W swap in the token reshape, the SR-conv grid or the head's resize would show here."""
+    torch.set_num_threads(8)
+    g, sd, x = golden_case("secc_d_r288x256")
+    feats, head, planes = R64.backbone(sd, torch.from_numpy(x))
+    errs = {"c1_s2": rel(feats[0][..., ::2, ::2].numpy(), g["c1_s2"]), "head_s8": rel(head[..., ::8, ::8].numpy(), g["head_s8"]),
+            "planes_s8": rel(planes[..., ::8, ::8].numpy(), g["planes_s8"])}
+    for i in (2, 3, 4):
+        errs["c%d" % i] = rel(feats[i - 1].numpy(), g["c%d" % i])
+    assert all(e <= 1e-4 for e in errs.values()), errs         # the golden's own fp32 rounding, as at 512^2
+
+
 def test_head_fold_equals_unfolded_head():
     g, sd, x = golden_case("secc_a_r64")
     feats = [torch.from_numpy(g["c%d" % i]).double() for i in range(1, 5)]
@@ -134,6 +146,49 @@ def test_c_entry_points_reject_bad_arguments_without_a_gpu():
     assert rc == -1 and b"bad argument" in lib.r3d_last_error()      # in place is not supported
     rc = lib.r3d_secc_layernorm(one, 16, 32, one, one, 0.0, one, None)
     assert rc == -1 and b"bad argument" in lib.r3d_last_error()
+    rc = lib.r3d_secc_conv(one, 1, 1, 1, 3, one, one, 17, 4, 2, 1, None, None, 0.0, ctypes.c_void_p(1 << 30), None)
+    assert rc == -1 and b"empty output" in lib.r3d_last_error()      # 1 + 2 - 4 < 0: nn.Conv2d has no output either
+
+
+def test_c_entry_points_reject_racing_overlaps_without_a_gpu():
+    """Outputs that overlap an input the same launch still reads (include/r3d_hip.h states each rule); addresses in floats."""
+    from real3dportrait_amd import _lib
+    lib = _lib.load()
+    at = lambda i: ctypes.c_void_p(4 * (1 << 20) + 4 * i)       # never dereferenced: validation fails first
+    w = ctypes.c_void_p(1 << 40)
+    # conv: x [1, 16, 16, 32] = 8192 floats, y [1, 8, 8, 64] = 4096
+    rc = lib.r3d_secc_conv(at(0), 1, 16, 16, 32, w, w, 64, 3, 2, 1, None, None, 0.0, at(8191), None)
+    assert rc == -1 and b"overlap" in lib.r3d_last_error()
+    rc = lib.r3d_secc_conv(at(4096), 1, 16, 16, 32, w, w, 64, 3, 2, 1, None, None, 0.0, at(1), None)
+    assert rc == -1 and b"overlap" in lib.r3d_last_error()
+    # embed1: x [1, 9, 64, 64] = 36864 floats, y [1, 16, 16, 32] = 8192
+    rc = lib.r3d_secc_embed1(at(0), 1, 9, 64, 64, w, w, w, w, w, w, at(36863), None)
+    assert rc == -1 and b"overlap" in lib.r3d_last_error()
+    rc = lib.r3d_secc_embed1(at(8191), 1, 9, 64, 64, w, w, w, w, w, w, at(0), None)
+    assert rc == -1 and b"overlap" in lib.r3d_last_error()
+    # attention: q / out [1, 64, 64] = 4096 floats, kv [1, 16, 128] = 2048
+    rc = lib.r3d_secc_attention(at(0), at(10000), 1, 64, 16, 64, 2, 0.17, at(12047), None)
+    assert rc == -1 and b"overlap" in lib.r3d_last_error()
+    rc = lib.r3d_secc_attention(at(0), at(10000), 1, 64, 16, 64, 2, 0.17, at(5905), None)
+    assert rc == -1 and b"overlap" in lib.r3d_last_error()
+    rc = lib.r3d_secc_attention(at(0), at(10000), 1, 64, 16, 64, 2, 0.17, at(32), None)
+    assert rc == -1 and b"overlap" in lib.r3d_last_error()      # out overlaps q without being q
+    # dwconv: [1, 4, 4, 128] = 2048 floats, any overlap
+    rc = lib.r3d_secc_dwconv_gelu(at(0), 1, 4, 4, 128, w, w, at(2047), None)
+    assert rc == -1 and b"overlap" in lib.r3d_last_error()
+    rc = lib.r3d_secc_dwconv_gelu(at(128), 1, 4, 4, 128, w, w, at(0), None)
+    assert rc == -1 and b"overlap" in lib.r3d_last_error()
+    # layernorm: partial overlap (y == x is in place and allowed)
+    rc = lib.r3d_secc_layernorm(at(0), 16, 32, w, w, 1e-5, at(32), None)
+    assert rc == -1 and b"overlap" in lib.r3d_last_error()
+    # head: out [1, 256, 8, 8] = 16384 floats; c1 2048, f2 4096, f3 1024, f4 256
+    ins = [at(100000), at(200000), at(300000), at(400000), at(500000)]      # c1, f2, f3, f4, w1f
+    for j in range(5):
+        args = list(ins)
+        args[j] = at(16383) if j % 2 else at(-100)
+        c1, f2, f3, f4, w1f = args
+        rc = lib.r3d_secc_head(c1, 1, 8, 8, w1f, f2, f3, f4, w, w, w, at(0), None)
+        assert rc == -1 and b"overlap" in lib.r3d_last_error(), j
 
 
 def _reference_like_backbone(mode="b0", pncc_cond_mode="cano_src_tgt"):
