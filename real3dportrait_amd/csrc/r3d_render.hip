@@ -17,7 +17,6 @@
 //
 // Behaviour restated from (upstream repo paths): modules/eg3ds/volumetric_rendering/renderer.py:118-297,
 // ray_marcher.py:25-57, math_utils.py:46-118, ray_sampler.py:24-63, modules/eg3ds/models/triplane.py:177-189.
-#include <stdlib.h>
 
 #include "r3d_common.h"
 #include "r3d_stamps.h"
@@ -28,15 +27,6 @@ static constexpr int kC = R3D_FEATURES;      // 32
 static constexpr int kHid = R3D_HIDDEN;      // 64
 static constexpr int kOut = R3D_DECODER_OUT; // 33
 static constexpr int kWavesPerBlock = 4;
-#ifndef R3D_RENDER_BIG_OCC_DEFAULT
-#define R3D_RENDER_BIG_OCC_DEFAULT 2
-#endif
-#ifndef R3D_RENDER_GPARK_ALL
-#define R3D_RENDER_GPARK_ALL 0   // experiment switch: 1 = every shape with a fine pass parks its colours in the workspace (no LDS parking: 45 KB blocks)
-#endif
-#ifndef R3D_RENDER_GPARK
-#define R3D_RENDER_GPARK 1       // experiment switch: 0 = the big shapes leave their coarse colours to the register allocator (round 4)
-#endif
 
 // -------------------------------------------------------------------------------------------------
 // layout kernel: NCHW [N*3][C][H*W] (+ optional add, optionally flipped along H / W per plane) -> [N*3][H*W][C]
@@ -395,18 +385,13 @@ __device__ __forceinline__ void split8_bounded(const float (&x)[8], h8& hi, h8& 
 // hi*hi + hi*lo + lo*hi accumulated in fp32; same scheme and probe as csrc/r3d_sr_f16x3.hip): K = 32 per MFMA, so
 // layer 1 (32 channels) is one k-step and layer 2 (64 hidden) two -> 24 MFMAs per 16-sample tile instead of 64
 // v_mfma_f32_16x16x4_f32 at half the issue cost each.
-#ifndef R3D_RAY_L2_F32
-#define R3D_RAY_L2_F32 0       // experiment (round 6): layer 2 on v_mfma_f32_16x16x4_f32 -- no hi/lo split of the 64 hidden values, 32 MFMAs of 32 cycles instead of 12 of 16
-#endif
+// (Layer 2 on v_mfma_f32_16x16x4_f32 -- no hi/lo split of the 64 hidden values, 32 MFMAs of 32 cycles instead of 12 of 16 -- measured +11 % per launch:
+// DESIGN "Retired experiment switches".)
 struct DecoderLds {
     uint4 w1f[4][2][64];       // [mt][hi|lo][lane]    A frag: W1'[16mt+(l&15)][8(l>>4)+j], j = 0..7
-#if R3D_RAY_L2_F32
-    float4 w2g[2][4][64];      // [ot][mt][lane]       A values of the four K = 4 steps r = 0..3 of hidden tile mt: W2'[1+16ot+(l&15)][16mt + 4(l>>4) + r]
-#else
     uint4 w2f[2][2][2][64];    // [ot][p][hi|lo][lane] A frag: W2'[1+16ot+(l&15)][u(p, l>>4, j)],
                                //   u(p,q,j) = 16(2p + (j>>2)) + 4q + (j&3): the hidden unit that accumulator register
                                //   (mt = 2p + (j>>2), reg = j&3) of k-slot q holds after layer 1
-#endif
     float w2s[kHid];           // W2'[0][:]  (density row, evaluated on the VALU)
     float b1[kHid];
     float b2[kOut];            // b2[0] density bias, b2[1..32] colour biases (times 2^-d, see DecFold)
@@ -435,13 +420,6 @@ __device__ __forceinline__ void stage_decoder(DecoderLds& L, const float* __rest
         h8 hi, lo; split8(v, hi, lo);
         L.w1f[mt][0][l] = *reinterpret_cast<uint4*>(&hi); L.w1f[mt][1][l] = *reinterpret_cast<uint4*>(&lo);
     }
-#if R3D_RAY_L2_F32
-    for (int i = threadIdx.x; i < 2 * 4 * 64; i += blockDim.x) {
-        const int l = i & 63, mt = (i >> 6) & 3, ot = i >> 8;
-        const float* r = w2 + (1 + 16 * ot + (l & 15)) * kHid + 16 * mt + 4 * (l >> 4);
-        L.w2g[ot][mt][l] = make_float4(r[0] * g2c, r[1] * g2c, r[2] * g2c, r[3] * g2c);
-    }
-#else
     for (int i = threadIdx.x; i < 2 * 2 * 64; i += blockDim.x) {
         const int l = i & 63, pp = (i >> 6) & 1, ot = i >> 7;
         float v[8];
@@ -451,7 +429,6 @@ __device__ __forceinline__ void stage_decoder(DecoderLds& L, const float* __rest
         h8 hi, lo; split8(v, hi, lo);
         L.w2f[ot][pp][0][l] = *reinterpret_cast<uint4*>(&hi); L.w2f[ot][pp][1][l] = *reinterpret_cast<uint4*>(&lo);
     }
-#endif
     for (int i = threadIdx.x; i < kHid; i += blockDim.x) { L.w2s[i] = w2[i] * (g2 * kLn2); L.b1[i] = b1[i] * kLog2e; }
     for (int i = threadIdx.x; i < kOut; i += blockDim.x) L.b2[i] = i == 0 ? b2[i] : b2[i] * kLog2e * F.b2s;
     if (threadIdx.x == 0) { L.xs3 = F.xs * (1.0f / 3.0f); L.hs = F.hs; L.ys = F.ys; }
@@ -660,20 +637,6 @@ __device__ __forceinline__ void decode_l2(const DecoderLds& L, int lane, const D
             col[ot][2] = L.b2[1 + 16 * ot + 4 * q + 2]; col[ot][3] = L.b2[1 + 16 * ot + 4 * q + 3];
         }
     }
-#if R3D_RAY_L2_F32
-    // K = 4 per MFMA: step (mt, r) multiplies hidden units 16 mt + 4 q + r (k-slot q = this lane's accumulator register r of tile mt) -- the fp32 values as they are;
-    // the two colour tiles alternate so that a dependent accumulate is two issue slots away
-#pragma unroll
-    for (int mt = 2 * PP; mt < 2 * PP + 2; ++mt) {
-        const float4 a0 = L.w2g[0][mt][lane], a1 = L.w2g[1][mt][lane];
-        const float A0[4] = {a0.x, a0.y, a0.z, a0.w}, A1[4] = {a1.x, a1.y, a1.z, a1.w};
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            col[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(A0[r], S.h[mt][r], col[0], 0, 0, 0);
-            col[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(A1[r], S.h[mt][r], col[1], 0, 0, 0);
-        }
-    }
-#else
     const float hv[8] = {S.h[2 * PP][0], S.h[2 * PP][1], S.h[2 * PP][2], S.h[2 * PP][3],
                          S.h[2 * PP + 1][0], S.h[2 * PP + 1][1], S.h[2 * PP + 1][2], S.h[2 * PP + 1][3]};
     h8 bh, bl;
@@ -686,7 +649,6 @@ __device__ __forceinline__ void decode_l2(const DecoderLds& L, int lane, const D
         col[ot] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, bl, col[ot], 0, 0, 0);
         col[ot] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, bh, col[ot], 0, 0, 0);
     }
-#endif
     if (PP == 1) {
         const float ys = L.ys;
         if (ys != 1.0f) {
@@ -1057,11 +1019,11 @@ __global__ __launch_bounds__(256, OCC) void render_kernel(RenderArgs a, int R)
     // The coarse pass's colours (8 registers per tile) wait in LDS while the fine pass runs: they are only needed again for the composite,
     // and the fine pass (its own colours + the gather pipeline's load buffers) is where the register file runs out (REF shape: 256 VGPRs and
     // spills to scratch, whose loads share vmcnt with the gather).  6 KB per wave; only for shapes whose block stays under 80 KB of LDS.
-    constexpr bool PARK = NTF > 0 && NTC <= 3 && !R3D_RENDER_GPARK_ALL;
+    constexpr bool PARK = NTF > 0 && NTC <= 3;
     // Round 5: the bigger shapes park ALL colours of a ray -- coarse and fine, tile by tile as the decode produces them -- in the workspace (2 (NTC +
     // NTF) KB per wave, each 16 B per lane written once and read once per ray, served by L2) instead of leaving 96 live registers to the allocator
     // (built without packed-f32 instructions <6,6> spilled 131 registers and BASELINE config 5's render took 15.0 instead of 12.5 ms).
-    constexpr bool GPARK = NTF > 0 && ((NTC > 3 && R3D_RENDER_GPARK) || R3D_RENDER_GPARK_ALL);
+    constexpr bool GPARK = NTF > 0 && NTC > 3;
     __shared__ __attribute__((aligned(16))) f32x4 park[PARK ? kWavesPerBlock : 1][PARK ? 2 * NTC : 1][64];
 
     stage_decoder(dec, a.w1, a.b1, a.w2, a.b2, a.fold);
@@ -1511,10 +1473,7 @@ __global__ __launch_bounds__(256, 2) void run_model_kernel(const float4* __restr
 static inline size_t render_state_bytes(size_t nrays) { return ((kStateHeader + 3 * ((nrays + kLimitsBlock - 1) / kLimitsBlock)) * sizeof(int) + 63) & ~(size_t)63; }
 // decoder fold record (64 bytes) + room for the partials of plane_absmax_kernel (when the caller passes none)
 static constexpr size_t kFoldBytes = 64 + kAbsmaxBlocks * sizeof(float);
-#ifndef R3D_RENDER_GRID
-#define R3D_RENDER_GRID 512         // blocks of a render launch: 2 per CU (experiment builds with 3 waves per SIMD: 768)
-#endif
-static constexpr int kMaxGrid = R3D_RENDER_GRID;
+static constexpr int kMaxGrid = 512;          // blocks of a render launch: 2 per CU
 
 // launches (plane_absmax_kernel if needed +) decoder_fold_kernel; returns the device address of the DecFold record
 static const DecFold* launch_decoder_fold(const float* planes_nhwc, size_t plane_floats, const float* plane_absmax, int n_plane_absmax,
@@ -1536,31 +1495,19 @@ static void launch_render(const RenderArgs& a, int R, int grid, hipStream_t st)
     // <OCC = 2 waves/SIMD, one plane (8 loads) in flight>: no scratch for every shape up to 64+64 samples (232 VGPRs at REF).
     // Measured at REF with the quad-coalesced gather: <2,1> 0.229 ms, <2,3> (24 loads in flight, 8 spilled registers) 0.232,
     // <3,1> (168-VGPR cap, 64 spilled) 0.353, <3,3> 0.423.  (Before the gather change <2,3> led <2,1> by 5 %: the loads were the limiter.)
-#if defined(R3D_RENDER_OCC) && defined(R3D_RENDER_GPF)          // experiment builds
-    hipLaunchKernelGGL((render_kernel<NTC, NTF, R3D_RENDER_OCC, R3D_RENDER_GPF>), dim3(grid), dim3(256), 0, st, a, R);
-#else
     hipLaunchKernelGGL((render_kernel<NTC, NTF, 2, 1>), dim3(grid), dim3(256), 0, st, a, R);
-#endif
 }
 
-// The shapes whose working set does not fit 256 registers (64+64 samples and up, the tri-grids): at 2 waves per SIMD hipcc spills to scratch
-// (<6,6>: 91 VGPRs, 312 B per lane; the cfg-5 launch then moved 16.5 GB through the memory system for 0.1 GB of compulsory bytes, VERDICT r4
-// weak 3).  At ONE wave per SIMD (min-waves-per-EU 1) the wave owns the SIMD's 512 registers and the same values live in AGPRs
-// (v_accvgpr_write / _read, one VALU instruction each): no scratch in any shape.  R3D_RENDER_BIG_OCC = 1 | 2 picks the variant (A/B).
-static int big_occ() { static const int v = getenv("R3D_RENDER_BIG_OCC") ? atoi(getenv("R3D_RENDER_BIG_OCC")) : R3D_RENDER_BIG_OCC_DEFAULT; return v; }
-template <int NTC, int NTF>
-static void launch_render_big(const RenderArgs& a, int R, int grid, hipStream_t st)
-{
-    if (big_occ() == 1) hipLaunchKernelGGL((render_kernel<NTC, NTF, 1, 1>), dim3(grid > 256 ? grid / 2 : grid), dim3(256), 0, st, a, R);
-    else hipLaunchKernelGGL((render_kernel<NTC, NTF, 2, 1>), dim3(grid), dim3(256), 0, st, a, R);
-}
+// The shapes whose working set does not fit 256 registers (64+64 samples and up, the tri-grids) run at two waves per SIMD like the others: <4,4>, <6,6>
+// and the tri-grid <6,6> park their colours in the workspace (GPARK), and what still does not fit (the tri-grids) spills to scratch.  At ONE wave per SIMD (the wave owns the SIMD's 512 registers, the same values
+// live in AGPRs, no scratch in any shape) config 5's render went 12.9 -> 16.3 ms and the tri-grids 0.331 -> 0.383 ms: the second wave's latency hiding is worth
+// more than the scratch traffic costs (profiles/r05/ray_big_shapes_one_wave_per_simd.txt; DESIGN "Retired experiment switches").
 
 // tri-grid variants: only the three covering shapes are instantiated (a secondary configuration)
 template <int NTC, int NTF>
 static void launch_render_tri(const RenderArgs& a, int R, int grid, hipStream_t st)
 {
-    if (big_occ() == 1) hipLaunchKernelGGL((render_kernel<NTC, NTF, 1, 3, true>), dim3(grid > 256 ? grid / 2 : grid), dim3(256), 0, st, a, R);
-    else hipLaunchKernelGGL((render_kernel<NTC, NTF, 2, 3, true>), dim3(grid), dim3(256), 0, st, a, R);
+    hipLaunchKernelGGL((render_kernel<NTC, NTF, 2, 3, true>), dim3(grid), dim3(256), 0, st, a, R);
 }
 
 }  // namespace r3d
@@ -1622,7 +1569,7 @@ static int render_grid(size_t nrays)
     const size_t max_blocks = ((nrays + kWavesPerBlock - 1) / kWavesPerBlock + 7) / 8 * 8;
     return max_blocks < (size_t)kMaxGrid ? (int)max_blocks : kMaxGrid;
 }
-static bool render_parks(int Nc, int Nf) { return ((Nc > 48 || Nf > 48) && Nf > 0) || R3D_RENDER_GPARK_ALL; }
+static bool render_parks(int Nc, int Nf) { return (Nc > 48 || Nf > 48) && Nf > 0; }
 // per wave of the grid: 2 (NTC + NTF) tiles of 64 f32x4; 24 covers <6,6> and its tri-grid twin (a tri-grid call with 49..64 samples runs <6,6> too)
 static size_t render_park_bytes(size_t nrays, int Nc, int Nf) { return render_parks(Nc, Nf) ? (size_t)render_grid(nrays) * kWavesPerBlock * 24 * 64 * sizeof(f32x4) : 0; }
 
@@ -1708,7 +1655,7 @@ extern "C" int r3d_render_forward(const float* planes_nhwc, int N, int H, int W,
     a.noise_c = noise_c; a.u_f = u_f; a.seed = seed;
     a.rgb = rgb; a.depth = depth; a.wsum = wsum; a.rgb_cm = rgb_channel_major ? 1 : 0;
     a.clk = prof_clock_slot(R3D_PROF_RENDER);
-    a.park_g = render_parks(Nc, Nf) ? park_g : nullptr;      // (exactly the calls the dispatch below sends to a parking shape: launch_render_big / the tri-grid <6,6>)
+    a.park_g = render_parks(Nc, Nf) ? park_g : nullptr;      // (exactly the calls the dispatch below sends to a parking shape: <4,4>, <6,6> and the tri-grid <6,6>)
 
     // (R computed above: square image -> XCD strip order; otherwise linear order)
     const int waves_needed = nrays;
@@ -1728,8 +1675,8 @@ extern "C" int r3d_render_forward(const float* planes_nhwc, int N, int H, int W,
     R3D_CASE(4, 0); R3D_CASE(6, 0);
     else if (ntf == 0 && ntc <= 6) launch_render<6, 0>(a, R, grid, st);
     else if (ntc <= 3 && ntf <= 3) launch_render<3, 3>(a, R, grid, st);
-    else if (ntc <= 4 && ntf <= 4) launch_render_big<4, 4>(a, R, grid, st);
-    else launch_render_big<6, 6>(a, R, grid, st);
+    else if (ntc <= 4 && ntf <= 4) launch_render<4, 4>(a, R, grid, st);
+    else launch_render<6, 6>(a, R, grid, st);
 #undef R3D_CASE
     }
     if (depth) {

@@ -17,8 +17,7 @@
 //                             demodulation * acc + bias -> lrelu*sqrt2 (+clamp) -> {fp32 CB8, fp32 NCHW, SPLIT} + toRGB partials
 //   upconv_fir_f16x3_kernel   up=2 layers: transposed conv (4 output phases) + FIR 4x4 + bias + lrelu + split, fused;
 //                             32 couts x 16x16 grid x 4 phases per block, the fp32 T never leaves the CU
-//   conv1x1_mfma_f16x3_kernel / tconv_mfma_f16x3_kernel (conv2_block): 1x1 convs of the fusion stacks; the per-phase
-//                             transposed conv is kept behind R3D_UPCONV=0 for A/B runs with fir_bias_act_split_kernel
+//   conv1x1_mfma_f16x3_kernel (conv2_block): 1x1 convs of the fusion stacks
 //   to_split / upsample2x_bilinear / rgb_finalize / prepack kernels: layout and glue
 // Behaviour restated from modules/eg3ds/models/networks_stylegan2.py:37-94,286-373,429-473 and
 // modules/eg3ds/torch_utils/ops/{conv2d_resample.py:116-133, upfirdn2d.py:171-215,317-354, bias_act.py:93-122}.
@@ -75,28 +74,10 @@ __device__ __forceinline__ void split1_folded(float v, _Float16& hi, _Float16& l
 // writes 8 contiguous bytes and a lane pair a whole record per store -- the straight order (dword 2 p + h) made every record two 8-byte
 // read-modify-writes (block1.conv0 wrote 153 MB for 134 MB, profiles/r04/pmc_summary.txt).
 __device__ __host__ __forceinline__ int mx_rec_chan(int dword) { return 8 * (dword & 1) + 4 * (dword >> 1); }     // first channel of a record dword
-#ifndef R3D_TAPS_CT
-#define R3D_TAPS_CT 3            // experiment switch (bisect): bit 0 = compile-time tap offsets in the f16 part, bit 1 = in the fp8 part
-#endif
-#ifndef R3D_MX_FREE_SCHED
-#define R3D_MX_FREE_SCHED 0   // experiment switch: 1 = no scheduling fences around the fp8 part of a sub-stage
-#endif
-#ifndef R3D_MX_DRAIN
-#define R3D_MX_DRAIN 0        // experiment switch: 1 = the MX conv waits for ALL its DMAs at every sub-stage (the spilling build's behaviour)
-#endif
-#ifndef R3D_MX_ACT_E4M3
-#define R3D_MX_ACT_E4M3 0     // experiment switch (A/B builds): 1 = the round-4 activation records, e4m3 of hi * 2^-7 / lo * 2^4
-#endif
 static constexpr float kMxWl = 256.0f /* 2^8 */, kMxWh = 0.125f /* 2^-3 */;
-#if R3D_MX_ACT_E4M3
-static constexpr int kMxFmtB = 0;                               // blgp: B operand (activation records) OCP e4m3
-static constexpr int kMxScaleA = 127, kMxScaleB = 126;          // E8M0 bytes: 2^0 * 2^-1
-static constexpr float kMxXh = 0.0078125f /* 2^-7 */, kMxXl = 16.0f /* 2^4 */;
-#else
 static constexpr int kMxFmtB = 1;                               // blgp: B operand (activation records) OCP e5m2
 static constexpr int kMxScaleA = 127, kMxScaleB = 119;          // E8M0 bytes: 2^0 * 2^-8
 static constexpr float kMxXh = 1.0f, kMxXl = 2048.0f /* 2^11 */;
-#endif
 
 __device__ __forceinline__ unsigned pack4_fp8(float a, float b, float c, float d)      // OCP e4m3: the weight records
 {
@@ -105,16 +86,12 @@ __device__ __forceinline__ unsigned pack4_fp8(float a, float b, float c, float d
     v = __builtin_amdgcn_cvt_pk_fp8_f32(c, d, v, true);
     return (unsigned)v;
 }
-__device__ __forceinline__ unsigned pack4_x8(float a, float b, float c, float d)       // the activation records (e5m2; e4m3 in the A/B build)
+__device__ __forceinline__ unsigned pack4_x8(float a, float b, float c, float d)       // OCP e5m2: the activation records
 {
-#if R3D_MX_ACT_E4M3
-    return pack4_fp8(a, b, c, d);
-#else
     int v = 0;
     v = __builtin_amdgcn_cvt_pk_bf8_f32(a, b, v, false);
     v = __builtin_amdgcn_cvt_pk_bf8_f32(c, d, v, true);
     return (unsigned)v;
-#endif
 }
 
 // ---- per-cout statistics of a weight tensor [CoutReal][row_len]: tail = {2^-kw[co], sum|w[co]|} (ConvTail), padded couts -> {1, 0}.
@@ -275,7 +252,8 @@ struct Conv2Args {
     const float* next_scale; size_t next_scale_stride_n;
     unsigned* y_absmax;                                    // [N] max |activated output| (uint bits of a non-negative float) or null
     const float* wrgb; size_t wrgb_stride_n; float* rgb_partial; size_t rgbp_stride_n;   // toRGB partials [Cout/128][3][OH*OW] or null
-    int Cin, Cout, CoutReal, H, W, nphase;    // Cout: padded to 128 (weight layout); CoutReal: channels that exist in the outputs
+    int Cin, Cout, CoutReal, H, W, nphase;    // Cout: padded to 128 (weight layout); CoutReal: channels that exist in the outputs; nphase: 1 (it and ph[1..3] served
+                                              // the per-phase transposed conv, DESIGN "Retired experiment switches"; they stay: the kernels' argument layout is unchanged)
     int act; float act_slope, act_gain, clamp; // act: leaky-relu(slope) * gain after the bias; clamp < 0: off
     unsigned long long* clk;                  // prof_clock_slot(R3D_PROF_CONV) or null (conv3x3_dma_block samples it)
     int order;                                // conv3x3_dma_block: 0 = (tile, cout tile) = (blockIdx.x, blockIdx.y); 1 / 2 = the cout tiles of a pixel tile adjacent in dispatch order on one XCD
@@ -295,12 +273,8 @@ struct Conv2Args {
 // round 1 measured); from LDS the loop has no global loads, so its stores stream out back to back.
 // The caller has passed a __syncthreads() after its last LDS read; `ev` may alias the main loop's buffers.
 static constexpr int EV_STRIDE = BLOCK_M;              // floats per staged vector
-#ifndef R3D_EPI_WIDE
-#define R3D_EPI_WIDE 1        // A/B switch: 0 = the 8-byte SPLIT stores of rounds 1-5 (same values, same bytes)
-#endif
-// PIXMAP = 1 (experiment): acc[mt][nt] holds column parity nt of the column pairs -- lane li <-> (row 4 wn + li / 8, columns 2 (li % 8) + nt).
-// PIXMAP != 0 (conv_wino_f16x3_kernel): the accumulators carry the transformed operands' factor 1/4 (r3d_sr_wino.h); 2 = the ordinary pixel map.
-template <bool FULL_EPI, int WN, int NT, int PIXMAP = 0, bool CAT = false>     // CAT: the concatenation-part output (y_mask, y_cat_*) is compiled in -- the 1x1 conv only: the 3x3 kernels sit at their register limit
+// WINO (conv_wino_f16x3_kernel): the accumulators carry the transformed operands' factor 1/4 (r3d_sr_wino.h); the pixel map is the same.
+template <int WN, int NT, bool WINO = false, bool CAT = false>     // CAT: the concatenation-part output (y_mask, y_cat_*) is compiled in -- the 1x1 conv only: the 3x3 kernels sit at their register limit
 __device__ __forceinline__ void conv_epilogue(const Conv2Args& a, const ConvPhase& ph, int n, f32x16 (&acc)[2][NT],
                                               int i0, int j0, int m0, float* ev)
 {
@@ -312,7 +286,7 @@ __device__ __forceinline__ void conv_epilogue(const Conv2Args& a, const ConvPhas
     const int li = lane & 31, h = lane >> 5;
     const int prow = li >> 4, pcol = ((li & 15) - 2 * prow) & 15;
     const int row0 = wn * 2 * NT;
-    const bool do_rgb = FULL_EPI && a.rgb_partial != nullptr;
+    const bool do_rgb = a.rgb_partial != nullptr;
     {   // stage: vector v of cout c -> ev[v * EV_STRIDE + c]; v = 0 out_scale (1), 1 bias (0), 2 next_scale (1), 3..5 toRGB rows (0)
         constexpr int NTHR = 128 * WN;
         for (int e = threadIdx.x; e < 6 * BLOCK_M; e += NTHR) {
@@ -320,11 +294,11 @@ __device__ __forceinline__ void conv_epilogue(const Conv2Args& a, const ConvPhas
             float val = (v == 0 || v == 2) ? 1.f : 0.f;
             if (co < a.CoutReal) {
                 if (v == 0) { if (a.out_scale) val = a.out_scale[(size_t)n * a.out_scale_stride_n + co]; }
-                else if (v == 1) { if (FULL_EPI && a.bias) val = a.bias[(size_t)n * a.bias_stride_n + co]; }
-                else if (v == 2) { if (FULL_EPI && a.y_split && a.next_scale) val = a.next_scale[(size_t)n * a.next_scale_stride_n + co]; }
+                else if (v == 1) { if (a.bias) val = a.bias[(size_t)n * a.bias_stride_n + co]; }
+                else if (v == 2) { if (a.y_split && a.next_scale) val = a.next_scale[(size_t)n * a.next_scale_stride_n + co]; }
                 else if (do_rgb) val = a.wrgb[(size_t)n * a.wrgb_stride_n + (size_t)(v - 3) * a.CoutReal + co];
             }
-            if (PIXMAP && v == 0) val *= 4.0f;
+            if (WINO && v == 0) val *= 4.0f;
             ev[e] = val;
         }
         __syncthreads();
@@ -346,17 +320,17 @@ __device__ __forceinline__ void conv_epilogue(const Conv2Args& a, const ConvPhas
     bool inside_nt[NT];
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) {
-        const int i = PIXMAP == 1 ? i0 + 4 * wn + (li >> 3) : i0 + row0 + nt * 2 + prow, j = PIXMAP == 1 ? j0 + 2 * (li & 7) + nt : j0 + pcol;
+        const int i = i0 + row0 + nt * 2 + prow, j = j0 + pcol;
         inside_nt[nt] = i < ph.outH && j < ph.outW;
         p0[nt] = (unsigned)(i * ph.oy_mul + ph.oy_add) * (unsigned)a.OW + (unsigned)(j * ph.ox_mul + ph.ox_add);
     }
     float* Yf = a.y_f32 ? a.y_f32 + (size_t)n * a.y_f32_stride_n + ph.out_off : nullptr;
-    float* Yn = (FULL_EPI && a.y_nchw) ? a.y_nchw + (size_t)n * a.y_nchw_stride_n : nullptr;
-    uint4* Ys = (FULL_EPI && a.y_split) ? a.y_split + (size_t)n * a.y_split_stride_n + (CAT ? (size_t)a.y_cat_off * a.OH * a.OW : 0) : nullptr;   // (y_cat_off even: record pairs stay aligned)
+    float* Yn = a.y_nchw ? a.y_nchw + (size_t)n * a.y_nchw_stride_n : nullptr;
+    uint4* Ys = a.y_split ? a.y_split + (size_t)n * a.y_split_stride_n + (CAT ? (size_t)a.y_cat_off * a.OH * a.OW : 0) : nullptr;   // (y_cat_off even: record pairs stay aligned)
     float ym[NT];
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) ym[nt] = 1.f;
-    const bool masked = CAT && FULL_EPI && a.y_mask != nullptr;
+    const bool masked = CAT && a.y_mask != nullptr;
     if (masked) {
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) {
@@ -364,7 +338,7 @@ __device__ __forceinline__ void conv_epilogue(const Conv2Args& a, const ConvPhas
             ym[nt] = a.y_mask_invert ? 1.0f - mk : mk;
         }
     }
-    const bool want_max = FULL_EPI && a.y_absmax != nullptr;
+    const bool want_max = a.y_absmax != nullptr;
 #pragma unroll
     for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
@@ -380,7 +354,7 @@ __device__ __forceinline__ void conv_epilogue(const Conv2Args& a, const ConvPhas
             const float4 w1 = *reinterpret_cast<const float4*>(ev + 4 * EV_STRIDE + cl);
             const float4 w2 = *reinterpret_cast<const float4*>(ev + 5 * EV_STRIDE + cl);
             const float dv[4] = {d4.x, d4.y, d4.z, d4.w}, bv[4] = {b4.x, b4.y, b4.z, b4.w}, sv[4] = {s4.x, s4.y, s4.z, s4.w};
-            constexpr bool WIDE = R3D_EPI_WIDE && (NT % 2 == 0);    // (the 8-row tiles have one N tile per wave: 8-byte stores)
+            constexpr bool WIDE = NT % 2 == 0;                          // (the 8-row tiles have one N tile per wave: 8-byte stores)
             uint2 hiw[NT], low[NT];
             unsigned xh8w[NT], xl8w[NT];
 #pragma unroll
@@ -389,13 +363,9 @@ __device__ __forceinline__ void conv_epilogue(const Conv2Args& a, const ConvPhas
                 float v[4];
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    float t;
-                    if (FULL_EPI) {
-                        t = __builtin_fmaf(acc[mt][nt][4 * g + r], dv[r], bv[r]);
-                        if (a.act) t = (t < 0.f ? t * a.act_slope : t) * a.act_gain;
-                        if (a.clamp >= 0.f) t = fminf(fmaxf(t, -a.clamp), a.clamp);
-                    }
-                    else t = acc[mt][nt][4 * g + r] * dv[r];
+                    float t = __builtin_fmaf(acc[mt][nt][4 * g + r], dv[r], bv[r]);
+                    if (a.act) t = (t < 0.f ? t * a.act_slope : t) * a.act_gain;
+                    if (a.clamp >= 0.f) t = fminf(fmaxf(t, -a.clamp), a.clamp);
                     v[r] = t;
                 }
                 if (do_rgb) {
@@ -507,7 +477,7 @@ __device__ __forceinline__ void conv_epilogue(const Conv2Args& a, const ConvPhas
             float* P = a.rgb_partial + (size_t)n * a.rgbp_stride_n + (size_t)(m0 / 64 + wm) * 3 * a.OH * a.OW;
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt) {
-                const int i = PIXMAP == 1 ? i0 + 4 * wn + (li >> 3) : i0 + row0 + nt * 2 + prow, j = PIXMAP == 1 ? j0 + 2 * (li & 7) + nt : j0 + pcol;
+                const int i = i0 + row0 + nt * 2 + prow, j = j0 + pcol;
                 if (i < ph.outH && j < ph.outW) {
                     const int oy = i * ph.oy_mul + ph.oy_add, ox = j * ph.ox_mul + ph.ox_add;
 #pragma unroll
@@ -525,7 +495,10 @@ __device__ __forceinline__ void conv_epilogue(const Conv2Args& a, const ConvPhas
 // sub-stages of SUB taps.  All global loads are register-prefetched one (sub-)stage ahead, and the weight loads are
 // issued BEFORE the patch loads, so the compiler's counted s_waitcnt vmcnt(N) at the weight ds_write leaves the slow
 // (MALL/HBM) patch loads in flight under the MFMAs.
-template <int NTAPS, bool FULL_EPI, int WN, int NT>
+// Only the 1x1 conv (NTAPS = 1, WN = 4, NT = 2) runs on this routine now: the 3x3 convs moved to conv3x3_dma_block, the transposed-conv phases
+// (NTAPS 4 / 2) and the 4-wave shape were retired (DESIGN "Retired experiment switches").  It stays generic in NTAPS: written out for one tap, hipcc
+// orders a few independent moves of the packed-f32 partner build's epilogue differently (profiles/switch_retirement/kernel_text_diff.txt).
+template <int NTAPS, int WN, int NT>
 __device__ __forceinline__ void conv2_block(const Conv2Args& a, const ConvPhase& ph, int n, uint4* lds)
 {
     static_assert(WN * NT == 8, "16 pixel rows per block");
@@ -682,7 +655,7 @@ __device__ __forceinline__ void conv2_block(const Conv2Args& a, const ConvPhase&
         }
     }
     __syncthreads();
-    conv_epilogue<FULL_EPI, WN, NT, 0, NTAPS == 1>(a, ph, n, acc, i0, j0, m0, reinterpret_cast<float*>(lds));
+    conv_epilogue<WN, NT, false, NTAPS == 1>(a, ph, n, acc, i0, j0, m0, reinterpret_cast<float*>(lds));
 }
 
 // ---- plain 3x3 conv, LDS-DMA pipeline ------------------------------------------------------------------------------
@@ -706,7 +679,7 @@ typedef int i8v __attribute__((ext_vector_type(8)));
 // TH = pixel rows per tile: 16 (the shape above), or 8 for layers whose 16x16 tiling leaves most of the chip idle (the 128^2 layers of
 // to_plane_cnn: 128 blocks for 512 block slots): 128 couts x 8x16 px per block, 8 waves x (64 couts x 32 px), twice the blocks, same
 // K order per output (bit-identical results).  LDS 2 x 12.3 KB patch + 2 x 16 KB weights = 57 KB.
-template <bool FULL_EPI, bool MX = false, int TH = F_TILE_H>
+template <bool MX = false, int TH = F_TILE_H>
 __device__ __forceinline__ void conv3x3_dma_block(const Conv2Args& a, const ConvPhase& ph, int n, uint4* lds)
 {
     static_assert(TH == 16 || TH == 8, "tile rows");
@@ -847,8 +820,8 @@ __device__ __forceinline__ void conv3x3_dma_block(const Conv2Args& a, const Conv
             // a patch DMA was issued AFTER the weights this sub-stage needs (at the top of uu = 0 / 5): leave it in flight.
             // (Counted waits need a kernel without scratch traffic -- it shares vmcnt.  Until the end of round 3 the MX instantiation
             // spilled: the tap offsets came from the ConvPhase argument, so hipcc kept 18 per-tap LDS addresses in VGPRs; as compile-time
-            // constants they are ds_read immediates: 128 + 23 spilled -> 119 VGPRs, 125 -> 117 for f16x3, and R3D_MX_DRAIN=1 is the old behaviour.)
-            const bool patch_behind = !(MX && R3D_MX_DRAIN) && ((uu == 1 && sp + 1 < nst) || (uu == 6 && sp + 2 < nst));
+            // constants they are ds_read immediates: 128 + 23 spilled -> 119 VGPRs, 125 -> 117 for f16x3.)
+            const bool patch_behind = ((uu == 1 && sp + 1 < nst) || (uu == 6 && sp + 2 < nst));
             if (patch_behind) {
                 if constexpr (KMAX == 3) { if (three) asm volatile("s_waitcnt vmcnt(3)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); }
                 else { if (three) asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(1)" ::: "memory"); }
@@ -879,11 +852,7 @@ __device__ __forceinline__ void conv3x3_dma_block(const Conv2Args& a, const Conv
                         ah[mt] = *reinterpret_cast<h8*>(&q0);
                         if (!MX) { uint4 q1 = curW[ts * 512 + aoff + mt * 32 + 128]; al[mt] = *reinterpret_cast<h8*>(&q1); }
                     }
-#if R3D_TAPS_CT & 1
                     const int toff = (t / 3 - 1) * F_PATCH_W + (t % 3 - 1);       // the plain 3x3 taps (sr_fill_conv3x3_phase): compile-time LDS offsets
-#else
-                    const int toff = ph.dy[t] * F_PATCH_W + ph.dx[t];
-#endif
 #pragma unroll
                     for (int nt = 0; nt < NT; ++nt) {
                         uint4 r0 = curP[boff[nt] + toff];
@@ -907,18 +876,10 @@ __device__ __forceinline__ void conv3x3_dma_block(const Conv2Args& a, const Conv
                 // One B record and one A record live at a time (8 + 8 VGPRs): the kernel has 64 registers besides its accumulators.
                 const int Tl0 = 2 * uu, Tl1 = 2 * uu + 1;
                 const int sl0 = Tl0 / 9, t0 = Tl0 - 9 * sl0, sl1 = Tl1 / 9, t1 = Tl1 - 9 * sl1;
-#if R3D_TAPS_CT & 2
                 const int toffa = (t0 / 3 - 1) * F_PATCH_W + (t0 % 3 - 1), toffb = (t1 / 3 - 1) * F_PATCH_W + (t1 % 3 - 1);
-#else
-                const int toffa = ph.dy[t0] * F_PATCH_W + ph.dx[t0], toffb = ph.dy[t1] * F_PATCH_W + ph.dx[t1];
-#endif
-#if !R3D_MX_FREE_SCHED
                 __builtin_amdgcn_sched_barrier(0);                  // fp8 operand loads stay behind this sub-stage's f16 MFMAs (register budget)
-#endif
                 int hh = h;
-#if !R3D_MX_FREE_SCHED
                 asm volatile("" : "+v"(hh));                        // keep the per-sub-stage address arithmetic inside the loop (9 hoisted VGPRs spill)
-#endif
                 // this lane half's tap: its stage's "lo" plane, pixel slot without the f16 chunk offset h * F_PATCH_PIX
                 const int p8 = 2 * PATCH_PIX + sl0 * PBUF + toffa + hh * ((sl1 - sl0) * PBUF + toffb - toffa - PATCH_PIX);
                 const uint4* P8 = pbuf + p8;
@@ -938,15 +899,13 @@ __device__ __forceinline__ void conv3x3_dma_block(const Conv2Args& a, const Conv
                         acc[mt][nt] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a8[mt], b8, acc[mt][nt], 0, kMxFmtB, 0, kMxScaleA, 0, kMxScaleB);
                     }
                 }
-#if !R3D_MX_FREE_SCHED
                 __builtin_amdgcn_sched_barrier(0);
-#endif
             }
         }
     }
     __syncthreads();
     R3D_STAMP(5);
-    conv_epilogue<FULL_EPI, WN, NT>(a, ph, n, acc, i0, j0, m0, reinterpret_cast<float*>(lds));
+    conv_epilogue<WN, NT>(a, ph, n, acc, i0, j0, m0, reinterpret_cast<float*>(lds));
     if (blockIdx.x == (gridDim.x >> 1) && blockIdx.y == 0 && blockIdx.z == 0 && threadIdx.x == 0) clk_end(kernarg_clk<Conv2Args>());
     R3D_STAMP(6);
 #ifdef R3D_STAMPS
@@ -965,13 +924,9 @@ static constexpr int F_LDS_UINT4 = 2 * 2 * F_PATCH_PIX + 2 * 3 * 2 * 256;      /
 template <int WN, int NT, int OCC, bool MX = false>
 __global__ __launch_bounds__(128 * WN, OCC) void conv_mfma_f16x3_kernel(Conv2Args a)
 {
-    if constexpr (WN == 4 && NT == 2) {
-        __shared__ uint4 lds[F3_LDS_UINT4];
-        conv3x3_dma_block<true, MX>(a, a.ph[0], blockIdx.z, lds);
-    } else {
-        __shared__ uint4 lds[F_LDS_UINT4];
-        conv2_block<9, true, WN, NT>(a, a.ph[0], blockIdx.z, lds);
-    }
+    static_assert(WN == 4 && NT == 2, "conv3x3_dma_block: 8 waves x (64 couts x 64 px)");
+    __shared__ uint4 lds[F3_LDS_UINT4];
+    conv3x3_dma_block<MX>(a, a.ph[0], blockIdx.z, lds);
 }
 
 // the same conv on 8x16-pixel tiles (conv3x3_dma_block TH = 8), for launches that would fill less than half of the chip's block slots
@@ -980,7 +935,7 @@ template <bool MX = false>
 __global__ __launch_bounds__(512, 4) void conv_mfma_f16x3_rows8_kernel(Conv2Args a)
 {
     __shared__ uint4 lds[F3S_LDS_UINT4];
-    conv3x3_dma_block<true, MX, 8>(a, a.ph[0], blockIdx.z, lds);
+    conv3x3_dma_block<MX, 8>(a, a.ph[0], blockIdx.z, lds);
 }
 
 // 1x1 conv with the full epilogue (nn.Conv2d(k=1) layers of the torso/background fusion stack)
@@ -988,7 +943,7 @@ template <int WN, int NT, int OCC>
 __global__ __launch_bounds__(128 * WN, OCC) void conv1x1_mfma_f16x3_kernel(Conv2Args a)
 {
     __shared__ uint4 lds[F_LDS_UINT4];
-    conv2_block<1, true, WN, NT>(a, a.ph[0], blockIdx.z, lds);
+    conv2_block<1, WN, NT>(a, a.ph[0], blockIdx.z, lds);
 }
 
 // ---- 1x1 conv with the alpha / occlusion blend + channel concatenation of its operand fused in (round 6) ------------------------------------------------------
@@ -1111,23 +1066,7 @@ __global__ __launch_bounds__(512, 2) void conv1x1_blend_f16x3_kernel(Conv2Args a
             }
         }
     }
-    conv_epilogue<true, WN, NT>(a, ph, n, acc, i0, j0, m0, reinterpret_cast<float*>(lds));
-}
-
-// stride-2 transposed conv phases (4/2/2/1 taps)
-template <int WN, int NT, int OCC>
-__global__ __launch_bounds__(128 * WN, OCC) void tconv_mfma_f16x3_kernel(Conv2Args a)
-{
-    __shared__ uint4 lds[F_LDS_UINT4];
-    const int n = blockIdx.z / a.nphase, p = blockIdx.z - n * a.nphase;
-    const ConvPhase& ph = a.ph[p];
-    const int tiles = ((ph.outW + F_TILE_W - 1) / F_TILE_W) * ((ph.outH + F_TILE_H - 1) / F_TILE_H);
-    if ((int)blockIdx.x >= tiles) return;
-    switch (ph.ntaps) {
-        case 4: conv2_block<4, false, WN, NT>(a, ph, n, lds); break;
-        case 2: conv2_block<2, false, WN, NT>(a, ph, n, lds); break;
-        default: conv2_block<1, false, WN, NT>(a, ph, n, lds); break;
-    }
+    conv_epilogue<WN, NT>(a, ph, n, acc, i0, j0, m0, reinterpret_cast<float*>(lds));
 }
 
 // ---- fused up-sampling conv: conv_transpose2d(stride 2) + FIR 4x4 (gain 4, pad 1) + bias + lrelu*sqrt2 -> SPLIT --------
@@ -1225,10 +1164,11 @@ __global__ void sr_prepack_up_mx_kernel(const float* __restrict__ w, int Cin, in
 // main loop spends, per 16-channel stage and N tile, 9 f16 MFMAs (hi * hi) + 5 fp8 K = 64 MFMAs -- the cross products of the tap pairs
 // (0,2) (6,8) -> phase 0, (1,7) -> phase 1, (3,5) -> phase 2 and of the centre tap 4 (phase 3, its second K half reads a zero record) --
 // instead of 27 f16 MFMAs: 608 instead of 864 matrix cycles.  Lane half h <-> the pair's tap h, as in conv3x3_dma_block<.., MX>.
-// NW = waves per block: 4 (two N tiles = 128 accumulator registers per wave, 2 waves per SIMD: the shape of the MFMA-bound layers) or
-// 8 (one N tile, 64 accumulators, ~110 VGPRs: 4 waves per SIMD at the same 2 blocks per CU) for layers with a handful of K stages --
-// block0.conv0 (Cin = 32: two stages) is ALL epilogue, and the epilogue's dependent LDS -> VALU -> store chains ran at 30 % of the VALU
-// rate with two waves per SIMD (round 4: 39.8 -> see DESIGN 4.2).  Same tile, same K order per output: bit-identical results.
+// NW = waves per block: 4 (two N tiles = 128 accumulator registers per wave, 2 waves per SIMD: the shape of the MFMA-bound layers) is the only value
+// instantiated.  NW = 8 (one N tile, 4 waves per SIMD at the same 2 blocks per CU) was built for block0.conv0 (Cin = 32: two K stages, ALL epilogue) and
+// measured neutral (0.173 vs 0.169-0.177 ms per frame for the family, bit-identical results): that launch is bound by the LDS-DMA fill rate of its two K
+// stages and by the VALU work of its epilogue one after the other, not by latency (DESIGN "Retired experiment switches").  The parameter stays: it is
+// part of the kernels' names, which the resource tests and the benchmark's kernel statistics match.
 template <bool CLAMP, bool MX = false, bool MXIN = false, int NW = 4>
 __global__ __launch_bounds__(64 * NW, NW == 8 ? 4 : 2) void upconv_fir_f16x3_kernel(UpArgs a)
 {
@@ -1600,82 +1540,6 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 4 : 2) void upconv_fir_f16x3_ker
 }
 R3D_STAMP_READER(r3d_debug_stamps_sr)
 
-// ---- FIR 4x4 (gain 4, pad 1) + bias + lrelu*sqrt2 on the transposed-conv output; writes SPLIT scaled by the next
-// conv's styles.  T is PHASE-MAJOR: T[p=(r&1)*2+(c&1)][C/8][Hin+1][Win+1][8] holds row r, col c of the (2Hin+1)x(2Win+1)
-// transposed-conv result (the conv epilogue's stores are then contiguous).  One thread = a 2x2 output quad x 8
-// channels from the 5x5 T window rows 2Y-1..2Y+3, cols 2X-1..2X+3 (25 loads for 4 outputs instead of 64).
-// (An XCD-banded block order and 2x4 strips per thread were measured slower: 164 / 240 us vs 152 us per frame.)
-__global__ void fir_bias_act_split_kernel(const float* __restrict__ T, size_t t_stride_n, const float* __restrict__ bias,
-                                          const float* __restrict__ next_scale, size_t vec_stride_n,
-                                          uint4* __restrict__ y, size_t y_stride_n, int C, int Hin, int Win, float clamp)
-{
-    const int n = blockIdx.z, cb = blockIdx.y;
-    const int bx = blockIdx.x;
-    const int Wq = Win;
-    const int q = bx * blockDim.x + threadIdx.x;
-    if (q >= Hin * Wq) return;
-    const int Y = q / Wq, X = q - Y * Wq;
-    const int PH = Hin + 1, PW = Win + 1, OH = 2 * Hin, OW = 2 * Win;
-    const size_t pplane = (size_t)(C / 8) * PH * PW * 8;
-    const float* Tn = T + (size_t)n * t_stride_n + (size_t)cb * PH * PW * 8;
-    const float f1[4] = {0.25f, 0.75f, 0.75f, 0.25f};
-    float acc[2][2][8];
-#pragma unroll
-    for (int a_ = 0; a_ < 2; ++a_)
-#pragma unroll
-        for (int b_ = 0; b_ < 2; ++b_)
-#pragma unroll
-            for (int c = 0; c < 8; ++c) acc[a_][b_][c] = 0.f;
-#pragma unroll
-    for (int rr = 0; rr < 5; ++rr) {
-        const int r = 2 * Y - 1 + rr;
-        if (r < 0 || r > 2 * Hin) continue;
-#pragma unroll
-        for (int cc = 0; cc < 5; ++cc) {
-            const int c = 2 * X - 1 + cc;
-            if (c < 0 || c > 2 * Win) continue;
-            const float4* s4 = reinterpret_cast<const float4*>(Tn + (size_t)((r & 1) * 2 + (c & 1)) * pplane + ((size_t)(r >> 1) * PW + (c >> 1)) * 8);
-            const float4 u = s4[0], v = s4[1];
-            const float tv[8] = {u.x, u.y, u.z, u.w, v.x, v.y, v.z, v.w};
-#pragma unroll
-            for (int dy = 0; dy < 2; ++dy) {
-                const int a_ = rr - dy;                 // tap index: r - (2Y+dy) + 1
-                if (a_ < 0 || a_ > 3) continue;
-#pragma unroll
-                for (int dx = 0; dx < 2; ++dx) {
-                    const int b_ = cc - dx;
-                    if (b_ < 0 || b_ > 3) continue;
-                    const float w = f1[a_] * f1[b_];
-#pragma unroll
-                    for (int ch = 0; ch < 8; ++ch) acc[dy][dx][ch] += tv[ch] * w;
-                }
-            }
-        }
-    }
-    const float4* b4 = reinterpret_cast<const float4*>(bias + (size_t)n * vec_stride_n + cb * 8);
-    const float4* n4 = reinterpret_cast<const float4*>(next_scale + (size_t)n * vec_stride_n + cb * 8);
-    const float4 b0 = b4[0], b1 = b4[1], n0 = n4[0], n1 = n4[1];
-    const float bv[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w}, nv[8] = {n0.x, n0.y, n0.z, n0.w, n1.x, n1.y, n1.z, n1.w};
-    const size_t plane = (size_t)(C / 8) * OH * OW;
-    uint4* d = y + (size_t)n * y_stride_n + (size_t)cb * OH * OW;
-#pragma unroll
-    for (int dy = 0; dy < 2; ++dy)
-#pragma unroll
-        for (int dx = 0; dx < 2; ++dx) {
-            h8 hi, lo;
-#pragma unroll
-            for (int ch = 0; ch < 8; ++ch) {
-                float t = acc[dy][dx][ch] + bv[ch];
-                t = (t < 0.f ? t * 0.2f : t) * 1.4142135623730951f;
-                if (clamp >= 0.f) t = fminf(fmaxf(t, -clamp), clamp);
-                _Float16 x0, x1; split1(t * nv[ch], x0, x1); hi[ch] = x0; lo[ch] = x1;
-            }
-            const size_t p = (size_t)(2 * Y + dy) * OW + (2 * X + dx);
-            d[p] = *reinterpret_cast<uint4*>(&hi);
-            d[plane + p] = *reinterpret_cast<uint4*>(&lo);
-        }
-}
-
 // ---- image finalize: img_out = upsample2d(img_in) + bias + sum_m partial[m]  (networks_stylegan2.py:463-469) ----
 // img_u8 != null: the block is the last one of the network and the frame leaves as uint8 HWC: clamp(-1,1) (the
 // `sr_image.clamp(-1, 1)` of triplane.py:136) then ((x + 1) / 2 * 255).int() (inference/real3d_infer.py:472,518-522), fused here
@@ -1916,24 +1780,18 @@ int sr_prepack_f16x3(int Cin, int Cout, const float* c0_w, const float* c1_w, vo
     return check_launch("sr_block_prepack");
 }
 
-// tuning switch (experiment): extra dynamic LDS per block of the two big kernels, e.g. 24576 -> one block per CU, which leaves room for a
-// ray-kernel block of another stream on the same CU
-static unsigned lds_pad() { static const unsigned v = getenv("R3D_SR_LDS_PAD") ? (unsigned)atoi(getenv("R3D_SR_LDS_PAD")) : 0u; return v; }
-
 // wino: a.wp is a Winograd pack (sr_prepack_wino_kernel), a.x plain SPLIT; mx selects the f16mx main loop
 static void launch_conv2(Conv2Args& a, int tiles, int N, hipStream_t st, bool mx = false, bool wino = false)
 {
     a.clk = prof_clock_slot(R3D_PROF_CONV);
-    dim3 grid(tiles, a.Cout / BLOCK_M, N * a.nphase);
+    dim3 grid(tiles, a.Cout / BLOCK_M, N);
+    a.order = (tiles & 7) == 0 ? 2 : 0;                                 // XCD-aware block order whenever the tiles divide over the 8 XCDs
     if (wino) {
-        static const int order = getenv("R3D_CONV_ORDER") ? atoi(getenv("R3D_CONV_ORDER")) : 2;
-        a.order = (tiles & 7) == 0 ? order : 0;
         if (mx) hipLaunchKernelGGL(conv_wino_f16x3_kernel<true>, grid, dim3(512), 0, st, a);
         else hipLaunchKernelGGL(conv_wino_f16x3_kernel<false>, grid, dim3(512), 0, st, a);
         return;
     }
-    static const int rows8 = getenv("R3D_CONV_ROWS8") ? atoi(getenv("R3D_CONV_ROWS8")) : 1;   // A/B switch: 0 = always 16x16 tiles
-    if (rows8 && (rows8 == 1 || (rows8 == 2 && !a.rgb_partial) || (rows8 == 3 && a.rgb_partial)) && a.nphase == 1 && a.ph[0].ntaps == 9 && (size_t)tiles * grid.y * grid.z <= 256) {
+    if (a.ph[0].ntaps == 9 && (size_t)tiles * grid.y * grid.z <= 256) {
         // under-filled launch (<= half of the 512 block slots): 8x16-pixel tiles, twice the blocks (bit-identical results)
         const int t8 = ((a.ph[0].outW + F_TILE_W - 1) / F_TILE_W) * ((a.ph[0].outH + 7) / 8);
         a.order = (t8 & 7) == 0 ? 2 : 0;
@@ -1941,20 +1799,10 @@ static void launch_conv2(Conv2Args& a, int tiles, int N, hipStream_t st, bool mx
         else hipLaunchKernelGGL(conv_mfma_f16x3_rows8_kernel<false>, dim3(t8, grid.y, grid.z), dim3(512), 0, st, a);
         return;
     }
-    static const int shape = getenv("R3D_CONV_SHAPE") ? atoi(getenv("R3D_CONV_SHAPE")) : 0;   // tuning switch, default 0
-    static const int order = getenv("R3D_CONV_ORDER") ? atoi(getenv("R3D_CONV_ORDER")) : 2;   // tuning switch (0: plain (x, y) order)
-    a.order = (tiles & 7) == 0 ? order : 0;
-    const int kind = a.nphase > 1 ? 2 : (a.ph[0].ntaps == 9 ? 0 : 1);      // 0: 3x3 conv, 1: 1x1 conv, 2: transposed-conv phases
-    if (shape == 1 && !mx) {    // 4 waves x (64 couts x 128 px), 2 blocks/CU (the switch has no MX instantiation: an R3D_FMT_SPLIT_MX input keeps the default shape)
-        if (kind == 0) hipLaunchKernelGGL((conv_mfma_f16x3_kernel<2, 4, 2>), grid, dim3(256), 0, st, a);
-        else if (kind == 1) hipLaunchKernelGGL((conv1x1_mfma_f16x3_kernel<2, 4, 2>), grid, dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((tconv_mfma_f16x3_kernel<2, 4, 2>), grid, dim3(256), 0, st, a);
-    } else {                    // 8 waves x (64 couts x 64 px): 4 waves/SIMD at 2 blocks/CU
-        if (kind == 0 && mx) hipLaunchKernelGGL((conv_mfma_f16x3_kernel<4, 2, 4, true>), grid, dim3(512), 0, st, a);
-        else if (kind == 0) hipLaunchKernelGGL((conv_mfma_f16x3_kernel<4, 2, 4>), grid, dim3(512), lds_pad(), st, a);
-        else if (kind == 1) hipLaunchKernelGGL((conv1x1_mfma_f16x3_kernel<4, 2, 4>), grid, dim3(512), 0, st, a);
-        else hipLaunchKernelGGL((tconv_mfma_f16x3_kernel<4, 2, 4>), grid, dim3(512), 0, st, a);
-    }
+    // 8 waves x (64 couts x 64 px): 4 waves/SIMD at 2 blocks/CU
+    if (a.ph[0].ntaps == 1) hipLaunchKernelGGL((conv1x1_mfma_f16x3_kernel<4, 2, 4>), grid, dim3(512), 0, st, a);
+    else if (mx) hipLaunchKernelGGL((conv_mfma_f16x3_kernel<4, 2, 4, true>), grid, dim3(512), 0, st, a);
+    else hipLaunchKernelGGL((conv_mfma_f16x3_kernel<4, 2, 4>), grid, dim3(512), 0, st, a);
 }
 
 static int tiles_of(int H, int W) { return ((W + F_TILE_W - 1) / F_TILE_W) * ((H + F_TILE_H - 1) / F_TILE_H); }
@@ -1971,9 +1819,9 @@ int sr_block_forward_f16x3(const void* prepacked, const void* styles, int N, int
     const int OH = up ? 2 * Hin : Hin, OW = up ? 2 * Win : Win;
     char* wsb = reinterpret_cast<char*>(workspace);
     uint4* xin = reinterpret_cast<uint4*>(wsb); wsb += align256((size_t)N * Cin * Hin * Win * 4);
-    const int PH = Hin + 1, PW = Win + 1;
-    const size_t pplane = (size_t)Cout * PH * PW;                 // floats per phase plane
-    float* T = reinterpret_cast<float*>(wsb);   wsb += align256((size_t)N * 4 * pplane * 4);
+    // the T slot (four fp32 phase planes [Cout][Hin + 1][Win + 1]: the per-phase transposed conv of the fp32 path, r3d_sr.hip) is unused here since the
+    // unfused up-sampling conv0 was retired; r3d_sr_block_workspace_bytes and the offsets of the slots behind it are one layout for all precisions
+    wsb += align256((size_t)N * 4 * Cout * (Hin + 1) * (Win + 1) * 4);
     uint4* y0 = reinterpret_cast<uint4*>(wsb);  wsb += align256((size_t)N * Cout * 4 * Hin * Win * 4);
     float* xo = reinterpret_cast<float*>(wsb);                    // fp32 CB8 x (only when an fp32 x_out is requested)
     float* rgbp = reinterpret_cast<float*>(wsb + align256((size_t)N * Cout * 4 * Hin * Win * 4));
@@ -1989,8 +1837,7 @@ int sr_block_forward_f16x3(const void* prepacked, const void* styles, int N, int
     // conv1 on the Winograd F(2,3) kernel: its operand is transformed in fp32 inside the kernel, so conv0 hands over plain SPLIT (no fp8 records)
     const bool wino1 = wino_shape_ok(Cout, Cout, OH, OW) && (wino_mode() == 1 || (wino_mode() == 2 && mx) || (wino_mode() == 3 && !mx));
     const bool mx0 = mx && !wino1;                            // does conv0's epilogue write the fp8 records of conv1's operand?
-    static const int fused_up = getenv("R3D_UPCONV") ? atoi(getenv("R3D_UPCONV")) : 1;   // A/B switch: 0 = per-phase T-conv + FIR kernel
-    if (up && fused_up) {
+    if (up) {
         // ---- conv0: fused transposed conv + FIR + bias + lrelu -> SPLIT (one kernel, T stays on chip) ----------------
         UpArgs u = {};
         u.x = xs; u.x_stride_n = (size_t)Cin / 8 * Hin * Win * 2;
@@ -2006,43 +1853,14 @@ int sr_block_forward_f16x3(const void* prepacked, const void* styles, int N, int
         u.clk = prof_clock_slot(R3D_PROF_UPCONV);
         ProfScope ps(R3D_PROF_UPCONV, st);
         const dim3 ugrid(8 * u.tiles_per_xcd * (Cout / 32), N);
-        // (NW = 8 -- one N tile per wave, 4 waves per SIMD -- was built for block0.conv0, the all-epilogue launch, and measured NEUTRAL in
-        // round 4 (0.173 vs 0.169-0.177 ms per frame for the family, bit-identical results), as was a first-round stagger of the CU's second
-        // block: that launch is bound by the LDS-DMA fill rate of its two K stages and by the VALU work of its epilogue one after the other,
-        // not by latency.  The instantiation stays available behind R3D_UPCONV_NW8=1 for experiments.)
-        static const int up8 = getenv("R3D_UPCONV_NW8") ? atoi(getenv("R3D_UPCONV_NW8")) : 0;
-        const bool nw8 = up8 && Cin <= 64 && !mx_in && !mx0 && clamp < 0.f;
         if (mx_in && clamp >= 0.f && mx0) hipLaunchKernelGGL((upconv_fir_f16x3_kernel<true, true, true>), ugrid, dim3(256), 0, st, u);
         else if (mx_in && mx0) hipLaunchKernelGGL((upconv_fir_f16x3_kernel<false, true, true>), ugrid, dim3(256), 0, st, u);
         else if (mx_in && clamp >= 0.f) hipLaunchKernelGGL((upconv_fir_f16x3_kernel<true, false, true>), ugrid, dim3(256), 0, st, u);
         else if (mx_in) hipLaunchKernelGGL((upconv_fir_f16x3_kernel<false, false, true>), ugrid, dim3(256), 0, st, u);
-        else if (nw8) hipLaunchKernelGGL((upconv_fir_f16x3_kernel<false, false, false, 8>), ugrid, dim3(512), 0, st, u);
         else if (mx0 && clamp >= 0.f) hipLaunchKernelGGL((upconv_fir_f16x3_kernel<true, true>), ugrid, dim3(256), 0, st, u);
         else if (mx0) hipLaunchKernelGGL((upconv_fir_f16x3_kernel<false, true>), ugrid, dim3(256), 0, st, u);
         else if (clamp >= 0.f) hipLaunchKernelGGL(upconv_fir_f16x3_kernel<true>, ugrid, dim3(256), 0, st, u);
-        else hipLaunchKernelGGL(upconv_fir_f16x3_kernel<false>, ugrid, dim3(256), lds_pad(), st, u);
-    } else if (up) {
-        // ---- conv0: stride-2 transposed conv as 4 phases -> T (demodulated, fp32), then FIR + bias + lrelu -> SPLIT ----
-        {
-            Conv2Args a = {};
-            a.x = xs; a.x_stride_n = (size_t)Cin / 8 * Hin * Win * 2;
-            a.wp = reinterpret_cast<const uint4*>(wpk);
-            a.out_scale = pk + L.d0f; a.out_scale_stride_n = L.total;
-            a.y_f32 = T; a.y_f32_stride_n = 4 * pplane; a.OH = PH; a.OW = PW;
-            a.Cin = Cin; a.Cout = Cout; a.CoutReal = Cout; a.H = Hin; a.W = Win; a.nphase = 4; a.act = 0; a.clamp = -1.f;
-            sr_fill_tconv_phases(a.ph, Hin, Win);
-            int maxtiles = 0;
-            for (int p = 0; p < 4; ++p) {                               // phase-major T: contiguous stores per phase
-                a.ph[p].oy_mul = 1; a.ph[p].oy_add = 0; a.ph[p].ox_mul = 1; a.ph[p].ox_add = 0; a.ph[p].out_off = p * pplane;
-                const int tiles = tiles_of(a.ph[p].outH, a.ph[p].outW);
-                if (tiles > maxtiles) maxtiles = tiles;
-            }
-            ProfScope ps(R3D_PROF_CONV, st);
-            launch_conv2(a, maxtiles, N, st);
-        }
-        ProfScope ps(R3D_PROF_UPCONV, st);
-        hipLaunchKernelGGL(fir_bias_act_split_kernel, dim3((Hin * Win + 255) / 256, Cout / 8, N), dim3(256), 0, st,
-                           T, 4 * pplane, pk + L.b0, pk + L.s1f, L.total, y0, (size_t)Cout / 8 * OH * OW * 2, Cout, Hin, Win, clamp);
+        else hipLaunchKernelGGL(upconv_fir_f16x3_kernel<false>, ugrid, dim3(256), 0, st, u);
     } else {
         // ---- conv0 of SynthesisBlockNoUp (superresolution.py:159-258): plain modulated 3x3 conv -> SPLIT for conv1 ----
         Conv2Args a = {};

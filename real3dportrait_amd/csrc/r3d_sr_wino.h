@@ -27,7 +27,7 @@
 // The transform of stage s + 1 rides inside the matrix pipeline of stage s in three 8-channel pieces (stage_body).
 // Measured (profiles/r06/winograd_kernel_findings.txt): f16x3 -13.7 % per launch against the direct kernel (the default there), f16mx +9 % (instruction-issue
 // bound at two waves per SIMD: the transform is 180 VALU instructions per wave and stage; stays on the direct kernel, also end to end: 1 650 vs 1 570 frames/s).
-// WG_X_* / WG_BD / WG_PD / WG_RL / WG_RS: experiment switches of that analysis (timing-only variants, prefetch depths); the defaults are the product.
+// The timing-only variants and the prefetch-depth sweep of that analysis are retired (DESIGN "Retired experiment switches"); the depths below are the product.
 
 static constexpr int WG_VPLANE = 18 * 8;                            // uint4 slots of one V plane: [V row 18][column pair 8]
 static constexpr int WG_VPOS = 4 * WG_VPLANE;                       // per position: hi chunk 0 | hi chunk 1 | (lo chunk 0 | lo chunk 1) or (rec_h | rec_l)
@@ -38,19 +38,10 @@ static constexpr int WG_RBUF = 9 * WG_RPLANE;                       // 1296 uint
 static constexpr int WG_RSEGS = (WG_RBUF + 63) / 64;                // 21 segments of 64 slots (one per wave and store instruction)
 static constexpr int WG_RSTRIDE = WG_RSEGS * 64;                    // 1344: the last segment's tail lanes land in padding
 static constexpr int WG_LDS_UINT4 = 8192;                           // main loop: 2 x 2304 + 2 x 1344 = 7296; epilogue exchange: 8192 (128 KB)
-#ifndef WG_X_PIECE
-#define WG_X_PIECE 0                // timing experiments: 1 = transform pieces without their LDS traffic, 2 = without their VALU work
-#endif
-#ifndef WG_PD
-#define WG_PD 3                     // a transform piece is consumed this many (odd: 1 or 3) steps after its LDS reads were issued
-#endif
-#ifndef WG_BD
-#define WG_BD 1                     // B operands are read this many steps ahead of their MFMAs
-#endif
-#ifndef WG_RL
-#define WG_RL 4
-#define WG_RS 10
-#endif
+static constexpr int WG_PD = 3;                                     // a transform piece is consumed this many (odd: 1 or 3) steps after its LDS reads were issued
+static constexpr int WG_BD = 1;                                     // B operands are read this many steps ahead of their MFMAs
+static constexpr int WG_RL = 4;                                     // f16mx: step that loads the raw patch of stage st + 2 (f16x3, 12 steps: step 6)
+static constexpr int WG_RS = 10;                                    // step that stores it to LDS (both precisions)
 static constexpr int WG_WBLK = 768;                                 // uint4 of weights per (cout tile, stage, wave)
 
 // d = (float)half(x, HI) * m + c  and  d = (float)half(x, HI) * m + (float)half(c, HI): hipcc selects v_fma_mix_f32 for these (one instruction instead of
@@ -217,24 +208,12 @@ __global__ __launch_bounds__(512, 2) void conv_wino_f16x3_kernel(Conv2Args a)
     auto tp_load = [&](int bufi, int pass) {
         const uint4* R = rbuf + bufi * WG_RSTRIDE;
         const int o = pass == 2 ? d2 : 0;
-#if WG_X_PIECE == 1
-        (void)R; (void)o;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) { tr[pass & 1][q] = make_uint4(0x3c003c00u + lane, 0x3c003c00u + pass, 0x38003800u, 0x34003400u + q); asm volatile("" : "+v"(tr[pass & 1][q].x), "+v"(tr[pass & 1][q].y), "+v"(tr[pass & 1][q].z), "+v"(tr[pass & 1][q].w)); }
-#else
         tr[pass & 1][0] = R[sAh + o + pass * 64]; tr[pass & 1][1] = R[sAl + o + pass * 64]; tr[pass & 1][2] = R[sBh + o + pass * 64]; tr[pass & 1][3] = R[sBl + o + pass * 64];
-#endif
     };
     auto tp_compute = [&](int bufi, int pass) {
         uint4* V = vbuf + bufi * WG_VBUF + vw_slot + pass * 64 + (pass == 2 ? d2 : 0);
         const unsigned* pah = reinterpret_cast<const unsigned*>(&tr[pass & 1][0]); const unsigned* pal = reinterpret_cast<const unsigned*>(&tr[pass & 1][1]);
         const unsigned* pbh = reinterpret_cast<const unsigned*>(&tr[pass & 1][2]); const unsigned* pbl = reinterpret_cast<const unsigned*>(&tr[pass & 1][3]);
-#if WG_X_PIECE == 2
-        V[wm * WG_VPLANE] = make_uint4(pah[0] ^ pbh[0], pah[1] ^ pbh[1], pah[2] ^ pbh[2], pah[3] ^ pbh[3]);
-        reinterpret_cast<uint2*>(V + 2 * WG_VPLANE)[wm] = make_uint2(pal[0], pal[1]);
-        reinterpret_cast<uint2*>(V + 3 * WG_VPLANE)[wm] = make_uint2(pbl[0], pbl[1]);
-        return;
-#endif
         float v[8], lo[8];
         unsigned hw[4];
 #pragma unroll
@@ -250,13 +229,6 @@ __global__ __launch_bounds__(512, 2) void conv_wino_f16x3_kernel(Conv2Args a)
             lo[2 * d] = mix_hf<0>(hw[d], neg1, v[2 * d]);
             lo[2 * d + 1] = mix_hf<1>(hw[d], neg1, v[2 * d + 1]);
         }
-#if WG_X_PIECE == 1
-        {
-            const unsigned r0 = pack4_x8(v[0], v[1], v[2], v[3]), r1 = pack4_x8(v[4], v[5], v[6], v[7]), r2 = pack4_x8(lo[0] * kMxXl, lo[1] * kMxXl, lo[2] * kMxXl, lo[3] * kMxXl), r3 = pack4_x8(lo[4] * kMxXl, lo[5] * kMxXl, lo[6] * kMxXl, lo[7] * kMxXl);
-            asm volatile("" :: "v"(hw[0]), "v"(hw[1]), "v"(hw[2]), "v"(hw[3]), "v"(r0), "v"(r1), "v"(r2), "v"(r3));
-            return;
-        }
-#endif
         V[wm * WG_VPLANE] = make_uint4(hw[0], hw[1], hw[2], hw[3]);
         if constexpr (MX) {
             // e5m2 records of V (hi part straight from the fp32 value) and of lo * 2^11: chunk wm = bytes [8 wm, +8) of the two 16-byte records of the stage
@@ -329,9 +301,6 @@ __global__ __launch_bounds__(512, 2) void conv_wino_f16x3_kernel(Conv2Args a)
             // steps: F(ky 0) x 2 | F(ky 1) x 2 | E(ky0 | ky1) x 4 | F(ky 2) x 2 | E(ky2 | zero) x 4;  F = f16 hi * hi on two N tiles, E = fp8 cross products on one
             h8 bf[WG_BD + 1][2], ak2[2];
             i8v b8[WG_BD + 1], a8p0[2], a8p1[2];
-#ifdef WG_X_NOA
-            ak2[0] = ca[0]; ak2[1] = ca[1]; a8p0[0] = a8p0[1] = a8p1[0] = a8p1[1] = (i8v){lane, li, h, 1, 2, 3, 4, 5};
-#endif
             auto rd_step = [&](int s) {                                // the B operands of step s
                 const bool isE = (s >= 4 && s < 8) || s >= 10;
                 if (!isE) {
@@ -350,7 +319,6 @@ __global__ __launch_bounds__(512, 2) void conv_wino_f16x3_kernel(Conv2Args a)
             for (int s = 0; s < 14; ++s) {
                 WG_SB;
                 if (s + WG_BD < 14) rd_step(s + WG_BD);
-#ifndef WG_X_NOA
                 if (s == 0) {
 #pragma unroll
                     for (int mt = 0; mt < 2; ++mt) a8p0[mt] = ldw_i8(lane16, W + (384 + (mt * 2 + 0) * 64) * 16, W + (384 + (mt * 2 + 1) * 64) * 16);
@@ -365,14 +333,9 @@ __global__ __launch_bounds__(512, 2) void conv_wino_f16x3_kernel(Conv2Args a)
                         a8p1[mt] = ldw_i8(z16, W + (640 + (mt * 2 + 0) * 32) * 16, W + (640 + (mt * 2 + 1) * 32) * 16);
                 }
                 if (s == 10) load_a_carried(min(st + 1, nst - 1));      // (last stage: loads its own operands again, unused)
-#endif
-#ifndef WG_X_NORAW
                 if (s == WG_RL) raw_load(min(st + 2, nst - 1), rr);
                 if (s == WG_RS) raw_store(rbuf + bufi * WG_RSTRIDE, rr);
-#endif
-#ifndef WG_X_NOPIECE
                 if (s < 6 && !(s & 1)) tp_load(nxt, s >> 1);
-#endif
                 const bool isE = (s >= 4 && s < 8) || s >= 10;
                 if (!isE) {
                     const int np = s & 1;
@@ -389,10 +352,7 @@ __global__ __launch_bounds__(512, 2) void conv_wino_f16x3_kernel(Conv2Args a)
                     for (int mt = 0; mt < 2; ++mt)
                         acc[mt][nt] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(s < 8 ? a8p0[mt] : a8p1[mt], b8[s % (WG_BD + 1)], acc[mt][nt], 0, kMxFmtB, 0, kMxScaleA, 0, kMxScaleB);
                 }
-#ifndef WG_X_NOPIECE
                 if (s >= WG_PD && s < 6 + WG_PD && ((s - WG_PD) & 1) == 0) tp_compute(nxt, (s - WG_PD) >> 1);
-#endif
-#ifndef WG_X_NOSGB
                 // order inside the step: LDS reads and global loads first, then the VALU work of the piece spread between the MFMAs, LDS writes last
                 __builtin_amdgcn_sched_group_barrier(0x100, 8, 0);
                 __builtin_amdgcn_sched_group_barrier(0x020, 8, 0);
@@ -404,7 +364,6 @@ __global__ __launch_bounds__(512, 2) void conv_wino_f16x3_kernel(Conv2Args a)
                     for (int i = 0; i < 2; ++i) { __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x002, 38, 0); }
                 }
                 __builtin_amdgcn_sched_group_barrier(0x200, 4, 0);
-#endif
             }
             WG_SB;
         } else {
@@ -430,7 +389,7 @@ __global__ __launch_bounds__(512, 2) void conv_wino_f16x3_kernel(Conv2Args a)
                 }
                 if (s == 8) load_a_carried(min(st + 1, nst - 1));
                 if (s == 6) raw_load(min(st + 2, nst - 1), rr);
-                if (s == 10) raw_store(rbuf + bufi * WG_RSTRIDE, rr);
+                if (s == WG_RS) raw_store(rbuf + bufi * WG_RSTRIDE, rr);
                 if (s < 6 && !(s & 1)) tp_load(nxt, s >> 1);
                 const int ky = s >> 2, nt = s & 3;
 #pragma unroll
@@ -485,9 +444,6 @@ __global__ __launch_bounds__(512, 2) void conv_wino_f16x3_kernel(Conv2Args a)
 
     // ---- the four positions of a pixel meet: two rounds (mt) through LDS; wave (pos, wm) ends up with output rows [4 pos, +4) of its couts
     f32x16 out[2][2];
-#ifdef WG_NO_EXCHANGE
-    for (int mt = 0; mt < 2; ++mt) for (int q = 0; q < 2; ++q) out[mt][q] = acc[mt][q] + acc[mt][q + 2];
-#else
 #pragma unroll
     for (int mt = 0; mt < 2; ++mt) {
         f32x4* Xc = reinterpret_cast<f32x4*>(lds);
@@ -515,9 +471,8 @@ __global__ __launch_bounds__(512, 2) void conv_wino_f16x3_kernel(Conv2Args a)
         }
         __syncthreads();
     }
-#endif
     R3D_STAMP(9);
-    conv_epilogue<true, 4, 2, 2>(a, ph, n, out, i0, j0, m0, reinterpret_cast<float*>(lds));
+    conv_epilogue<4, 2, true>(a, ph, n, out, i0, j0, m0, reinterpret_cast<float*>(lds));
     R3D_STAMP(10);
     if (blockIdx.x == (gridDim.x >> 1) && blockIdx.y == 0 && blockIdx.z == 0 && threadIdx.x == 0) clk_end(kernarg_clk<Conv2Args>());
 #ifdef R3D_STAMPS

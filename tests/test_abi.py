@@ -124,6 +124,30 @@ def test_product_has_no_oracle_dependency():
                 assert "r3d_oracle" not in txt and "from oracle" not in txt and "import oracle" not in txt, f
 
 
+# The kernel sources carry no experiment switches (DESIGN "Retired experiment switches"): a build option or an environment variable read inside the library
+# is a deliberate addition to one of these two lists, with its test, not a silent #ifndef.
+CSRC_CONDITIONAL_MACROS = {"R3D_STAMPS"}          # the instrumented build (scripts/gpu_*_stamps.py)
+CSRC_GETENV_NAMES = {"R3D_CONV_WINO"}             # include/r3d_hip.h; tests/test_gpu_wino.py
+
+
+def test_kernel_sources_carry_no_experiment_switches():
+    csrc = os.path.join(ROOT, "real3dportrait_amd", "csrc")
+    files = sorted(f for f in os.listdir(csrc) if f.endswith((".hip", ".h")))
+    assert len(files) >= 10
+    for f in files:
+        src = open(os.path.join(csrc, f)).read()
+        lines = src.split("\n")
+        for i, ln in enumerate(lines):
+            m = re.match(r"\s*#\s*(if|ifdef|ifndef|elif)\b([^/]*)", ln)           # (#else / #endif belong to one of these)
+            if not m:
+                continue
+            names = set(re.findall(r"[A-Za-z_]\w*", m.group(2))) - {"defined"}
+            include_guard = m.group(1) == "ifndef" and len(names) == 1 and re.match(r"\s*#\s*define\s+%s\s*$" % min(names), lines[i + 1]) is not None
+            assert include_guard or (names and names <= CSRC_CONDITIONAL_MACROS), "%s:%d: %s" % (f, i + 1, ln.strip())
+        for m in re.finditer(r"getenv\s*\(([^)]*)\)", src):
+            assert m.group(1).strip().strip('"') in CSRC_GETENV_NAMES, "%s: getenv(%s)" % (f, m.group(1))
+
+
 def test_render_workspace_grows_for_the_shapes_that_park_colours():
     """r3d_render_workspace_bytes: per-ray limits + the fold record, plus -- when Nc or Nf exceeds 48 AND there is a fine pass, i.e. the kernel shapes that
     park a ray's colours -- grid x 4 waves x 2 (6 + 6) tiles x 1 KB, with the grid the launch really uses (round 6, ADVICE r5: a fixed 48 MB before)."""

@@ -195,7 +195,7 @@ SPIKES = [6, 10, 14]
 # EVERY spike since round 5: its activation records are OCP e5m2 (a per-element exponent, 29 binades of normal range under the fold's bound),
 # so the typical outputs no longer depend on how far the tensor's bound sits above them.  Until round 4 the records were e4m3 with one exponent
 # per tensor and went subnormal from max / rms = 2^10 on (far 1.6e-4 at 2^10, 3.6e-4 at 2^14: asserted 1e-3 then, and the reason 'f16mx' was
-# not the library default); profiles/r05/mx_format_model.txt is the numpy model of both formats, `make EXTRA=-DR3D_MX_ACT_E4M3=1` the A/B build.
+# not the library default); profiles/r05/mx_format_model.txt is the numpy model of both formats (the e4m3 A/B build is retired: DESIGN.md, "Retired experiment switches").
 # Round 6: the f16mx tiers are asserted at 1e-4 near / 5e-5 far instead of at the stated tolerance itself (measured 6.3e-5 / 2.5e-5
 # in round 5: a 3 x regression would have passed unnoticed).  The far figure only means something where a spike has a far field (`where == "input"`).
 _TIER = {"f16x3": 2e-5, "f16mx": 1e-4}
