@@ -431,6 +431,37 @@ int r3d_secc_dwconv_gelu(const float* x, int B, int H, int W, int C, const float
 int r3d_secc_head(const float* c1, int B, int H1, int W1, const float* w1f, const float* f2, const float* f3, const float* f4,
                   const float* hconst, const float* bn_scale, const float* bn_shift, float* out, r3d_stream_t stream);
 
+/* --- torso generator: the second half of the face-vid2vid torso network, inference (ABI 0.8.0) --------------------------------
+ * WarpBasedTorsoModelMediaPipe.infer_forward_stage2 (modules/real3d/facev2v_warp/model2.py:329-336) = deform_based_generator, the
+ * Generator of network2.py:248-301 (a trilinear warp of the appearance volume, then in_conv, mid_conv, six ResBlock2D, two UpBlock2D
+ * and out_conv), and occlusion_2_predictor (model2.py:212-219, called at :262).  Exact fp32 (every product of the convolutions on the
+ * f32 MFMA).  Activations are channel-last [B, H, W, C]; conv weights [Cout, Cin, k, k] are passed as [Cout, k, k, Cin] with spectral
+ * norm and the eval BatchNorms folded in once per parameter version by the Python module (real3dportrait_amd/torso_generator.py). */
+
+/* fs [N, C, D, H, W] -> out [N, D, H, W, C]: the source layout of r3d_torso_warp (the appearance features are constant over a clip;
+ * the Python module caches this copy).  out must not overlap fs. */
+int r3d_torso_volume_to_cl(const float* fs, int N, int C, int D, int H, int W, float* out, r3d_stream_t stream);
+/* Generator.get_deformed_feature (network2.py:297-301): F.grid_sample(fs, grid, align_corners=True, padding_mode='border') of a 5-D
+ * volume.  fs_cl [N, D, H, W, C] (r3d_torso_volume_to_cl), grid [N, Do, Ho, Wo, 3] with component 0 indexing W, 1 H, 2 D:
+ * i = (g + 1) / 2 * (size - 1) clipped to [0, size - 1], trilinear over floor(i) and floor(i) + 1 (a corner equal to `size` has weight 0
+ * and is not read).  NaN grid entries are not defined.  out: channel_last == 0: [N, C, Do, Ho, Wo], the reference's tensor before its
+ * .view(N, C D, H, W); channel_last != 0: [N, Ho, Wo, C Do] with channel c Do + d, the same tensor as the next conv reads it.
+ * out must not overlap an input. */
+int r3d_torso_warp(const float* fs_cl, int N, int C, int D, int H, int W, const float* grid, int Do, int Ho, int Wo, float* out,
+                   int channel_last, r3d_stream_t stream);
+/* Stride-1 convolution, ksize 1, 3 or 7, zero padding ksize / 2 (nn.Conv2d(Cin, Cout, k, 1, k // 2)) over an Hs x Ws image, or
+ * (upsample = 1) over its nearest x2 up-sampling, which is read through the tap addresses x[h >> 1, w >> 1] and never written
+ * (UpBlock2D, layers.py:77-93).  x [B, Hs, Ws, Cin], or [B, Cin, Hs, Ws] with in_nchw != 0 (the predictor's concatenated input).
+ * Prologue (pro_scale, pro_shift [Cin], both or neither): each tap is a = pro_scale[c] x + pro_shift[c], then a < 0 ? pro_slope a : a,
+ * and 0 outside the image after that -- the BatchNorm + ReLU in front of the padded conv of a "NAC" block (ResBlock2D, layers.py:96-105).
+ * w [Cout, ksize, ksize, Cin]; bias [Cout] or NULL.  Epilogue: v = sum + bias; act 0: none, 1: v < 0 ? act_slope v : v (ReLU: slope 0),
+ * 2: sigmoid; then + residual [B, H, W, Cout] (may be y itself).  Outputs with H = Hs << upsample, W = Ws << upsample: y [B, H, W, Cout]
+ * and / or y_nchw [B, Cout, H, W] (at least one).  Any Cin, Cout in 1 .. 4096; x, w and the prologue vectors are read 16 bytes at a time
+ * when Cin % 4 == 0, the input is channel-last and they are 16-byte aligned.  Outputs must not overlap an input or each other. */
+int r3d_torso_conv(const float* x, int B, int Hs, int Ws, int Cin, int in_nchw, int upsample, const float* pro_scale,
+                   const float* pro_shift, float pro_slope, const float* w, const float* bias, int Cout, int ksize, int act,
+                   float act_slope, const float* residual, float* y, float* y_nchw, r3d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

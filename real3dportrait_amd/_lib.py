@@ -74,6 +74,9 @@ SIGNATURES = {
     "r3d_secc_attention": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, c_float, P, P]),
     "r3d_secc_dwconv_gelu": (c_int, [P, c_int, c_int, c_int, c_int, P, P, P, P]),
     "r3d_secc_head": (c_int, [P, c_int, c_int, c_int, P, P, P, P, P, P, P, P, P]),
+    "r3d_torso_volume_to_cl": (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, P]),
+    "r3d_torso_warp": (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, c_int, c_int, c_int, P, c_int, P]),
+    "r3d_torso_conv": (c_int, [P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, c_float, P, P, c_int, c_int, c_int, c_float, P, P, P, P]),
 }
 
 
@@ -93,7 +96,7 @@ class ChainOp(ctypes.Structure):
 
 CHAIN_SR_BLOCK, CHAIN_CONV, CHAIN_SR_BLOCK_TAIL, CHAIN_SRC_NONE, CHAIN_MAX_OPS, CHAIN_MAX_EXT, CHAIN_MAX_ZERO = 0, 1, 2, -1000, 12, 4, 4
 
-ABI_VERSION = 70          # r3d_version() of the library this table mirrors (include/r3d_hip.h)
+ABI_VERSION = 80          # r3d_version() of the library this table mirrors (include/r3d_hip.h)
 _lib = None
 
 

@@ -276,3 +276,107 @@ def synth_secc_backbone(seed, pncc_cond_mode="cano_src_tgt", out_channels=96, qk
                 v[: shape[0] // 2] *= np.float32(qk_gain)
         sd[key] = np.asarray(v, dtype=np.int64 if last == "num_batches_tracked" else np.float32)
     return sd
+
+
+TORSO_C, TORSO_D = 32, 16          # the appearance volume [N, 32, 16, H, W] (facev2v_warp/network2.py:248-256)
+
+
+def torso_generator_shapes():
+    """[(state_dict key, shape)] of Generator() at standard / small scale (modules/real3d/facev2v_warp/network2.py:248-280): 139 entries."""
+    sn = lambda p, co, ci, k: [(p + "bias", (co,)), (p + "weight_orig", (co, ci, k, k)), (p + "weight_u", (co,)), (p + "weight_v", (ci * k * k,))]
+    bn = lambda p, c: [(p + n, (c,)) for n in ("weight", "bias", "running_mean", "running_var")] + [(p + "num_batches_tracked", ())]
+    out = sn("in_conv.layers.0.", 256, TORSO_C * TORSO_D, 3) + bn("in_conv.layers.1.", 256)
+    out += [("mid_conv.weight", (256, 256, 1, 1)), ("mid_conv.bias", (256,))]
+    for i in range(6):
+        for j in range(2):
+            p = "res.%d.layers.%d.layers." % (i, j)
+            out += bn(p + "0.", 256) + sn(p + "2.", 256, 256, 3)
+    for i, (ci, co) in enumerate(((256, 128), (128, 64))):
+        p = "up.%d.layers.1.layers." % i
+        out += sn(p + "0.", co, ci, 3) + bn(p + "1.", co)
+    return out + [("out_conv.weight", (3, 64, 7, 7)), ("out_conv.bias", (3,))]
+
+
+def torso_predictor_shapes():
+    """occlusion_2_predictor (facev2v_warp/model2.py:212-219)."""
+    out = []
+    for i, (ci, co) in zip((0, 2, 4), ((65, 32), (32, 32), (32, 1))):
+        out += [("%d.weight" % i, (co, ci, 3, 3)), ("%d.bias" % i, (co,))]
+    return out
+
+
+def synth_torso_generator(seed):
+    """A full state_dict (numpy) of the torso Generator.  Conv weights ~ N(0, gain^2 / fan_in); a spectral-normed conv's gain alternates
+    between 0.5 and 2 from layer to layer, so that sigma is far from 1 everywhere (the effective weight, weight_orig / sigma, does not
+    depend on it).  weight_u / weight_v come from one power iteration on weight_orig started at a hash vector, then perturbed by 10 %:
+    random u, v would make sigma tiny and the activations astronomically large.  BatchNorm: weight 1.5 (1 + 0.1 n) (it makes up for the
+    1 / sigma and the ReLU in front of each conv), bias and running_mean 0.3 n, running_var in [0.5, 2]."""
+    sd = {}
+    shapes = torso_generator_shapes()
+    n_sn = 0
+    for i, (key, shape) in enumerate(shapes):
+        st = 3000 + i
+        last = key.rsplit(".", 1)[-1]
+        if last in ("weight_u", "weight_v"):
+            continue                                                 # with their weight_orig
+        if last == "num_batches_tracked":
+            v = np.array(0, dtype=np.int64)
+        elif last == "running_var":
+            v = np.float32(0.5) + np.float32(1.5) * hash_uniform(seed, shape[0], st)
+        elif last == "running_mean" or (last == "bias" and len(shape) == 1 and (key[:-4] + "running_mean") in dict(shapes)):
+            v = hash_unitvar(seed, shape, st) * np.float32(0.3)
+        elif last == "bias":
+            v = hash_unitvar(seed, shape, st) * np.float32(0.1)
+        elif len(shape) == 1:                                        # BatchNorm weight
+            v = np.float32(1.5) * (np.float32(1.0) + hash_unitvar(seed, shape, st) * np.float32(0.1))
+        else:
+            fan_in = int(np.prod(shape[1:]))
+            v = hash_unitvar(seed, shape, st) * np.float32(1.0 / math.sqrt(fan_in))
+            if last == "weight_orig":
+                v = v * np.float32(2.0 if n_sn % 2 else 0.5)
+                n_sn += 1
+                wm = v.reshape(shape[0], -1).astype(np.float64)
+                unit = lambda a: a / np.linalg.norm(a)
+                v0 = unit(hash_unitvar(seed, (wm.shape[1],), st + 500).astype(np.float64))
+                u = unit(wm @ v0)
+                vv = unit(wm.T @ u)
+                u = unit(u + 0.1 * hash_unitvar(seed, u.shape, st + 1000) / math.sqrt(u.size))
+                vv = unit(vv + 0.1 * hash_unitvar(seed, vv.shape, st + 1500) / math.sqrt(vv.size))
+                sd[key[:-4] + "u"], sd[key[:-4] + "v"] = u.astype(np.float32), vv.astype(np.float32)
+        sd[key] = np.asarray(v, dtype=np.int64 if last == "num_batches_tracked" else np.float32)
+    return {k: sd[k] for k, _ in shapes}
+
+
+def synth_torso_predictor(seed):
+    """occlusion_2_predictor's state_dict: weights ~ N(0, 2 / fan_in) (the first conv's, which reads a non-negative hid at rms of 6 or so,
+    N(0, 0.05 / fan_in)), biases 0.1 n: the output logits stay O(1), a sigmoid that is neither saturated nor flat."""
+    sd = {}
+    for i, (key, shape) in enumerate(torso_predictor_shapes()):
+        if len(shape) == 1:
+            sd[key] = hash_unitvar(seed, shape, 3400 + i) * np.float32(0.1)
+        else:
+            sd[key] = hash_unitvar(seed, shape, 3400 + i) * np.float32(math.sqrt((0.05 if i == 0 else 2.0) / int(np.prod(shape[1:]))))
+    return sd
+
+
+def synth_torso_inputs(seed, N=1, H=64, W=64, noise=0.15):
+    """Inputs of WarpBasedTorsoModelMediaPipe.infer_forward_stage2 and of the forward tail after it (facev2v_warp/model2.py:260-263):
+    torso_appearance_feats [N, 32, 16, H, W] (unit variance), deformation [N, 16, H, W, 3] = the identity grid of align_corners=True + a
+    smooth field of amplitude 0.1 + `noise` x N(0, 1), with a few rows forced to exactly -1, exactly 1 and exactly the identity (on source
+    nodes), occlusion [N, 1, H, W] and the low-resolution occlusion_2 [N, 1, H, W] in [0, 1].  Every sample differs."""
+    D = TORSO_D
+    fs = hash_unitvar(seed, (N, TORSO_C, D, H, W), stream=11)
+    lin = lambda n: (np.linspace(-1.0, 1.0, n) if n > 1 else np.zeros(1)).astype(np.float32)
+    ident = np.stack(np.broadcast_arrays(lin(W)[None, None, :], lin(H)[None, :, None], lin(D)[:, None, None]), axis=-1).astype(np.float32)
+    zz, yy, xx = np.meshgrid(lin(D), lin(H), lin(W), indexing="ij")
+    grid = np.empty((N, D, H, W, 3), np.float32)
+    for n in range(N):
+        smooth = np.stack([np.sin(2.0 * yy + 3.0 * zz + n), np.cos(2.5 * xx - zz + 2 * n), np.sin(1.5 * xx + 2.0 * yy - n)], axis=-1)
+        grid[n] = ident + np.float32(0.1) * smooth.astype(np.float32) + np.float32(noise) * hash_unitvar(seed, (D, H, W, 3), stream=12 + 10 * n)
+    grid[:, 0, 0, :, :] = ident[0, 0]                  # exactly on source nodes
+    grid[:, -1, -1, :, :] = ident[-1, -1]
+    grid[:, D // 2, H // 2, : W // 2, :] = -1.0
+    grid[:, D // 2, H // 2, W // 2:, :] = 1.0
+    occ = hash_uniform(seed, N * H * W, stream=13).reshape(N, 1, H, W)
+    occ2 = hash_uniform(seed, N * H * W, stream=14).reshape(N, 1, H, W)
+    return {"torso_appearance_feats": fs, "deformation": grid, "occlusion": occ, "occlusion_2": occ2}

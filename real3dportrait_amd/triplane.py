@@ -180,7 +180,7 @@ def _reference_hparams(model):
     return hp
 
 
-def patch_model(model, fuse_warp_sr=True, precision=None, secc_encoder=False):
+def patch_model(model, fuse_warp_sr=True, precision=None, secc_encoder=False, torso_generator=False):
     """Swap the hot-path operators of a constructed reference model for the HIP ones (in place).  INFERENCE ONLY: the HIP modules
     detach their inputs and build no autograd graph (the reference runs this path under torch.no_grad(), real3d_infer.py:435,479).
     precision: SR precision of the installed blocks (None = the library default 'f16mx': inside the 2e-4 of SURVEY 8(d) on every golden and heavy-tail sweep,
@@ -199,6 +199,11 @@ def patch_model(model, fuse_warp_sr=True, precision=None, secc_encoder=False):
     * secc_encoder=True (opt-in): model.secc_img2plane_backbone, when it is the reference's SegFormerSECC2PlaneBackbone in mode b0
       (segformer.py:672-731), -> the HIP SegFormerSECC2PlaneBackbone (segformer.py of this package: prenet, MiT-b0 and the head in
       exact fp32, to_plane_cnn as a ConvStack).  Other backbones are left as they are.
+    * torso_generator=True (opt-in): model.superresolution.torso_model.deform_based_generator, when it is the reference's Generator at
+      standard / small scale (facev2v_warp/network2.py:248-301), -> the HIP Generator, and torso_model.occlusion_2_predictor
+      (model2.py:212-219) -> the HIP Occlusion2Predictor (torso_generator.py of this package: the warp and every conv in exact fp32).
+      torso_model.forward and infer_forward_stage2 reach them unchanged; the appearance extractor and the motion-field estimator
+      (stage 1) stay PyTorch.  Other generators are left as they are.
     Parameters are copied with strict key matching; the decoder module is left untouched (the renderer reads
     decoder.net[0|2].{weight,bias} directly)."""
     import types
@@ -245,6 +250,13 @@ def patch_model(model, fuse_warp_sr=True, precision=None, secc_encoder=False):
                 and getattr(bb, "mode", None) == "b0"):
             from .segformer import SegFormerSECC2PlaneBackbone as HipSECC
             model.secc_img2plane_backbone = HipSECC.from_reference(bb)
+    if torso_generator:
+        from . import torso_generator as tg
+        tm = getattr(model.superresolution, "torso_model", None)
+        if tm is not None and tg.is_reference_generator(getattr(tm, "deform_based_generator", None)):
+            tm.deform_based_generator = tg.Generator.from_reference(tm.deform_based_generator)
+            if tg.is_reference_predictor(getattr(tm, "occlusion_2_predictor", None)):
+                tm.occlusion_2_predictor = tg.Occlusion2Predictor.from_reference(tm.occlusion_2_predictor)
     for owner in (getattr(model, "secc_img2plane_backbone", None), getattr(model, "img2plane_backbone", None)):
         _patch_sequential(owner, "to_plane_cnn", dev)       # per-frame plane producer tail (segformer.py:691-700)
     from .superresolution import set_sr_precision

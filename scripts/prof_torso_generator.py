@@ -1,0 +1,126 @@
+"""Time the torso generator (Generator + occlusion_2_predictor) at B = 1 and the product size (64^2 feature grid, 256^2
+output) and print one JSON line:
+
+  * the HIP modules (real3dportrait_amd/torso_generator.py) against eager fp32 torch of the same math on the same GPU: F.grid_sample,
+    then tests/torso_ref64.py in float32, which recomputes weight_orig / sigma per call as the reference's spectral-norm hook does in
+    eval mode.  Both sides include the forward tail's F.interpolate + torch.cat in front of the predictor.  Device events around every
+    call, `calls` calls per block, the two sides alternated for `blocks` blocks each after a warm-up; reported: the median of the
+    block medians and the spread (max - min) of the block medians, in ms;
+  * kernel launches of the HIP forward (counted at the C entry points);
+  * the share of the fp32-matrix floor (92.5 GFLOP / 157.3 TFLOP/s = 0.588 ms) the HIP forward reaches.
+
+    python scripts/prof_torso_generator.py [--calls 200] [--blocks 5] [--out DIR]     (writes DIR/prof_torso_generator.json)
+    python scripts/prof_torso_generator.py --forwards 20        only runs that many HIP forwards after a warm-up, for
+        rocprofv3 --kernel-trace --stats -d DIR -o torso -- python scripts/prof_torso_generator.py --forwards 20
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+import torch.nn.functional as F  # noqa: E402
+
+import torso_ref64 as R  # noqa: E402
+from real3dportrait_amd import _lib, synth  # noqa: E402
+from real3dportrait_amd.torso_generator import Generator, Occlusion2Predictor  # noqa: E402
+
+GFLOP, PEAK_TFLOPS = 92.5, 157.3
+
+
+def block_median(fn, calls):
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(calls + 1)]
+    ev[0].record()
+    for i in range(calls):
+        fn()
+        ev[i + 1].record()
+    ev[-1].synchronize()
+    return statistics.median(ev[i].elapsed_time(ev[i + 1]) for i in range(calls))
+
+
+def count_launches(fn):
+    lib = _lib.load()
+    names = [n for n in _lib.SIGNATURES if n.startswith("r3d_torso_")]
+    orig = {n: getattr(lib, n) for n in names}
+    count = {n: 0 for n in names}
+
+    def wrap(n, f):
+        def g(*a):
+            count[n] += 1
+            return f(*a)
+        return g
+
+    for n in names:
+        setattr(lib, n, wrap(n, orig[n]))
+    try:
+        fn()
+    finally:
+        for n in names:
+            setattr(lib, n, orig[n])
+    return count
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--calls", type=int, default=200)
+    ap.add_argument("--blocks", type=int, default=5)
+    ap.add_argument("--forwards", type=int, default=0)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    dev = "cuda:0"
+    T = lambda sd: {k: torch.from_numpy(np.ascontiguousarray(v)) for k, v in sd.items()}
+    sd, psd = synth.synth_torso_generator(71), synth.synth_torso_predictor(72)
+    gen, pred = Generator(), Occlusion2Predictor()
+    gen.load_state_dict(T(sd), strict=True)
+    pred.load_state_dict(T(psd), strict=True)
+    gen, pred = gen.to(dev).eval(), pred.to(dev).eval()
+    i = {k: torch.from_numpy(v).to(dev) for k, v in synth.synth_torso_inputs(73, 1, 64, 64).items()}
+    sdd, psdd = {k: v.to(dev) for k, v in T(sd).items()}, {k: v.to(dev) for k, v in T(psd).items()}
+    fs, grid, occ, occ2 = i["torso_appearance_feats"], i["deformation"], i["occlusion"], i["occlusion_2"]
+
+    def hip():
+        rgb, hid = gen(fs, grid, occ, return_hid=True)
+        return rgb, hid, pred(torch.cat([hid, F.interpolate(occ2, size=(256, 256), mode="bilinear")], dim=1))
+
+    def eager():
+        d = F.grid_sample(fs, grid, align_corners=True, padding_mode="border").view(1, -1, 64, 64)
+        rgb, hid = R.decoder(sdd, d, torch.float32)
+        return rgb, hid, R.predictor(psdd, torch.cat([hid, F.interpolate(occ2, size=(256, 256), mode="bilinear")], dim=1), torch.float32)
+
+    with torch.no_grad():
+        if a.forwards:
+            for _ in range(5 + a.forwards):
+                hip()
+            torch.cuda.synchronize()
+            return
+        for _ in range(10):
+            hip()
+            eager()
+        hb, eb = [], []
+        for _ in range(a.blocks):
+            hb.append(block_median(hip, a.calls))
+            eb.append(block_median(eager, a.calls))
+        launches = count_launches(hip)
+        diffs = [float((x - y).abs().max() / y.abs().max()) for x, y in zip(hip(), eager())]
+    h, e = statistics.median(hb), statistics.median(eb)
+    out = {"metric": "torso_generator_b1_64", "B": 1, "grid": [64, 64], "calls_per_block": a.calls, "blocks": a.blocks,
+           "hip_ms": round(h, 4), "hip_block_medians_ms": [round(v, 4) for v in hb], "hip_spread_ms": round(max(hb) - min(hb), 4),
+           "eager_fp32_torch_ms": round(e, 4), "eager_block_medians_ms": [round(v, 4) for v in eb], "eager_spread_ms": round(max(eb) - min(eb), 4),
+           "speedup_vs_eager": round(e / h, 3), "faster_by_more_than_the_spread": bool(e - h > max(max(hb) - min(hb), max(eb) - min(eb))),
+           "launches_per_forward": sum(launches.values()), "launches_by_entry_point": launches,
+           "fp32_matrix_floor_ms": round(GFLOP / PEAK_TFLOPS, 4), "share_of_floor": round(GFLOP / PEAK_TFLOPS / h, 3),
+           "hip_vs_eager_max_rel_diff_rgb_hid_occ2": diffs}
+    print(json.dumps(out))
+    if a.out:
+        os.makedirs(a.out, exist_ok=True)
+        with open(os.path.join(a.out, "prof_torso_generator.json"), "w") as f:
+            f.write(json.dumps(out, indent=1) + "\n")
+
+
+if __name__ == "__main__":
+    main()
