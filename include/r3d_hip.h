@@ -462,6 +462,50 @@ int r3d_torso_conv(const float* x, int B, int Hs, int Ws, int Cin, int in_nchw, 
                    const float* pro_shift, float pro_slope, const float* w, const float* bias, int Cout, int ksize, int act,
                    float act_slope, const float* residual, float* y, float* y_nchw, r3d_stream_t stream);
 
+/* --- torso motion field: the per-frame first half of the face-vid2vid torso network, inference (added under ABI 0.8.0) --------
+ * MotionFieldEstimator.forward (modules/real3d/facev2v_warp/network2.py:204-236) and create_occlusion (:239-244), as
+ * WarpBasedTorsoModelMediaPipe.forward calls it (model2.py:250).  Exact fp32.  Activations are channel-last [N, D, H, W, C]; Conv3d
+ * weights [Cout, Cin, kd, kh, kw] are passed as [Cout, kd, kh, kw, Cin] with the eval BatchNorms folded in and the channel groups
+ * padded to multiples of 4 (zero columns) once per parameter version by the Python module (real3dportrait_amd/torso_motion.py).
+ * Grid components: 0 indexes W, 1 H, 2 D (func_utils.py:91-103). */
+
+/* Stride-1 Conv3d with a cubic kernel, ksize 1, 3 or 7, zero padding ksize / 2 in depth, height and width (nn.Conv3d(Cin, Cout, k, 1,
+ * k // 2): compress / the convs of DownBlock3D and UpBlock3D / tgt_head_fuser / mask_conv, network2.py:187-197), the same kernel as
+ * r3d_torso_conv with a depth tap.  x [B, D, Hs, Ws, Cin]; w [Cout, ksize, ksize, ksize, Cin]; bias [Cout] or NULL.
+ * upsample = 1: the conv runs over the nearest x2 up-sampling of H and W (not D), read through the tap addresses x[d, h >> 1, w >> 1] and
+ *   never written (UpBlock3D: nn.Upsample(scale_factor=(1, 2, 2)), layers.py:77-93).
+ * Epilogue: v = sum + bias; act 0: none, 1: v < 0 ? act_slope v : v, 2: sigmoid.
+ * pool = 1: then the average of each 2 x 2 window of H and W (DownBlock3D: conv, BatchNorm, ReLU, nn.AvgPool3d((1, 2, 2)), layers.py:
+ *   58-75); the un-pooled tensor is never written; an odd H or W is R3D_ERR_INVALID_ARG, and y_ncdhw must be NULL.
+ * full_depth = 1: one output depth, the depth kernel spans all of D without padding, w [Cout, D, ksize, ksize, Cin]: nn.Conv2d(Cin D,
+ *   Cout, k, 1, k // 2) on x.view(N, Cin D, H, W) of the NCDHW tensor (occlusion_conv / occlusion_conv2, network2.py:199-200,233,239-244),
+ *   whose weight [Cout, Cin D, k, k] the caller passes as .view(Cout, Cin, D, k, k).permute(0, 2, 3, 4, 1).
+ * Outputs, with H = Hs << upsample, W = Ws << upsample, Do = full_depth ? 1 : D: y, rows of y_cstride floats, one per (b, d, h, w) (per
+ *   pooled position with pool = 1), of which this conv writes channels [y_coffset, y_coffset + Cout) and leaves the others untouched (a
+ *   slice of a concatenation); and / or y_ncdhw [B, Cout, Do, H, W].  Any Cin, Cout in 1 .. 4096, D <= 1024; x and w are read 16 bytes
+ *   at a time when Cin % 4 == 0 and they are 16-byte aligned.  Outputs must not overlap an input or each other. */
+int r3d_torso_conv3d(const float* x, int B, int D, int Hs, int Ws, int Cin, int upsample, const float* w, const float* bias,
+                     int Cout, int ksize, int full_depth, int act, float act_slope, int pool, float* y, int y_cstride,
+                     int y_coffset, float* y_ncdhw, r3d_stream_t stream);
+/* The hourglass input (network2.py:205-214; func_utils.py:139-191): compress (nn.Conv3d(C, 4, 1)), create_heatmap_representations,
+ * create_sparse_motions and create_deformed_source_image in one pass.  fs_cl [N, D, H, W, C] (r3d_torso_volume_to_cl), compress_w [4, C],
+ * compress_b [4], kp_s / kp_d [N, K, 3], J [N, 3, 3] = Rs Rd^-1.  For voxel p with grid point g and k = 0 .. K: the sparse motion is
+ * s = g (k = 0) or J (g - kp_d[k-1]) + kp_s[k-1]; channel 5 k of the output is exp(-|g - kp_d[k-1]|^2 / 0.02) - exp(-|g - kp_s[k-1]|^2
+ * / 0.02) (0 for k = 0), channels 5 k + 1 .. 5 k + 4 are F.grid_sample(compressed, s, align_corners=True, padding_mode='zeros'): trilinear,
+ * a corner outside the volume contributes 0.  inp [N, D, H, W, inp_channels], inp_channels >= 5 (K + 1), the channels from 5 (K + 1) on
+ * written 0; fuse (or NULL): the same inp_channels channels at the start of rows of fuse_cstride floats.  D, H, W >= 2, K <= 64. */
+int r3d_torso_motion_input(const float* fs_cl, int N, int C, int D, int H, int W, const float* compress_w, const float* compress_b,
+                           const float* kp_s, const float* kp_d, const float* J, int K, float* inp, int inp_channels, float* fuse,
+                           int fuse_cstride, r3d_stream_t stream);
+/* deformation = sum_k softmax_k(mask) sparse_motion_k (network2.py:227-231): mask [N, D, H, W, K + 1] (mask_conv's logits), the sparse
+ * motions recomputed as in r3d_torso_motion_input; out [N, D, H, W, 3], the grid r3d_torso_warp reads. */
+int r3d_torso_motion_deform(const float* mask, int N, int D, int H, int W, int K, const float* kp_s, const float* kp_d, const float* J,
+                            float* out, r3d_stream_t stream);
+/* tgt_head_feats.unsqueeze(2).repeat(1, 1, D, 1, 1) into its slice of the fuser's input (network2.py:224): feats [N, C, H, W] ->
+ * channels [fuse_coffset, fuse_coffset + C) of fuse [N, D, H, W, fuse_cstride]. */
+int r3d_torso_motion_broadcast(const float* feats, int N, int C, int H, int W, int D, float* fuse, int fuse_cstride, int fuse_coffset,
+                               r3d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,6 +7,7 @@ Operators keep the reference's names and signatures (see each module's docstring
     TriPlaneGenerator (.synthesis contract), patch_model (triplane.py)
     SegFormerSECC2PlaneBackbone                          (segformer.py: the per-frame SECC encoder, mode b0)
     TorsoGenerator, Occlusion2Predictor                  (torso_generator.py: the torso network's warp + decoder, its Generator)
+    TorsoMotionFieldEstimator                            (torso_motion.py: the torso network's per-frame MotionFieldEstimator)
     render_clip_sharded                                  (frames.py: frame sharding + RCCL gather)
 All compute goes through libr3d_hip.so (include/r3d_hip.h); there is no eager/CPU fallback.
 """
@@ -29,6 +30,9 @@ def __getattr__(name):      # lazy: importing the package (e.g. for synth) must 
     if name in ("TorsoGenerator", "Occlusion2Predictor"):
         from . import torso_generator as m
         return getattr(m, "Generator" if name == "TorsoGenerator" else name)
+    if name == "TorsoMotionFieldEstimator":
+        from . import torso_motion as m
+        return m.MotionFieldEstimator
     if name in ("render_clip_sharded", "shard_frames"):
         from . import frames as m
         return getattr(m, name)

@@ -77,6 +77,10 @@ SIGNATURES = {
     "r3d_torso_volume_to_cl": (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, P]),
     "r3d_torso_warp": (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, c_int, c_int, c_int, P, c_int, P]),
     "r3d_torso_conv": (c_int, [P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, c_float, P, P, c_int, c_int, c_int, c_float, P, P, P, P]),
+    "r3d_torso_conv3d": (c_int, [P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, c_int, c_int, c_int, c_int, c_float, c_int, P, c_int, c_int, P, P]),
+    "r3d_torso_motion_input": (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, P, P, P, P, c_int, P, c_int, P, c_int, P]),
+    "r3d_torso_motion_deform": (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, P, P, P, P]),
+    "r3d_torso_motion_broadcast": (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, c_int, c_int, P]),
 }
 
 
@@ -126,7 +130,11 @@ def load():
     except OSError as e:
         raise RuntimeError("real3dportrait_amd: cannot load %s: %s" % (LIB_PATH, e))
     for name, (res, args) in SIGNATURES.items():
-        fn = getattr(lib, name)      # AttributeError if the ABI and this table drift apart
+        try:
+            fn = getattr(lib, name)
+        except AttributeError:       # functions are added without a new ABI number: a stale in-tree build lacks them
+            raise RuntimeError("real3dportrait_amd: %s does not export %s, which this package binds -- rebuild it (`make -C %s`)"
+                               % (LIB_PATH, name, CSRC))
         fn.restype, fn.argtypes = res, args
     for name, (res, args) in OPTIONAL_SIGNATURES.items():
         fn = getattr(lib, name, None)

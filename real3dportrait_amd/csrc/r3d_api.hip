@@ -143,7 +143,7 @@ __global__ void person_occlusion_kernel(const float* __restrict__ alpha, const f
 
 using namespace r3d;
 
-extern "C" int r3d_version(void) { return 80; }   // 0.8.0: the torso generator (r3d_torso_*); 0.7.0: the SECC SegFormer encoder (r3d_secc_*); 0.6.1: r3d_conv_forward_blend; 0.6.0: r3d_sr_block_prepacked_bytes grew by conv1's Winograd F(2,3) pack; r3d_render_workspace_bytes follows the real grid (0.5.0: e5m2 activation records); real3dportrait_amd/_lib.py checks the number
+extern "C" int r3d_version(void) { return 80; }   // 0.8.0: the torso generator (r3d_torso_*), and since then, added without a new number (no existing argument list changed): r3d_torso_conv3d, r3d_torso_motion_input / _deform / _broadcast (the motion-field estimator); 0.7.0: the SECC SegFormer encoder (r3d_secc_*); 0.6.1: r3d_conv_forward_blend; 0.6.0: r3d_sr_block_prepacked_bytes grew by conv1's Winograd F(2,3) pack; r3d_render_workspace_bytes follows the real grid (0.5.0: e5m2 activation records); real3dportrait_amd/_lib.py checks the number
 
 extern "C" int r3d_resize_bilinear(const float* x, int planes, int H, int W, float* y, int OH, int OW, int antialias, r3d_stream_t stream)
 {

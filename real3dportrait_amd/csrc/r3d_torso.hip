@@ -7,13 +7,14 @@
 //                        of the C channels.
 //   torso_warp           F.grid_sample(fs, grid, align_corners=True, padding_mode='border') on the 5-D volume, 8 taps per output value.
 //   torso_conv<VEC, WM, WN, TM, TN>
-//                        implicit-GEMM stride-1 convolution, zero padding ksize / 2: a (WM TM 16) x (WN TN 16) tile of pixels x output
+//                        (the D3 = false instantiation of conv_tile, r3d_torso_conv.h) implicit-GEMM stride-1 convolution, zero padding ksize / 2: a (WM TM 16) x (WN TN 16) tile of pixels x output
 //                        channels per 256-thread block, K = (ky, kx, ci) staged 32 at a time through two LDS buffers while the next two
 //                        steps are in flight in registers.  Tap loads apply the prologue act(s[c] x + t[c]) (zero outside the image AFTER it:
 //                        the reference pads the activated tensor) and nearest x2 up-sampling in the addressing; the epilogue adds the bias,
 //                        applies LeakyReLU / sigmoid, adds a residual and writes channel-last and / or NCHW.  VEC: Cin % 4 == 0,
 //                        channel-last input, 16-byte loads; otherwise one element per load (NCHW input, Cin = 65, 3, 1).
 #include "r3d_common.h"
+#include "r3d_torso_conv.h"
 #include <math.h>
 #include <initializer_list>
 
@@ -85,246 +86,11 @@ __global__ void __launch_bounds__(256) torso_warp(WarpArgs a)
     else a.out[((n * a.C + c) * a.Do + d) * hw + px] = acc;
 }
 
-constexpr int BK = 32, LDK = BK + 4;     // LDS rows of 36 floats: 16-byte aligned, and 16 rows at one k offset touch 64 distinct banks
+using tconv::ConvArgs;
 
-struct ConvArgs {
-    const float* x; int B, Hs, Ws, Cin;          // stored input [B, Hs, Ws, Cin] (in_nchw: [B, Cin, Hs, Ws])
-    int H, W;                                    // the conv's grid: Hs x Ws, or twice that (up: the input is x[h >> 1, w >> 1])
-    int up, in_nchw, ks;
-    const float* ps; const float* pt; float pslope;      // prologue a = ps[c] x + pt[c]; a < 0 ? pslope a : a  (ps == nullptr: none)
-    const float* w; int Cout;                    // [Cout, ks, ks, Cin]
-    const float* bias;                           // [Cout] or nullptr
-    int act; float slope;                        // 0 none, 1 v < 0 ? slope v : v, 2 sigmoid
-    const float* res;                            // [M, Cout] or nullptr (may alias y: each element is read, then written, by one lane)
-    float* y; float* y_nchw;                     // [B, H, W, Cout] and / or [B, Cout, H, W]
-    int M, K;
-    int ntn;                                     // tiles along Cout (set by the launcher)
-};
-
-__device__ __forceinline__ float leaky(float v, float slope) { return v < 0.0f ? slope * v : v; }
-
-// the position of a running k = (ky ks + kx) Cin + ci
-struct KPos {
-    int ci, kx, ky;
-    __device__ __forceinline__ void init(int k, int Cin, int ks) { ci = k % Cin; const int tap = k / Cin; ky = tap / ks; kx = tap - ky * ks; }
-    __device__ __forceinline__ void advance(int dk, int Cin, int ks)
-    {
-        ci += dk;
-        while (ci >= Cin) { ci -= Cin; if (++kx == ks) { kx = 0; ++ky; } }
-    }
-};
-
+// the 2-D instantiation of the shared tile (r3d_torso_conv.h)
 template <bool VEC, int WM, int WN, int TM, int TN>
-__global__ void __launch_bounds__(256) torso_conv(ConvArgs g)
-{
-    static_assert(WM * WN == 4, "four waves");
-    constexpr int BM = WM * TM * 16, BN = WN * TN * 16;
-    constexpr int AV = BM / 32, WV = (BN + 31) / 32;           // VEC: float4 loads per thread (A, W)
-    constexpr int AS = BM / 8, WS = BN / 8, KSTEP = 256 / BM;  // scalar: elements per thread; A's k stride between them
-    __shared__ __attribute__((aligned(16))) float As[2][BM * LDK];
-    __shared__ __attribute__((aligned(16))) float Ws[2][BN * LDK];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    // Blocks are dealt to the 8 XCDs round-robin, and each XCD has an L2 of its own: block b takes tile (b % 8) (nblk / 8) + b / 8, so that
-    // one XCD works on neighbouring pixel tiles (which share their taps' rows) and on all channel tiles of each (which share the taps).
-    const int nblk = gridDim.x, bid = blockIdx.x;
-    const int tile = nblk % 8 == 0 ? (bid % 8) * (nblk / 8) + bid / 8 : bid;
-    const int m0 = (tile / g.ntn) * BM, n0 = (tile % g.ntn) * BN;
-    const int pad = g.ks >> 1, hw = g.H * g.W;
-    const int nsteps = (g.K + BK - 1) / BK;
-
-    // ---- loader state ---------------------------------------------------------------------------------------------------------------
-    // VEC: slot j is row (t >> 3) + 32 j of the tile, k entries 4 (t & 7) .. + 3 of the step (one tap, four channels);
-    // scalar: row t % BM, k entries t / BM + KSTEP j (consecutive lanes read consecutive pixels: coalesced for an NCHW input)
-    constexpr int NR = VEC ? AV : 1;
-    int roy[NR], rox[NR]; size_t rbase[NR];                     // a row's pixel (oy < 0: no such row) and its sample's offset
-#pragma unroll
-    for (int j = 0; j < NR; ++j) {
-        const int m = m0 + (VEC ? (t >> 3) + 32 * j : t % BM);
-        if (m < g.M) {
-            const int b = m / hw, r = m - b * hw;
-            roy[j] = r / g.W; rox[j] = r - roy[j] * g.W;
-            rbase[j] = (size_t)b * g.Hs * g.Ws * g.Cin;
-        } else { roy[j] = -1000000; rox[j] = 0; rbase[j] = 0; }
-    }
-    KPos kp;
-    kp.init(VEC ? 4 * (t & 7) : t / BM, g.Cin, g.ks);
-    int kcur = VEC ? 4 * (t & 7) : t / BM;                      // the k of kp
-
-    const int wm = (wave / WN) * TM * 16, wn = (wave % WN) * TN * 16;
-    f32x4 acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j) acc[i][j] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-
-    // the registers of one k step in flight between its global loads and its LDS stores
-    struct Stage {
-        float4 av4[VEC ? AV : 1], wv4[VEC ? WV : 1], ps4, pt4;
-        float avs[VEC ? 1 : AS], wvs[VEC ? 1 : WS], pss[VEC ? 1 : AS], pts[VEC ? 1 : AS];
-        unsigned inside;                                        // bit j: slot / element j came from inside the image
-    };
-    int knext = 0;                                              // the step the next load() fetches (steps are loaded in order)
-
-    auto load = [&](Stage& r) {
-        r.inside = 0;
-        if (knext >= nsteps) return;
-        const int k0 = knext * BK;
-        ++knext;
-        if constexpr (VEC) {
-            const bool kin = kcur < g.K;
-#pragma unroll
-            for (int j = 0; j < AV; ++j) {
-                const int iy = roy[j] - pad + kp.ky, ix = rox[j] - pad + kp.kx;
-                r.av4[j] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-                if (kin && iy >= 0 && iy < g.H && ix >= 0 && ix < g.W) {
-                    const size_t off = rbase[j] + ((size_t)(iy >> g.up) * g.Ws + (ix >> g.up)) * g.Cin + kp.ci;
-                    r.av4[j] = *reinterpret_cast<const float4*>(g.x + off);
-                    r.inside |= 1u << j;
-                }
-            }
-            if (g.ps && kin) {
-                r.ps4 = *reinterpret_cast<const float4*>(g.ps + kp.ci);
-                r.pt4 = *reinterpret_cast<const float4*>(g.pt + kp.ci);
-            }
-#pragma unroll
-            for (int j = 0; j < WV; ++j) {
-                const int row = (t >> 3) + 32 * j, n = n0 + row;
-                r.wv4[j] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-                if (row < BN && n < g.Cout && kin) r.wv4[j] = *reinterpret_cast<const float4*>(g.w + (size_t)n * g.K + kcur);
-            }
-            kp.advance(BK, g.Cin, g.ks);
-            kcur += BK;
-        } else {
-#pragma unroll
-            for (int j = 0; j < AS; ++j) {
-                const int iy = roy[0] - pad + kp.ky, ix = rox[0] - pad + kp.kx;
-                r.avs[j] = 0.0f; r.pss[j] = 1.0f; r.pts[j] = 0.0f;
-                if (kcur < g.K && iy >= 0 && iy < g.H && ix >= 0 && ix < g.W) {
-                    const int sy = iy >> g.up, sx = ix >> g.up;
-                    const size_t off = g.in_nchw ? rbase[0] + ((size_t)kp.ci * g.Hs + sy) * g.Ws + sx
-                                                 : rbase[0] + ((size_t)sy * g.Ws + sx) * g.Cin + kp.ci;
-                    r.avs[j] = g.x[off];
-                    if (g.ps) { r.pss[j] = g.ps[kp.ci]; r.pts[j] = g.pt[kp.ci]; }
-                    r.inside |= 1u << j;
-                }
-                kp.advance(KSTEP, g.Cin, g.ks);
-                kcur += KSTEP;
-            }
-#pragma unroll
-            for (int j = 0; j < WS; ++j) {
-                const int e = t + 256 * j, n = n0 + (e >> 5), k = k0 + (e & 31);
-                r.wvs[j] = (n < g.Cout && k < g.K) ? g.w[(size_t)n * g.K + k] : 0.0f;
-            }
-        }
-    };
-    auto store = [&](const Stage& r, int buf) {
-        if constexpr (VEC) {
-#pragma unroll
-            for (int j = 0; j < AV; ++j) {
-                float4 v = r.av4[j];
-                if (g.ps && (r.inside >> j & 1)) {
-                    v.x = leaky(fmaf(r.ps4.x, v.x, r.pt4.x), g.pslope); v.y = leaky(fmaf(r.ps4.y, v.y, r.pt4.y), g.pslope);
-                    v.z = leaky(fmaf(r.ps4.z, v.z, r.pt4.z), g.pslope); v.w = leaky(fmaf(r.ps4.w, v.w, r.pt4.w), g.pslope);
-                }
-                *reinterpret_cast<float4*>(&As[buf][((t >> 3) + 32 * j) * LDK + 4 * (t & 7)]) = v;
-            }
-#pragma unroll
-            for (int j = 0; j < WV; ++j) {
-                const int row = (t >> 3) + 32 * j;
-                if (row < BN) *reinterpret_cast<float4*>(&Ws[buf][row * LDK + 4 * (t & 7)]) = r.wv4[j];
-            }
-        } else {
-#pragma unroll
-            for (int j = 0; j < AS; ++j) {
-                float v = r.avs[j];
-                if (g.ps && (r.inside >> j & 1)) v = leaky(fmaf(r.pss[j], v, r.pts[j]), g.pslope);
-                As[buf][(t % BM) * LDK + t / BM + KSTEP * j] = v;
-            }
-#pragma unroll
-            for (int j = 0; j < WS; ++j) { const int e = t + 256 * j; Ws[buf][(e >> 5) * LDK + (e & 31)] = r.wvs[j]; }
-        }
-    };
-    // one k step of the block's tile out of LDS buffer `cur`
-    auto compute = [&](int cur) {
-        // lane group lane >> 4 owns k entries 8 (lane >> 4) .. + 7 of the step, one per MFMA: the order of the sum is fixed, whichever
-        float a[TM][8], b[TN][8];
-#pragma unroll
-        for (int i = 0; i < TM; ++i) {
-            const float* p = &As[cur][(wm + i * 16 + (lane & 15)) * LDK + 8 * (lane >> 4)];
-            const float4 lo = *reinterpret_cast<const float4*>(p), hi = *reinterpret_cast<const float4*>(p + 4);
-            a[i][0] = lo.x; a[i][1] = lo.y; a[i][2] = lo.z; a[i][3] = lo.w; a[i][4] = hi.x; a[i][5] = hi.y; a[i][6] = hi.z; a[i][7] = hi.w;
-        }
-#pragma unroll
-        for (int j = 0; j < TN; ++j) {
-            const float* p = &Ws[cur][(wn + j * 16 + (lane & 15)) * LDK + 8 * (lane >> 4)];
-            const float4 lo = *reinterpret_cast<const float4*>(p), hi = *reinterpret_cast<const float4*>(p + 4);
-            b[j][0] = lo.x; b[j][1] = lo.y; b[j][2] = lo.z; b[j][3] = lo.w; b[j][4] = hi.x; b[j][5] = hi.y; b[j][6] = hi.z; b[j][7] = hi.w;
-        }
-#pragma unroll
-        for (int kk = 0; kk < 8; ++kk)
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-#pragma unroll
-                for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i][kk], b[j][kk], acc[i][j], 0, 0, 0);
-    };
-
-    // Two register stages and two LDS buffers: step s is computed out of buffer s & 1 while step s + 1 (loaded one iteration earlier)
-    // goes from its stage into the other buffer and step s + 3 leaves for that stage, so a load has two compute phases to arrive.
-    Stage r0, r1;
-    load(r0);                       // step 0
-    store(r0, 0);
-    load(r0);                       // step 1
-    load(r1);                       // step 2
-    __syncthreads();
-    for (int s = 0; s < nsteps; s += 2) {
-        compute(0);
-        if (s + 1 < nsteps) store(r0, 1);
-        load(r0);                   // step s + 3
-        __syncthreads();
-        if (s + 1 >= nsteps) break;
-        compute(1);
-        if (s + 2 < nsteps) store(r1, 0);
-        load(r1);                   // step s + 4
-        __syncthreads();
-    }
-
-    // D layout of 16x16x4: column lane & 15, rows 4 (lane >> 4) + r.  The bias and the residuals are fetched before they are needed.
-    float bias[TN];
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-        const int n = n0 + wn + j * 16 + (lane & 15);
-        bias[j] = (g.bias && n < g.Cout) ? g.bias[n] : 0.0f;
-    }
-    float res[TM][4][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-#pragma unroll
-            for (int j = 0; j < TN; ++j) {
-                const int m = m0 + wm + i * 16 + (lane >> 4) * 4 + r, n = n0 + wn + j * 16 + (lane & 15);
-                res[i][r][j] = (g.res && m < g.M && n < g.Cout) ? g.res[(size_t)m * g.Cout + n] : 0.0f;
-            }
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int m = m0 + wm + i * 16 + (lane >> 4) * 4 + r;
-            if (m >= g.M) continue;
-            const int b = m / hw, px = m - b * hw;
-#pragma unroll
-            for (int j = 0; j < TN; ++j) {
-                const int n = n0 + wn + j * 16 + (lane & 15);
-                if (n >= g.Cout) continue;
-                float v = acc[i][j][r] + bias[j];
-                if (g.act == 1) v = leaky(v, g.slope);
-                else if (g.act == 2) v = 1.0f / (1.0f + expf(-v));
-                v += res[i][r][j];
-                if (g.y) g.y[(size_t)m * g.Cout + n] = v;
-                if (g.y_nchw) g.y_nchw[((size_t)b * g.Cout + n) * hw + px] = v;
-            }
-        }
-}
+__global__ void __launch_bounds__(256) torso_conv(ConvArgs g) { tconv::conv_tile<VEC, false, WM, WN, TM, TN>(g); }
 
 template <bool VEC, int WM, int WN, int TM, int TN>
 static void launch_conv(ConvArgs g, hipStream_t st)

@@ -1,0 +1,350 @@
+// The implicit-GEMM stride-1 convolution of the torso network on v_mfma_f32_16x16x4_f32, shared by the 2-D kernels of
+// r3d_torso.hip (torso_conv) and the 3-D ones of r3d_torso_motion.hip (conv3d): one body, conv_tile<VEC, D3, WM, WN, TM, TN>.
+//
+// A (WM TM 16) x (WN TN 16) tile of output positions x output channels per 256-thread block, K = (kz, ky, kx, ci) staged 32 at a time through
+// two LDS buffers while the next two steps are in flight in registers.  Tap loads apply the prologue act(s[c] x + t[c]) (zero outside the image
+// AFTER it: the reference pads the activated tensor) and nearest x2 up-sampling of H and W in the addressing; the epilogue adds the bias,
+// applies LeakyReLU / sigmoid, adds a residual and writes channel-last and / or channel-first.  VEC: Cin % 4 == 0, channel-last input,
+// 16-byte loads; otherwise one element per load.
+//
+// D3 = false is the 2-D convolution (D = 1, one depth tap): the depth fields of ConvArgs are not read and the code is the one r3d_torso_conv
+// has always run.  D3 = true adds
+//   * a depth tap: activations [B, D, Hs, Ws, Cin], weights [Cout, kd, ks, ks, Cin], zero padding padz in depth; the full-depth form is
+//     kd = D, padz = 0, Do = 1 (a Conv2d over x.view(N, C D, H, W) whose weights were permuted on the host);
+//   * AvgPool3d((1, 2, 2)) after the activation: the rows of a tile are enumerated quad-major (row 4 q + r is pixel (2 py + (r >> 1),
+//     2 px + (r & 1)) of pooled position q), so the four accumulators a lane holds (rows 4 (lane >> 4) + r) are one window, averaged in the
+//     epilogue; the un-pooled tensor is never written;
+//   * an output channel stride and offset (a producer writes its slice of a concatenation);
+//   * m-fast tile order for layers with fewer positions than output channels (every XCD streams its own share of the weights once).
+#pragma once
+#include "r3d_common.h"
+#include <math.h>
+
+namespace r3d {
+namespace tconv {
+
+constexpr int BK = 32, LDK = BK + 4;     // LDS rows of 36 floats: 16-byte aligned, and 16 rows at one k offset touch 64 distinct banks
+
+struct ConvArgs {
+    const float* x; int B, Hs, Ws, Cin;          // stored input [B, Hs, Ws, Cin] (in_nchw: [B, Cin, Hs, Ws]); D3: [B, D, Hs, Ws, Cin]
+    int H, W;                                    // the conv's grid: Hs x Ws, or twice that (up: the input is x[h >> 1, w >> 1])
+    int up, in_nchw, ks;
+    const float* ps; const float* pt; float pslope;      // prologue a = ps[c] x + pt[c]; a < 0 ? pslope a : a  (ps == nullptr: none)
+    const float* w; int Cout;                    // [Cout, ks, ks, Cin]; D3: [Cout, kd, ks, ks, Cin]
+    const float* bias;                           // [Cout] or nullptr
+    int act; float slope;                        // 0 none, 1 v < 0 ? slope v : v, 2 sigmoid
+    const float* res;                            // [M, Cout] or nullptr (may alias y: each element is read, then written, by one lane)
+    float* y; float* y_nchw;                     // [B, H, W, Cout] and / or [B, Cout, H, W]; D3: rows of ycs floats and / or [B, Cout, Do, H, W]
+    int M, K;
+    int ntn;                                     // tiles along Cout (set by the launcher)
+    // D3 only
+    int D, Do, kd, padz;                         // stored depth, output depths (D, or 1: full-depth), depth taps, depth padding
+    int pool;                                    // average each 2 x 2 (H, W) window: M counts the un-pooled positions, quad-major
+    int ycs, yco;                                // y's row length and this conv's first channel in it
+    int ntm, mfast;                              // tiles along M; mfast: consecutive tiles share their channels, not their positions
+};
+
+__device__ __forceinline__ float leaky(float v, float slope) { return v < 0.0f ? slope * v : v; }
+
+// the position of a running k = ((kz ks + ky) ks + kx) Cin + ci
+template <bool D3>
+struct KPos {
+    int ci, kx, ky, kz;
+    __device__ __forceinline__ void init(int k, int Cin, int ks)
+    {
+        ci = k % Cin;
+        int tap = k / Cin;
+        kz = 0;
+        if constexpr (D3) { kz = tap / (ks * ks); tap -= kz * ks * ks; }
+        ky = tap / ks; kx = tap - ky * ks;
+    }
+    __device__ __forceinline__ void advance(int dk, int Cin, int ks)
+    {
+        ci += dk;
+        while (ci >= Cin) {
+            ci -= Cin;
+            if (++kx == ks) {
+                kx = 0; ++ky;
+                if constexpr (D3) { if (ky == ks) { ky = 0; ++kz; } }
+            }
+        }
+    }
+};
+
+template <bool VEC, bool D3, int WM, int WN, int TM, int TN>
+__device__ __forceinline__ void conv_tile(const ConvArgs& g)
+{
+    static_assert(WM * WN == 4, "four waves");
+    constexpr int BM = WM * TM * 16, BN = WN * TN * 16;
+    constexpr int AV = BM / 32, WV = (BN + 31) / 32;           // VEC: float4 loads per thread (A, W)
+    constexpr int AS = BM / 8, WS = BN / 8, KSTEP = 256 / BM;  // scalar: elements per thread; A's k stride between them
+    __shared__ __attribute__((aligned(16))) float As[2][BM * LDK];
+    __shared__ __attribute__((aligned(16))) float Ws[2][BN * LDK];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    // Blocks are dealt to the 8 XCDs round-robin, and each XCD has an L2 of its own: block b takes tile (b % 8) (nblk / 8) + b / 8, so that
+    // one XCD works on neighbouring pixel tiles (which share their taps' rows) and on all channel tiles of each (which share the taps).
+    const int nblk = gridDim.x, bid = blockIdx.x;
+    const int tile = nblk % 8 == 0 ? (bid % 8) * (nblk / 8) + bid / 8 : bid;
+    int m0 = (tile / g.ntn) * BM, n0 = (tile % g.ntn) * BN;
+    if constexpr (D3) { if (g.mfast) { m0 = (tile % g.ntm) * BM; n0 = (tile / g.ntm) * BN; } }
+    const int pad = g.ks >> 1, hw = g.H * g.W;
+    const int nsteps = (g.K + BK - 1) / BK;
+
+    // ---- loader state ---------------------------------------------------------------------------------------------------------------
+    // VEC: slot j is row (t >> 3) + 32 j of the tile, k entries 4 (t & 7) .. + 3 of the step (one tap, four channels);
+    // scalar: row t % BM, k entries t / BM + KSTEP j (consecutive lanes read consecutive pixels: coalesced for an NCHW input)
+    constexpr int NR = VEC ? AV : 1;
+    int roy[NR], rox[NR], roz[D3 ? NR : 1]; size_t rbase[NR];   // a row's position (oy < 0: no such row) and its sample's offset
+#pragma unroll
+    for (int j = 0; j < NR; ++j) {
+        const int m = m0 + (VEC ? (t >> 3) + 32 * j : t % BM);
+        if constexpr (D3) roz[j] = 0;
+        if (m < g.M) {
+            if constexpr (D3) {
+                int plane;
+                if (g.pool) {
+                    const int q = m >> 2, w2 = g.W >> 1, h2 = g.H >> 1, tq = q / w2, px = q - tq * w2;
+                    plane = tq / h2;
+                    roy[j] = 2 * (tq - plane * h2) + ((m >> 1) & 1); rox[j] = 2 * px + (m & 1);
+                } else {
+                    plane = m / hw;
+                    const int r = m - plane * hw;
+                    roy[j] = r / g.W; rox[j] = r - roy[j] * g.W;
+                }
+                const int b = plane / g.Do;
+                roz[j] = plane - b * g.Do;
+                rbase[j] = (size_t)b * g.D * g.Hs * g.Ws * g.Cin;
+            } else {
+                const int b = m / hw, r = m - b * hw;
+                roy[j] = r / g.W; rox[j] = r - roy[j] * g.W;
+                rbase[j] = (size_t)b * g.Hs * g.Ws * g.Cin;
+            }
+        } else { roy[j] = -1000000; rox[j] = 0; rbase[j] = 0; }
+    }
+    KPos<D3> kp;
+    kp.init(VEC ? 4 * (t & 7) : t / BM, g.Cin, g.ks);
+    int kcur = VEC ? 4 * (t & 7) : t / BM;                      // the k of kp
+
+    const int wm = (wave / WN) * TM * 16, wn = (wave % WN) * TN * 16;
+    f32x4 acc[TM][TN];
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int j = 0; j < TN; ++j) acc[i][j] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+
+    // the registers of one k step in flight between its global loads and its LDS stores
+    struct Stage {
+        float4 av4[VEC ? AV : 1], wv4[VEC ? WV : 1], ps4, pt4;
+        float avs[VEC ? 1 : AS], wvs[VEC ? 1 : WS], pss[VEC ? 1 : AS], pts[VEC ? 1 : AS];
+        unsigned inside;                                        // bit j: slot / element j came from inside the image
+    };
+    int knext = 0;                                              // the step the next load() fetches (steps are loaded in order)
+
+    // the offset of tap (kz, ky, kx) of row slot j inside its sample, in pixels; false outside the (padded) volume
+    auto tap = [&](int j, size_t& pix) -> bool {
+        const int iy = roy[j] - pad + kp.ky, ix = rox[j] - pad + kp.kx;
+        if (!(iy >= 0 && iy < g.H && ix >= 0 && ix < g.W)) return false;
+        pix = (size_t)(iy >> g.up) * g.Ws + (ix >> g.up);
+        if constexpr (D3) {
+            const int iz = roz[j] - g.padz + kp.kz;
+            if (!(iz >= 0 && iz < g.D)) return false;
+            pix += (size_t)iz * g.Hs * g.Ws;
+        }
+        return true;
+    };
+
+    auto load = [&](Stage& r) {
+        r.inside = 0;
+        if (knext >= nsteps) return;
+        const int k0 = knext * BK;
+        ++knext;
+        if constexpr (VEC) {
+            const bool kin = kcur < g.K;
+#pragma unroll
+            for (int j = 0; j < AV; ++j) {
+                size_t pix;
+                r.av4[j] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                if (kin && tap(j, pix)) {
+                    r.av4[j] = *reinterpret_cast<const float4*>(g.x + rbase[j] + pix * g.Cin + kp.ci);
+                    r.inside |= 1u << j;
+                }
+            }
+            if (g.ps && kin) {
+                r.ps4 = *reinterpret_cast<const float4*>(g.ps + kp.ci);
+                r.pt4 = *reinterpret_cast<const float4*>(g.pt + kp.ci);
+            }
+#pragma unroll
+            for (int j = 0; j < WV; ++j) {
+                const int row = (t >> 3) + 32 * j, n = n0 + row;
+                r.wv4[j] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                if (row < BN && n < g.Cout && kin) r.wv4[j] = *reinterpret_cast<const float4*>(g.w + (size_t)n * g.K + kcur);
+            }
+            kp.advance(BK, g.Cin, g.ks);
+            kcur += BK;
+        } else {
+#pragma unroll
+            for (int j = 0; j < AS; ++j) {
+                size_t pix;
+                r.avs[j] = 0.0f; r.pss[j] = 1.0f; r.pts[j] = 0.0f;
+                if (kcur < g.K && tap(0, pix)) {
+                    const size_t off = g.in_nchw ? rbase[0] + (size_t)kp.ci * g.Hs * g.Ws + pix : rbase[0] + pix * g.Cin + kp.ci;
+                    r.avs[j] = g.x[off];
+                    if (g.ps) { r.pss[j] = g.ps[kp.ci]; r.pts[j] = g.pt[kp.ci]; }
+                    r.inside |= 1u << j;
+                }
+                kp.advance(KSTEP, g.Cin, g.ks);
+                kcur += KSTEP;
+            }
+#pragma unroll
+            for (int j = 0; j < WS; ++j) {
+                const int e = t + 256 * j, n = n0 + (e >> 5), k = k0 + (e & 31);
+                r.wvs[j] = (n < g.Cout && k < g.K) ? g.w[(size_t)n * g.K + k] : 0.0f;
+            }
+        }
+    };
+    auto store = [&](const Stage& r, int buf) {
+        if constexpr (VEC) {
+#pragma unroll
+            for (int j = 0; j < AV; ++j) {
+                float4 v = r.av4[j];
+                if (g.ps && (r.inside >> j & 1)) {
+                    v.x = leaky(fmaf(r.ps4.x, v.x, r.pt4.x), g.pslope); v.y = leaky(fmaf(r.ps4.y, v.y, r.pt4.y), g.pslope);
+                    v.z = leaky(fmaf(r.ps4.z, v.z, r.pt4.z), g.pslope); v.w = leaky(fmaf(r.ps4.w, v.w, r.pt4.w), g.pslope);
+                }
+                *reinterpret_cast<float4*>(&As[buf][((t >> 3) + 32 * j) * LDK + 4 * (t & 7)]) = v;
+            }
+#pragma unroll
+            for (int j = 0; j < WV; ++j) {
+                const int row = (t >> 3) + 32 * j;
+                if (row < BN) *reinterpret_cast<float4*>(&Ws[buf][row * LDK + 4 * (t & 7)]) = r.wv4[j];
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < AS; ++j) {
+                float v = r.avs[j];
+                if (g.ps && (r.inside >> j & 1)) v = leaky(fmaf(r.pss[j], v, r.pts[j]), g.pslope);
+                As[buf][(t % BM) * LDK + t / BM + KSTEP * j] = v;
+            }
+#pragma unroll
+            for (int j = 0; j < WS; ++j) { const int e = t + 256 * j; Ws[buf][(e >> 5) * LDK + (e & 31)] = r.wvs[j]; }
+        }
+    };
+    // one k step of the block's tile out of LDS buffer `cur`
+    auto compute = [&](int cur) {
+        // lane group lane >> 4 owns k entries 8 (lane >> 4) .. + 7 of the step, one per MFMA: the order of the sum is fixed, whichever
+        float a[TM][8], b[TN][8];
+#pragma unroll
+        for (int i = 0; i < TM; ++i) {
+            const float* p = &As[cur][(wm + i * 16 + (lane & 15)) * LDK + 8 * (lane >> 4)];
+            const float4 lo = *reinterpret_cast<const float4*>(p), hi = *reinterpret_cast<const float4*>(p + 4);
+            a[i][0] = lo.x; a[i][1] = lo.y; a[i][2] = lo.z; a[i][3] = lo.w; a[i][4] = hi.x; a[i][5] = hi.y; a[i][6] = hi.z; a[i][7] = hi.w;
+        }
+#pragma unroll
+        for (int j = 0; j < TN; ++j) {
+            const float* p = &Ws[cur][(wn + j * 16 + (lane & 15)) * LDK + 8 * (lane >> 4)];
+            const float4 lo = *reinterpret_cast<const float4*>(p), hi = *reinterpret_cast<const float4*>(p + 4);
+            b[j][0] = lo.x; b[j][1] = lo.y; b[j][2] = lo.z; b[j][3] = lo.w; b[j][4] = hi.x; b[j][5] = hi.y; b[j][6] = hi.z; b[j][7] = hi.w;
+        }
+#pragma unroll
+        for (int kk = 0; kk < 8; ++kk)
+#pragma unroll
+            for (int i = 0; i < TM; ++i)
+#pragma unroll
+                for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i][kk], b[j][kk], acc[i][j], 0, 0, 0);
+    };
+
+    // Two register stages and two LDS buffers: step s is computed out of buffer s & 1 while step s + 1 (loaded one iteration earlier)
+    // goes from its stage into the other buffer and step s + 3 leaves for that stage, so a load has two compute phases to arrive.
+    Stage r0, r1;
+    load(r0);                       // step 0
+    store(r0, 0);
+    load(r0);                       // step 1
+    load(r1);                       // step 2
+    __syncthreads();
+    for (int s = 0; s < nsteps; s += 2) {
+        compute(0);
+        if (s + 1 < nsteps) store(r0, 1);
+        load(r0);                   // step s + 3
+        __syncthreads();
+        if (s + 1 >= nsteps) break;
+        compute(1);
+        if (s + 2 < nsteps) store(r1, 0);
+        load(r1);                   // step s + 4
+        __syncthreads();
+    }
+
+    // D layout of 16x16x4: column lane & 15, rows 4 (lane >> 4) + r.  The bias and the residuals are fetched before they are needed.
+    float bias[TN];
+#pragma unroll
+    for (int j = 0; j < TN; ++j) {
+        const int n = n0 + wn + j * 16 + (lane & 15);
+        bias[j] = (g.bias && n < g.Cout) ? g.bias[n] : 0.0f;
+    }
+    if constexpr (D3) {
+        auto activate = [&](float v) {
+            if (g.act == 1) v = leaky(v, g.slope);
+            else if (g.act == 2) v = 1.0f / (1.0f + expf(-v));
+            return v;
+        };
+#pragma unroll
+        for (int i = 0; i < TM; ++i) {
+            const int mq = m0 + wm + i * 16 + (lane >> 4) * 4;          // the lane's four rows mq .. mq + 3: one pooling window
+            if (mq >= g.M) continue;
+#pragma unroll
+            for (int j = 0; j < TN; ++j) {
+                const int n = n0 + wn + j * 16 + (lane & 15);
+                if (n >= g.Cout) continue;
+                if (g.pool) {                                           // M % 4 == 0: the window is whole
+                    const float v0 = activate(acc[i][j][0] + bias[j]), v1 = activate(acc[i][j][1] + bias[j]);
+                    const float v2 = activate(acc[i][j][2] + bias[j]), v3 = activate(acc[i][j][3] + bias[j]);
+                    g.y[(size_t)(mq >> 2) * g.ycs + g.yco + n] = 0.25f * ((v0 + v1) + (v2 + v3));
+                    continue;
+                }
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int m = mq + r;
+                    if (m >= g.M) continue;
+                    const float v = activate(acc[i][j][r] + bias[j]);
+                    if (g.y) g.y[(size_t)m * g.ycs + g.yco + n] = v;
+                    if (g.y_nchw) {
+                        const int plane = m / hw, px = m - plane * hw, b = plane / g.Do, d = plane - b * g.Do;
+                        g.y_nchw[(((size_t)b * g.Cout + n) * g.Do + d) * hw + px] = v;
+                    }
+                }
+            }
+        }
+    } else {
+        float res[TM][4][TN];
+#pragma unroll
+        for (int i = 0; i < TM; ++i)
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+#pragma unroll
+                for (int j = 0; j < TN; ++j) {
+                    const int m = m0 + wm + i * 16 + (lane >> 4) * 4 + r, n = n0 + wn + j * 16 + (lane & 15);
+                    res[i][r][j] = (g.res && m < g.M && n < g.Cout) ? g.res[(size_t)m * g.Cout + n] : 0.0f;
+                }
+#pragma unroll
+        for (int i = 0; i < TM; ++i)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int m = m0 + wm + i * 16 + (lane >> 4) * 4 + r;
+                if (m >= g.M) continue;
+                const int b = m / hw, px = m - b * hw;
+#pragma unroll
+                for (int j = 0; j < TN; ++j) {
+                    const int n = n0 + wn + j * 16 + (lane & 15);
+                    if (n >= g.Cout) continue;
+                    float v = acc[i][j][r] + bias[j];
+                    if (g.act == 1) v = leaky(v, g.slope);
+                    else if (g.act == 2) v = 1.0f / (1.0f + expf(-v));
+                    v += res[i][r][j];
+                    if (g.y) g.y[(size_t)m * g.Cout + n] = v;
+                    if (g.y_nchw) g.y_nchw[((size_t)b * g.Cout + n) * hw + px] = v;
+                }
+            }
+    }
+}
+
+}  // namespace tconv
+}  // namespace r3d

@@ -380,3 +380,101 @@ def synth_torso_inputs(seed, N=1, H=64, W=64, noise=0.15):
     occ = hash_uniform(seed, N * H * W, stream=13).reshape(N, 1, H, W)
     occ2 = hash_uniform(seed, N * H * W, stream=14).reshape(N, 1, H, W)
     return {"torso_appearance_feats": fs, "deformation": grid, "occlusion": occ, "occlusion_2": occ2}
+
+
+MOTION_D, MOTION_HW = 16, 64       # the estimator's fixed feature grid (facev2v_warp/network2.py:162-173, 220-222)
+
+
+def torso_motion_shapes(K=4, input_channels=34):
+    """[(state_dict key, shape)] of MotionFieldEstimator('standard', input_channels, K) (modules/real3d/facev2v_warp/network2.py:174-202):
+    129 entries."""
+    bn = lambda p, c: [(p + n, (c,)) for n in ("weight", "bias", "running_mean", "running_var")] + [(p + "num_batches_tracked", ())]
+    conv = lambda p, co, ci, *k: [(p + "weight", (co, ci) + k), (p + "bias", (co,))]
+    down, up = [5 * (K + 1), 64, 128, 256, 512, 1024], [1024, 512, 256, 128, 64, 32]
+    out = conv("compress.", 4, input_channels, 1, 1, 1)
+    for i in range(5):
+        out += conv("down.%d.layers.0.layers.0." % i, down[i + 1], down[i], 3, 3, 3) + bn("down.%d.layers.0.layers.1." % i, down[i + 1])
+    for i in range(5):
+        out += conv("up.%d.layers.1.layers.0." % i, up[i + 1], up[i], 3, 3, 3) + bn("up.%d.layers.1.layers.1." % i, up[i + 1])
+    out += conv("tgt_head_encoder.0.layers.0.", 32, 4, 7, 7) + bn("tgt_head_encoder.0.layers.1.", 32)
+    for i in range(1, 4):
+        for j in range(2):
+            p = "tgt_head_encoder.%d.layers.%d.layers." % (i, j)
+            out += bn(p + "0.", 32) + conv(p + "2.", 32, 32, 3, 3)
+    out += conv("tgt_head_fuser.", 32, 32 + down[0] + 32, 7, 7, 7) + conv("mask_conv.", K + 1, 32, 7, 7, 7)
+    return out + conv("occlusion_conv.", 1, 32 * MOTION_D, 7, 7) + conv("occlusion_conv2.", 1, 32 * MOTION_D, 7, 7)
+
+
+# weight gains of synth_torso_motion (x 1 / sqrt(fan_in)), chosen so that on synth_torso_motion_inputs every activation stays O(1), the three
+# channel groups of the fuser's input all matter, the mask's softmax is decided in places and open in others and the occlusions are neither
+# saturated nor flat (tests/golden/make_golden_torso_motion.py asserts all of it on the reference's output)
+MOTION_GAINS = {"compress": 1.0, "down": 2.0, "up": 1.6, "tgt_head_encoder.0": 2.0, "tgt_head_encoder": 1.0, "tgt_head_fuser": 1.0,
+                "mask_conv": 4.0, "occlusion_conv": 0.8, "occlusion_conv2": 0.8}
+
+
+def synth_torso_motion(seed, K=4, input_channels=34):
+    """A full state_dict (numpy) of the motion-field estimator.  Conv weights ~ N(0, gain^2 / fan_in) with MOTION_GAINS by module, biases
+    0.1 n (0.3 n in front of a BatchNorm); BatchNorm: weight 1 + 0.1 n, bias
+    and running_mean 0.3 n, running_var in [0.5, 2]."""
+    sd = {}
+    shapes = torso_motion_shapes(K, input_channels)
+    names = dict(shapes)
+    for i, (key, shape) in enumerate(shapes):
+        st = 4000 + i
+        last = key.rsplit(".", 1)[-1]
+        if last == "num_batches_tracked":
+            v = np.array(0, dtype=np.int64)
+        elif last == "running_var":
+            v = np.float32(0.5) + np.float32(1.5) * hash_uniform(seed, shape[0], st)
+        elif last == "running_mean":
+            v = hash_unitvar(seed, shape, st) * np.float32(0.3)
+        elif len(shape) == 1 and (key[:-len(last)] + "running_mean") in names:           # BatchNorm weight / bias
+            v = hash_unitvar(seed, shape, st) * np.float32(0.3) if last == "bias" else np.float32(1.0) + hash_unitvar(seed, shape, st) * np.float32(0.1)
+        elif last == "bias":
+            front = key[:-6].rsplit(".", 1)[0] + ".1.running_mean" in names              # a "CNA" conv: its bias meets the BatchNorm's mean
+            v = hash_unitvar(seed, shape, st) * np.float32(0.3 if front else 0.1)
+        else:
+            gain = next(g for p, g in MOTION_GAINS.items() if key.startswith(p))
+            v = hash_unitvar(seed, shape, st) * np.float32(gain / math.sqrt(int(np.prod(shape[1:]))))
+            if key == "mask_conv.weight":          # no response to a channel's mean: otherwise one component's logit leads everywhere
+                v = v - v.mean(axis=(2, 3, 4), keepdims=True)
+        sd[key] = np.asarray(v, dtype=np.int64 if last == "num_batches_tracked" else np.float32)
+    return sd
+
+
+def _rotation(yaw, pitch, roll):
+    cy, sy, cp, sp, cr, sr = math.cos(yaw), math.sin(yaw), math.cos(pitch), math.sin(pitch), math.cos(roll), math.sin(roll)
+    ry = np.array([[cy, 0, sy], [0, 1, 0], [-sy, 0, cy]])
+    rx = np.array([[1, 0, 0], [0, cp, -sp], [0, sp, cp]])
+    rz = np.array([[cr, -sr, 0], [sr, cr, 0], [0, 0, 1]])
+    return (rz @ ry @ rx).astype(np.float32)
+
+
+def synth_torso_motion_inputs(seed, N=1, K=4, rotate=False):
+    """Inputs of MotionFieldEstimator.forward as WarpBasedTorsoModelMediaPipe.forward passes them (facev2v_warp/model2.py:236-250):
+    fs [N, 34, 16, 64, 64] (unit variance), kp_s / kp_d [N, K, 3] inside the volume (|kp_s| <= 0.55, kp_d = kp_s + an offset of 0.1 .. 0.3
+    per axis with alternating signs, so that a good part of every sparse motion leaves the volume on one side or the other), Rs / Rd [N, 3, 3]
+    (the identity as in the product, or with rotate two different rotations of up to 0.35 rad per axis), tgt_head_img [N, 3, 256, 256] in
+    [-1, 1] (a smooth pattern + noise) and tgt_head_weights [N, 1, 256, 256] in [0, 1].  Every sample differs."""
+    D, S = MOTION_D, MOTION_HW
+    fs = hash_unitvar(seed, (N, 34, D, S, S), stream=21)
+    kp_s = (hash_uniform(seed, N * K * 3, stream=22).reshape(N, K, 3) * np.float32(1.1) - np.float32(0.55)).astype(np.float32)
+    u = hash_uniform(seed, N * K * 3, stream=23).reshape(N, K, 3)
+    n_, k_, a_ = np.meshgrid(np.arange(N), np.arange(K), np.arange(3), indexing="ij")
+    sign = np.where((n_ + k_ + a_) % 2 == 0, 1.0, -1.0)                # both signs on every axis
+    kp_d = (kp_s + sign * (0.1 + 0.2 * u)).astype(np.float32)
+    Rs = np.tile(np.eye(3, dtype=np.float32), (N, 1, 1))
+    Rd = Rs.copy()
+    if rotate:
+        a = hash_uniform(seed, N * 6, stream=25).reshape(N, 6) * 0.7 - 0.35
+        for n in range(N):
+            Rs[n], Rd[n] = _rotation(*a[n, :3]), _rotation(*a[n, 3:])
+    lin = np.linspace(-1.0, 1.0, 256, dtype=np.float32)
+    yy, xx = np.meshgrid(lin, lin, indexing="ij")
+    img = np.empty((N, 3, 256, 256), np.float32)
+    wts = np.empty((N, 1, 256, 256), np.float32)
+    for n in range(N):
+        for c in range(3):
+            img[n, c] = 0.6 * np.sin(3.0 * xx * (c + 1) + 2.0 * yy + n) + 0.3 * hash_unitvar(seed, (256, 256), stream=26 + 4 * n + c)
+        wts[n, 0] = 1.0 / (1.0 + np.exp(-6.0 * (0.5 - np.hypot(xx - 0.1 * n, yy + 0.1)))) * (0.8 + 0.2 * hash_uniform(seed, 65536, stream=40 + n).reshape(256, 256))
+    return {"fs": fs, "kp_s": kp_s, "kp_d": kp_d, "Rs": Rs, "Rd": Rd, "tgt_head_img": np.clip(img, -1.0, 1.0), "tgt_head_weights": wts.astype(np.float32)}

@@ -1,0 +1,247 @@
+"""The per-frame first half of the face-vid2vid torso network on the HIP torso kernels (r3d_torso_conv3d and r3d_torso_motion_* of
+include/r3d_hip.h):
+
+    MotionFieldEstimator  modules/real3d/facev2v_warp/network2.py:162-244 (version v2: with the target-head branch): compress, the
+                          heatmaps and the sparse motions, the Conv3d hourglass, tgt_head_encoder, tgt_head_fuser, mask_conv, the
+                          mask-weighted deformation and the two occlusion maps
+
+in exact fp32.  It keeps the reference's attribute names and its 129 state_dict keys, so a reference checkpoint loads with strict=True.
+INFERENCE ONLY (eval semantics: BatchNorm on its running statistics); inputs are detached and no autograd graph is built.  The BatchNorms
+are folded into the conv weights, biases and prologue vectors in fp64 once per parameter version (_prepare), where the channel groups
+are also padded to multiples of 4 and the occlusion weights permuted to the kernel's full-depth form.
+"""
+import torch
+import torch.nn as nn
+
+from . import _lib
+from .torso_generator import BN_EPS, LEAKY, NONE, SIGMOID, _check_f32, _conv, _kernel_weight, _params_key, bn_affine64
+
+DEPTH, GRID, HEAD, HID = 16, 64, 256, 32          # the feature volume [N, C, 16, 64, 64], the head image 256^2, tgt_head_hid_dim
+
+
+def _pad4(c):
+    return (c + 3) // 4 * 4
+
+
+class _ConvBlock(nn.Module):
+    """ConvBlock2D / ConvBlock3D (layers.py:6-55) without weight norm and with SyncBatchNorm: `layers` holds the modules in the pattern's order."""
+
+    def __init__(self, dim, pattern, cin, cout, k):
+        super().__init__()
+        self.pattern = pattern
+        conv, norm = (nn.Conv2d, nn.BatchNorm2d) if dim == 2 else (nn.Conv3d, nn.BatchNorm3d)
+        mods = {"C": conv(cin, cout, k, 1, k // 2), "N": norm(cout if pattern.find("C") < pattern.find("N") else cin, eps=BN_EPS), "A": nn.ReLU()}
+        self.layers = nn.Sequential(*[mods[c] for c in pattern])
+
+    conv = property(lambda self: self.layers[self.pattern.index("C")])
+    bn = property(lambda self: self.layers[self.pattern.index("N")])
+
+
+class _DownBlock3D(nn.Module):
+    def __init__(self, cin, cout):
+        super().__init__()
+        self.layers = nn.Sequential(_ConvBlock(3, "CNA", cin, cout, 3), nn.AvgPool3d((1, 2, 2)))
+
+
+class _UpBlock3D(nn.Module):
+    def __init__(self, cin, cout):
+        super().__init__()
+        self.layers = nn.Sequential(nn.Upsample(scale_factor=(1, 2, 2)), _ConvBlock(3, "CNA", cin, cout, 3))
+
+
+class _ResBlock2D(nn.Module):
+    def __init__(self, c):
+        super().__init__()
+        self.layers = nn.Sequential(_ConvBlock(2, "NAC", c, c, 3), _ConvBlock(2, "NAC", c, c, 3))
+
+
+def _kernel_weight3d(w64, dtype, groups=None):
+    """[Cout, Cin, kd, kh, kw] fp64 -> the kernel's [Cout, kd, kh, kw, Cin'] in `dtype`; groups: the sizes of the input's channel groups,
+    each padded with zero columns to a multiple of 4 (default: the whole input as one group)."""
+    w = w64.permute(0, 2, 3, 4, 1)
+    parts, c0 = [], 0
+    for c in groups or [w.shape[-1]]:
+        parts.append(w[..., c0:c0 + c])
+        if _pad4(c) != c:
+            parts.append(w.new_zeros(w.shape[:-1] + (_pad4(c) - c,)))
+        c0 += c
+    assert c0 == w.shape[-1]
+    return torch.cat(parts, dim=-1).contiguous().to(dtype)
+
+
+def fold_motion(m, dtype=torch.float32):
+    """The estimator's convolutions as kernel calls, folded in fp64 and rounded once to `dtype` (float64: the fold itself, for the tests).
+    A dict:  compress (w [4, C], b);  enc: tgt_head_encoder as seven r3d_torso_conv layers in fold_generator's format;  down / up: five
+    r3d_torso_conv3d layers each (w [Cout, 3, 3, 3, Cin'], b; the BatchNorm is in the rows and the bias, ReLU and the pool / up-sampling are
+    the kernel's);  fuser, mask (k 7);  occ: occlusion_conv and occlusion_conv2 as one full-depth layer with two output channels."""
+    f = lambda v: None if v is None else v.to(dtype).contiguous()
+    d64 = lambda p: p.detach().double()
+    K = m.num_keypoints
+    cm = 5 * (K + 1)
+    F = {"compress": {"w": f(d64(m.compress.weight).reshape(4, -1)), "b": f(d64(m.compress.bias))}, "enc": [], "down": [], "up": []}
+
+    def layer2d(w, b, k, ps=None, pt=None, act=NONE, res=False):
+        F["enc"].append({"w": _kernel_weight(w, dtype), "b": f(b), "ps": f(ps), "pt": f(pt), "k": k, "up": 0, "act": act, "slope": 0.0, "res": res})
+
+    first = m.tgt_head_encoder[0]
+    s, t = bn_affine64(first.bn)
+    layer2d(d64(first.conv.weight) * s[:, None, None, None], d64(first.conv.bias) * s + t, 7, act=LEAKY)
+    for blk in list(m.tgt_head_encoder)[1:]:
+        a, b = blk.layers[0], blk.layers[1]
+        s1, t1 = bn_affine64(a.bn)
+        s2, t2 = bn_affine64(b.bn)
+        # the first conv's only reader is the second block's BatchNorm + ReLU: they go into its rows, bias and epilogue
+        layer2d(d64(a.conv.weight) * s2[:, None, None, None], d64(a.conv.bias) * s2 + t2, 3, ps=s1, pt=t1, act=LEAKY)
+        layer2d(d64(b.conv.weight), d64(b.conv.bias), 3, res=True)
+    for name, seq, pos in (("down", m.down, 0), ("up", m.up, 1)):
+        for blk in seq:
+            cb = blk.layers[pos]
+            s, t = bn_affine64(cb.bn)
+            w = d64(cb.conv.weight) * s[:, None, None, None, None]
+            F[name].append({"w": _kernel_weight3d(w, dtype), "b": f(d64(cb.conv.bias) * s + t)})
+    F["fuser"] = {"w": _kernel_weight3d(d64(m.tgt_head_fuser.weight), dtype, [cm, HID, HID]), "b": f(d64(m.tgt_head_fuser.bias))}
+    F["mask"] = {"w": _kernel_weight3d(d64(m.mask_conv.weight), dtype), "b": f(d64(m.mask_conv.bias))}
+    # Conv2d over x.view(N, 32 D, H, W), channel c D + d  ->  [2, D, 7, 7, 32]
+    ow = torch.cat([d64(c.weight).reshape(1, HID, DEPTH, 7, 7) for c in (m.occlusion_conv, m.occlusion_conv2)], dim=0)
+    F["occ"] = {"w": _kernel_weight3d(ow, dtype), "b": f(torch.cat([d64(m.occlusion_conv.bias), d64(m.occlusion_conv2.bias)]))}
+    return F
+
+
+def jacobian(Rs, Rd):
+    """J = Rs Rd^-1 [N, 3, 3] in elementwise torch ops (the inverse by cross products of Rd's rows): no LAPACK call, no host
+    synchronisation, and a sample's J does not depend on the batch it is in."""
+    r0, r1, r2 = Rd[:, 0], Rd[:, 1], Rd[:, 2]
+    c0, c1, c2 = torch.linalg.cross(r1, r2), torch.linalg.cross(r2, r0), torch.linalg.cross(r0, r1)
+    inv = torch.stack([c0, c1, c2], dim=-1) / (r0 * c0).sum(-1)[:, None, None]
+    return (Rs[:, :, :, None] * inv[:, None, :, :]).sum(dim=2).contiguous()
+
+
+def _conv3d(x, B, D, Hs, Ws, cin, L, k, y, ycs=None, yco=0, up=0, act=NONE, pool=0, full_depth=0, y_ncdhw=None):
+    P = _lib.ptr
+    cout = L["w"].shape[0]
+    _lib.check(_lib.load().r3d_torso_conv3d(P(x), B, D, Hs, Ws, cin, up, P(L["w"]), P(L["b"]), cout, k, full_depth, act, 0.0, pool, P(y),
+                                            cout if ycs is None else ycs, yco, P(y_ncdhw), _lib.stream_ptr()), "torso_conv3d")
+
+
+class MotionFieldEstimator(nn.Module):
+    """network2.py:162-244.  forward(fs [N, C, 16, 64, 64], kp_s [N, K, 3], kp_d [N, K, 3], Rs [N, 3, 3], Rd [N, 3, 3], tgt_head_img
+    [N, 3, 256, 256], tgt_head_weights [N, 1, 256, 256]) -> (deformation [N, 16, 64, 64, 3], occlusion [N, 1, 64, 64], occlusion_2
+    [N, 1, 64, 64]).  The reference fixes these sizes (its resizes to 128^2 and 64^2, :220-222); others raise ValueError."""
+
+    def __init__(self, model_scale="standard", input_channels=34, num_keypoints=4, predict_multiref_occ=True):
+        super().__init__()
+        if model_scale not in ("standard", "large") or not predict_multiref_occ:
+            raise NotImplementedError("MotionFieldEstimator: only model_scale 'standard' with predict_multiref_occ has a HIP implementation "
+                                      "(network2.py:177-183,232-236; got %r, predict_multiref_occ=%r)" % (model_scale, predict_multiref_occ))
+        K = num_keypoints
+        down, up = [5 * (K + 1), 64, 128, 256, 512, 1024], [1024, 512, 256, 128, 64, 32]
+        self.input_channels, self.num_keypoints, self.predict_multiref_occ = input_channels, K, True
+        self.compress = nn.Conv3d(input_channels, 4, 1, 1, 0)
+        self.down = nn.Sequential(*[_DownBlock3D(down[i], down[i + 1]) for i in range(5)])
+        self.up = nn.Sequential(*[_UpBlock3D(up[i], up[i + 1]) for i in range(5)])
+        self.tgt_head_encoder = nn.Sequential(_ConvBlock(2, "CNA", 4, HID, 7), *[_ResBlock2D(HID) for _ in range(3)])
+        self.tgt_head_fuser = nn.Conv3d(HID + down[0] + up[-1], HID, 7, 1, 3)
+        self.mask_conv = nn.Conv3d(HID, K + 1, 7, 1, 3)
+        self.occlusion_conv = nn.Conv2d(HID * DEPTH, 1, 7, 1, 3)
+        self.occlusion_conv2 = nn.Conv2d(HID * DEPTH, 1, 7, 1, 3)
+        self.C, self.D = down[0] + up[-1], DEPTH
+        self._derived_key, self._derived = None, None
+        self._work = {}          # (device, stream, N) -> activation buffers: two streams in flight never share one
+
+    def _prepare(self):
+        key = _params_key(self)
+        if key != self._derived_key:
+            with torch.no_grad():
+                self._derived_key, self._derived = key, fold_motion(self)
+        return self._derived
+
+    def _buffers_for(self, N, dev):
+        key = (dev, _lib.stream_ptr(), N)
+        w = self._work.get(key)
+        if w is None:
+            e = lambda *n: torch.empty(*n, device=dev, dtype=torch.float32)
+            cp = _pad4(5 * (self.num_keypoints + 1))
+            vox = N * DEPTH * GRID * GRID
+            w = self._work[key] = {
+                "fs": e(vox * self.input_channels), "inp": e(vox * cp), "fuse": e(vox * (cp + 2 * HID)),
+                "down": [e(N * DEPTH * (GRID >> (i + 1)) ** 2 * c) for i, c in enumerate((64, 128, 256, 512, 1024))],
+                "up": [e(N * DEPTH * (4 << i) ** 2 * c) for i, c in enumerate((512, 256, 128, 64))],
+                "head": e(N, 4, 128, 128), "e0": e(N * 128 * 128 * HID), "e1": e(N * 128 * 128 * HID), "feats": e(N, HID, 128, 128),
+                "feats64": e(N, HID, GRID, GRID), "x": e(vox * HID), "mask": e(vox * (self.num_keypoints + 1))}
+        return w
+
+    @torch.no_grad()
+    def forward(self, fs, kp_s, kp_d, Rs, Rd, tgt_head_img, tgt_head_weights):
+        K, C, D, S = self.num_keypoints, self.input_channels, DEPTH, GRID
+        fs = _check_f32(fs, "fs", 5)
+        N = fs.shape[0]
+        img, wts = _check_f32(tgt_head_img, "tgt_head_img", 4), _check_f32(tgt_head_weights, "tgt_head_weights", 4)
+        kp_s, kp_d = _check_f32(kp_s, "kp_s", 3), _check_f32(kp_d, "kp_d", 3)
+        Rs, Rd = _check_f32(Rs, "Rs", 3), _check_f32(Rd, "Rd", 3)
+        if tuple(fs.shape) != (N, C, D, S, S) or tuple(img.shape) != (N, 3, HEAD, HEAD) or tuple(wts.shape) != (N, 1, HEAD, HEAD):
+            raise ValueError("MotionFieldEstimator: expected fs [N, %d, %d, %d, %d], tgt_head_img [N, 3, %d, %d] and tgt_head_weights "
+                             "[N, 1, %d, %d] (network2.py:220-222), got %s, %s and %s"
+                             % (C, D, S, S, HEAD, HEAD, HEAD, HEAD, tuple(fs.shape), tuple(img.shape), tuple(wts.shape)))
+        if tuple(kp_s.shape) != (N, K, 3) or tuple(kp_d.shape) != (N, K, 3) or tuple(Rs.shape) != (N, 3, 3) or tuple(Rd.shape) != (N, 3, 3):
+            raise ValueError("MotionFieldEstimator: expected kp_s, kp_d [N, %d, 3] and Rs, Rd [N, 3, 3], got %s, %s, %s and %s"
+                             % (K, tuple(kp_s.shape), tuple(kp_d.shape), tuple(Rs.shape), tuple(Rd.shape)))
+        dev = fs.device
+        F, w = self._prepare(), self._buffers_for(N, dev)
+        lib, P, st = _lib.load(), _lib.ptr, _lib.stream_ptr()
+        cp = _pad4(5 * (K + 1))
+        fcs = cp + 2 * HID
+        J = jacobian(Rs, Rd)
+        # the hourglass input, also the first channel group of the fuser's input
+        _lib.check(lib.r3d_torso_volume_to_cl(P(fs), N, C, D, S, S, P(w["fs"]), st), "torso_volume_to_cl")
+        _lib.check(lib.r3d_torso_motion_input(P(w["fs"]), N, C, D, S, S, P(F["compress"]["w"]), P(F["compress"]["b"]), P(kp_s), P(kp_d), P(J),
+                                              K, P(w["inp"]), cp, P(w["fuse"]), fcs, st), "torso_motion_input")
+        # the hourglass; its last conv writes the second group
+        x, cin, size = w["inp"], cp, S
+        for i, L in enumerate(F["down"]):
+            _conv3d(x, N, D, size, size, cin, L, 3, w["down"][i], act=LEAKY, pool=1)
+            x, cin, size = w["down"][i], L["w"].shape[0], size // 2
+        for i, L in enumerate(F["up"]):
+            last = i == 4
+            _conv3d(x, N, D, size, size, cin, L, 3, w["fuse"] if last else w["up"][i], ycs=fcs if last else None, yco=cp if last else 0,
+                    up=1, act=LEAKY)
+            x, cin, size = (None if last else w["up"][i]), L["w"].shape[0], size * 2
+        # the head branch: 256^2 -> 128^2, tgt_head_encoder, -> 64^2, repeated over depth into the third group
+        head_in = torch.cat([img, wts], dim=1)
+        _lib.check(lib.r3d_resize_bilinear(P(head_in), N * 4, HEAD, HEAD, P(w["head"]), 128, 128, 0, st), "resize_bilinear")
+        E = F["enc"]
+        _conv(w["head"], N, 128, 128, 4, E[0], y=w["e0"], in_nchw=True)
+        for i in range(3):
+            _conv(w["e0"], N, 128, 128, HID, E[1 + 2 * i], y=w["e1"])
+            if i < 2:
+                _conv(w["e1"], N, 128, 128, HID, E[2 + 2 * i], y=w["e0"], res=w["e0"])
+            else:
+                _conv(w["e1"], N, 128, 128, HID, E[2 + 2 * i], y_nchw=w["feats"], res=w["e0"])
+        _lib.check(lib.r3d_resize_bilinear(P(w["feats"]), N * HID, 128, 128, P(w["feats64"]), S, S, 0, st), "resize_bilinear")
+        _lib.check(lib.r3d_torso_motion_broadcast(P(w["feats64"]), N, HID, S, S, D, P(w["fuse"]), fcs, cp + HID, st), "torso_motion_broadcast")
+        # fuser, mask, deformation, occlusions
+        _conv3d(w["fuse"], N, D, S, S, fcs, F["fuser"], 7, w["x"])
+        _conv3d(w["x"], N, D, S, S, HID, F["mask"], 7, w["mask"])
+        deformation = torch.empty(N, D, S, S, 3, device=dev, dtype=torch.float32)
+        _lib.check(lib.r3d_torso_motion_deform(P(w["mask"]), N, D, S, S, K, P(kp_s), P(kp_d), P(J), P(deformation), st), "torso_motion_deform")
+        occ = torch.empty(N, 2, S, S, device=dev, dtype=torch.float32)
+        _conv3d(w["x"], N, D, S, S, HID, F["occ"], 7, None, act=SIGMOID, full_depth=1, y_ncdhw=occ)
+        return deformation, occ[:, 0:1].contiguous(), occ[:, 1:2].contiguous()
+
+    @classmethod
+    def from_reference(cls, ref):
+        """A HIP copy of a constructed reference MotionFieldEstimator at standard scale (strict key copy)."""
+        m = cls(input_channels=ref.compress.in_channels, num_keypoints=ref.mask_conv.out_channels - 1)
+        m.load_state_dict(ref.state_dict(), strict=True)
+        return m.to(next(ref.parameters()).device).eval()
+
+
+def is_reference_motion_estimator(m):
+    """The reference's v2 MotionFieldEstimator (network2.py: with tgt_head_encoder; network.py's v1 has no target-head branch) at standard
+    scale with both occlusion maps."""
+    try:
+        return (type(m).__name__ == "MotionFieldEstimator" and not type(m).__module__.startswith("real3dportrait_amd")
+                and hasattr(m, "tgt_head_encoder") and hasattr(m, "tgt_head_fuser") and len(m.down) == 5 and len(m.up) == 5
+                and m.down[0].layers[0].layers[0].out_channels == 64 and m.up[4].layers[1].layers[0].out_channels == 32
+                and m.compress.out_channels == 4 and bool(getattr(m, "predict_multiref_occ", False)))
+    except (AttributeError, IndexError, TypeError):
+        return False

@@ -180,7 +180,7 @@ def _reference_hparams(model):
     return hp
 
 
-def patch_model(model, fuse_warp_sr=True, precision=None, secc_encoder=False, torso_generator=False):
+def patch_model(model, fuse_warp_sr=True, precision=None, secc_encoder=False, torso_generator=False, torso_motion=False):
     """Swap the hot-path operators of a constructed reference model for the HIP ones (in place).  INFERENCE ONLY: the HIP modules
     detach their inputs and build no autograd graph (the reference runs this path under torch.no_grad(), real3d_infer.py:435,479).
     precision: SR precision of the installed blocks (None = the library default 'f16mx': inside the 2e-4 of SURVEY 8(d) on every golden and heavy-tail sweep,
@@ -202,8 +202,12 @@ def patch_model(model, fuse_warp_sr=True, precision=None, secc_encoder=False, to
     * torso_generator=True (opt-in): model.superresolution.torso_model.deform_based_generator, when it is the reference's Generator at
       standard / small scale (facev2v_warp/network2.py:248-301), -> the HIP Generator, and torso_model.occlusion_2_predictor
       (model2.py:212-219) -> the HIP Occlusion2Predictor (torso_generator.py of this package: the warp and every conv in exact fp32).
-      torso_model.forward and infer_forward_stage2 reach them unchanged; the appearance extractor and the motion-field estimator
-      (stage 1) stay PyTorch.  Other generators are left as they are.
+      torso_model.forward and infer_forward_stage2 reach them unchanged.  Other generators are left as they are.
+    * torso_motion=True (opt-in): model.superresolution.torso_model.motion_field_estimator, when it is the reference's v2
+      MotionFieldEstimator at standard scale (facev2v_warp/network2.py:162-244, with the target-head branch), -> the HIP
+      MotionFieldEstimator (torso_motion.py of this package: the Conv3d hourglass, the fuser, the mask and the occlusion maps in exact
+      fp32).  torso_model.forward reaches it unchanged (model2.py:250).  The v1 estimator of network.py (no target-head branch) and
+      anything else are left as they are; the appearance extractor (per-clip work) stays PyTorch.
     Parameters are copied with strict key matching; the decoder module is left untouched (the renderer reads
     decoder.net[0|2].{weight,bias} directly)."""
     import types
@@ -257,6 +261,11 @@ def patch_model(model, fuse_warp_sr=True, precision=None, secc_encoder=False, to
             tm.deform_based_generator = tg.Generator.from_reference(tm.deform_based_generator)
             if tg.is_reference_predictor(getattr(tm, "occlusion_2_predictor", None)):
                 tm.occlusion_2_predictor = tg.Occlusion2Predictor.from_reference(tm.occlusion_2_predictor)
+    if torso_motion:
+        from . import torso_motion as tmo
+        tm = getattr(model.superresolution, "torso_model", None)
+        if tm is not None and tmo.is_reference_motion_estimator(getattr(tm, "motion_field_estimator", None)):
+            tm.motion_field_estimator = tmo.MotionFieldEstimator.from_reference(tm.motion_field_estimator)
     for owner in (getattr(model, "secc_img2plane_backbone", None), getattr(model, "img2plane_backbone", None)):
         _patch_sequential(owner, "to_plane_cnn", dev)       # per-frame plane producer tail (segformer.py:691-700)
     from .superresolution import set_sr_precision

@@ -1,0 +1,176 @@
+"""Time the torso network's motion-field estimator at B = 1 and the product shapes (K = 4 keypoints, a 16 x 64 x 64 feature
+volume, a 256^2 head image) and print one JSON line:
+
+  * the HIP module (real3dportrait_amd/torso_motion.py) against eager fp32 torch of the same math on the same GPU in the same run:
+    tests/torso_motion_ref64.py evaluated in float32 (F.conv3d, F.grid_sample's arithmetic spelt out, torch.linalg.inv).  Device events
+    around every call, `calls` calls per block, the two sides alternated for `blocks` blocks each after a warm-up; reported: the median of
+    the block medians and the spread (max - min) of the block medians, in ms.  When one eager call takes longer than 50 ms its blocks are
+    shortened to about 10 s each (eager_calls_per_block says to what);
+  * kernel launches of the HIP forward (counted at the C entry points);
+  * the share of the fp32-matrix floor (208.6 GFLOP / 157.3 TFLOP/s = 1.33 ms) the HIP forward reaches.
+
+    python scripts/prof_torso_motion.py [--calls 200] [--blocks 5] [--out DIR]     (writes DIR/prof_torso_motion.json)
+    python scripts/prof_torso_motion.py --forwards 20        only runs that many HIP forwards after a warm-up, for
+        rocprofv3 --kernel-trace --stats -d DIR -o motion -- python scripts/prof_torso_motion.py --forwards 20
+    python scripts/prof_torso_motion.py --summarise DIR/.../motion_kernel_trace.csv --forwards 20
+        the per-launch table of that trace (median over the forwards), with each layer's GFLOP and TFLOP/s
+"""
+import argparse
+import csv
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+GFLOP, PEAK_TFLOPS = 208.6, 157.3
+INPUT_ORDER = ("fs", "kp_s", "kp_d", "Rs", "Rd", "tgt_head_img", "tgt_head_weights")
+
+
+def layers(K=4):
+    """(label, GFLOP at B = 1) of the module's library launches, in launch order (real channel counts, not the padded ones)."""
+    vox, cm = 16 * 64 * 64, 5 * (K + 1)
+    conv = lambda pos, k3, ci, co: 2e-9 * pos * k3 * ci * co
+    out = [("volume_to_cl", 0.0), ("motion input (compress + heatmaps + sample)", 2e-9 * vox * (K + 1) * 8 * 4 * 34)]
+    chans = [cm, 64, 128, 256, 512, 1024]
+    for i in range(5):
+        out.append(("down.%d 3^3 %d->%d @%d^2 + pool" % (i, chans[i], chans[i + 1], 64 >> i), conv(16 * (64 >> i) ** 2, 27, chans[i], chans[i + 1])))
+    up = [1024, 512, 256, 128, 64, 32]
+    for i in range(5):
+        out.append(("up.%d x2 + 3^3 %d->%d @%d^2" % (i, up[i], up[i + 1], 4 << i), conv(16 * (4 << i) ** 2, 27, up[i], up[i + 1])))
+    out += [("resize 256->128 (head)", 0.0), ("encoder 7x7 4->32 @128^2", conv(128 * 128, 49, 4, 32))]
+    for i in range(3):
+        out += [("encoder res.%d conv 0 (prologue)" % i, conv(128 * 128, 9, 32, 32)), ("encoder res.%d conv 1 (+residual)" % i, conv(128 * 128, 9, 32, 32))]
+    out += [("resize 128->64 (head features)", 0.0), ("broadcast over depth", 0.0), ("tgt_head_fuser 7^3 %d->32" % (cm + 64), conv(vox, 343, cm + 64, 32)),
+            ("mask_conv 7^3 32->%d" % (K + 1), conv(vox, 343, 32, K + 1)), ("deformation (softmax + sum)", 0.0),
+            ("occlusion convs 7x7 512->2 (full depth)", conv(64 * 64, 49, 512, 2))]
+    return out
+
+
+def summarise(path, forwards):
+    rows = []
+    with open(path) as f:
+        for r in csv.DictReader(f):
+            rows.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name"]))
+    rows.sort()
+    starts = [i for i, r in enumerate(rows) if "torso_volume_to_cl" in r[2]]
+    segs = [rows[starts[i]:starts[i + 1]] for i in range(len(starts) - 1)][-forwards:]
+    n = min(len(s) for s in segs)
+    assert all(len(s) == len(segs[0]) for s in segs), sorted(set(len(s) for s in segs))
+    lab = iter(layers())
+    total = 0.0
+    print("%-52s %-44s %9s %8s %8s" % ("launch", "kernel", "us", "GFLOP", "TFLOP/s"))
+    for p in range(n):
+        name = segs[0][p][2]
+        us = statistics.median((s[p][1] - s[p][0]) / 1e3 for s in segs)
+        total += us
+        label, gf = next(lab) if "r3d::" in name else ("(torch)", 0.0)
+        short = name.replace("void ", "").split("(")[0][-44:]
+        print("%-52s %-44s %9.1f %8.2f %8.1f" % (label, short, us, gf, gf / us * 1e3 if us else 0.0))
+    span = statistics.median((s[-1][1] - s[0][0]) / 1e3 for s in segs)
+    print("\nsum of kernel durations %.1f us; first start to last end %.1f us; %.1f GFLOP at the %.1f TFLOP/s f32-matrix peak: %.0f us"
+          % (total, span, GFLOP, PEAK_TFLOPS, GFLOP / PEAK_TFLOPS * 1e3))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--calls", type=int, default=200)
+    ap.add_argument("--blocks", type=int, default=5)
+    ap.add_argument("--forwards", type=int, default=0)
+    ap.add_argument("--summarise", default=None)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    if a.summarise:
+        return summarise(a.summarise, a.forwards or 20)
+    import numpy as np
+    import torch
+
+    import torso_motion_ref64 as R
+    from real3dportrait_amd import _lib, synth
+    from real3dportrait_amd.torso_motion import MotionFieldEstimator
+
+    def block_median(fn, calls):
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(calls + 1)]
+        ev[0].record()
+        for i in range(calls):
+            fn()
+            ev[i + 1].record()
+        ev[-1].synchronize()
+        return statistics.median(ev[i].elapsed_time(ev[i + 1]) for i in range(calls))
+
+    def count_launches(fn):
+        lib = _lib.load()
+        names = [n for n in _lib.SIGNATURES if n.startswith("r3d_torso_") or n == "r3d_resize_bilinear"]
+        orig = {n: getattr(lib, n) for n in names}
+        count = {n: 0 for n in names}
+
+        def wrap(n, f):
+            def g(*args):
+                count[n] += 1
+                return f(*args)
+            return g
+
+        for n in names:
+            setattr(lib, n, wrap(n, orig[n]))
+        try:
+            fn()
+        finally:
+            for n in names:
+                setattr(lib, n, orig[n])
+        return {n: c for n, c in count.items() if c}
+
+    dev = "cuda:0"
+    sd = synth.synth_torso_motion(171, 4)
+    m = MotionFieldEstimator()
+    m.load_state_dict({k: torch.from_numpy(np.ascontiguousarray(v)) for k, v in sd.items()}, strict=True)
+    m = m.to(dev).eval()
+    inp = synth.synth_torso_motion_inputs(173, 1, 4)
+    args = [torch.from_numpy(inp[k]).to(dev) for k in INPUT_ORDER]
+    sdd = {k: torch.from_numpy(np.ascontiguousarray(v)).to(dev) for k, v in sd.items()}
+    hip = lambda: m(*args)
+    eager = lambda: R.estimator(sdd, *args, dtype=torch.float32)
+
+    with torch.no_grad():
+        if a.forwards:
+            for _ in range(5 + a.forwards):
+                hip()
+            torch.cuda.synchronize()
+            return
+        for _ in range(3):
+            hip()
+            eager()
+        torch.cuda.synchronize()
+        t0 = time.time()
+        eager()
+        torch.cuda.synchronize()
+        warm_ms = (time.time() - t0) * 1e3
+        ecalls = a.calls if warm_ms <= 50.0 else max(5, min(a.calls, int(10000.0 / warm_ms)))
+        for _ in range(7):
+            hip()
+        hb, eb = [], []
+        for _ in range(a.blocks):
+            hb.append(block_median(hip, a.calls))
+            eb.append(block_median(eager, ecalls))
+        launches = count_launches(hip)
+        diffs = [float((x - y).abs().max() / y.abs().max()) for x, y in zip(hip(), eager())]
+    h, e = statistics.median(hb), statistics.median(eb)
+    out = {"metric": "torso_motion_b1_k4", "B": 1, "K": 4, "calls_per_block": a.calls, "eager_calls_per_block": ecalls, "blocks": a.blocks,
+           "hip_ms": round(h, 4), "hip_block_medians_ms": [round(v, 4) for v in hb], "hip_spread_ms": round(max(hb) - min(hb), 4),
+           "eager_fp32_torch_ms": round(e, 4), "eager_block_medians_ms": [round(v, 4) for v in eb], "eager_spread_ms": round(max(eb) - min(eb), 4),
+           "speedup_vs_eager": round(e / h, 3), "faster_by_more_than_the_spread": bool(e - h > max(max(hb) - min(hb), max(eb) - min(eb))),
+           "launches_per_forward": sum(launches.values()), "launches_by_entry_point": launches,
+           "fp32_matrix_floor_ms": round(GFLOP / PEAK_TFLOPS, 4), "share_of_floor": round(GFLOP / PEAK_TFLOPS / h, 3),
+           "hip_vs_eager_max_rel_diff_deformation_occ_occ2": diffs}
+    print(json.dumps(out))
+    if a.out:
+        os.makedirs(a.out, exist_ok=True)
+        with open(os.path.join(a.out, "prof_torso_motion.json"), "w") as f:
+            f.write(json.dumps(out, indent=1) + "\n")
+
+
+if __name__ == "__main__":
+    main()
