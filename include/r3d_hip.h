@@ -506,6 +506,35 @@ int r3d_torso_motion_deform(const float* mask, int N, int D, int H, int W, int K
 int r3d_torso_motion_broadcast(const float* feats, int N, int C, int H, int W, int D, float* fuse, int fuse_cstride, int fuse_coffset,
                                r3d_stream_t stream);
 
+/* --- a second precision tier for the torso convolutions (added under ABI 0.8.0; opt-in, the entry points above are unchanged) -------
+ * r3d_torso_conv_prec / r3d_torso_conv3d_prec take the argument lists of r3d_torso_conv / r3d_torso_conv3d with `precision` in front of
+ * `stream`; argument checks, overlap rules and everything outside the products (prologue, zero padding, bias, activation, residual, pool,
+ * slices, output layouts, tile selection) are those functions'.  Any other precision is R3D_ERR_INVALID_ARG.
+ *   R3D_TORSO_F32     the kernels of r3d_torso_conv / r3d_torso_conv3d, bit-identical to them.
+ *   R3D_TORSO_BF16X3  every staged activation (after the prologue and the zero outside the image) and every staged weight is split into
+ *     three bf16 pieces, x = h + m + l exactly: h = bf16(clamp(x, +-0x7f7f0000)), m = bf16(x - h), l = bf16(x - h - m), round to nearest
+ *     even (the clamp keeps values that would round to infinity finite; both subtractions are exact in fp32).  Per 32 k entries six piece
+ *     products are added on v_mfma_f32_16x16x32_bf16 to the fp32 accumulator in the fixed order
+ *         xl wh, xh wl, xm wm, xm wh, xh wm, xh wh      (x: activation, w: weight)
+ *     and the three below 2^-25 |x| |w| (xl wm, xm wl, xl wl) are left out.  The accumulator, the order of the k steps and of the k entries
+ *     inside a step are the exact tier's, so the result is fp32-class (same test bound as the exact kernels) and, like theirs, depends on
+ *     nothing but the operands: bit-identical across batch sizes, runs and streams.  bf16 has fp32's exponent range: there is no range
+ *     fold, no scale and no per-tensor state, and operands up to fp32 max are split exactly.  Pieces below bf16's smallest normal are read
+ *     as zero, so for |x| below about 2^-110 the value degrades to two, then one piece (relative accuracy 2^-16, 2^-8).  A non-finite
+ *     operand gives a non-finite (possibly NaN where the exact tier gives an infinity) result.  Weights stay fp32 in memory. */
+#define R3D_TORSO_F32 0
+#define R3D_TORSO_BF16X3 1
+int r3d_torso_conv_prec(const float* x, int B, int Hs, int Ws, int Cin, int in_nchw, int upsample, const float* pro_scale,
+                        const float* pro_shift, float pro_slope, const float* w, const float* bias, int Cout, int ksize, int act,
+                        float act_slope, const float* residual, float* y, float* y_nchw, int precision, r3d_stream_t stream);
+int r3d_torso_conv3d_prec(const float* x, int B, int D, int Hs, int Ws, int Cin, int upsample, const float* w, const float* bias,
+                          int Cout, int ksize, int full_depth, int act, float act_slope, int pool, float* y, int y_cstride,
+                          int y_coffset, float* y_ncdhw, int precision, r3d_stream_t stream);
+/* The split of R3D_TORSO_BF16X3, by the device function the convolutions' staging calls: h[i], m[i], l[i] = the 16 bits of the pieces of
+ * x[i] (a piece as fp32 is its bits << 16), i < n, 1 <= n < 2^31.  For tests (real3dportrait_amd/torso_precision.py:split_bf16x3 is its
+ * host mirror).  The outputs must not overlap x or each other. */
+int r3d_torso_split_bf16x3(const float* x, size_t n, uint16_t* h, uint16_t* m, uint16_t* l, r3d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,6 +13,8 @@
 //                        the reference pads the activated tensor) and nearest x2 up-sampling in the addressing; the epilogue adds the bias,
 //                        applies LeakyReLU / sigmoid, adds a residual and writes channel-last and / or NCHW.  VEC: Cin % 4 == 0,
 //                        channel-last input, 16-byte loads; otherwise one element per load (NCHW input, Cin = 65, 3, 1).
+//   torso_bf3::torso_conv<...>  the same tiles with the products on the BF16X3 tier (r3d_torso_conv_prec), and
+//   torso_bf3::torso_split      that tier's split of a plain array (r3d_torso_split_bf16x3, for the tests).
 #include "r3d_common.h"
 #include "r3d_torso_conv.h"
 #include <math.h>
@@ -90,15 +92,47 @@ using tconv::ConvArgs;
 
 // the 2-D instantiation of the shared tile (r3d_torso_conv.h)
 template <bool VEC, int WM, int WN, int TM, int TN>
-__global__ void __launch_bounds__(256) torso_conv(ConvArgs g) { tconv::conv_tile<VEC, false, WM, WN, TM, TN>(g); }
+__global__ void __launch_bounds__(256) torso_conv(ConvArgs g) { tconv::conv_tile<tconv::F32, VEC, false, WM, WN, TM, TN>(g); }
+
+}  // namespace torso
+
+// the kernels of the BF16X3 tier (R3D_TORSO_BF16X3)
+namespace torso_bf3 {
 
 template <bool VEC, int WM, int WN, int TM, int TN>
+__global__ void __launch_bounds__(256) torso_conv(tconv::ConvArgs g) { tconv::conv_tile<tconv::BF16X3, VEC, false, WM, WN, TM, TN>(g); }
+
+// r3d_torso_split_bf16x3: the staging split of the tier, one element per thread
+__global__ void __launch_bounds__(256) torso_split(const float* x, size_t n, uint16_t* h, uint16_t* m, uint16_t* l)
+{
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) tconv::split_bf16x3(x[i], h[i], m[i], l[i]);
+}
+
+}  // namespace torso_bf3
+
+namespace torso {
+
+template <int PREC, bool VEC, int WM, int WN, int TM, int TN>
 static void launch_conv(ConvArgs g, hipStream_t st)
 {
     constexpr int BM = WM * TM * 16, BN = WN * TN * 16;
     g.ntn = (g.Cout + BN - 1) / BN;
     const long long nblk = (long long)((g.M + BM - 1) / BM) * g.ntn;
-    hipLaunchKernelGGL((torso_conv<VEC, WM, WN, TM, TN>), dim3((unsigned)nblk), dim3(256), 0, st, g);
+    if constexpr (PREC == tconv::BF16X3) hipLaunchKernelGGL((torso_bf3::torso_conv<VEC, WM, WN, TM, TN>), dim3((unsigned)nblk), dim3(256), 0, st, g);
+    else hipLaunchKernelGGL((torso_conv<VEC, WM, WN, TM, TN>), dim3((unsigned)nblk), dim3(256), 0, st, g);
+}
+
+// the tile follows Cout: 64 x 64 (pixels x channels) or 32 x 64, 128 x 32 up to 32 channels, 128 x 16 up to 16 (out_conv's 3, the predictor's 1)
+// (32 x 64 where 64 x 64 tiles would give the 256 CUs fewer than two blocks each: the 64^2 layers, one wave per SIMD otherwise)
+template <int PREC>
+static void dispatch_conv(const ConvArgs& g, bool vec, hipStream_t st)
+{
+    const long long big = (long long)((g.M + 63) / 64) * ((g.Cout + 63) / 64);
+    if (g.Cout > 32 && big < 512) { if (vec) launch_conv<PREC, true, 2, 2, 1, 2>(g, st); else launch_conv<PREC, false, 2, 2, 1, 2>(g, st); }
+    else if (g.Cout > 32) { if (vec) launch_conv<PREC, true, 2, 2, 2, 2>(g, st); else launch_conv<PREC, false, 2, 2, 2, 2>(g, st); }
+    else if (g.Cout > 16) { if (vec) launch_conv<PREC, true, 4, 1, 2, 2>(g, st); else launch_conv<PREC, false, 4, 1, 2, 2>(g, st); }
+    else { if (vec) launch_conv<PREC, true, 4, 1, 2, 1>(g, st); else launch_conv<PREC, false, 4, 1, 2, 1>(g, st); }
 }
 
 }  // namespace torso
@@ -135,10 +169,12 @@ extern "C" int r3d_torso_warp(const float* fs_cl, int N, int C, int D, int H, in
     return check_launch("torso_warp");
 }
 
-extern "C" int r3d_torso_conv(const float* x, int B, int Hs, int Ws, int Cin, int in_nchw, int upsample, const float* pro_scale,
-                              const float* pro_shift, float pro_slope, const float* w, const float* bias, int Cout, int ksize, int act,
-                              float act_slope, const float* residual, float* y, float* y_nchw, r3d_stream_t stream)
+static int torso_conv_impl(const float* x, int B, int Hs, int Ws, int Cin, int in_nchw, int upsample, const float* pro_scale,
+                           const float* pro_shift, float pro_slope, const float* w, const float* bias, int Cout, int ksize, int act,
+                           float act_slope, const float* residual, float* y, float* y_nchw, int precision, r3d_stream_t stream)
 {
+    if (precision != R3D_TORSO_F32 && precision != R3D_TORSO_BF16X3)
+        { set_error("torso_conv: precision %d is not 0 (R3D_TORSO_F32) or 1 (R3D_TORSO_BF16X3)", precision); return R3D_ERR_INVALID_ARG; }
     if (!x || !w || (!y && !y_nchw) || (!pro_scale) != (!pro_shift)) { set_error("torso_conv: NULL pointer"); return R3D_ERR_INVALID_ARG; }
     if (B <= 0 || Hs <= 0 || Ws <= 0 || Cin <= 0 || Cout <= 0 || Cin > 4096 || Cout > 4096)
         { set_error("torso_conv: bad argument (B, Hs, Ws > 0, 1 <= Cin, Cout <= 4096)"); return R3D_ERR_INVALID_ARG; }
@@ -165,12 +201,39 @@ extern "C" int r3d_torso_conv(const float* x, int B, int Hs, int Ws, int Cin, in
     g.res = residual; g.y = y; g.y_nchw = y_nchw; g.M = B * H * W; g.K = ksize * ksize * Cin;
     auto aligned = [](const void* p) { return p == nullptr || ((uintptr_t)p & 15) == 0; };
     const bool vec = !in_nchw && Cin % 4 == 0 && aligned(x) && aligned(w) && aligned(pro_scale) && aligned(pro_shift);
-    // the tile follows Cout: 64 x 64 (pixels x channels) or 32 x 64, 128 x 32 up to 32 channels, 128 x 16 up to 16 (out_conv's 3, the predictor's 1)
-    // (32 x 64 where 64 x 64 tiles would give the 256 CUs fewer than two blocks each: the 64^2 layers, one wave per SIMD otherwise)
-    const long long big = (long long)((g.M + 63) / 64) * ((Cout + 63) / 64);
-    if (Cout > 32 && big < 512) { if (vec) launch_conv<true, 2, 2, 1, 2>(g, st); else launch_conv<false, 2, 2, 1, 2>(g, st); }
-    else if (Cout > 32) { if (vec) launch_conv<true, 2, 2, 2, 2>(g, st); else launch_conv<false, 2, 2, 2, 2>(g, st); }
-    else if (Cout > 16) { if (vec) launch_conv<true, 4, 1, 2, 2>(g, st); else launch_conv<false, 4, 1, 2, 2>(g, st); }
-    else { if (vec) launch_conv<true, 4, 1, 2, 1>(g, st); else launch_conv<false, 4, 1, 2, 1>(g, st); }
+    if (precision == R3D_TORSO_BF16X3) dispatch_conv<tconv::BF16X3>(g, vec, st);
+    else dispatch_conv<tconv::F32>(g, vec, st);
     return check_launch("torso_conv");
+}
+
+extern "C" int r3d_torso_conv(const float* x, int B, int Hs, int Ws, int Cin, int in_nchw, int upsample, const float* pro_scale,
+                              const float* pro_shift, float pro_slope, const float* w, const float* bias, int Cout, int ksize, int act,
+                              float act_slope, const float* residual, float* y, float* y_nchw, r3d_stream_t stream)
+{
+    return torso_conv_impl(x, B, Hs, Ws, Cin, in_nchw, upsample, pro_scale, pro_shift, pro_slope, w, bias, Cout, ksize, act, act_slope, residual,
+                           y, y_nchw, R3D_TORSO_F32, stream);
+}
+
+extern "C" int r3d_torso_conv_prec(const float* x, int B, int Hs, int Ws, int Cin, int in_nchw, int upsample, const float* pro_scale,
+                                   const float* pro_shift, float pro_slope, const float* w, const float* bias, int Cout, int ksize, int act,
+                                   float act_slope, const float* residual, float* y, float* y_nchw, int precision, r3d_stream_t stream)
+{
+    return torso_conv_impl(x, B, Hs, Ws, Cin, in_nchw, upsample, pro_scale, pro_shift, pro_slope, w, bias, Cout, ksize, act, act_slope, residual,
+                           y, y_nchw, precision, stream);
+}
+
+extern "C" int r3d_torso_split_bf16x3(const float* x, size_t n, uint16_t* h, uint16_t* m, uint16_t* l, r3d_stream_t stream)
+{
+    if (!x || !h || !m || !l) { set_error("torso_split_bf16x3: NULL pointer"); return R3D_ERR_INVALID_ARG; }
+    if (n == 0 || n > 2147483647u) { set_error("torso_split_bf16x3: n is not in 1 .. 2^31 - 1"); return R3D_ERR_INVALID_ARG; }
+    const char *xb = (const char*)x, *xe = xb + 4 * n;
+    uint16_t* const out[3] = {h, m, l};
+    for (int i = 0; i < 3; ++i) {
+        const char *ob = (const char*)out[i], *oe = ob + 2 * n;
+        if (ob < xe && xb < oe) { set_error("torso_split_bf16x3: an output overlaps x"); return R3D_ERR_INVALID_ARG; }
+        for (int j = 0; j < i; ++j)
+            if (out[i] < out[j] + n && out[j] < out[i] + n) { set_error("torso_split_bf16x3: two outputs overlap"); return R3D_ERR_INVALID_ARG; }
+    }
+    hipLaunchKernelGGL(torso_bf3::torso_split, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, n, h, m, l);
+    return check_launch("torso_split_bf16x3");
 }

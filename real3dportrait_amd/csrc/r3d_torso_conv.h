@@ -16,14 +16,64 @@
 //     epilogue; the un-pooled tensor is never written;
 //   * an output channel stride and offset (a producer writes its slice of a concatenation);
 //   * m-fast tile order for layers with fewer positions than output channels (every XCD streams its own share of the weights once).
+//
+// PREC selects the arithmetic of the products; loaders, tile order and epilogues are the same code for both.
+//   F32     the fp32 operands as they are, 8 v_mfma_f32_16x16x4_f32 per 16 x 16 tile and k step.
+//   BF16X3  store() splits every staged value into three bf16 pieces h + m + l == x (split_bf16x3) and compute() sums six of the nine
+//           piece products on v_mfma_f32_16x16x32_bf16 into the same fp32 accumulators, smallest first:
+//           l.h, h.l, m.m, m.h, h.m, h.h (activation piece . weight piece).  The dropped l.m, m.l, l.l are below 2^-25 of |x||w|.
+//           bf16 has fp32's exponent: no range fold, no per-tensor state.
 #pragma once
 #include "r3d_common.h"
 #include <math.h>
+#include <type_traits>
 
 namespace r3d {
 namespace tconv {
 
 constexpr int BK = 32, LDK = BK + 4;     // LDS rows of 36 floats: 16-byte aligned, and 16 rows at one k offset touch 64 distinct banks
+constexpr int F32 = 0, BF16X3 = 1;       // PREC (R3D_TORSO_F32, R3D_TORSO_BF16X3)
+
+// BF16X3's LDS row, in bf16 elements: [h: 32 k][m: 32 k][l: 32 k][8 of padding] = 208 bytes.  A piece's 32 k entries are four 16-byte slots,
+// one per lane group of compute(); slot g of row r is stored at position g ^ bf3_swz(r).  ds_read_b128 serves 16 lanes at a time, rows
+// {0-3, 12-15} of group g with rows {4-11} of group g + 1 (and the other way round): 13 r + (g ^ swz(r)) mod 16 takes 16 distinct values on
+// either set, so every read touches each 16-byte slot of the 256-byte bank row once.  The 16 bytes of padding are for the element loader's
+// 2-byte stores, where consecutive lanes write consecutive rows: 52 r mod 32 dwords takes 8 values (192-byte rows: 2).
+constexpr int LDH = 3 * BK + 8;
+__device__ __forceinline__ int bf3_swz(int row) { return ((row >> 2) ^ (row >> 3)) & 1; }
+// the bf16 index of k entry k (0 .. 31) of piece p in row `row`
+__device__ __forceinline__ int bf3_at(int row, int p, int k) { return row * LDH + p * BK + ((((k >> 3) ^ bf3_swz(row)) << 3) | (k & 7)); }
+
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+
+// ---- THE split of the BF16X3 tier: x == h + m + l exactly, three bf16 pieces (their 16 bits; a piece widened to fp32 is piece << 16).
+//   h = bf16(clamp(x, -C, C)),  m = bf16(x - h),  l = bf16(x - h - m),  round-to-nearest-even, C = 0x7f7f0000 the largest finite bf16
+// (without the clamp values above C would round to infinity; with it fp32 max splits exactly as well).  Both subtractions are exact in fp32:
+// |x - h| <= ulp_bf16(x) / 2 has at most 16 significant bits, and after m at most 8 are left, so l is exact too -- down to |x| ~ 2^-110, where
+// l (2^-16 |x|) falls below bf16's smallest normal and the matrix unit reads it as zero.  A non-finite x gives non-finite pieces (NaN for an
+// infinity).  as_rounded(): the value is split as it was rounded to fp32, whatever produced it (a prologue multiply must not be contracted
+// into the first subtraction at one use and not at another).  real3dportrait_amd/torso_precision.py:split_bf16x3 mirrors it bit for bit.
+__device__ __forceinline__ void split_bf16x3(float x, uint16_t& h, uint16_t& m, uint16_t& l)
+{
+    x = as_rounded(x);
+    const float big = __uint_as_float(0x7f7f0000u);
+    const __bf16 hb = (__bf16)__builtin_amdgcn_fmed3f(x, -big, big);
+    const float r1 = as_rounded(x - (float)hb);
+    const __bf16 mb = (__bf16)r1;
+    const float r2 = as_rounded(r1 - (float)mb);
+    const __bf16 lb = (__bf16)r2;
+    h = __builtin_bit_cast(uint16_t, hb); m = __builtin_bit_cast(uint16_t, mb); l = __builtin_bit_cast(uint16_t, lb);
+}
+// four consecutive k entries -> each piece's 8 bytes
+__device__ __forceinline__ void split_bf16x3(const float4& v, uint2& h, uint2& m, uint2& l)
+{
+    uint16_t a[4], b[4], c[4];
+    split_bf16x3(v.x, a[0], b[0], c[0]); split_bf16x3(v.y, a[1], b[1], c[1]);
+    split_bf16x3(v.z, a[2], b[2], c[2]); split_bf16x3(v.w, a[3], b[3], c[3]);
+    h = make_uint2(a[0] | (uint32_t)a[1] << 16, a[2] | (uint32_t)a[3] << 16);
+    m = make_uint2(b[0] | (uint32_t)b[1] << 16, b[2] | (uint32_t)b[3] << 16);
+    l = make_uint2(c[0] | (uint32_t)c[1] << 16, c[2] | (uint32_t)c[3] << 16);
+}
 
 struct ConvArgs {
     const float* x; int B, Hs, Ws, Cin;          // stored input [B, Hs, Ws, Cin] (in_nchw: [B, Cin, Hs, Ws]); D3: [B, D, Hs, Ws, Cin]
@@ -71,15 +121,18 @@ struct KPos {
     }
 };
 
-template <bool VEC, bool D3, int WM, int WN, int TM, int TN>
+template <int PREC, bool VEC, bool D3, int WM, int WN, int TM, int TN>
 __device__ __forceinline__ void conv_tile(const ConvArgs& g)
 {
     static_assert(WM * WN == 4, "four waves");
+    static_assert(PREC == F32 || PREC == BF16X3, "precision");
     constexpr int BM = WM * TM * 16, BN = WN * TN * 16;
     constexpr int AV = BM / 32, WV = (BN + 31) / 32;           // VEC: float4 loads per thread (A, W)
     constexpr int AS = BM / 8, WS = BN / 8, KSTEP = 256 / BM;  // scalar: elements per thread; A's k stride between them
-    __shared__ __attribute__((aligned(16))) float As[2][BM * LDK];
-    __shared__ __attribute__((aligned(16))) float Ws[2][BN * LDK];
+    typedef typename std::conditional<PREC == BF16X3, uint16_t, float>::type lds_t;      // BF16X3: rows of LDH bf16 (bf3_at)
+    constexpr int LDR = PREC == BF16X3 ? LDH : LDK;
+    __shared__ __attribute__((aligned(16))) lds_t As[2][BM * LDR];
+    __shared__ __attribute__((aligned(16))) lds_t Ws[2][BN * LDR];
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     // Blocks are dealt to the 8 XCDs round-robin, and each XCD has an L2 of its own: block b takes tile (b % 8) (nblk / 8) + b / 8, so that
     // one XCD works on neighbouring pixel tiles (which share their taps' rows) and on all channel tiles of each (which share the taps).
@@ -202,6 +255,22 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& g)
             }
         }
     };
+    // BF16X3: a staged value goes to LDS as its three pieces (after the prologue and the zero outside the image)
+    auto put4 = [&](lds_t* T, int row, const float4& v) {       // k entries 4 (t & 7) .. + 3 of the step
+        if constexpr (PREC == BF16X3) {
+            uint2 h, m, l;
+            split_bf16x3(v, h, m, l);
+            *reinterpret_cast<uint2*>(&T[bf3_at(row, 0, 4 * (t & 7))]) = h;
+            *reinterpret_cast<uint2*>(&T[bf3_at(row, 1, 4 * (t & 7))]) = m;
+            *reinterpret_cast<uint2*>(&T[bf3_at(row, 2, 4 * (t & 7))]) = l;
+        } else {
+            *reinterpret_cast<float4*>(&T[row * LDK + 4 * (t & 7)]) = v;
+        }
+    };
+    auto put1 = [&](lds_t* T, int row, int k, float v) {
+        if constexpr (PREC == BF16X3) split_bf16x3(v, T[bf3_at(row, 0, k)], T[bf3_at(row, 1, k)], T[bf3_at(row, 2, k)]);
+        else T[row * LDK + k] = v;
+    };
     auto store = [&](const Stage& r, int buf) {
         if constexpr (VEC) {
 #pragma unroll
@@ -211,46 +280,68 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& g)
                     v.x = leaky(fmaf(r.ps4.x, v.x, r.pt4.x), g.pslope); v.y = leaky(fmaf(r.ps4.y, v.y, r.pt4.y), g.pslope);
                     v.z = leaky(fmaf(r.ps4.z, v.z, r.pt4.z), g.pslope); v.w = leaky(fmaf(r.ps4.w, v.w, r.pt4.w), g.pslope);
                 }
-                *reinterpret_cast<float4*>(&As[buf][((t >> 3) + 32 * j) * LDK + 4 * (t & 7)]) = v;
+                put4(As[buf], (t >> 3) + 32 * j, v);
             }
 #pragma unroll
             for (int j = 0; j < WV; ++j) {
                 const int row = (t >> 3) + 32 * j;
-                if (row < BN) *reinterpret_cast<float4*>(&Ws[buf][row * LDK + 4 * (t & 7)]) = r.wv4[j];
+                if (row < BN) put4(Ws[buf], row, r.wv4[j]);
             }
         } else {
 #pragma unroll
             for (int j = 0; j < AS; ++j) {
                 float v = r.avs[j];
                 if (g.ps && (r.inside >> j & 1)) v = leaky(fmaf(r.pss[j], v, r.pts[j]), g.pslope);
-                As[buf][(t % BM) * LDK + t / BM + KSTEP * j] = v;
+                put1(As[buf], t % BM, t / BM + KSTEP * j, v);
             }
 #pragma unroll
-            for (int j = 0; j < WS; ++j) { const int e = t + 256 * j; Ws[buf][(e >> 5) * LDK + (e & 31)] = r.wvs[j]; }
+            for (int j = 0; j < WS; ++j) { const int e = t + 256 * j; put1(Ws[buf], e >> 5, e & 31, r.wvs[j]); }
         }
     };
     // one k step of the block's tile out of LDS buffer `cur`
     auto compute = [&](int cur) {
-        // lane group lane >> 4 owns k entries 8 (lane >> 4) .. + 7 of the step, one per MFMA: the order of the sum is fixed, whichever
-        float a[TM][8], b[TN][8];
-#pragma unroll
-        for (int i = 0; i < TM; ++i) {
-            const float* p = &As[cur][(wm + i * 16 + (lane & 15)) * LDK + 8 * (lane >> 4)];
-            const float4 lo = *reinterpret_cast<const float4*>(p), hi = *reinterpret_cast<const float4*>(p + 4);
-            a[i][0] = lo.x; a[i][1] = lo.y; a[i][2] = lo.z; a[i][3] = lo.w; a[i][4] = hi.x; a[i][5] = hi.y; a[i][6] = hi.z; a[i][7] = hi.w;
-        }
-#pragma unroll
-        for (int j = 0; j < TN; ++j) {
-            const float* p = &Ws[cur][(wn + j * 16 + (lane & 15)) * LDK + 8 * (lane >> 4)];
-            const float4 lo = *reinterpret_cast<const float4*>(p), hi = *reinterpret_cast<const float4*>(p + 4);
-            b[j][0] = lo.x; b[j][1] = lo.y; b[j][2] = lo.z; b[j][3] = lo.w; b[j][4] = hi.x; b[j][5] = hi.y; b[j][6] = hi.z; b[j][7] = hi.w;
-        }
-#pragma unroll
-        for (int kk = 0; kk < 8; ++kk)
+        if constexpr (PREC == BF16X3) {
+            // lane group lane >> 4 owns the same k entries 8 (lane >> 4) .. + 7, all eight in one MFMA: a piece's fragment is one 16-byte read
+            bf16x8 a[TM][3], b[TN][3];
 #pragma unroll
             for (int i = 0; i < TM; ++i)
 #pragma unroll
-                for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i][kk], b[j][kk], acc[i][j], 0, 0, 0);
+                for (int p = 0; p < 3; ++p) a[i][p] = *reinterpret_cast<const bf16x8*>(&As[cur][bf3_at(wm + i * 16 + (lane & 15), p, 8 * (lane >> 4))]);
+#pragma unroll
+            for (int j = 0; j < TN; ++j)
+#pragma unroll
+                for (int p = 0; p < 3; ++p) b[j][p] = *reinterpret_cast<const bf16x8*>(&Ws[cur][bf3_at(wn + j * 16 + (lane & 15), p, 8 * (lane >> 4))]);
+            // the six products, smallest first: (activation piece, weight piece) = l.h, h.l, m.m, m.h, h.m, h.h
+            constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PW[6] = {0, 2, 1, 0, 1, 0};
+#pragma unroll
+            for (int q = 0; q < 6; ++q)
+#pragma unroll
+                for (int i = 0; i < TM; ++i)
+#pragma unroll
+                    for (int j = 0; j < TN; ++j)
+                        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[i][PA[q]], b[j][PW[q]], acc[i][j], 0, 0, 0);
+        } else {
+            // lane group lane >> 4 owns k entries 8 (lane >> 4) .. + 7 of the step, one per MFMA: the order of the sum is fixed, whichever
+            float a[TM][8], b[TN][8];
+#pragma unroll
+            for (int i = 0; i < TM; ++i) {
+                const float* p = &As[cur][(wm + i * 16 + (lane & 15)) * LDK + 8 * (lane >> 4)];
+                const float4 lo = *reinterpret_cast<const float4*>(p), hi = *reinterpret_cast<const float4*>(p + 4);
+                a[i][0] = lo.x; a[i][1] = lo.y; a[i][2] = lo.z; a[i][3] = lo.w; a[i][4] = hi.x; a[i][5] = hi.y; a[i][6] = hi.z; a[i][7] = hi.w;
+            }
+#pragma unroll
+            for (int j = 0; j < TN; ++j) {
+                const float* p = &Ws[cur][(wn + j * 16 + (lane & 15)) * LDK + 8 * (lane >> 4)];
+                const float4 lo = *reinterpret_cast<const float4*>(p), hi = *reinterpret_cast<const float4*>(p + 4);
+                b[j][0] = lo.x; b[j][1] = lo.y; b[j][2] = lo.z; b[j][3] = lo.w; b[j][4] = hi.x; b[j][5] = hi.y; b[j][6] = hi.z; b[j][7] = hi.w;
+            }
+#pragma unroll
+            for (int kk = 0; kk < 8; ++kk)
+#pragma unroll
+                for (int i = 0; i < TM; ++i)
+#pragma unroll
+                    for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i][kk], b[j][kk], acc[i][j], 0, 0, 0);
+        }
     };
 
     // Two register stages and two LDS buffers: step s is computed out of buffer s & 1 while step s + 1 (loaded one iteration earlier)

@@ -3,6 +3,7 @@
 //   conv3d<VEC, WM, WN, TM, TN>  the D3 = true instantiation of conv_tile (r3d_torso_conv.h): stride-1 Conv3d on v_mfma_f32_16x16x4_f32
 //                                with nearest x2 up-sampling of H and W in the tap addresses, AvgPool3d((1, 2, 2)) in the epilogue, an output
 //                                channel slice, and the full-depth form (a Conv2d over x.view(N, C D, H, W)).
+//   tmotion_bf3::conv3d<...>     the same tiles with the products on the BF16X3 tier (r3d_torso_conv3d_prec).
 //   motion_input                 compress (Conv3d 1x1x1) + the heatmaps + the sparse motions + grid_sample(align_corners=True, zeros
 //                                padding) of the compressed volume, one thread per (voxel, k): the hourglass input.
 //   motion_deform                softmax over the K + 1 mask logits and the mask-weighted sum of the sparse motions, one thread per voxel.
@@ -18,16 +19,41 @@ namespace tmotion {
 using tconv::ConvArgs;
 
 template <bool VEC, int WM, int WN, int TM, int TN>
-__global__ void __launch_bounds__(256) conv3d(ConvArgs g) { tconv::conv_tile<VEC, true, WM, WN, TM, TN>(g); }
+__global__ void __launch_bounds__(256) conv3d(ConvArgs g) { tconv::conv_tile<tconv::F32, VEC, true, WM, WN, TM, TN>(g); }
+
+}  // namespace tmotion
+
+// the kernels of the BF16X3 tier (R3D_TORSO_BF16X3)
+namespace tmotion_bf3 {
 
 template <bool VEC, int WM, int WN, int TM, int TN>
+__global__ void __launch_bounds__(256) conv3d(tconv::ConvArgs g) { tconv::conv_tile<tconv::BF16X3, VEC, true, WM, WN, TM, TN>(g); }
+
+}  // namespace tmotion_bf3
+
+namespace tmotion {
+
+template <int PREC, bool VEC, int WM, int WN, int TM, int TN>
 static void launch_conv3d(ConvArgs g, hipStream_t st)
 {
     constexpr int BM = WM * TM * 16, BN = WN * TN * 16;
     g.ntn = (g.Cout + BN - 1) / BN;
     g.ntm = (g.M + BM - 1) / BM;
     const long long nblk = (long long)g.ntm * g.ntn;
-    hipLaunchKernelGGL((conv3d<VEC, WM, WN, TM, TN>), dim3((unsigned)nblk), dim3(256), 0, st, g);
+    if constexpr (PREC == tconv::BF16X3) hipLaunchKernelGGL((tmotion_bf3::conv3d<VEC, WM, WN, TM, TN>), dim3((unsigned)nblk), dim3(256), 0, st, g);
+    else hipLaunchKernelGGL((conv3d<VEC, WM, WN, TM, TN>), dim3((unsigned)nblk), dim3(256), 0, st, g);
+}
+
+// the tile follows Cout as in r3d_torso_conv; up to 16 channels a 64 x 16 tile where 128 x 16 ones would leave most CUs without a block
+template <int PREC>
+static void dispatch_conv3d(const ConvArgs& g, bool vec, hipStream_t st)
+{
+    const long long big = (long long)((g.M + 63) / 64) * ((g.Cout + 63) / 64);
+    if (g.Cout > 32 && big < 512) { if (vec) launch_conv3d<PREC, true, 2, 2, 1, 2>(g, st); else launch_conv3d<PREC, false, 2, 2, 1, 2>(g, st); }
+    else if (g.Cout > 32) { if (vec) launch_conv3d<PREC, true, 2, 2, 2, 2>(g, st); else launch_conv3d<PREC, false, 2, 2, 2, 2>(g, st); }
+    else if (g.Cout > 16) { if (vec) launch_conv3d<PREC, true, 4, 1, 2, 2>(g, st); else launch_conv3d<PREC, false, 4, 1, 2, 2>(g, st); }
+    else if ((g.M + 127) / 128 < 256) { if (vec) launch_conv3d<PREC, true, 4, 1, 1, 1>(g, st); else launch_conv3d<PREC, false, 4, 1, 1, 1>(g, st); }
+    else { if (vec) launch_conv3d<PREC, true, 4, 1, 2, 1>(g, st); else launch_conv3d<PREC, false, 4, 1, 2, 1>(g, st); }
 }
 
 struct MotionArgs {
@@ -176,10 +202,12 @@ using namespace r3d::tmotion;
 // [a, a + na) and [b, b + nb) (counts of floats) share an element
 static bool overlap(const float* a, size_t na, const float* b, size_t nb) { return a < b + nb && b < a + na; }
 
-extern "C" int r3d_torso_conv3d(const float* x, int B, int D, int Hs, int Ws, int Cin, int upsample, const float* w, const float* bias,
-                                int Cout, int ksize, int full_depth, int act, float act_slope, int pool, float* y, int y_cstride,
-                                int y_coffset, float* y_ncdhw, r3d_stream_t stream)
+static int torso_conv3d_impl(const float* x, int B, int D, int Hs, int Ws, int Cin, int upsample, const float* w, const float* bias,
+                             int Cout, int ksize, int full_depth, int act, float act_slope, int pool, float* y, int y_cstride,
+                             int y_coffset, float* y_ncdhw, int precision, r3d_stream_t stream)
 {
+    if (precision != R3D_TORSO_F32 && precision != R3D_TORSO_BF16X3)
+        { set_error("torso_conv3d: precision %d is not 0 (R3D_TORSO_F32) or 1 (R3D_TORSO_BF16X3)", precision); return R3D_ERR_INVALID_ARG; }
     if (!x || !w || (!y && !y_ncdhw)) { set_error("torso_conv3d: NULL pointer"); return R3D_ERR_INVALID_ARG; }
     if (B <= 0 || D <= 0 || Hs <= 0 || Ws <= 0 || Cin <= 0 || Cout <= 0 || Cin > 4096 || Cout > 4096 || D > 1024)
         { set_error("torso_conv3d: bad argument (B, Hs, Ws > 0, 1 <= D <= 1024, 1 <= Cin, Cout <= 4096)"); return R3D_ERR_INVALID_ARG; }
@@ -217,14 +245,25 @@ extern "C" int r3d_torso_conv3d(const float* x, int B, int D, int Hs, int Ws, in
     g.mfast = g.M < Cout;
     auto aligned = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
     const bool vec = Cin % 4 == 0 && aligned(x) && aligned(w);
-    // the tile follows Cout as in r3d_torso_conv; up to 16 channels a 64 x 16 tile where 128 x 16 ones would leave most CUs without a block
-    const long long big = (long long)((g.M + 63) / 64) * ((Cout + 63) / 64);
-    if (Cout > 32 && big < 512) { if (vec) launch_conv3d<true, 2, 2, 1, 2>(g, st); else launch_conv3d<false, 2, 2, 1, 2>(g, st); }
-    else if (Cout > 32) { if (vec) launch_conv3d<true, 2, 2, 2, 2>(g, st); else launch_conv3d<false, 2, 2, 2, 2>(g, st); }
-    else if (Cout > 16) { if (vec) launch_conv3d<true, 4, 1, 2, 2>(g, st); else launch_conv3d<false, 4, 1, 2, 2>(g, st); }
-    else if ((g.M + 127) / 128 < 256) { if (vec) launch_conv3d<true, 4, 1, 1, 1>(g, st); else launch_conv3d<false, 4, 1, 1, 1>(g, st); }
-    else { if (vec) launch_conv3d<true, 4, 1, 2, 1>(g, st); else launch_conv3d<false, 4, 1, 2, 1>(g, st); }
+    if (precision == R3D_TORSO_BF16X3) dispatch_conv3d<tconv::BF16X3>(g, vec, st);
+    else dispatch_conv3d<tconv::F32>(g, vec, st);
     return check_launch("torso_conv3d");
+}
+
+extern "C" int r3d_torso_conv3d(const float* x, int B, int D, int Hs, int Ws, int Cin, int upsample, const float* w, const float* bias,
+                                int Cout, int ksize, int full_depth, int act, float act_slope, int pool, float* y, int y_cstride,
+                                int y_coffset, float* y_ncdhw, r3d_stream_t stream)
+{
+    return torso_conv3d_impl(x, B, D, Hs, Ws, Cin, upsample, w, bias, Cout, ksize, full_depth, act, act_slope, pool, y, y_cstride, y_coffset,
+                             y_ncdhw, R3D_TORSO_F32, stream);
+}
+
+extern "C" int r3d_torso_conv3d_prec(const float* x, int B, int D, int Hs, int Ws, int Cin, int upsample, const float* w, const float* bias,
+                                     int Cout, int ksize, int full_depth, int act, float act_slope, int pool, float* y, int y_cstride,
+                                     int y_coffset, float* y_ncdhw, int precision, r3d_stream_t stream)
+{
+    return torso_conv3d_impl(x, B, D, Hs, Ws, Cin, upsample, w, bias, Cout, ksize, full_depth, act, act_slope, pool, y, y_cstride, y_coffset,
+                             y_ncdhw, precision, stream);
 }
 
 static int motion_common(const char* what, const float* kp_s, const float* kp_d, const float* J, int N, int D, int H, int W, int K)

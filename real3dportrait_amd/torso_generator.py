@@ -4,7 +4,8 @@
                          the appearance volume, in_conv, mid_conv, six ResBlock2D, two UpBlock2D, out_conv
     Occlusion2Predictor  the nn.Sequential occlusion_2_predictor of WarpBasedTorsoModelMediaPipe (model2.py:212-219)
 
-in exact fp32.  Both keep the reference's attribute names and state_dict keys, so a reference checkpoint loads with strict=True.
+in exact fp32 by default (precision='f32'), or with precision='bf16x3' with every convolution on the split-precision tier of
+torso_precision.py (the warp stays as it is).  Both keep the reference's attribute names and state_dict keys, so a reference checkpoint loads with strict=True.
 INFERENCE ONLY (eval semantics: spectral norm without power iteration, BatchNorm on its running statistics); inputs are detached and
 no autograd graph is built.  Spectral norm and the BatchNorms are folded into the conv weights, biases and prologue vectors in fp64
 once per parameter version (_prepare).
@@ -13,6 +14,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from .torso_precision import F32, PRECISIONS, check_precision
 
 NONE, LEAKY, SIGMOID = 0, 1, 2          # r3d_torso_conv's `act`
 BN_EPS = 1e-5
@@ -124,11 +126,15 @@ class _Cached:
 _VOLUME_CL = {}          # stream -> _Cached: the channel-last copy of the appearance volume (constant over a clip)
 
 
-def _conv(x, B, Hs, Ws, cin, L, y=None, y_nchw=None, in_nchw=False, res=None):
+def _conv(x, B, Hs, Ws, cin, L, y=None, y_nchw=None, in_nchw=False, res=None, precision=F32):
+    """One r3d_torso_conv launch; a tier other than 'f32' goes through r3d_torso_conv_prec."""
     P = _lib.ptr
-    _lib.check(_lib.load().r3d_torso_conv(P(x), B, Hs, Ws, cin, int(in_nchw), L["up"], P(L["ps"]), P(L["pt"]), 0.0, P(L["w"]), P(L["b"]),
-                                          L["w"].shape[0], L["k"], L["act"], L["slope"], P(res), P(y), P(y_nchw), _lib.stream_ptr()),
-               "torso_conv")
+    args = (P(x), B, Hs, Ws, cin, int(in_nchw), L["up"], P(L["ps"]), P(L["pt"]), 0.0, P(L["w"]), P(L["b"]), L["w"].shape[0], L["k"], L["act"],
+            L["slope"], P(res), P(y), P(y_nchw))
+    if precision == F32:
+        _lib.check(_lib.load().r3d_torso_conv(*args, _lib.stream_ptr()), "torso_conv")
+    else:
+        _lib.check(_lib.load().r3d_torso_conv_prec(*args, PRECISIONS[precision], _lib.stream_ptr()), "torso_conv_prec")
 
 
 def _check_f32(t, what, dims):
@@ -141,8 +147,9 @@ class Generator(nn.Module):
     """network2.py:248-301.  forward(fs [N, 32, 16, H, W], deformation [N, 16, H, W, 3], occlusion) -> rgb [N, 3, 4H, 4W]
     (and hid [N, 64, 4H, 4W] with return_hid=True); `occlusion` is accepted and unused, as in the reference."""
 
-    def __init__(self, input_channels=32, model_scale="standard", more_res=False):
+    def __init__(self, input_channels=32, model_scale="standard", more_res=False, precision=F32):
         super().__init__()
+        self.precision = check_precision(precision, "Generator: precision")
         if model_scale not in ("standard", "small") or more_res:
             raise NotImplementedError("Generator: only model_scale 'standard' / 'small' without more_res has a HIP implementation "
                                       "(network2.py:261-270; got %r, more_res=%r)" % (model_scale, more_res))
@@ -206,17 +213,17 @@ class Generator(nn.Module):
         dev = x.device
         L = self._prepare()
         w = self._buffers_for(N, H, W, dev)
-        X, Hb = w["x"], w["h"]
-        _conv(x, N, H, W, self.input_channels * self.depth, L[0], y=Hb, in_nchw=in_nchw)
-        _conv(Hb, N, H, W, 256, L[1], y=X)
+        X, Hb, pr = w["x"], w["h"], self.precision
+        _conv(x, N, H, W, self.input_channels * self.depth, L[0], y=Hb, in_nchw=in_nchw, precision=pr)
+        _conv(Hb, N, H, W, 256, L[1], y=X, precision=pr)
         for i in range(6):
-            _conv(X, N, H, W, 256, L[2 + 2 * i], y=Hb)
-            _conv(Hb, N, H, W, 256, L[3 + 2 * i], y=X, res=X)
-        _conv(X, N, H, W, 256, L[14], y=w["u0"])
+            _conv(X, N, H, W, 256, L[2 + 2 * i], y=Hb, precision=pr)
+            _conv(Hb, N, H, W, 256, L[3 + 2 * i], y=X, res=X, precision=pr)
+        _conv(X, N, H, W, 256, L[14], y=w["u0"], precision=pr)
         hid = torch.empty(N, 64, 4 * H, 4 * W, device=dev, dtype=torch.float32) if return_hid else None
-        _conv(w["u0"], N, 2 * H, 2 * W, 128, L[15], y=w["u1"], y_nchw=hid)
+        _conv(w["u0"], N, 2 * H, 2 * W, 128, L[15], y=w["u1"], y_nchw=hid, precision=pr)
         rgb = torch.empty(N, 3, 4 * H, 4 * W, device=dev, dtype=torch.float32)
-        _conv(w["u1"], N, 4 * H, 4 * W, 64, L[16], y_nchw=rgb)
+        _conv(w["u1"], N, 4 * H, 4 * W, 64, L[16], y_nchw=rgb, precision=pr)
         return (rgb, hid) if return_hid else rgb
 
     @torch.no_grad()
@@ -239,9 +246,9 @@ class Generator(nn.Module):
         return self._decode(x, True, N, H, W, return_hid)
 
     @classmethod
-    def from_reference(cls, ref):
+    def from_reference(cls, ref, precision=F32):
         """A HIP copy of a constructed reference Generator at standard / small scale (strict key copy)."""
-        m = cls(input_channels=ref.in_conv.layers[0].in_channels // 16)
+        m = cls(input_channels=ref.in_conv.layers[0].in_channels // 16, precision=precision)
         m.load_state_dict(ref.state_dict(), strict=True)
         return m.to(next(ref.parameters()).device).eval()
 
@@ -257,8 +264,9 @@ class Occlusion2Predictor(nn.Module):
     """occlusion_2_predictor (model2.py:212-219): Conv2d(65, 32, 3, 1, 1), ReLU, Conv2d(32, 32, 3, 1, 1), ReLU, Conv2d(32, 1, 3, 1, 1),
     Sigmoid, with the nn.Sequential's keys ('0.weight', ..., '4.bias').  Called with cat([hid, occlusion_2 at 256^2]) [N, 65, H, W]."""
 
-    def __init__(self, in_channels=65, hidden=32):
+    def __init__(self, in_channels=65, hidden=32, precision=F32):
         super().__init__()
+        self.precision = check_precision(precision, "Occlusion2Predictor: precision")
         for i, (ci, co) in zip((0, 2, 4), ((in_channels, hidden), (hidden, hidden), (hidden, 1))):
             self.add_module(str(i), nn.Conv2d(ci, co, 3, 1, 1))
         self._derived_key, self._derived = None, None
@@ -289,14 +297,14 @@ class Occlusion2Predictor(nn.Module):
             hid = L[0]["w"].shape[0]
             w = self._work[key] = [torch.empty(N * H * W * hid, device=x.device, dtype=torch.float32) for _ in range(2)]
         out = torch.empty(N, 1, H, W, device=x.device, dtype=torch.float32)
-        _conv(x, N, H, W, C, L[0], y=w[0], in_nchw=True)
-        _conv(w[0], N, H, W, L[1]["w"].shape[3], L[1], y=w[1])
-        _conv(w[1], N, H, W, L[2]["w"].shape[3], L[2], y_nchw=out)
+        _conv(x, N, H, W, C, L[0], y=w[0], in_nchw=True, precision=self.precision)
+        _conv(w[0], N, H, W, L[1]["w"].shape[3], L[1], y=w[1], precision=self.precision)
+        _conv(w[1], N, H, W, L[2]["w"].shape[3], L[2], y_nchw=out, precision=self.precision)
         return out
 
     @classmethod
-    def from_reference(cls, seq):
-        m = cls(seq[0].in_channels, seq[0].out_channels)
+    def from_reference(cls, seq, precision=F32):
+        m = cls(seq[0].in_channels, seq[0].out_channels, precision=precision)
         m.load_state_dict(seq.state_dict(), strict=True)
         return m.to(seq[0].weight.device).eval()
 

@@ -5,7 +5,9 @@ include/r3d_hip.h):
                           heatmaps and the sparse motions, the Conv3d hourglass, tgt_head_encoder, tgt_head_fuser, mask_conv, the
                           mask-weighted deformation and the two occlusion maps
 
-in exact fp32.  It keeps the reference's attribute names and its 129 state_dict keys, so a reference checkpoint loads with strict=True.
+in exact fp32 by default (precision='f32'), or with precision='bf16x3' with every convolution on the split-precision tier of
+torso_precision.py (the motion input, the deformation, the resizes and the folds are the same).  It keeps the reference's attribute
+names and its 129 state_dict keys, so a reference checkpoint loads with strict=True.
 INFERENCE ONLY (eval semantics: BatchNorm on its running statistics); inputs are detached and no autograd graph is built.  The BatchNorms
 are folded into the conv weights, biases and prologue vectors in fp64 once per parameter version (_prepare), where the channel groups
 are also padded to multiples of 4 and the occlusion weights permuted to the kernel's full-depth form.
@@ -14,6 +16,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from .torso_precision import F32, PRECISIONS, check_precision
 from .torso_generator import BN_EPS, LEAKY, NONE, SIGMOID, _check_f32, _conv, _kernel_weight, _params_key, bn_affine64
 
 DEPTH, GRID, HEAD, HID = 16, 64, 256, 32          # the feature volume [N, C, 16, 64, 64], the head image 256^2, tgt_head_hid_dim
@@ -116,11 +119,16 @@ def jacobian(Rs, Rd):
     return (Rs[:, :, :, None] * inv[:, None, :, :]).sum(dim=2).contiguous()
 
 
-def _conv3d(x, B, D, Hs, Ws, cin, L, k, y, ycs=None, yco=0, up=0, act=NONE, pool=0, full_depth=0, y_ncdhw=None):
+def _conv3d(x, B, D, Hs, Ws, cin, L, k, y, ycs=None, yco=0, up=0, act=NONE, pool=0, full_depth=0, y_ncdhw=None, precision=F32):
+    """One r3d_torso_conv3d launch; a tier other than 'f32' goes through r3d_torso_conv3d_prec."""
     P = _lib.ptr
     cout = L["w"].shape[0]
-    _lib.check(_lib.load().r3d_torso_conv3d(P(x), B, D, Hs, Ws, cin, up, P(L["w"]), P(L["b"]), cout, k, full_depth, act, 0.0, pool, P(y),
-                                            cout if ycs is None else ycs, yco, P(y_ncdhw), _lib.stream_ptr()), "torso_conv3d")
+    args = (P(x), B, D, Hs, Ws, cin, up, P(L["w"]), P(L["b"]), cout, k, full_depth, act, 0.0, pool, P(y), cout if ycs is None else ycs, yco,
+            P(y_ncdhw))
+    if precision == F32:
+        _lib.check(_lib.load().r3d_torso_conv3d(*args, _lib.stream_ptr()), "torso_conv3d")
+    else:
+        _lib.check(_lib.load().r3d_torso_conv3d_prec(*args, PRECISIONS[precision], _lib.stream_ptr()), "torso_conv3d_prec")
 
 
 class MotionFieldEstimator(nn.Module):
@@ -128,8 +136,9 @@ class MotionFieldEstimator(nn.Module):
     [N, 3, 256, 256], tgt_head_weights [N, 1, 256, 256]) -> (deformation [N, 16, 64, 64, 3], occlusion [N, 1, 64, 64], occlusion_2
     [N, 1, 64, 64]).  The reference fixes these sizes (its resizes to 128^2 and 64^2, :220-222); others raise ValueError."""
 
-    def __init__(self, model_scale="standard", input_channels=34, num_keypoints=4, predict_multiref_occ=True):
+    def __init__(self, model_scale="standard", input_channels=34, num_keypoints=4, predict_multiref_occ=True, precision=F32):
         super().__init__()
+        self.precision = check_precision(precision, "MotionFieldEstimator: precision")
         if model_scale not in ("standard", "large") or not predict_multiref_occ:
             raise NotImplementedError("MotionFieldEstimator: only model_scale 'standard' with predict_multiref_occ has a HIP implementation "
                                       "(network2.py:177-183,232-236; got %r, predict_multiref_occ=%r)" % (model_scale, predict_multiref_occ))
@@ -188,7 +197,7 @@ class MotionFieldEstimator(nn.Module):
         dev = fs.device
         F, w = self._prepare(), self._buffers_for(N, dev)
         lib, P, st = _lib.load(), _lib.ptr, _lib.stream_ptr()
-        cp = _pad4(5 * (K + 1))
+        cp, pr = _pad4(5 * (K + 1)), self.precision
         fcs = cp + 2 * HID
         J = jacobian(Rs, Rd)
         # the hourglass input, also the first channel group of the fuser's input
@@ -198,39 +207,39 @@ class MotionFieldEstimator(nn.Module):
         # the hourglass; its last conv writes the second group
         x, cin, size = w["inp"], cp, S
         for i, L in enumerate(F["down"]):
-            _conv3d(x, N, D, size, size, cin, L, 3, w["down"][i], act=LEAKY, pool=1)
+            _conv3d(x, N, D, size, size, cin, L, 3, w["down"][i], act=LEAKY, pool=1, precision=pr)
             x, cin, size = w["down"][i], L["w"].shape[0], size // 2
         for i, L in enumerate(F["up"]):
             last = i == 4
             _conv3d(x, N, D, size, size, cin, L, 3, w["fuse"] if last else w["up"][i], ycs=fcs if last else None, yco=cp if last else 0,
-                    up=1, act=LEAKY)
+                    up=1, act=LEAKY, precision=pr)
             x, cin, size = (None if last else w["up"][i]), L["w"].shape[0], size * 2
         # the head branch: 256^2 -> 128^2, tgt_head_encoder, -> 64^2, repeated over depth into the third group
         head_in = torch.cat([img, wts], dim=1)
         _lib.check(lib.r3d_resize_bilinear(P(head_in), N * 4, HEAD, HEAD, P(w["head"]), 128, 128, 0, st), "resize_bilinear")
         E = F["enc"]
-        _conv(w["head"], N, 128, 128, 4, E[0], y=w["e0"], in_nchw=True)
+        _conv(w["head"], N, 128, 128, 4, E[0], y=w["e0"], in_nchw=True, precision=pr)
         for i in range(3):
-            _conv(w["e0"], N, 128, 128, HID, E[1 + 2 * i], y=w["e1"])
+            _conv(w["e0"], N, 128, 128, HID, E[1 + 2 * i], y=w["e1"], precision=pr)
             if i < 2:
-                _conv(w["e1"], N, 128, 128, HID, E[2 + 2 * i], y=w["e0"], res=w["e0"])
+                _conv(w["e1"], N, 128, 128, HID, E[2 + 2 * i], y=w["e0"], res=w["e0"], precision=pr)
             else:
-                _conv(w["e1"], N, 128, 128, HID, E[2 + 2 * i], y_nchw=w["feats"], res=w["e0"])
+                _conv(w["e1"], N, 128, 128, HID, E[2 + 2 * i], y_nchw=w["feats"], res=w["e0"], precision=pr)
         _lib.check(lib.r3d_resize_bilinear(P(w["feats"]), N * HID, 128, 128, P(w["feats64"]), S, S, 0, st), "resize_bilinear")
         _lib.check(lib.r3d_torso_motion_broadcast(P(w["feats64"]), N, HID, S, S, D, P(w["fuse"]), fcs, cp + HID, st), "torso_motion_broadcast")
         # fuser, mask, deformation, occlusions
-        _conv3d(w["fuse"], N, D, S, S, fcs, F["fuser"], 7, w["x"])
-        _conv3d(w["x"], N, D, S, S, HID, F["mask"], 7, w["mask"])
+        _conv3d(w["fuse"], N, D, S, S, fcs, F["fuser"], 7, w["x"], precision=pr)
+        _conv3d(w["x"], N, D, S, S, HID, F["mask"], 7, w["mask"], precision=pr)
         deformation = torch.empty(N, D, S, S, 3, device=dev, dtype=torch.float32)
         _lib.check(lib.r3d_torso_motion_deform(P(w["mask"]), N, D, S, S, K, P(kp_s), P(kp_d), P(J), P(deformation), st), "torso_motion_deform")
         occ = torch.empty(N, 2, S, S, device=dev, dtype=torch.float32)
-        _conv3d(w["x"], N, D, S, S, HID, F["occ"], 7, None, act=SIGMOID, full_depth=1, y_ncdhw=occ)
+        _conv3d(w["x"], N, D, S, S, HID, F["occ"], 7, None, act=SIGMOID, full_depth=1, y_ncdhw=occ, precision=pr)
         return deformation, occ[:, 0:1].contiguous(), occ[:, 1:2].contiguous()
 
     @classmethod
-    def from_reference(cls, ref):
+    def from_reference(cls, ref, precision=F32):
         """A HIP copy of a constructed reference MotionFieldEstimator at standard scale (strict key copy)."""
-        m = cls(input_channels=ref.compress.in_channels, num_keypoints=ref.mask_conv.out_channels - 1)
+        m = cls(input_channels=ref.compress.in_channels, num_keypoints=ref.mask_conv.out_channels - 1, precision=precision)
         m.load_state_dict(ref.state_dict(), strict=True)
         return m.to(next(ref.parameters()).device).eval()
 

@@ -12,6 +12,9 @@ output) and print one JSON line:
     python scripts/prof_torso_generator.py [--calls 200] [--blocks 5] [--out DIR]     (writes DIR/prof_torso_generator.json)
     python scripts/prof_torso_generator.py --forwards 20        only runs that many HIP forwards after a warm-up, for
         rocprofv3 --kernel-trace --stats -d DIR -o torso -- python scripts/prof_torso_generator.py --forwards 20
+    python scripts/prof_torso_generator.py --precision both [--calls 200] [--blocks 5] [--out DIR]
+        the two precision tiers of the convolutions in alternating blocks in one run, no eager side
+        (writes DIR/prof_torso_generator_precision.json); --precision bf16x3 with --forwards: that tier's forwards for a trace
 """
 import argparse
 import json
@@ -65,25 +68,46 @@ def count_launches(fn):
     return count
 
 
+def compare_tiers(fns, calls, blocks, block_median):
+    """fns: {tier: callable}.  The tiers timed in alternating blocks in one run: per tier the median of the block medians, the block
+    medians and their spread (max - min), in ms; faster_by_more_than_the_spreads: f32 - bf16x3 exceeds the sum of the two spreads."""
+    meds = {t: [] for t in fns}
+    for _ in range(blocks):
+        for t, fn in fns.items():
+            meds[t].append(block_median(fn, calls))
+    out = {}
+    for t, v in meds.items():
+        out[t] = {"ms": round(statistics.median(v), 4), "block_medians_ms": [round(x, 4) for x in v], "spread_ms": round(max(v) - min(v), 4)}
+    gain = out["f32"]["ms"] - out["bf16x3"]["ms"]
+    out["f32_minus_bf16x3_ms"] = round(gain, 4)
+    out["f32_over_bf16x3"] = round(out["f32"]["ms"] / out["bf16x3"]["ms"], 3)
+    out["faster_by_more_than_the_spreads"] = bool(gain > out["f32"]["spread_ms"] + out["bf16x3"]["spread_ms"])
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--calls", type=int, default=200)
     ap.add_argument("--blocks", type=int, default=5)
     ap.add_argument("--forwards", type=int, default=0)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--precision", default="f32", choices=("f32", "bf16x3", "both"))
     a = ap.parse_args()
     dev = "cuda:0"
     T = lambda sd: {k: torch.from_numpy(np.ascontiguousarray(v)) for k, v in sd.items()}
     sd, psd = synth.synth_torso_generator(71), synth.synth_torso_predictor(72)
-    gen, pred = Generator(), Occlusion2Predictor()
-    gen.load_state_dict(T(sd), strict=True)
-    pred.load_state_dict(T(psd), strict=True)
-    gen, pred = gen.to(dev).eval(), pred.to(dev).eval()
+    def modules(precision):
+        g, p = Generator(precision=precision), Occlusion2Predictor(precision=precision)
+        g.load_state_dict(T(sd), strict=True)
+        p.load_state_dict(T(psd), strict=True)
+        return g.to(dev).eval(), p.to(dev).eval()
+
+    gen, pred = modules("f32" if a.precision == "both" else a.precision)
     i = {k: torch.from_numpy(v).to(dev) for k, v in synth.synth_torso_inputs(73, 1, 64, 64).items()}
     sdd, psdd = {k: v.to(dev) for k, v in T(sd).items()}, {k: v.to(dev) for k, v in T(psd).items()}
     fs, grid, occ, occ2 = i["torso_appearance_feats"], i["deformation"], i["occlusion"], i["occlusion_2"]
 
-    def hip():
+    def hip(gen=gen, pred=pred):
         rgb, hid = gen(fs, grid, occ, return_hid=True)
         return rgb, hid, pred(torch.cat([hid, F.interpolate(occ2, size=(256, 256), mode="bilinear")], dim=1))
 
@@ -97,6 +121,22 @@ def main():
             for _ in range(5 + a.forwards):
                 hip()
             torch.cuda.synchronize()
+            return
+        if a.precision == "both":
+            gb, pb = modules("bf16x3")
+            fns = {"f32": hip, "bf16x3": lambda: hip(gb, pb)}
+            for _ in range(10):
+                for fn in fns.values():
+                    fn()
+            out = {"metric": "torso_generator_b1_64_precision_tiers", "B": 1, "grid": [64, 64], "calls_per_block": a.calls, "blocks": a.blocks}
+            out.update(compare_tiers(fns, a.calls, a.blocks, block_median))
+            out["launches_by_entry_point"] = {t: {n: c for n, c in count_launches(fn).items() if c} for t, fn in fns.items()}
+            out["bf16x3_vs_f32_max_rel_diff_rgb_hid_occ2"] = [float((x - y).abs().max() / y.abs().max()) for x, y in zip(fns["bf16x3"](), hip())]
+            print(json.dumps(out))
+            if a.out:
+                os.makedirs(a.out, exist_ok=True)
+                with open(os.path.join(a.out, "prof_torso_generator_precision.json"), "w") as f:
+                    f.write(json.dumps(out, indent=1) + "\n")
             return
         for _ in range(10):
             hip()

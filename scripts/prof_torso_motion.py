@@ -14,6 +14,9 @@ volume, a 256^2 head image) and print one JSON line:
         rocprofv3 --kernel-trace --stats -d DIR -o motion -- python scripts/prof_torso_motion.py --forwards 20
     python scripts/prof_torso_motion.py --summarise DIR/.../motion_kernel_trace.csv --forwards 20
         the per-launch table of that trace (median over the forwards), with each layer's GFLOP and TFLOP/s
+    python scripts/prof_torso_motion.py --precision both [--calls 100] [--blocks 5] [--out DIR]
+        the two precision tiers of the convolutions in alternating blocks in one run, no eager side
+        (writes DIR/prof_torso_motion_precision.json); --precision bf16x3 with --forwards: that tier's forwards for a trace
 """
 import argparse
 import csv
@@ -76,6 +79,23 @@ def summarise(path, forwards):
           % (total, span, GFLOP, PEAK_TFLOPS, GFLOP / PEAK_TFLOPS * 1e3))
 
 
+def compare_tiers(fns, calls, blocks, block_median):
+    """fns: {tier: callable}.  The tiers timed in alternating blocks in one run: per tier the median of the block medians, the block
+    medians and their spread (max - min), in ms; faster_by_more_than_the_spreads: f32 - bf16x3 exceeds the sum of the two spreads."""
+    meds = {t: [] for t in fns}
+    for _ in range(blocks):
+        for t, fn in fns.items():
+            meds[t].append(block_median(fn, calls))
+    out = {}
+    for t, v in meds.items():
+        out[t] = {"ms": round(statistics.median(v), 4), "block_medians_ms": [round(x, 4) for x in v], "spread_ms": round(max(v) - min(v), 4)}
+    gain = out["f32"]["ms"] - out["bf16x3"]["ms"]
+    out["f32_minus_bf16x3_ms"] = round(gain, 4)
+    out["f32_over_bf16x3"] = round(out["f32"]["ms"] / out["bf16x3"]["ms"], 3)
+    out["faster_by_more_than_the_spreads"] = bool(gain > out["f32"]["spread_ms"] + out["bf16x3"]["spread_ms"])
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--calls", type=int, default=200)
@@ -83,6 +103,7 @@ def main():
     ap.add_argument("--forwards", type=int, default=0)
     ap.add_argument("--summarise", default=None)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--precision", default="f32", choices=("f32", "bf16x3", "both"))
     a = ap.parse_args()
     if a.summarise:
         return summarise(a.summarise, a.forwards or 20)
@@ -125,9 +146,12 @@ def main():
 
     dev = "cuda:0"
     sd = synth.synth_torso_motion(171, 4)
-    m = MotionFieldEstimator()
-    m.load_state_dict({k: torch.from_numpy(np.ascontiguousarray(v)) for k, v in sd.items()}, strict=True)
-    m = m.to(dev).eval()
+    def module(precision):
+        mod = MotionFieldEstimator(precision=precision)
+        mod.load_state_dict({k: torch.from_numpy(np.ascontiguousarray(v)) for k, v in sd.items()}, strict=True)
+        return mod.to(dev).eval()
+
+    m = module("f32" if a.precision == "both" else a.precision)
     inp = synth.synth_torso_motion_inputs(173, 1, 4)
     args = [torch.from_numpy(inp[k]).to(dev) for k in INPUT_ORDER]
     sdd = {k: torch.from_numpy(np.ascontiguousarray(v)).to(dev) for k, v in sd.items()}
@@ -139,6 +163,22 @@ def main():
             for _ in range(5 + a.forwards):
                 hip()
             torch.cuda.synchronize()
+            return
+        if a.precision == "both":
+            mb = module("bf16x3")
+            fns = {"f32": hip, "bf16x3": lambda: mb(*args)}
+            for _ in range(10):
+                for fn in fns.values():
+                    fn()
+            out = {"metric": "torso_motion_b1_k4_precision_tiers", "B": 1, "K": 4, "calls_per_block": a.calls, "blocks": a.blocks}
+            out.update(compare_tiers(fns, a.calls, a.blocks, block_median))
+            out["launches_by_entry_point"] = {t: count_launches(fn) for t, fn in fns.items()}
+            out["bf16x3_vs_f32_max_rel_diff_deformation_occ_occ2"] = [float((x - y).abs().max() / y.abs().max()) for x, y in zip(fns["bf16x3"](), hip())]
+            print(json.dumps(out))
+            if a.out:
+                os.makedirs(a.out, exist_ok=True)
+                with open(os.path.join(a.out, "prof_torso_motion_precision.json"), "w") as f:
+                    f.write(json.dumps(out, indent=1) + "\n")
             return
         for _ in range(3):
             hip()
