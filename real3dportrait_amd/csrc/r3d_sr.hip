@@ -189,10 +189,10 @@ __global__ __launch_bounds__(256) void chain_fold_kernel(ChainArgs a)
                 for (int i = tid; i < op.Cout; i += 256)
                     touch += base[L.s1 + i] + base[L.d0 + i] + base[L.d1 + i] + base[L.wi0 + i] + base[L.wi1 + i] + base[L.b0 + i] + base[L.b1 + i] + base[L.c0 + i] + base[L.c1 + i];
             } else {
-                const int Ci = (op.Cin + 15) / 16 * 16, Co = (op.Cout + BLOCK_M - 1) / BLOCK_M * BLOCK_M;
-                const ConvTail T = conv_tail_layout(Co);
-                const float* tail = reinterpret_cast<const float*>(op.prepacked) + (size_t)(op.ksize * op.ksize) * Ci * Co;
-                for (int i = tid; i < Co; i += 256) touch += tail[T.winv + i] + tail[T.l1 + i] + (op.bias && i < op.Cout ? op.bias[i] : 0.f);
+                const ConvPackLayout P = conv_pack_layout(op.Cin, op.Cout, op.ksize);
+                const ConvTail T = conv_tail_layout(P.Co);
+                const float* tail = reinterpret_cast<const float*>(op.prepacked) + P.tail;
+                for (int i = tid; i < P.Co; i += 256) touch += tail[T.winv + i] + tail[T.l1 + i] + (op.bias && i < op.Cout ? op.bias[i] : 0.f);
             }
         }
         if (touch == 1.2345e-33f && a.nzero < 0) extv[0] = touch;     // (never true: keeps the loads)
@@ -249,11 +249,12 @@ __global__ __launch_bounds__(256) void chain_fold_kernel(ChainArgs a)
             }
             Bout = Bin;
         } else {
-            const int Ci = (op.Cin + 15) / 16 * 16, Co = (op.Cout + BLOCK_M - 1) / BLOCK_M * BLOCK_M;
+            const ConvPackLayout P = conv_pack_layout(op.Cin, op.Cout, op.ksize);
+            const int Ci = P.Ci, Co = P.Co;
             const ConvScales S = conv_scales_layout(Ci, Co);
             const ConvTail T = conv_tail_layout(Co);
             float* base = reinterpret_cast<float*>(op.scales) + (size_t)n * S.total;
-            const float* tail = reinterpret_cast<const float*>(op.prepacked) + (size_t)(op.ksize * op.ksize) * Ci * Co;
+            const float* tail = reinterpret_cast<const float*>(op.prepacked) + P.tail;
             const int e = act_exp(B, 1.0f);
             const float up = pow2f(e), dn = pow2f(-e);
             for (int i = tid; i < Ci; i += 256) base[S.in_vec + i] = up;
@@ -557,28 +558,14 @@ __global__ void torgb_upsample_kernel(const float* __restrict__ x, size_t x_stri
 
 using namespace r3d;
 
-extern "C" size_t r3d_sr_block_prepacked_bytes(int Cin, int Cout)
-{
-    // conv0 (plain layout) + conv1 + conv0 again in the fused up-conv layout (f16x3) + the two per-cout weight-row tails + conv0 with fp8
-    // records in the up-conv layout and in the plain layout (R3D_SR_F16MX: SynthesisBlock / SynthesisBlockNoUp on R3D_FMT_SPLIT_MX inputs)
-    // + conv1 again as the 12 transformed tap matrices of the Winograd F(2,3) kernel (r3d_sr_wino.h)
-    return ((size_t)4 * 9 * Cin * Cout + (size_t)9 * Cout * Cout + 2 * conv_tail_layout(Cout).total + (size_t)12 * Cout * Cout) * sizeof(float);
-}
+extern "C" size_t r3d_sr_block_prepacked_bytes(int Cin, int Cout) { return sr_pack_layout(Cin, Cout).total * sizeof(float); }
 
 extern "C" size_t r3d_sr_block_styles_bytes(int N, int Cin, int Cout)
 {
     return (size_t)N * sr_style_layout(Cin, Cout).total * sizeof(float);
 }
 
-extern "C" size_t r3d_sr_block_workspace_bytes(int N, int Cin, int Cout, int Hin, int Win)
-{
-    const size_t xin = align256((size_t)N * Cin * Hin * Win * 4);
-    const size_t T = align256((size_t)N * Cout * 4 * (Hin + 1) * (Win + 1) * 4);
-    const size_t y0 = align256((size_t)N * Cout * 4 * Hin * Win * 4);
-    const size_t xo = align256((size_t)N * Cout * 4 * Hin * Win * 4);
-    const size_t rgbp = align256((size_t)N * (Cout / 64) * 3 * 4 * Hin * Win * 4);     // toRGB partial planes, one per 64 couts
-    return xin + T + y0 + xo + rgbp;
-}
+extern "C" size_t r3d_sr_block_workspace_bytes(int N, int Cin, int Cout, int Hin, int Win) { return sr_workspace_layout(N, Cin, Cout, Hin, Win).total; }
 
 namespace r3d {
 // T[2i+pa][2j+pb] = sum_{ky = pa (mod 2), kx = pb (mod 2)} x[i - ky/2][j - kx/2] w[ky][kx]   (conv_transpose2d stride 2)
@@ -604,6 +591,12 @@ void sr_fill_conv3x3_phase(ConvPhase* ph, int H, int W)
     for (int ky = 0; ky < 3; ++ky)
         for (int kx = 0; kx < 3; ++kx) { p.dy[ky * 3 + kx] = ky - 1; p.dx[ky * 3 + kx] = kx - 1; p.widx[ky * 3 + kx] = ky * 3 + kx; }
 }
+void sr_fill_conv1x1_phase(ConvPhase* ph, int H, int W)
+{
+    ConvPhase& p = ph[0];
+    p.outH = H; p.outW = W; p.oy_mul = 1; p.oy_add = 0; p.ox_mul = 1; p.ox_add = 0; p.out_off = 0;
+    p.ntaps = 1; p.dy[0] = 0; p.dx[0] = 0; p.widx[0] = 0;
+}
 }  // namespace r3d
 
 static int sr_check_dims(const char* what, int Cin, int Cout)
@@ -626,9 +619,9 @@ extern "C" int r3d_sr_block_prepack(int Cin, int Cout, const float* c0_w, const 
     ProfScope ps(R3D_PROF_PACK, st);
     if (precision != R3D_SR_F32) return sr_prepack_f16x3(Cin, Cout, c0_w, c1_w, prepacked, st, precision == R3D_SR_F16MX);
     const size_t n0 = (size_t)9 * (Cin / 8) * Cout * 2, n1 = (size_t)9 * (Cout / 8) * Cout * 2;
-    hipLaunchKernelGGL(sr_prepack_kernel, dim3((unsigned)((n0 + 255) / 256)), dim3(256), 0, st, c0_w, Cin, Cout, out);
-    hipLaunchKernelGGL(sr_prepack_kernel, dim3((unsigned)((n1 + 255) / 256)), dim3(256), 0, st, c1_w, Cout, Cout,
-                       out + (size_t)9 * Cin * Cout);
+    const SrPackLayout P = sr_pack_layout(Cin, Cout);
+    hipLaunchKernelGGL(sr_prepack_kernel, dim3((unsigned)((n0 + 255) / 256)), dim3(256), 0, st, c0_w, Cin, Cout, out + P.c0);
+    hipLaunchKernelGGL(sr_prepack_kernel, dim3((unsigned)((n1 + 255) / 256)), dim3(256), 0, st, c1_w, Cout, Cout, out + P.c1);
     return check_launch("sr_block_prepack");
 }
 
@@ -684,17 +677,19 @@ extern "C" int r3d_sr_block_forward(const void* prepacked, const void* styles, i
     hipStream_t st = (hipStream_t)stream;
     if (f16)
         return sr_block_forward_f16x3(prepacked, styles, N, Cin, Cout, Hin, Win, up, x, x_format, img, clamp, x_out, x_out_format,
-                                      next_scale, next_scale_stride, img_out, img_u8, x_absmax, workspace, workspace_bytes, st, precision == R3D_SR_F16MX);
+                                      next_scale, next_scale_stride, img_out, img_u8, x_absmax, workspace, st, precision == R3D_SR_F16MX);
 
     const SrStyleLayout L = sr_style_layout(Cin, Cout);
     const float* pk = reinterpret_cast<const float*>(styles);
     const float* wpk = reinterpret_cast<const float*>(prepacked);
+    const SrPackLayout P = sr_pack_layout(Cin, Cout);
     const int OH = 2 * Hin, OW = 2 * Win, TH = OH + 1, TW = OW + 1;
+    const SrWorkspaceLayout WS = sr_workspace_layout(N, Cin, Cout, Hin, Win);
     char* wsb = reinterpret_cast<char*>(workspace);
-    float* xin = reinterpret_cast<float*>(wsb); wsb += align256((size_t)N * Cin * Hin * Win * 4);
-    float* T = reinterpret_cast<float*>(wsb);   wsb += align256((size_t)N * Cout * 4 * (Hin + 1) * (Win + 1) * 4);
-    float* y0 = reinterpret_cast<float*>(wsb);  wsb += align256((size_t)N * Cout * OH * OW * 4);
-    float* xo = reinterpret_cast<float*>(wsb);
+    float* xin = reinterpret_cast<float*>(wsb + WS.xin);
+    float* T = reinterpret_cast<float*>(wsb + WS.T);
+    float* y0 = reinterpret_cast<float*>(wsb + WS.y0);
+    float* xo = reinterpret_cast<float*>(wsb + WS.xo);
 
     const float* xcb = reinterpret_cast<const float*>(x);
     if (x_format == R3D_FMT_NCHW) {
@@ -706,7 +701,7 @@ extern "C" int r3d_sr_block_forward(const void* prepacked, const void* styles, i
     {
         ConvArgs a;
         a.x = xcb; a.x_stride_n = (size_t)Cin * Hin * Win;
-        a.wp = wpk; a.in_scale = pk + L.s0; a.out_scale = pk + L.d0; a.vec_stride_n = L.total;
+        a.wp = wpk + P.c0; a.in_scale = pk + L.s0; a.out_scale = pk + L.d0; a.vec_stride_n = L.total;
         a.bias = nullptr;
         a.y = T; a.y_stride_n = (size_t)Cout * TH * TW;
         a.Cin = Cin; a.Cout = Cout; a.H = Hin; a.W = Win; a.OH = TH; a.OW = TW;
@@ -730,7 +725,7 @@ extern "C" int r3d_sr_block_forward(const void* prepacked, const void* styles, i
     {
         ConvArgs a;
         a.x = y0; a.x_stride_n = (size_t)Cout * OH * OW;
-        a.wp = wpk + (size_t)9 * Cin * Cout; a.in_scale = pk + L.s1; a.out_scale = pk + L.d1; a.vec_stride_n = L.total;
+        a.wp = wpk + P.c1; a.in_scale = pk + L.s1; a.out_scale = pk + L.d1; a.vec_stride_n = L.total;
         a.bias = pk + L.b1;
         a.y = xo_cb; a.y_stride_n = (size_t)Cout * OH * OW;
         a.Cin = Cout; a.Cout = Cout; a.H = OH; a.W = OW; a.OH = OH; a.OW = OW;
@@ -759,11 +754,13 @@ extern "C" size_t r3d_conv_prepacked_bytes(int Cin, int Cout, int ksize) { retur
 extern "C" size_t r3d_conv_workspace_bytes(int N, int Cin, int H, int W) { return r3d::conv_workspace_bytes_f16x3(N, Cin, H, W); }
 extern "C" size_t r3d_conv_scales_bytes(int N, int Cin, int Cout)
 {
-    return (size_t)N * conv_scales_layout((Cin + 15) / 16 * 16, (Cout + BLOCK_M - 1) / BLOCK_M * BLOCK_M).total * sizeof(float);
+    const ConvPackLayout P = conv_pack_layout(Cin, Cout, 1);
+    return (size_t)N * conv_scales_layout(P.Ci, P.Co).total * sizeof(float);
 }
 extern "C" size_t r3d_conv_scales_bound_offset(int Cin, int Cout)
 {
-    return conv_scales_layout((Cin + 15) / 16 * 16, (Cout + BLOCK_M - 1) / BLOCK_M * BLOCK_M).meta + 1;
+    const ConvPackLayout P = conv_pack_layout(Cin, Cout, 1);
+    return conv_scales_layout(P.Ci, P.Co).meta + 1;
 }
 extern "C" size_t r3d_sr_block_bound_offset(int Cin, int Cout) { return sr_style_layout(Cin, Cout).meta + SR_META_BOUND_OUT; }
 
@@ -853,8 +850,7 @@ extern "C" int r3d_conv_forward(const void* prepacked, const void* scales, const
     if (x_format < R3D_FMT_SPLIT && (!workspace || workspace_bytes < r3d_conv_workspace_bytes(N, Cin, H, W))) {
         set_error("conv_forward: workspace too small"); return R3D_ERR_WORKSPACE;
     }
-    const size_t stride = conv_scales_layout((Cin + 15) / 16 * 16, (Cout + BLOCK_M - 1) / BLOCK_M * BLOCK_M).total;
-    return conv_forward_f16x3(prepacked, reinterpret_cast<const float*>(scales), stride, bias, N, Cin, Cout, H, W, ksize, x, x_format,
+    return conv_forward_f16x3(prepacked, reinterpret_cast<const float*>(scales), bias, N, Cin, Cout, H, W, ksize, x, x_format,
                               act, act_slope, act_gain, clamp, y, y_format, next_scale, next_scale_stride, y_absmax,
                               workspace, (hipStream_t)stream);
 }
@@ -885,9 +881,8 @@ extern "C" int r3d_conv_forward_cat(const void* prepacked, const void* scales, c
     if (x_format < R3D_FMT_SPLIT && (!workspace || workspace_bytes < r3d_conv_workspace_bytes(N, Cin, H, W))) {
         set_error("conv_forward_cat: workspace too small"); return R3D_ERR_WORKSPACE;
     }
-    const size_t stride = conv_scales_layout((Cin + 15) / 16 * 16, (Cout + BLOCK_M - 1) / BLOCK_M * BLOCK_M).total;
     const ConvCat cat = {mask, mask_invert ? 1 : 0, C_total, chan_off};
-    return conv_forward_f16x3(prepacked, reinterpret_cast<const float*>(scales), stride, bias, N, Cin, Cout, H, W, ksize, x, x_format,
+    return conv_forward_f16x3(prepacked, reinterpret_cast<const float*>(scales), bias, N, Cin, Cout, H, W, ksize, x, x_format,
                               act, act_slope, act_gain, clamp, y_cat, y_format, next_scale, next_scale_stride, nullptr,
                               workspace, (hipStream_t)stream, &cat);
 }
@@ -912,8 +907,7 @@ extern "C" int r3d_conv_forward_blend(const void* prepacked, const void* scales,
         const size_t cmax = (size_t)((Ca + Cb > Cout ? Ca + Cb : Cout) + BLOCK_M);
         if (cmax * H * W >= ((size_t)1 << 32)) { set_error("conv_forward_blend: activation of %zu elements per sample exceeds the 32-bit index range", cmax * H * W); return R3D_ERR_INVALID_ARG; }
     }
-    const size_t stride = conv_scales_layout(Ca + Cb, (Cout + BLOCK_M - 1) / BLOCK_M * BLOCK_M).total;
-    return conv_forward_blend_f16x3(prepacked, reinterpret_cast<const float*>(scales), stride, bias, N, Ca, Cb, Cout, H, W, a, b, mask,
+    return conv_forward_blend_f16x3(prepacked, reinterpret_cast<const float*>(scales), bias, N, Ca, Cb, Cout, H, W, a, b, mask,
                                     act, act_slope, act_gain, clamp, y, y_format, next_scale, next_scale_stride, y_absmax, (hipStream_t)stream);
 }
 

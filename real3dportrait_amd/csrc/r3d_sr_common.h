@@ -6,7 +6,7 @@ namespace r3d {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 static constexpr int BLOCK_M = 128;                    // output channels per conv block
-static inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+static __host__ __device__ inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 // ---- fp16 range management of the f16x3 path (exact power-of-two pre-scaling) --------------------------------------
 // The 3-term fp16 split x = hi + lo is fp32-accurate while the STORED tensor has rms >= 2^-3 and max < 65504 (16 binades);
@@ -82,6 +82,56 @@ static __host__ __device__ inline ConvScales conv_scales_layout(int CinPadded, i
     ConvScales S; S.in_vec = 0; S.out_vec = CinPadded; S.meta = (size_t)CinPadded + CoutPadded; S.total = (S.meta + 4 + 3) & ~(size_t)3; return S;
 }
 
+// Prepacked weights of one SR block (r3d_sr_block_prepack), float offsets.  R3D_SR_F32 writes and reads c0 and c1 only (sr_prepack_kernel, conv_mfma_kernel).
+struct SrPackLayout { size_t c0, c1, c0_up, tail0, tail1, c0_up_mx, c0_mx, c1_wino, total; };
+static __host__ __device__ inline SrPackLayout sr_pack_layout(int Cin, int Cout)
+{
+    SrPackLayout P;
+    const size_t w0 = (size_t)9 * Cin * Cout, w1 = (size_t)9 * Cout * Cout;
+    size_t o = 0;
+    P.c0 = o; o += w0;                              // sr_prepack_f16_kernel -> conv0 of SynthesisBlockNoUp (conv_mfma_f16x3 kernels)
+    P.c1 = o; o += w1;                              // sr_prepack_f16_kernel | sr_prepack_mx_kernel (R3D_SR_F16MX) -> conv1 on the direct kernels
+    P.c0_up = o; o += w0;                           // sr_prepack_up_kernel -> upconv_fir_f16x3_kernel
+    P.tail0 = o; o += conv_tail_layout(Cout).total; // weight_row_stats_kernel (conv0) -> the prepack kernels' 2^-kw[co]
+    P.tail1 = o; o += conv_tail_layout(Cout).total; // ... of conv1
+    P.c0_up_mx = o; o += w0;                        // sr_prepack_up_mx_kernel (R3D_SR_F16MX) -> upconv_fir_f16x3_kernel<.., MXIN> on a SPLIT_MX input
+    P.c0_mx = o; o += w0;                           // sr_prepack_mx_kernel (R3D_SR_F16MX, Cin % 16 == 0) -> conv0 of SynthesisBlockNoUp on a SPLIT_MX input
+    P.c1_wino = o; o += (size_t)12 * Cout * Cout;   // sr_prepack_wino_kernel -> conv_wino_f16x3_kernel (conv1, 12 transformed tap matrices)
+    P.total = o;
+    return P;
+}
+// Prepacked weights of one plain conv (r3d_conv_prepack), float offsets, from the UNPADDED channel counts: Ci / Co are the padded ones every
+// kernel, ConvTail and ConvScales of the layer is sized by (this is the one place the padding rule is written).  The last two regions are empty for 1x1.
+struct ConvPackLayout { int Ci, Co; size_t w, tail, w_mx, w_wino, total; };
+static __host__ __device__ inline ConvPackLayout conv_pack_layout(int Cin, int Cout, int ksize)
+{
+    ConvPackLayout P;
+    P.Ci = (Cin + 15) / 16 * 16; P.Co = (Cout + BLOCK_M - 1) / BLOCK_M * BLOCK_M;
+    const size_t cc = (size_t)P.Ci * P.Co, w = (size_t)(ksize * ksize) * cc;   // one tap's padded weight matrix; all taps
+    size_t o = 0;
+    P.w = o; o += w;                                                // sr_prepack_f16_kernel -> the direct conv kernels on a SPLIT input
+    P.tail = o; o += conv_tail_layout(P.Co).total;                  // weight_row_stats_kernel -> the prepack kernels, chain_fold_kernel
+    P.w_mx = o; o += ksize == 3 ? w : 0;                            // sr_prepack_mx_kernel -> the direct 3x3 kernels on a SPLIT_MX input
+    P.w_wino = o; o += ksize == 3 ? 12 * cc : 0;                  // sr_prepack_wino_kernel -> conv_wino_f16x3_kernel
+    P.total = o;
+    return P;
+}
+// Workspace of one SR block forward, BYTE offsets; one layout for all precisions (the sizes are public: r3d_sr_block_workspace_bytes)
+struct SrWorkspaceLayout { size_t xin, T, y0, xo, rgbp, total; };
+static __host__ __device__ inline SrWorkspaceLayout sr_workspace_layout(int N, int Cin, int Cout, int Hin, int Win)
+{
+    SrWorkspaceLayout L;
+    const size_t y = align256((size_t)N * Cout * 4 * Hin * Win * 4);
+    size_t o = 0;
+    L.xin = o; o += align256((size_t)N * Cin * Hin * Win * 4);                          // nchw_to_cb8_kernel | to_split_kernel -> conv0
+    L.T = o; o += align256((size_t)N * Cout * 4 * (Hin + 1) * (Win + 1) * 4);           // R3D_SR_F32 only: conv0's four phase planes -> fir_bias_act_kernel
+    L.y0 = o; o += y;                                                                   // conv0 -> conv1
+    L.xo = o; o += y;                                                                   // R3D_SR_F32 only: conv1's CB8 x -> torgb_upsample_kernel, cb8_to_nchw_kernel
+    L.rgbp = o; o += align256((size_t)N * (Cout / 64) * 3 * 4 * Hin * Win * 4);         // f16x3 / f16mx: conv1's toRGB partial planes, one per 64 couts -> rgb_finalize_kernel
+    L.total = o;
+    return L;
+}
+
 // A "phase" is a set of taps writing to a strided output lattice (plain conv: 1 phase of 9 taps;
 // stride-2 transposed conv: 4 phases of 4/2/2/1 taps).
 struct ConvPhase {
@@ -94,26 +144,27 @@ struct ConvPhase {
 
 void sr_fill_tconv_phases(ConvPhase* ph, int Hin, int Win);
 void sr_fill_conv3x3_phase(ConvPhase* ph, int H, int W);
+void sr_fill_conv1x1_phase(ConvPhase* ph, int H, int W);
 
 // f16x3 implementation (r3d_sr_f16x3.hip)
 int sr_prepack_f16x3(int Cin, int Cout, const float* c0_w, const float* c1_w, void* prepacked, hipStream_t st, bool mx);
 int sr_block_forward_f16x3(const void* prepacked, const void* styles, int N, int Cin, int Cout, int Hin, int Win, int up,
                            const void* x, int x_format, const float* img, float clamp,
                            void* x_out, int x_out_format, const float* next_scale, size_t next_scale_stride,
-                           float* img_out, uint8_t* img_u8, float* x_absmax, void* workspace, size_t workspace_bytes, hipStream_t st, bool mx);
+                           float* img_out, uint8_t* img_u8, float* x_absmax, void* workspace, hipStream_t st, bool mx);
 
 size_t conv_prepacked_bytes_f16x3(int Cin, int Cout, int ksize);
 int conv_prepack_f16x3(const float* w, int Cin, int Cout, int ksize, void* prepacked, hipStream_t st);
 size_t conv_workspace_bytes_f16x3(int N, int Cin, int H, int W);
 // the conv's SPLIT output as one part of a channel concatenation (r3d_conv_forward_cat): channels [chan_off, chan_off + Cout) of C_total, times mask or 1 - mask per pixel
 struct ConvCat { const float* mask; int mask_invert; int C_total; int chan_off; };
-int conv_forward_f16x3(const void* prepacked, const float* scales, size_t scales_stride, const float* bias,
+int conv_forward_f16x3(const void* prepacked, const float* scales, const float* bias,
                        int N, int Cin, int Cout, int H, int W, int ksize,
                        const void* x, int x_format, int act, float slope, float gain, float clamp,
                        void* y, int y_format, const float* next_scale, size_t next_scale_stride, float* y_absmax,
                        void* workspace, hipStream_t st, const ConvCat* cat = nullptr);
 
-int conv_forward_blend_f16x3(const void* prepacked, const float* scales, size_t scales_stride, const float* bias,
+int conv_forward_blend_f16x3(const void* prepacked, const float* scales, const float* bias,
                              int N, int Ca, int Cb, int Cout, int H, int W, const float* xa, const float* xb, const float* mask,
                              int act, float slope, float gain, float clamp,
                              void* y, int y_format, const float* next_scale, size_t next_scale_stride, float* y_absmax, hipStream_t st);

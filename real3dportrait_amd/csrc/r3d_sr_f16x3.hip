@@ -1739,43 +1739,41 @@ static bool wino_shape_ok(int Cin, int Cout, int H, int W)
     // (the kernel addresses one sample's SPLIT activation and the weight pack through 32-bit buffer offsets)
     return wino_mode() && (H & 15) == 0 && (W & 15) == 0 && (Cin & 15) == 0 && (Cout % BLOCK_M) == 0 && (size_t)Cin * H * W * 4 < ((size_t)1 << 31) && (size_t)48 * Cin * Cout < ((size_t)1 << 31);
 }
-// float offset of conv1's Winograd pack inside an SR block's prepacked buffer (after everything sr_prepack_f16x3 wrote before round 6)
-static size_t sr_wino_offset(int Cin, int Cout) { return (size_t)4 * 9 * Cin * Cout + (size_t)9 * Cout * Cout + 2 * conv_tail_layout(Cout).total; }
 
-// prepacked = conv0 (plain layout) ++ conv1 ++ conv0 (fused up-conv layout) ++ ConvTail(conv0) ++ ConvTail(conv1) ++ conv0 (up-conv layout
-// with fp8 records, for R3D_FMT_SPLIT_MX inputs; written for R3D_SR_F16MX only) ++ conv0 (plain layout with fp8 records) ++ conv1 (Winograd pack)
+// prepacked: SrPackLayout (r3d_sr_common.h)
 int sr_prepack_f16x3(int Cin, int Cout, const float* c0_w, const float* c1_w, void* prepacked, hipStream_t st, bool mx)
 {
     float* out = reinterpret_cast<float*>(prepacked);
     const size_t m0 = (size_t)9 * (Cin / 8) * Cout, m1 = (size_t)9 * (Cout / 8) * Cout;
+    const SrPackLayout P = sr_pack_layout(Cin, Cout);
     const ConvTail T = conv_tail_layout(Cout);
-    float* tail0 = out + (size_t)2 * 9 * Cin * Cout + (size_t)9 * Cout * Cout;
-    float* tail1 = tail0 + T.total;
+    float* tail0 = out + P.tail0;
+    float* tail1 = out + P.tail1;
     hipLaunchKernelGGL(weight_row_stats_kernel, dim3(Cout), dim3(256), 0, st, c0_w, Cin * 9, Cout, Cout, tail0);
     hipLaunchKernelGGL(weight_row_stats_kernel, dim3(Cout), dim3(256), 0, st, c1_w, Cout * 9, Cout, Cout, tail1);
     hipLaunchKernelGGL(sr_prepack_f16_kernel, dim3((unsigned)((m0 + 255) / 256)), dim3(256), 0, st, c0_w, Cin, Cout, 9, Cin, Cout,
-                       tail0 + T.winv, reinterpret_cast<uint4*>(out));
+                       tail0 + T.winv, reinterpret_cast<uint4*>(out + P.c0));
     if (mx)         // conv1 consumes the fp8 records of the up-sampling conv's epilogue (R3D_SR_F16MX)
         hipLaunchKernelGGL(sr_prepack_mx_kernel, dim3((unsigned)((m1 / 2 + 255) / 256)), dim3(256), 0, st, c1_w, Cout, Cout, 9, Cout, Cout,
-                           tail1 + T.winv, reinterpret_cast<uint4*>(out + (size_t)9 * Cin * Cout));
+                           tail1 + T.winv, reinterpret_cast<uint4*>(out + P.c1));
     else
         hipLaunchKernelGGL(sr_prepack_f16_kernel, dim3((unsigned)((m1 + 255) / 256)), dim3(256), 0, st, c1_w, Cout, Cout, 9, Cout, Cout,
-                           tail1 + T.winv, reinterpret_cast<uint4*>(out + (size_t)9 * Cin * Cout));
+                           tail1 + T.winv, reinterpret_cast<uint4*>(out + P.c1));
     // conv0 again in the fused up-conv layout (SynthesisBlock; the plain layout above serves SynthesisBlockNoUp)
     const size_t mu = (size_t)9 * (Cin / 8) * Cout * 2;
     hipLaunchKernelGGL(sr_prepack_up_kernel, dim3((unsigned)((mu + 255) / 256)), dim3(256), 0, st, c0_w, Cin, Cout, tail0 + T.winv,
-                       reinterpret_cast<uint4*>(out + (size_t)9 * Cin * Cout + (size_t)9 * Cout * Cout));
+                       reinterpret_cast<uint4*>(out + P.c0_up));
     if (mx) {
         hipLaunchKernelGGL(sr_prepack_up_mx_kernel, dim3((unsigned)((mu + 255) / 256)), dim3(256), 0, st, c0_w, Cin, Cout, tail0 + T.winv,
-                           reinterpret_cast<uint4*>(tail1 + T.total));
+                           reinterpret_cast<uint4*>(out + P.c0_up_mx));
         if ((Cin & 15) == 0)        // conv0 in the plain layout with fp8 records: SynthesisBlockNoUp's conv0 on an R3D_FMT_SPLIT_MX input
             hipLaunchKernelGGL(sr_prepack_mx_kernel, dim3((unsigned)((m0 / 2 + 255) / 256)), dim3(256), 0, st, c0_w, Cin, Cout, 9, Cin, Cout,
-                               tail0 + T.winv, reinterpret_cast<uint4*>(tail1 + T.total + (size_t)9 * Cin * Cout));
+                               tail0 + T.winv, reinterpret_cast<uint4*>(out + P.c0_mx));
     }
     {   // conv1 for conv_wino_f16x3_kernel: 12 transformed tap matrices [Cout / 128][Cout / 16][wave 8][WG_WBLK]
         const size_t mw = (size_t)(Cout >> 7) * (Cout >> 4) * 8 * 3 * 2 * 32;
         hipLaunchKernelGGL(sr_prepack_wino_kernel, dim3((unsigned)((mw + 255) / 256)), dim3(256), 0, st, c1_w, Cout, Cout, Cout, Cout, tail1 + T.winv,
-                           reinterpret_cast<uint4*>(out + sr_wino_offset(Cin, Cout)), mx ? 1 : 0);
+                           reinterpret_cast<uint4*>(out + P.c1_wino), mx ? 1 : 0);
     }
     return check_launch("sr_block_prepack");
 }
@@ -1807,24 +1805,38 @@ static void launch_conv2(Conv2Args& a, int tiles, int N, hipStream_t st, bool mx
 
 static int tiles_of(int H, int W) { return ((W + F_TILE_W - 1) / F_TILE_W) * ((H + F_TILE_H - 1) / F_TILE_H); }
 
+// where a conv's epilogue writes y [N][Cout][H][W] in y_format (R3D_FMT_NONE: nowhere); the SPLIT formats are multiplied by next_scale
+static void conv_set_output(Conv2Args& a, void* y, int y_format, int Cout, int H, int W, const float* next_scale, size_t next_scale_stride)
+{
+    if (y_format == R3D_FMT_CB8) { a.y_f32 = reinterpret_cast<float*>(y); a.y_f32_stride_n = (size_t)Cout * H * W; }
+    else if (y_format == R3D_FMT_NCHW) { a.y_nchw = reinterpret_cast<float*>(y); a.y_nchw_stride_n = (size_t)Cout * H * W; }
+    else if (y_format == R3D_FMT_SPLIT || y_format == R3D_FMT_SPLIT_MX) {
+        a.y_split = reinterpret_cast<uint4*>(y); a.y_split_stride_n = (size_t)Cout / 8 * H * W * 2;
+        a.next_scale = next_scale; a.next_scale_stride_n = next_scale_stride;
+        a.y_split_mx = y_format == R3D_FMT_SPLIT_MX ? 1 : 0;
+    }
+}
+
+// upconv_fir_f16x3_kernel<CLAMP, MX, MXIN>: clamp compiled in | the epilogue writes conv1's fp8 records | the input carries fp8 records
+static void (*const kUpconv[2][2][2])(UpArgs) = {
+    {{upconv_fir_f16x3_kernel<false, false, false>, upconv_fir_f16x3_kernel<false, false, true>}, {upconv_fir_f16x3_kernel<false, true, false>, upconv_fir_f16x3_kernel<false, true, true>}},
+    {{upconv_fir_f16x3_kernel<true, false, false>, upconv_fir_f16x3_kernel<true, false, true>}, {upconv_fir_f16x3_kernel<true, true, false>, upconv_fir_f16x3_kernel<true, true, true>}}};
+
 int sr_block_forward_f16x3(const void* prepacked, const void* styles, int N, int Cin, int Cout, int Hin, int Win, int up,
                            const void* x, int x_format, const float* img, float clamp,
                            void* x_out, int x_out_format, const float* next_scale, size_t next_scale_stride,
-                           float* img_out, uint8_t* img_u8, float* x_absmax, void* workspace, size_t workspace_bytes, hipStream_t st, bool mx)
+                           float* img_out, uint8_t* img_u8, float* x_absmax, void* workspace, hipStream_t st, bool mx)
 {
-    (void)workspace_bytes;
     const SrStyleLayout L = sr_style_layout(Cin, Cout);
     const float* pk = reinterpret_cast<const float*>(styles);
     const float* wpk = reinterpret_cast<const float*>(prepacked);
+    const SrPackLayout P = sr_pack_layout(Cin, Cout);
     const int OH = up ? 2 * Hin : Hin, OW = up ? 2 * Win : Win;
+    const SrWorkspaceLayout WS = sr_workspace_layout(N, Cin, Cout, Hin, Win);     // (the T and xo slots serve R3D_SR_F32 only)
     char* wsb = reinterpret_cast<char*>(workspace);
-    uint4* xin = reinterpret_cast<uint4*>(wsb); wsb += align256((size_t)N * Cin * Hin * Win * 4);
-    // the T slot (four fp32 phase planes [Cout][Hin + 1][Win + 1]: the per-phase transposed conv of the fp32 path, r3d_sr.hip) is unused here since the
-    // unfused up-sampling conv0 was retired; r3d_sr_block_workspace_bytes and the offsets of the slots behind it are one layout for all precisions
-    wsb += align256((size_t)N * 4 * Cout * (Hin + 1) * (Win + 1) * 4);
-    uint4* y0 = reinterpret_cast<uint4*>(wsb);  wsb += align256((size_t)N * Cout * 4 * Hin * Win * 4);
-    float* xo = reinterpret_cast<float*>(wsb);                    // fp32 CB8 x (only when an fp32 x_out is requested)
-    float* rgbp = reinterpret_cast<float*>(wsb + align256((size_t)N * Cout * 4 * Hin * Win * 4));
+    uint4* xin = reinterpret_cast<uint4*>(wsb + WS.xin);
+    uint4* y0 = reinterpret_cast<uint4*>(wsb + WS.y0);
+    float* rgbp = reinterpret_cast<float*>(wsb + WS.rgbp);
 
     const uint4* xs = reinterpret_cast<const uint4*>(x);
     const bool mx_in = x_format == R3D_FMT_SPLIT_MX;          // (validated by the caller: up = 1, R3D_SR_F16MX)
@@ -1841,8 +1853,7 @@ int sr_block_forward_f16x3(const void* prepacked, const void* styles, int N, int
         // ---- conv0: fused transposed conv + FIR + bias + lrelu -> SPLIT (one kernel, T stays on chip) ----------------
         UpArgs u = {};
         u.x = xs; u.x_stride_n = (size_t)Cin / 8 * Hin * Win * 2;
-        u.wp = reinterpret_cast<const uint4*>(wpk + (size_t)9 * Cin * Cout + (size_t)9 * Cout * Cout);
-        if (mx_in) u.wp = reinterpret_cast<const uint4*>(wpk + (size_t)2 * 9 * Cin * Cout + (size_t)9 * Cout * Cout + 2 * conv_tail_layout(Cout).total);
+        u.wp = reinterpret_cast<const uint4*>(wpk + (mx_in ? P.c0_up_mx : P.c0_up));
         u.out_scale = pk + L.d0f; u.bias = pk + L.b0; u.next_scale = pk + L.s1f; u.vec_stride_n = L.total;
         u.y = y0; u.y_stride_n = (size_t)Cout / 8 * OH * OW * 2;
         u.Cin = Cin; u.Cout = Cout; u.H = Hin; u.W = Win;
@@ -1853,24 +1864,15 @@ int sr_block_forward_f16x3(const void* prepacked, const void* styles, int N, int
         u.clk = prof_clock_slot(R3D_PROF_UPCONV);
         ProfScope ps(R3D_PROF_UPCONV, st);
         const dim3 ugrid(8 * u.tiles_per_xcd * (Cout / 32), N);
-        if (mx_in && clamp >= 0.f && mx0) hipLaunchKernelGGL((upconv_fir_f16x3_kernel<true, true, true>), ugrid, dim3(256), 0, st, u);
-        else if (mx_in && mx0) hipLaunchKernelGGL((upconv_fir_f16x3_kernel<false, true, true>), ugrid, dim3(256), 0, st, u);
-        else if (mx_in && clamp >= 0.f) hipLaunchKernelGGL((upconv_fir_f16x3_kernel<true, false, true>), ugrid, dim3(256), 0, st, u);
-        else if (mx_in) hipLaunchKernelGGL((upconv_fir_f16x3_kernel<false, false, true>), ugrid, dim3(256), 0, st, u);
-        else if (mx0 && clamp >= 0.f) hipLaunchKernelGGL((upconv_fir_f16x3_kernel<true, true>), ugrid, dim3(256), 0, st, u);
-        else if (mx0) hipLaunchKernelGGL((upconv_fir_f16x3_kernel<false, true>), ugrid, dim3(256), 0, st, u);
-        else if (clamp >= 0.f) hipLaunchKernelGGL(upconv_fir_f16x3_kernel<true>, ugrid, dim3(256), 0, st, u);
-        else hipLaunchKernelGGL(upconv_fir_f16x3_kernel<false>, ugrid, dim3(256), 0, st, u);
+        hipLaunchKernelGGL(kUpconv[clamp >= 0.f][mx0][mx_in], ugrid, dim3(256), 0, st, u);
     } else {
         // ---- conv0 of SynthesisBlockNoUp (superresolution.py:159-258): plain modulated 3x3 conv -> SPLIT for conv1 ----
         Conv2Args a = {};
         a.x = xs; a.x_stride_n = (size_t)Cin / 8 * Hin * Win * 2;
-        a.wp = reinterpret_cast<const uint4*>(wpk);
+        a.wp = reinterpret_cast<const uint4*>(wpk + (mx_in ? P.c0_mx : P.c0));
         a.out_scale = pk + L.d0f; a.out_scale_stride_n = L.total; a.bias = pk + L.b0; a.bias_stride_n = L.total;
         a.OH = OH; a.OW = OW;
-        a.y_split = y0; a.y_split_stride_n = (size_t)Cout / 8 * OH * OW * 2; a.next_scale = pk + L.s1f; a.next_scale_stride_n = L.total;
-        a.y_split_mx = mx0 ? 1 : 0;                                  // f16mx: conv1 reads fp8 records (the Winograd kernel: plain SPLIT)
-        if (mx_in) a.wp = reinterpret_cast<const uint4*>(wpk + (size_t)3 * 9 * Cin * Cout + (size_t)9 * Cout * Cout + 2 * conv_tail_layout(Cout).total);
+        conv_set_output(a, y0, mx0 ? R3D_FMT_SPLIT_MX : R3D_FMT_SPLIT, Cout, OH, OW, pk + L.s1f, L.total);      // f16mx: conv1 reads fp8 records (the Winograd kernel: plain SPLIT)
         a.Cin = Cin; a.Cout = Cout; a.CoutReal = Cout; a.H = Hin; a.W = Win; a.nphase = 1;
         a.act = 1; a.act_slope = 0.2f; a.act_gain = 1.4142135623730951f; a.clamp = clamp;
         sr_fill_conv3x3_phase(a.ph, OH, OW);
@@ -1881,26 +1883,18 @@ int sr_block_forward_f16x3(const void* prepacked, const void* styles, int N, int
     {
         Conv2Args a = {};
         a.x = y0; a.x_stride_n = (size_t)Cout / 8 * OH * OW * 2;
-        a.wp = reinterpret_cast<const uint4*>(wpk + (size_t)9 * Cin * Cout);
+        a.wp = reinterpret_cast<const uint4*>(wpk + (wino1 ? P.c1_wino : P.c1));
         a.out_scale = pk + L.d1f; a.out_scale_stride_n = L.total; a.bias = pk + L.b1; a.bias_stride_n = L.total;
         a.OH = OH; a.OW = OW;
-        if (x_out && x_out_format == R3D_FMT_CB8) { a.y_f32 = reinterpret_cast<float*>(x_out); a.y_f32_stride_n = (size_t)Cout * OH * OW; }
-        if (x_out && x_out_format == R3D_FMT_NCHW) { a.y_nchw = reinterpret_cast<float*>(x_out); a.y_nchw_stride_n = (size_t)Cout * OH * OW; }
-        if (x_out && (x_out_format == R3D_FMT_SPLIT || x_out_format == R3D_FMT_SPLIT_MX)) {
-            a.y_split = reinterpret_cast<uint4*>(x_out); a.y_split_stride_n = (size_t)Cout / 8 * OH * OW * 2;
-            a.next_scale = next_scale; a.next_scale_stride_n = next_scale_stride;
-            a.y_split_mx = x_out_format == R3D_FMT_SPLIT_MX ? 1 : 0;
-        }
+        if (x_out) conv_set_output(a, x_out, x_out_format, Cout, OH, OW, next_scale, next_scale_stride);
         a.y_absmax = reinterpret_cast<unsigned*>(x_absmax);
         a.wrgb = pk + L.wrgb; a.wrgb_stride_n = L.total; a.rgb_partial = rgbp; a.rgbp_stride_n = (size_t)(Cout / 64) * 3 * OH * OW;
         a.Cin = Cout; a.Cout = Cout; a.CoutReal = Cout; a.H = OH; a.W = OW; a.nphase = 1;
         a.act = 1; a.act_slope = 0.2f; a.act_gain = 1.4142135623730951f; a.clamp = clamp;
         sr_fill_conv3x3_phase(a.ph, OH, OW);
-        if (wino1) a.wp = reinterpret_cast<const uint4*>(wpk + sr_wino_offset(Cin, Cout));
         ProfScope ps(R3D_PROF_CONV, st);
         launch_conv2(a, tiles_of(OH, OW), N, st, mx, wino1);
     }
-    (void)xo;
     {
         ProfScope ps(R3D_PROF_TORGB, st);
         hipLaunchKernelGGL(rgb_finalize_kernel, dim3((OH * OW + 255) / 256, N), dim3(256), 0, st, img, rgbp,
@@ -1911,50 +1905,43 @@ int sr_block_forward_f16x3(const void* prepacked, const void* styles, int N, int
 
 // ---- generic convolution layer (nn.Conv2d k = 1 | 3, stride 1, padding k/2, + bias + optional LeakyReLU) on the same kernel:
 // the torso / background fusion stacks of SuperresolutionHybrid8XDC_Warp (modules/real3d/super_resolution/sr_with_ref.py:24-63)
-static inline int pad_to(int v, int m) { return (v + m - 1) / m * m; }
+size_t conv_prepacked_bytes_f16x3(int Cin, int Cout, int ksize) { return conv_pack_layout(Cin, Cout, ksize).total * sizeof(float); }
 
-size_t conv_prepacked_bytes_f16x3(int Cin, int Cout, int ksize)
-{
-    const int Co = pad_to(Cout, BLOCK_M);
-    const size_t w = (size_t)(ksize * ksize) * pad_to(Cin, 16) * Co;
-    // 3x3: the weights again with fp8 records (R3D_FMT_SPLIT_MX inputs) and as the 12 transformed tap matrices of the Winograd F(2,3) kernel (plain SPLIT inputs, r3d_sr_wino.h)
-    return (w + conv_tail_layout(Co).total + (ksize == 3 ? w + (size_t)12 * pad_to(Cin, 16) * Co : 0)) * sizeof(float);
-}
-
-// prepacked = split weights (rows pre-scaled by 2^kw[co]) ++ ConvTail {2^-kw[co], sum|w[co]|} ++ (3x3 only) the weights in the f16mx layout
+// prepacked: ConvPackLayout (r3d_sr_common.h); the weight rows are pre-scaled by 2^kw[co]
 int conv_prepack_f16x3(const float* w, int Cin, int Cout, int ksize, void* prepacked, hipStream_t st)
 {
-    const int Ci = pad_to(Cin, 16), Co = pad_to(Cout, BLOCK_M), nt = ksize * ksize;
+    const ConvPackLayout P = conv_pack_layout(Cin, Cout, ksize);
+    const int Ci = P.Ci, Co = P.Co, nt = ksize * ksize;
     const size_t m = (size_t)nt * (Ci / 8) * Co;
-    float* tail = reinterpret_cast<float*>(prepacked) + (size_t)nt * Ci * Co;
+    float* out = reinterpret_cast<float*>(prepacked);
+    float* tail = out + P.tail;
     ProfScope ps(R3D_PROF_PACK, st);
     hipLaunchKernelGGL(weight_row_stats_kernel, dim3(Co), dim3(256), 0, st, w, Cin * nt, Cout, Co, tail);
     hipLaunchKernelGGL(sr_prepack_f16_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, w, Cin, Cout, nt, Ci, Co,
-                       tail + conv_tail_layout(Co).winv, reinterpret_cast<uint4*>(prepacked));
+                       tail + conv_tail_layout(Co).winv, reinterpret_cast<uint4*>(out + P.w));
     if (ksize == 3) {
         hipLaunchKernelGGL(sr_prepack_mx_kernel, dim3((unsigned)((m / 2 + 255) / 256)), dim3(256), 0, st, w, Cin, Cout, nt, Ci, Co,
-                           tail + conv_tail_layout(Co).winv, reinterpret_cast<uint4*>(tail + conv_tail_layout(Co).total));
+                           tail + conv_tail_layout(Co).winv, reinterpret_cast<uint4*>(out + P.w_mx));
         const size_t mw = (size_t)(Co >> 7) * (Ci >> 4) * 8 * 3 * 2 * 32;
         hipLaunchKernelGGL(sr_prepack_wino_kernel, dim3((unsigned)((mw + 255) / 256)), dim3(256), 0, st, w, Cin, Cout, Ci, Co, tail + conv_tail_layout(Co).winv,
-                           reinterpret_cast<uint4*>(tail + conv_tail_layout(Co).total + (size_t)nt * Ci * Co), 0);      // (a plain SPLIT input: the f16x3 form)
+                           reinterpret_cast<uint4*>(out + P.w_wino), 0);      // (a plain SPLIT input: the f16x3 form)
     }
     return check_launch("conv_prepack");
 }
 
-size_t conv_workspace_bytes_f16x3(int N, int Cin, int H, int W)
-{
-    return align256((size_t)N * pad_to(Cin, 16) * H * W * 4) + 256;
-}
+// an NCHW | CB8 input as SPLIT: the padded Cin (of any Cout, ksize)
+size_t conv_workspace_bytes_f16x3(int N, int Cin, int H, int W) { return align256((size_t)N * conv_pack_layout(Cin, 1, 1).Ci * H * W * 4) + 256; }
 
-// scales: per-sample ConvScales vectors written by r3d_conv_chain_scales (in_vec: multiplier of the fp32 -> SPLIT input
+// scales: per-sample ConvScales vectors (stride S.total) written by r3d_conv_chain_scales (in_vec: multiplier of the fp32 -> SPLIT input
 // conversion; out_vec: epilogue multiplier 2^-kw[co] * 2^-e_in); bias [Cout] shared by the batch (or null)
-int conv_forward_f16x3(const void* prepacked, const float* scales, size_t scales_stride, const float* bias,
+int conv_forward_f16x3(const void* prepacked, const float* scales, const float* bias,
                        int N, int Cin, int Cout, int H, int W, int ksize,
                        const void* x, int x_format, int act, float slope, float gain, float clamp,
                        void* y, int y_format, const float* next_scale, size_t next_scale_stride, float* y_absmax,
                        void* workspace, hipStream_t st, const ConvCat* cat)
 {
-    const int Ci = pad_to(Cin, 16), Co = pad_to(Cout, BLOCK_M);
+    const ConvPackLayout P = conv_pack_layout(Cin, Cout, ksize);
+    const int Ci = P.Ci, Co = P.Co;
     const ConvScales S = conv_scales_layout(Ci, Co);
     const uint4* xs = reinterpret_cast<const uint4*>(x);
     const bool mx_in = x_format == R3D_FMT_SPLIT_MX;          // (validated by the caller: ksize 3, Cin % 16 == 0): the f16mx main loop
@@ -1962,64 +1949,51 @@ int conv_forward_f16x3(const void* prepacked, const float* scales, size_t scales
         uint4* xin = reinterpret_cast<uint4*>(workspace);
         ProfScope ps(R3D_PROF_LAYOUT, st);
         hipLaunchKernelGGL(to_split_kernel, dim3((H * W + 255) / 256, Ci / 8, N), dim3(256), 0, st,
-                           reinterpret_cast<const float*>(x), x_format == R3D_FMT_CB8 ? 1 : 0, scales + S.in_vec, scales_stride, xin, Ci, Cin, H * W);
+                           reinterpret_cast<const float*>(x), x_format == R3D_FMT_CB8 ? 1 : 0, scales + S.in_vec, S.total, xin, Ci, Cin, H * W);
         xs = xin;
     }
     Conv2Args a = {};
     a.x = xs; a.x_stride_n = (size_t)Ci / 8 * H * W * 2;
-    a.wp = reinterpret_cast<const uint4*>(prepacked);
-    if (mx_in) a.wp = reinterpret_cast<const uint4*>(reinterpret_cast<const float*>(prepacked) + (size_t)ksize * ksize * Ci * Co + conv_tail_layout(Co).total);
-    a.out_scale = scales + S.out_vec; a.out_scale_stride_n = scales_stride; a.bias = bias; a.bias_stride_n = 0;
+    a.out_scale = scales + S.out_vec; a.out_scale_stride_n = S.total; a.bias = bias; a.bias_stride_n = 0;
     a.OH = H; a.OW = W;
-    if (y_format == R3D_FMT_CB8) { a.y_f32 = reinterpret_cast<float*>(y); a.y_f32_stride_n = (size_t)Cout * H * W; }
-    else if (y_format == R3D_FMT_NCHW) { a.y_nchw = reinterpret_cast<float*>(y); a.y_nchw_stride_n = (size_t)Cout * H * W; }
-    else { a.y_split = reinterpret_cast<uint4*>(y); a.y_split_stride_n = (size_t)Cout / 8 * H * W * 2; a.next_scale = next_scale; a.next_scale_stride_n = next_scale_stride;
-           a.y_split_mx = y_format == R3D_FMT_SPLIT_MX ? 1 : 0;
-           if (cat) {      // y is the whole concatenated tensor [N][hi|lo][C_total / 8][H][W][8]; next_scale the consumer's whole in-multiplier vector
-               a.y_split_stride_n = (size_t)cat->C_total / 8 * H * W * 2; a.y_cat_chunks = cat->C_total / 8; a.y_cat_off = cat->chan_off / 8;
-               a.y_mask = cat->mask; a.y_mask_invert = cat->mask_invert;
-               if (next_scale) a.next_scale = next_scale + cat->chan_off;
-           } }
+    conv_set_output(a, y, y_format, Cout, H, W, next_scale, next_scale_stride);
+    if (cat) {      // (SPLIT | SPLIT_MX) y is the whole concatenated tensor [N][hi|lo][C_total / 8][H][W][8]; next_scale the consumer's whole in-multiplier vector
+        a.y_split_stride_n = (size_t)cat->C_total / 8 * H * W * 2; a.y_cat_chunks = cat->C_total / 8; a.y_cat_off = cat->chan_off / 8;
+        a.y_mask = cat->mask; a.y_mask_invert = cat->mask_invert;
+        if (next_scale) a.next_scale = next_scale + cat->chan_off;
+    }
     a.y_absmax = reinterpret_cast<unsigned*>(y_absmax);
     a.Cin = Ci; a.Cout = Co; a.CoutReal = Cout; a.H = H; a.W = W; a.nphase = 1;
     a.act = act; a.act_slope = slope; a.act_gain = gain; a.clamp = clamp;
     if (ksize == 3) sr_fill_conv3x3_phase(a.ph, H, W);
-    else {
-        ConvPhase& p = a.ph[0];
-        p.outH = H; p.outW = W; p.oy_mul = 1; p.oy_add = 0; p.ox_mul = 1; p.ox_add = 0; p.out_off = 0;
-        p.ntaps = 1; p.dy[0] = 0; p.dx[0] = 0; p.widx[0] = 0;
-    }
+    else sr_fill_conv1x1_phase(a.ph, H, W);
     // a plain SPLIT operand (the f16x3 precision, or a producer that does not write records): Winograd F(2,3) when the shape allows it
     const bool wino = ksize == 3 && !mx_in && wino_shape_ok(Ci, Co, H, W) && (wino_mode() == 1 || wino_mode() == 3);
-    if (wino) a.wp = reinterpret_cast<const uint4*>(reinterpret_cast<const float*>(prepacked) + (size_t)2 * 9 * Ci * Co + conv_tail_layout(Co).total);
+    a.wp = reinterpret_cast<const uint4*>(reinterpret_cast<const float*>(prepacked) + (mx_in ? P.w_mx : wino ? P.w_wino : P.w));
     ProfScope ps(R3D_PROF_CONV, st);
     launch_conv2(a, tiles_of(H, W), N, st, mx_in, wino);
     return check_launch("conv_forward");
 }
 
 // cat([a * mask, b * (1 - mask)]) -> 1x1 conv in one kernel (conv1x1_blend_f16x3_kernel); the caller validated: ksize 1, a / b CB8, Ca % 8 == Cb % 8 == 0, (Ca + Cb) % 64 == 0
-int conv_forward_blend_f16x3(const void* prepacked, const float* scales, size_t scales_stride, const float* bias,
+int conv_forward_blend_f16x3(const void* prepacked, const float* scales, const float* bias,
                              int N, int Ca, int Cb, int Cout, int H, int W, const float* xa, const float* xb, const float* mask,
                              int act, float slope, float gain, float clamp,
                              void* y, int y_format, const float* next_scale, size_t next_scale_stride, float* y_absmax, hipStream_t st)
 {
-    const int Ci = Ca + Cb, Co = pad_to(Cout, BLOCK_M);
+    const ConvPackLayout P = conv_pack_layout(Ca + Cb, Cout, 1);
+    const int Ci = P.Ci, Co = P.Co;
     const ConvScales S = conv_scales_layout(Ci, Co);
     Conv2Args a = {};
-    a.wp = reinterpret_cast<const uint4*>(prepacked);
-    a.bl_a = xa; a.bl_b = xb; a.bl_mask = mask; a.bl_scale = scales + S.in_vec; a.bl_scale_stride_n = scales_stride; a.bl_Ca = Ca;
-    a.out_scale = scales + S.out_vec; a.out_scale_stride_n = scales_stride; a.bias = bias; a.bias_stride_n = 0;
+    a.wp = reinterpret_cast<const uint4*>(reinterpret_cast<const float*>(prepacked) + P.w);
+    a.bl_a = xa; a.bl_b = xb; a.bl_mask = mask; a.bl_scale = scales + S.in_vec; a.bl_scale_stride_n = S.total; a.bl_Ca = Ca;
+    a.out_scale = scales + S.out_vec; a.out_scale_stride_n = S.total; a.bias = bias; a.bias_stride_n = 0;
     a.OH = H; a.OW = W;
-    if (y_format == R3D_FMT_CB8) { a.y_f32 = reinterpret_cast<float*>(y); a.y_f32_stride_n = (size_t)Cout * H * W; }
-    else if (y_format == R3D_FMT_NCHW) { a.y_nchw = reinterpret_cast<float*>(y); a.y_nchw_stride_n = (size_t)Cout * H * W; }
-    else { a.y_split = reinterpret_cast<uint4*>(y); a.y_split_stride_n = (size_t)Cout / 8 * H * W * 2; a.next_scale = next_scale; a.next_scale_stride_n = next_scale_stride;
-           a.y_split_mx = y_format == R3D_FMT_SPLIT_MX ? 1 : 0; }
+    conv_set_output(a, y, y_format, Cout, H, W, next_scale, next_scale_stride);
     a.y_absmax = reinterpret_cast<unsigned*>(y_absmax);
     a.Cin = Ci; a.Cout = Co; a.CoutReal = Cout; a.H = H; a.W = W; a.nphase = 1;
     a.act = act; a.act_slope = slope; a.act_gain = gain; a.clamp = clamp;
-    ConvPhase& p = a.ph[0];
-    p.outH = H; p.outW = W; p.oy_mul = 1; p.oy_add = 0; p.ox_mul = 1; p.ox_add = 0; p.out_off = 0;
-    p.ntaps = 1; p.dy[0] = 0; p.dx[0] = 0; p.widx[0] = 0;
+    sr_fill_conv1x1_phase(a.ph, H, W);
     ProfScope ps(R3D_PROF_CONV, st);
     hipLaunchKernelGGL(conv1x1_blend_f16x3_kernel, dim3(tiles_of(H, W), Co / BLOCK_M, N), dim3(512), 0, st, a);
     return check_launch("conv_forward_blend");

@@ -37,6 +37,22 @@ def test_version_and_sizes():
     assert lib.r3d_sr_block_workspace_bytes(1, 32, 256, 128, 128) > 256 * 257 * 257 * 4
 
 
+def test_pack_and_workspace_sizes_are_pinned():
+    """The sizes SrPackLayout / ConvPackLayout / SrWorkspaceLayout (csrc/r3d_sr_common.h) add up to, at shapes that pad both channel counts and
+    have every region; the numbers are those of the library before the layouts were named (formulas in the comments)."""
+    from real3dportrait_amd import _lib
+    lib = _lib.load()
+    assert lib.r3d_sr_block_prepacked_bytes(16, 128) == 1673216          # (4 * 9 * 16 * 128 + 9 * 128^2 + 2 * 2 * 128 + 12 * 128^2) * 4
+    assert lib.r3d_conv_prepacked_bytes(65, 3, 1) == 41984               # 1x1, padded to 80 x 128: (80 * 128 + 2 * 128) * 4
+    assert lib.r3d_conv_prepacked_bytes(20, 132, 3) == 985088            # padded to 32 x 256: (2 * 9 * 32 * 256 + 2 * 256 + 12 * 32 * 256) * 4
+    assert lib.r3d_sr_block_workspace_bytes(1, 16, 128, 8, 8) == 438272  # xin 4096 + T 165888 + y0 131072 + xo 131072 + rgbp 6144
+    assert lib.r3d_sr_block_workspace_bytes(2, 16, 128, 5, 7) == 494848  # every slot rounded up to 256 bytes: 4608 + 196608 + 2 * 143360 + 6912
+    assert lib.r3d_conv_scales_bytes(1, 65, 3) == 848 and lib.r3d_conv_scales_bytes(2, 65, 3) == 1696        # (80 + 128 + 4) * 4 per sample
+    assert lib.r3d_conv_scales_bytes(1, 20, 132) == 1168 and lib.r3d_conv_scales_bytes(3, 20, 132) == 3504   # (32 + 256 + 4) * 4
+    assert lib.r3d_conv_scales_bound_offset(65, 3) == 209 and lib.r3d_conv_scales_bound_offset(20, 132) == 289
+    assert lib.r3d_conv_workspace_bytes(1, 17, 5, 7) == 4864             # Cin padded to 32: 32 * 35 * 4 rounded up to 256, + 256
+
+
 def test_argument_errors_are_reported_not_thrown():
     from real3dportrait_amd import _lib
     lib = _lib.load()
