@@ -30,10 +30,15 @@ __host__ __device__ inline int pow2_ceil_exp(float m)
 }
 __host__ __device__ inline float pow2f(int e) { return ldexpf(1.0f, e < -120 ? -120 : (e > 120 ? 120 : e)); }
 __host__ __device__ inline int weight_row_exp(float rowmax) { return rowmax > 0.f ? kWeightTargetExp + 1 - pow2_ceil_exp(rowmax) : 0; }
-// multiplier exponent for an activation with bound B whose per-channel multipliers have max |s|max (0 -> treated as 1)
+// multiplier exponent for an activation with bound B whose per-channel multipliers have max |s|max (0 -> treated as 1):
+// |x| <= B < 2^eb and |s| <= smax <= 2^es give |x s 2^e| < 2^15 for e = 15 - eb - es.  es belongs to the smallest power of two that is >= smax, not
+// > smax: a plain conv (multiplier 1) has es = 0 and its stored bound B 2^e lies in [2^14, 2^15) as documented -- with frexp's exponent alone (1 for
+// smax = 1) every plain conv stored its operand one binade lower, [2^13, 2^14) (tests/test_gpu_sr_ops.py check_in_multiplier)
 __host__ __device__ inline int act_exp(float B, float smax)
 {
-    const int eb = B > 0.f ? pow2_ceil_exp(B) : 0, es = smax > 0.f ? pow2_ceil_exp(smax) : 0;
+    const int eb = B > 0.f ? pow2_ceil_exp(B) : 0;
+    int es = smax > 0.f ? pow2_ceil_exp(smax) : 0;
+    if (smax > 0.f && smax < 3.0e38f && ldexpf(1.0f, es - 1) == smax) --es;
     return kActTargetExp - eb - es;
 }
 

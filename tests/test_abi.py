@@ -130,6 +130,36 @@ def test_argument_errors_are_reported_not_thrown():
         assert "multiple of 8" in str(e)
 
 
+def test_sr_resampling_and_image_op_argument_errors():
+    """The small kernels around the SR convs refuse what they do not cover before any launch (tests/test_gpu_sr_ops.py runs them)."""
+    from real3dportrait_amd import _lib
+    lib = _lib.load()
+    one = ctypes.c_void_p(64)      # never dereferenced: validation fails first
+    CB8, SPLIT, SPLIT_MX = 1, 2, 3
+    rc = lib.r3d_upsample2x_bilinear(one, 1, 12, 4, 4, one, CB8, None, 0, None)
+    assert rc == -1 and b"multiple of 8" in lib.r3d_last_error()
+    rc = lib.r3d_upsample2x_bilinear(one, 1, 16, 4, 4, one, 0, None, 0, None)
+    assert rc == -1 and b"y_format" in lib.r3d_last_error()                    # NCHW is not an output format of this kernel
+    rc = lib.r3d_upsample2x_bilinear(one, 1, 16, 4, 4, one, 4, None, 0, None)
+    assert rc == -1 and b"y_format" in lib.r3d_last_error()
+    rc = lib.r3d_upsample2x_bilinear(one, 1, 24, 4, 4, one, SPLIT_MX, None, 0, None)
+    assert rc == -1 and b"SPLIT_MX needs C % 16" in lib.r3d_last_error()      # whole 16-channel record groups
+    assert lib.r3d_upsample2x_bilinear(None, 1, 16, 4, 4, one, SPLIT, None, 0, None) == -1 and b"upsample2x_bilinear" in lib.r3d_last_error()
+    assert lib.r3d_upsample2x_bilinear(one, 1, 16, 4, 4, None, SPLIT, None, 0, None) == -1 and b"upsample2x_bilinear" in lib.r3d_last_error()
+    assert lib.r3d_upsample2x_bilinear(one, 1, 16, 0, 4, one, CB8, None, 0, None) == -1
+    for args in ((0, 4, 4, 2, 2), (1, 0, 4, 2, 2), (1, 4, 0, 2, 2), (1, 4, 4, 0, 2), (1, 4, 4, 2, 0)):          # planes, H, W, OH, OW
+        rc = lib.r3d_resize_bilinear(one, args[0], args[1], args[2], one, args[3], args[4], 1, None)
+        assert rc == -1 and b"resize_bilinear" in lib.r3d_last_error(), args
+    assert lib.r3d_resize_bilinear(None, 1, 4, 4, one, 2, 2, 0, None) == -1
+    for args in ((None, one, one, one), (one, None, one, one), (one, one, None, one), (one, one, one, None)):       # a, b, mask, out
+        rc = lib.r3d_blend(args[0], args[1], args[2], 1, 3, 4, 4, args[3], None)
+        assert rc == -1 and b"blend" in lib.r3d_last_error()
+    assert lib.r3d_blend(one, one, one, 1, 0, 4, 4, one, None) == -1
+    rc = lib.r3d_person_occlusion(one, one, 0.5, 0, one, None)
+    assert rc == -1 and b"person_occlusion" in lib.r3d_last_error()
+    assert lib.r3d_person_occlusion(one, None, 0.5, 16, one, None) == -1
+
+
 def test_product_has_no_oracle_dependency():
     """The oracle is test infrastructure: nothing under real3dportrait_amd/ may import or load it."""
     pkg = os.path.join(ROOT, "real3dportrait_amd")
