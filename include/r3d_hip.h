@@ -535,6 +535,44 @@ int r3d_torso_conv3d_prec(const float* x, int B, int D, int Hs, int Ws, int Cin,
  * host mirror).  The outputs must not overlap x or each other. */
 int r3d_torso_split_bf16x3(const float* x, size_t n, uint16_t* h, uint16_t* m, uint16_t* l, r3d_stream_t stream);
 
+/* --- torso appearance extractor: the third module of the face-vid2vid torso network, inference (added under ABI 0.8.0) -------------
+ * AppearanceFeatureExtractor.forward (modules/real3d/facev2v_warp/network2.py:38-45), as WarpBasedTorsoModelMediaPipe.forward calls it on
+ * every frame (model2.py:230).  in_conv is r3d_torso_conv_prec; the three functions below are the rest.  They run the 3-D body of
+ * r3d_torso_conv3d (a 2-D layer as one depth with ONE depth tap, K = ksize ksize Cin) and sum in its order: with pool = 0 / depth = 1 /
+ * no prologue and no residual each equals r3d_torso_conv_prec / r3d_torso_conv3d_prec bit for bit, on both tiers.  `precision` is
+ * R3D_TORSO_F32 or R3D_TORSO_BF16X3 as above; anything else is R3D_ERR_INVALID_ARG.  Weights [Cout, Cin, k, k] / [Cout, Cin, k, k, k]
+ * are passed as [Cout, k, k, Cin] / [Cout, k, k, k, Cin] with the eval BatchNorms folded in once per parameter version by the Python
+ * module (real3dportrait_amd/torso_appearance.py).  Any Cin, Cout in 1 .. 4096; x, w and the prologue vectors are read 16 bytes at a
+ * time when Cin % 4 == 0, the input is channel-last and they are 16-byte aligned.  All arguments are checked before any launch. */
+
+/* DownBlock2D (layers.py:58-69: conv 3 x 3, BatchNorm, ReLU, nn.AvgPool2d((2, 2))): the stride-1 convolution of r3d_torso_conv
+ * (ksize 1, 3 or 7, zero padding ksize / 2; x [B, Hs, Ws, Cin], or [B, Cin, Hs, Ws] with in_nchw != 0; w [Cout, ksize, ksize, Cin];
+ * bias [Cout] or NULL; v = sum + bias; act 0: none, 1: v < 0 ? act_slope v : v, 2: sigmoid), then with pool = 1 the average of each
+ * 2 x 2 window, 0.25 ((v00 + v01) + (v10 + v11)) -- after the activation, so it cannot go into the weights.  The un-pooled tensor is
+ * never written.  y [B, Hs >> pool, Ws >> pool, Cout].  pool = 1 with an odd Hs or Ws is R3D_ERR_INVALID_ARG.  y must not overlap x,
+ * w or bias. */
+int r3d_torso_conv_pool(const float* x, int B, int Hs, int Ws, int Cin, int in_nchw, const float* w, const float* bias, int Cout,
+                        int ksize, int act, float act_slope, int pool, float* y, int precision, r3d_stream_t stream);
+/* mid_conv followed by x.view(N, C, D, H, W) (network2.py:41-43): the same convolution with a depth-split store.  Cout = C depth.  The
+ * caller passes the weight rows (and the bias) DEPTH-MAJOR: row d C + c is the reference's output channel c depth + d
+ * (weight.view(C, depth, Cin, k, k).transpose(0, 1)), so that a lane group stores a contiguous run of C.  Row d C + c of position
+ * (b, h, w) lands at y[b, d, h, w, c] of the channel-last volume y [B, depth, Hs, Ws, C], the layout r3d_torso_conv3d_res reads;
+ * exactly B depth Hs Ws C floats are written, there is no [B, H, W, C depth] intermediate and no transpose launch.  depth = 1 is the
+ * plain convolution.  depth < 1 or Cout % depth != 0 is R3D_ERR_INVALID_ARG.  y must not overlap x, w or bias. */
+int r3d_torso_conv_split(const float* x, int B, int Hs, int Ws, int Cin, int in_nchw, const float* w, const float* bias, int Cout,
+                         int ksize, int act, float act_slope, int depth, float* y, int precision, r3d_stream_t stream);
+/* The convolutions of ResBlock3D (layers.py:96-115: x + NAC(NAC(x)), each NAC = BatchNorm, ReLU, nn.Conv3d(C, C, 3, 1, 1)): the
+ * stride-1 Conv3d of r3d_torso_conv3d (cubic kernel, ksize 1, 3 or 7, zero padding ksize / 2 in depth, height and width; x [B, D, Hs,
+ * Ws, Cin]; w [Cout, ksize, ksize, ksize, Cin]; bias [Cout] or NULL) with
+ *   a prologue (pro_scale, pro_shift [Cin], both or neither): each tap is a = pro_scale[c] x + pro_shift[c], then a < 0 ? pro_slope a : a,
+ *     and 0 outside the volume AFTER that, in depth as well as in height and width (the reference pads the activated tensor);
+ *   the epilogue v = sum + bias; act as above; then + residual [B, D, Hs, Ws, Cout] (or NULL), which may be y itself.
+ * Outputs: y [B, D, Hs, Ws, Cout] and / or y_ncdhw [B, Cout, D, Hs, Ws] (at least one), both writable from one launch.  Outputs must
+ * not overlap an input (other than residual == y) or each other. */
+int r3d_torso_conv3d_res(const float* x, int B, int D, int Hs, int Ws, int Cin, const float* pro_scale, const float* pro_shift,
+                         float pro_slope, const float* w, const float* bias, int Cout, int ksize, int act, float act_slope,
+                         const float* residual, float* y, float* y_ncdhw, int precision, r3d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,6 +8,7 @@ Operators keep the reference's names and signatures (see each module's docstring
     SegFormerSECC2PlaneBackbone                          (segformer.py: the per-frame SECC encoder, mode b0)
     TorsoGenerator, Occlusion2Predictor                  (torso_generator.py: the torso network's warp + decoder, its Generator)
     TorsoMotionFieldEstimator                            (torso_motion.py: the torso network's per-frame MotionFieldEstimator)
+    TorsoAppearanceFeatureExtractor                      (torso_appearance.py: the torso network's AppearanceFeatureExtractor)
     render_clip_sharded                                  (frames.py: frame sharding + RCCL gather)
 All compute goes through libr3d_hip.so (include/r3d_hip.h); there is no eager/CPU fallback.
 """
@@ -33,6 +34,9 @@ def __getattr__(name):      # lazy: importing the package (e.g. for synth) must 
     if name == "TorsoMotionFieldEstimator":
         from . import torso_motion as m
         return m.MotionFieldEstimator
+    if name == "TorsoAppearanceFeatureExtractor":
+        from . import torso_appearance as m
+        return m.AppearanceFeatureExtractor
     if name in ("render_clip_sharded", "shard_frames"):
         from . import frames as m
         return getattr(m, name)

@@ -84,6 +84,9 @@ SIGNATURES = {
     "r3d_torso_conv_prec": (c_int, [P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, c_float, P, P, c_int, c_int, c_int, c_float, P, P, P, c_int, P]),
     "r3d_torso_conv3d_prec": (c_int, [P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, c_int, c_int, c_int, c_int, c_float, c_int, P, c_int, c_int, P, c_int, P]),
     "r3d_torso_split_bf16x3": (c_int, [P, c_size_t, P, P, P, P]),
+    "r3d_torso_conv_pool": (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, P, c_int, c_int, c_int, c_float, c_int, P, c_int, P]),
+    "r3d_torso_conv_split": (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, P, c_int, c_int, c_int, c_float, c_int, P, c_int, P]),
+    "r3d_torso_conv3d_res": (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, P, c_float, P, P, c_int, c_int, c_int, c_float, P, P, P, c_int, P]),
 }
 
 

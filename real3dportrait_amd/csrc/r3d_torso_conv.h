@@ -17,6 +17,12 @@
 //   * an output channel stride and offset (a producer writes its slice of a concatenation);
 //   * m-fast tile order for layers with fewer positions than output channels (every XCD streams its own share of the weights once).
 //
+// EXT = true (with D3; the appearance extractor's kernels, r3d_torso_appearance.hip) adds to that epilogue
+//   * + residual [M, Cout] after the activation (may alias y: each element is read, then written, by one lane);
+//   * the depth-split store of a 2-D layer (D = Do = 1): output channel n = d C + c, C = Cout / split, goes to [b, d, h, w, c] of a volume
+//     [B, split, H, W, C] -- a Conv2d followed by x.view(N, C, D, H, W) whose weight rows the caller ordered depth-major.
+// EXT = false compiles neither: the kernels of r3d_torso_conv3d are the code they were.
+//
 // PREC selects the arithmetic of the products; loaders, tile order and epilogues are the same code for both.
 //   F32     the fp32 operands as they are, 8 v_mfma_f32_16x16x4_f32 per 16 x 16 tile and k step.
 //   BF16X3  store() splits every staged value into three bf16 pieces h + m + l == x (split_bf16x3) and compute() sums six of the nine
@@ -79,6 +85,8 @@ struct ConvArgs {
     const float* x; int B, Hs, Ws, Cin;          // stored input [B, Hs, Ws, Cin] (in_nchw: [B, Cin, Hs, Ws]); D3: [B, D, Hs, Ws, Cin]
     int H, W;                                    // the conv's grid: Hs x Ws, or twice that (up: the input is x[h >> 1, w >> 1])
     int up, in_nchw, ks;
+    int split;                                   // D3 and EXT only: > 1: the depth-split store, y [B, split, H, W, Cout / split] (D = Do = 1, no pool).
+                                                 // It sits in what was padding in front of the next pointer: no other field moves, the struct keeps its size
     const float* ps; const float* pt; float pslope;      // prologue a = ps[c] x + pt[c]; a < 0 ? pslope a : a  (ps == nullptr: none)
     const float* w; int Cout;                    // [Cout, ks, ks, Cin]; D3: [Cout, kd, ks, ks, Cin]
     const float* bias;                           // [Cout] or nullptr
@@ -121,10 +129,11 @@ struct KPos {
     }
 };
 
-template <int PREC, bool VEC, bool D3, int WM, int WN, int TM, int TN>
+template <int PREC, bool VEC, bool D3, int WM, int WN, int TM, int TN, bool EXT = false>
 __device__ __forceinline__ void conv_tile(const ConvArgs& g)
 {
     static_assert(WM * WN == 4, "four waves");
+    static_assert(D3 || !EXT, "the extended epilogue belongs to the 3-D body");
     static_assert(PREC == F32 || PREC == BF16X3, "precision");
     constexpr int BM = WM * TM * 16, BN = WN * TN * 16;
     constexpr int AV = BM / 32, WV = (BN + 31) / 32;           // VEC: float4 loads per thread (A, W)
@@ -377,6 +386,18 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& g)
             else if (g.act == 2) v = 1.0f / (1.0f + expf(-v));
             return v;
         };
+        float res[EXT ? TM : 1][4][EXT ? TN : 1];
+        if constexpr (EXT) {
+#pragma unroll
+            for (int i = 0; i < TM; ++i)
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+#pragma unroll
+                    for (int j = 0; j < TN; ++j) {
+                        const int m = m0 + wm + i * 16 + (lane >> 4) * 4 + r, n = n0 + wn + j * 16 + (lane & 15);
+                        res[i][r][j] = (g.res && m < g.M && n < g.Cout) ? g.res[(size_t)m * g.Cout + n] : 0.0f;
+                    }
+        }
 #pragma unroll
         for (int i = 0; i < TM; ++i) {
             const int mq = m0 + wm + i * 16 + (lane >> 4) * 4;          // the lane's four rows mq .. mq + 3: one pooling window
@@ -395,7 +416,15 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& g)
                 for (int r = 0; r < 4; ++r) {
                     const int m = mq + r;
                     if (m >= g.M) continue;
-                    const float v = activate(acc[i][j][r] + bias[j]);
+                    float v = activate(acc[i][j][r] + bias[j]);
+                    if constexpr (EXT) {
+                        v += res[i][r][j];
+                        if (g.split > 1) {                              // D = Do = 1: m = b hw + px
+                            const int C = g.Cout / g.split, d = n / C, b = m / hw;
+                            g.y[(((size_t)b * g.split + d) * hw + (m - b * hw)) * C + (n - d * C)] = v;
+                            continue;
+                        }
+                    }
                     if (g.y) g.y[(size_t)m * g.ycs + g.yco + n] = v;
                     if (g.y_nchw) {
                         const int plane = m / hw, px = m - plane * hw, b = plane / g.Do, d = plane - b * g.Do;

@@ -478,3 +478,69 @@ def synth_torso_motion_inputs(seed, N=1, K=4, rotate=False):
             img[n, c] = 0.6 * np.sin(3.0 * xx * (c + 1) + 2.0 * yy + n) + 0.3 * hash_unitvar(seed, (256, 256), stream=26 + 4 * n + c)
         wts[n, 0] = 1.0 / (1.0 + np.exp(-6.0 * (0.5 - np.hypot(xx - 0.1 * n, yy + 0.1)))) * (0.8 + 0.2 * hash_uniform(seed, 65536, stream=40 + n).reshape(256, 256))
     return {"fs": fs, "kp_s": kp_s, "kp_d": kp_d, "Rs": Rs, "Rd": Rd, "tgt_head_img": np.clip(img, -1.0, 1.0), "tgt_head_weights": wts.astype(np.float32)}
+
+
+def torso_appearance_shapes(in_dim=3):
+    """[(state_dict key, shape)] of AppearanceFeatureExtractor(in_dim) (modules/real3d/facev2v_warp/network2.py:24-36): 107 entries."""
+    bn = lambda p, c: [(p + n, (c,)) for n in ("weight", "bias", "running_mean", "running_var")] + [(p + "num_batches_tracked", ())]
+    conv = lambda p, co, ci, *k: [(p + "weight", (co, ci) + k), (p + "bias", (co,))]
+    out = conv("in_conv.layers.0.", 64, in_dim, 7, 7) + bn("in_conv.layers.1.", 64)
+    for i, (ci, co) in enumerate(((64, 128), (128, 256))):
+        out += conv("down.%d.layers.0.layers.0." % i, co, ci, 3, 3) + bn("down.%d.layers.0.layers.1." % i, co)
+    out += conv("mid_conv.", TORSO_C * TORSO_D, 256, 1, 1)
+    for i in range(6):
+        for j in range(2):
+            p = "res.%d.layers.%d.layers." % (i, j)
+            out += bn(p + "0.", TORSO_C) + conv(p + "2.", TORSO_C, TORSO_C, 3, 3, 3)
+    return out
+
+
+# weight gains of synth_torso_appearance (x 1 / sqrt(fan_in)), chosen so that on synth_torso_appearance_inputs every ReLU zeroes a
+# middling share of its inputs and every ResBlock3D's branch and input both carry a good part of its output
+# (tests/golden/make_golden_torso_appearance.py asserts all of it on the reference's output)
+APPEARANCE_GAINS = {"in_conv": 1.5, "down": 2.0, "mid_conv": 1.5, "res": 1.4}
+
+
+def synth_torso_appearance(seed, in_dim=3):
+    """A full state_dict (numpy) of the appearance feature extractor.  Conv weights ~ N(0, gain^2 / fan_in) with APPEARANCE_GAINS by
+    module, biases 0.1 n (0.3 n in front of a BatchNorm); BatchNorm: weight 1 + 0.1 n, bias and running_mean 0.3 n, running_var in
+    [0.5, 2]."""
+    sd = {}
+    shapes = torso_appearance_shapes(in_dim)
+    names = dict(shapes)
+    for i, (key, shape) in enumerate(shapes):
+        st = 5000 + i
+        last = key.rsplit(".", 1)[-1]
+        if last == "num_batches_tracked":
+            v = np.array(0, dtype=np.int64)
+        elif last == "running_var":
+            v = np.float32(0.5) + np.float32(1.5) * hash_uniform(seed, shape[0], st)
+        elif last == "running_mean":
+            v = hash_unitvar(seed, shape, st) * np.float32(0.3)
+        elif len(shape) == 1 and (key[:-len(last)] + "running_mean") in names:           # BatchNorm weight / bias
+            v = hash_unitvar(seed, shape, st) * np.float32(0.3) if last == "bias" else np.float32(1.0) + hash_unitvar(seed, shape, st) * np.float32(0.1)
+        elif last == "bias":
+            front = key[:-6].rsplit(".", 1)[0] + ".1.running_mean" in names              # a "CNA" conv: its bias meets the BatchNorm's mean
+            v = hash_unitvar(seed, shape, st) * np.float32(0.3 if front else 0.1)
+        else:
+            gain = next(g for p, g in APPEARANCE_GAINS.items() if key.startswith(p))
+            v = hash_unitvar(seed, shape, st) * np.float32(gain / math.sqrt(int(np.prod(shape[1:]))))
+        sd[key] = np.asarray(v, dtype=np.int64 if last == "num_batches_tracked" else np.float32)
+    return sd
+
+
+def synth_torso_appearance_inputs(seed, N=1, in_dim=3, H=256, W=256):
+    """The input of AppearanceFeatureExtractor.forward as WarpBasedTorsoModelMediaPipe.forward builds it (facev2v_warp/model2.py:226-230):
+    x [N, in_dim, H, W]: channels 0 .. 2 an image in [-1, 1] (a smooth pattern + noise), any further channels (rgb_alpha: the torso and
+    head masks) in [0, 1].  Every sample differs."""
+    ly, lx = np.linspace(-1.0, 1.0, H, dtype=np.float32), np.linspace(-1.0, 1.0, W, dtype=np.float32)
+    yy, xx = np.meshgrid(ly, lx, indexing="ij")
+    x = np.empty((N, in_dim, H, W), np.float32)
+    for n in range(N):
+        for c in range(in_dim):
+            noise = hash_unitvar(seed, (H, W), stream=51 + 8 * n + c)
+            if c < 3:
+                x[n, c] = np.clip(0.6 * np.sin(3.0 * xx * (c + 1) + 2.0 * yy + n) + 0.3 * noise, -1.0, 1.0)
+            else:
+                x[n, c] = np.clip(1.0 / (1.0 + np.exp(-6.0 * (0.5 - np.hypot(xx - 0.1 * n, yy + 0.2 * (c - 3))))) + 0.1 * noise, 0.0, 1.0)
+    return {"x": x}

@@ -180,7 +180,8 @@ def _reference_hparams(model):
     return hp
 
 
-def patch_model(model, fuse_warp_sr=True, precision=None, secc_encoder=False, torso_generator=False, torso_motion=False, torso_precision=None):
+def patch_model(model, fuse_warp_sr=True, precision=None, secc_encoder=False, torso_generator=False, torso_motion=False, torso_precision=None,
+                torso_appearance=False):
     """Swap the hot-path operators of a constructed reference model for the HIP ones (in place).  INFERENCE ONLY: the HIP modules
     detach their inputs and build no autograd graph (the reference runs this path under torch.no_grad(), real3d_infer.py:435,479).
     precision: SR precision of the installed blocks (None = the library default 'f16mx': inside the 2e-4 of SURVEY 8(d) on every golden and heavy-tail sweep,
@@ -207,17 +208,21 @@ def patch_model(model, fuse_warp_sr=True, precision=None, secc_encoder=False, to
       MotionFieldEstimator at standard scale (facev2v_warp/network2.py:162-244, with the target-head branch), -> the HIP
       MotionFieldEstimator (torso_motion.py of this package: the Conv3d hourglass, the fuser, the mask and the occlusion maps in exact
       fp32).  torso_model.forward reaches it unchanged (model2.py:250).  The v1 estimator of network.py (no target-head branch) and
-      anything else are left as they are; the appearance extractor (per-clip work) stays PyTorch.
-    * torso_precision: the tier of the convolutions of the modules the two torso switches install (torso_precision.py): None = 'f32',
+      anything else are left as they are.
+    * torso_appearance=True (opt-in): model.superresolution.torso_model.appearance_extractor, when it is the reference's
+      AppearanceFeatureExtractor (facev2v_warp/network2.py:16-45), -> the HIP AppearanceFeatureExtractor (torso_appearance.py of this
+      package: every conv in exact fp32, 16 launches per call).  torso_model.forward reaches it unchanged, on every frame
+      (model2.py:230); nothing is cached across calls.  Anything else is left as it is.
+    * torso_precision: the tier of the convolutions of the modules the three torso switches install (torso_precision.py): None = 'f32',
       every product on the fp32 matrix instruction (the exact tier, the default and the recommendation); 'bf16x3' = each operand split into
-      three bf16 pieces and six piece products summed in fp32, fp32-class, no range state.  Given without torso_generator or torso_motion it
-      is a ValueError, as is an unknown name.
+      three bf16 pieces and six piece products summed in fp32, fp32-class, no range state.  Given without torso_generator, torso_motion or
+      torso_appearance it is a ValueError, as is an unknown name.
     Parameters are copied with strict key matching; the decoder module is left untouched (the renderer reads
     decoder.net[0|2].{weight,bias} directly)."""
     import types
     from .torso_precision import F32, check_precision
-    if torso_precision is not None and not (torso_generator or torso_motion):
-        raise ValueError("patch_model: torso_precision=%r needs torso_generator=True or torso_motion=True" % (torso_precision,))
+    if torso_precision is not None and not (torso_generator or torso_motion or torso_appearance):
+        raise ValueError("patch_model: torso_precision=%r needs torso_generator=True, torso_motion=True or torso_appearance=True" % (torso_precision,))
     torso_precision = check_precision(F32 if torso_precision is None else torso_precision, "patch_model: torso_precision")
     dev = next(model.parameters()).device
     hp = _reference_hparams(model)
@@ -274,6 +279,11 @@ def patch_model(model, fuse_warp_sr=True, precision=None, secc_encoder=False, to
         tm = getattr(model.superresolution, "torso_model", None)
         if tm is not None and tmo.is_reference_motion_estimator(getattr(tm, "motion_field_estimator", None)):
             tm.motion_field_estimator = tmo.MotionFieldEstimator.from_reference(tm.motion_field_estimator, torso_precision)
+    if torso_appearance:
+        from . import torso_appearance as tap
+        tm = getattr(model.superresolution, "torso_model", None)
+        if tm is not None and tap.is_reference_appearance_extractor(getattr(tm, "appearance_extractor", None)):
+            tm.appearance_extractor = tap.AppearanceFeatureExtractor.from_reference(tm.appearance_extractor, torso_precision)
     for owner in (getattr(model, "secc_img2plane_backbone", None), getattr(model, "img2plane_backbone", None)):
         _patch_sequential(owner, "to_plane_cnn", dev)       # per-frame plane producer tail (segformer.py:691-700)
     from .superresolution import set_sr_precision
