@@ -573,6 +573,32 @@ int r3d_torso_conv3d_res(const float* x, int B, int D, int Hs, int Ws, int Cin, 
                          float pro_slope, const float* w, const float* bias, int Cout, int ksize, int act, float act_slope,
                          const float* residual, float* y, float* y_ncdhw, int precision, r3d_stream_t stream);
 
+/* --- torso forward glue: what WarpBasedTorsoModelMediaPipe.forward does between its three modules, inference (added under ABI 0.8.0) ----
+ * modules/real3d/facev2v_warp/model2.py:226-236, fp32.  Both functions resize two channels c0, c1 (2 and 4 in the reference) of
+ * segmap [N, Cs, Hs, Ws] with the semantics of F.interpolate(mode='bilinear', align_corners=False, antialias=False):
+ * src = max((dst + 0.5) in / out - 0.5, 0), the upper neighbour clamped at the edge.  c0 or c1 outside 0 .. Cs - 1 is
+ * R3D_ERR_INVALID_ARG.  A NaN in the segmap is not defined.  All arguments are checked before any launch. */
+
+/* model2.py:226-228, in_conv's input in rgb_alpha mode: out [N, Ci + 2, OH, OW] = cat(img [N, Ci, OH, OW], resize(segmap[:, [c0, c1]],
+ * (OH, OW))), NCHW.  The image channels are copied bit for bit; Ci = 0 (img may then be NULL) gives the resized pair alone.  out must not
+ * overlap img or segmap. */
+int r3d_torso_seg_input(const float* img, int N, int Ci, const float* segmap, int Cs, int Hs, int Ws, int c0, int c1, float* out, int OH,
+                        int OW, r3d_stream_t stream);
+/* model2.py:231-236 in one launch, on the channel-last volume feats_cl [N, D, H, W, C] (r3d_torso_conv3d_res's y):
+ *   seg = resize(segmap[:, [c0, c1]], (H, W));  mask = seg0 + seg1;  mask_d = the maximum of mask over the ksize x ksize window with
+ *   `reflect` indexing at the border (utils/commons/image_utils.py:10-15: F.pad(mode='reflect') + max_pool2d): ksize odd and
+ *   (ksize - 1) / 2 < min(H, W), reflect padding's own condition, anything else is R3D_ERR_INVALID_ARG (as is a ksize above 117, whose
+ *   window does not fit a tile's LDS);
+ *   masked_cl [N, D, H, W, C] = feats_cl mask_d (mul_mask != 0) or a copy of feats_cl (mul_mask == 0): the source layout of r3d_torso_warp;
+ *   motion_cl [N, D, H, W, C + 2] = the same values followed by seg0, seg1, repeated over depth: what r3d_torso_volume_to_cl of the
+ *   reference's torch.cat would hold, the fs_cl of r3d_torso_motion_input.
+ * masked_cl may be feats_cl itself (each element is read, then written, by one lane); any other overlap between an output and an input
+ * or the other output is R3D_ERR_INVALID_ARG.  The resize and the dilation are computed once per pixel tile and run of depth slices,
+ * not per voxel; the volume is read and written 16 bytes at a time when C % 4 == 0 and the pointers are 16-byte (motion_cl: 8-byte)
+ * aligned. */
+int r3d_torso_mask_volume(const float* feats_cl, int N, int D, int H, int W, int C, const float* segmap, int Cs, int Hs, int Ws, int c0,
+                          int c1, int ksize, int mul_mask, float* masked_cl, float* motion_cl, r3d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,6 +9,7 @@ Operators keep the reference's names and signatures (see each module's docstring
     TorsoGenerator, Occlusion2Predictor                  (torso_generator.py: the torso network's warp + decoder, its Generator)
     TorsoMotionFieldEstimator                            (torso_motion.py: the torso network's per-frame MotionFieldEstimator)
     TorsoAppearanceFeatureExtractor                      (torso_appearance.py: the torso network's AppearanceFeatureExtractor)
+    torso_model_forward, torso_seg_input, torso_mask_volume (torso_forward.py: the torso model's forward over the three, its two glue kernels)
     render_clip_sharded                                  (frames.py: frame sharding + RCCL gather)
 All compute goes through libr3d_hip.so (include/r3d_hip.h); there is no eager/CPU fallback.
 """
@@ -37,6 +38,10 @@ def __getattr__(name):      # lazy: importing the package (e.g. for synth) must 
     if name == "TorsoAppearanceFeatureExtractor":
         from . import torso_appearance as m
         return m.AppearanceFeatureExtractor
+    if name in ("torso_model_forward", "torso_seg_input", "torso_mask_volume"):
+        import importlib
+        m = importlib.import_module(".torso_forward", __name__)          # the submodule's name is not an attribute this function serves
+        return getattr(m, {"torso_model_forward": "forward", "torso_seg_input": "seg_input", "torso_mask_volume": "mask_volume"}[name])
     if name in ("render_clip_sharded", "shard_frames"):
         from . import frames as m
         return getattr(m, name)

@@ -87,6 +87,8 @@ SIGNATURES = {
     "r3d_torso_conv_pool": (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, P, c_int, c_int, c_int, c_float, c_int, P, c_int, P]),
     "r3d_torso_conv_split": (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, P, c_int, c_int, c_int, c_float, c_int, P, c_int, P]),
     "r3d_torso_conv3d_res": (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, P, c_float, P, P, c_int, c_int, c_int, c_float, P, P, P, c_int, P]),
+    "r3d_torso_seg_input": (c_int, [P, c_int, c_int, P, c_int, c_int, c_int, c_int, c_int, P, c_int, c_int, P]),
+    "r3d_torso_mask_volume": (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P]),
 }
 
 

@@ -544,3 +544,39 @@ def synth_torso_appearance_inputs(seed, N=1, in_dim=3, H=256, W=256):
             else:
                 x[n, c] = np.clip(1.0 / (1.0 + np.exp(-6.0 * (0.5 - np.hypot(xx - 0.1 * n, yy + 0.2 * (c - 3))))) + 0.1 * noise, 0.0, 1.0)
     return {"x": x}
+
+
+def synth_torso_glue_inputs(seed, N=1, Cs=6, Hs=512, Ws=512, C=32, D=16, h=64, w=64):
+    """Inputs of the glue of WarpBasedTorsoModelMediaPipe.forward (facev2v_warp/model2.py:231-236): segmap [N, Cs, Hs, Ws] in [0, 1] (per
+    class a soft blob + noise, so that the resized pair, their sum and its dilation all vary over the image) and the extractor's volume
+    feats [N, C, D, h, w], unit variance.  Every sample differs."""
+    ly, lx = np.linspace(-1.0, 1.0, Hs, dtype=np.float32), np.linspace(-1.0, 1.0, Ws, dtype=np.float32)
+    yy, xx = np.meshgrid(ly, lx, indexing="ij")
+    seg = np.empty((N, Cs, Hs, Ws), np.float32)
+    for n in range(N):
+        for c in range(Cs):
+            cx, cy = 0.8 * hash_uniform(seed, 2, stream=300 + 16 * n + c) - 0.4
+            blob = 1.0 / (1.0 + np.exp(-5.0 * (0.45 - np.hypot(xx - cx, yy - cy))))
+            seg[n, c] = np.clip(0.6 * blob + 0.12 * hash_unitvar(seed, (Hs, Ws), stream=400 + 16 * n + c), 0.0, 1.0)
+    return {"segmap": seg, "feats": hash_unitvar(seed, (N, C, D, h, w), stream=500)}
+
+
+def synth_torso_onehot_segmap(seed, N=1, Cs=6, Hs=512, Ws=512, centres=10, specks=24, ratio=8, torso=(2, 4)):
+    """A one-hot segmap [N, Cs, Hs, Ws] whose label image consists of blobs: the class of the nearest of `centres` points, point i of
+    class i % Cs, plus `specks` single pixels of class torso[0] outside the torso classes, on rows and columns that a resize by the even
+    integer `ratio` reads (they resize to 1/4, which the dilation then spreads where no blob is near).  At such a ratio every bilinear
+    weight is 1/2, so fp32 evaluates the glue of facev2v_warp/model2.py:231-236 exactly."""
+    ly, lx = np.linspace(0.0, 1.0, Hs, dtype=np.float32), np.linspace(0.0, 1.0, Ws, dtype=np.float32)
+    yy, xx = np.meshgrid(ly, lx, indexing="ij")
+    seg = np.zeros((N, Cs, Hs, Ws), np.float32)
+    for n in range(N):
+        p = hash_uniform(seed, 2 * centres, stream=600 + n).reshape(centres, 2)
+        label = np.argmin([np.hypot(xx - px, yy - py) for px, py in p], axis=0) % Cs
+        q = hash_uniform(seed, 2 * specks, stream=700 + n).reshape(specks, 2)
+        for qy, qx in q:
+            y, x = int(qy * Hs) // ratio * ratio + ratio // 2 - 1, int(qx * Ws) // ratio * ratio + ratio // 2 - 1
+            if label[y, x] not in torso:
+                label[y, x] = torso[0]
+        for c in range(Cs):
+            seg[n, c] = label == c
+    return seg

@@ -120,8 +120,7 @@ class AppearanceFeatureExtractor(nn.Module):
                                    "x": e(px // 16 * C * DEPTH), "h": e(px // 16 * C * DEPTH)}
         return w
 
-    @torch.no_grad()
-    def forward(self, x):
+    def _run(self, x, channel_last):
         x = _check_f32(x, "AppearanceFeatureExtractor input", 4)
         N, cin, H, W = x.shape
         if cin != self.in_dim or N < 1 or H < 4 or W < 4 or H % 4 or W % 4:
@@ -134,15 +133,27 @@ class AppearanceFeatureExtractor(nn.Module):
         _conv_pool(w["a0"], N, H, W, DOWN[0], F["down"][0], w["a1"], pr)
         _conv_pool(w["a1"], N, H // 2, W // 2, DOWN[1], F["down"][1], w["a2"], pr)
         _conv_split(w["a2"], N, h4, w4, DOWN[2], F["mid"], DEPTH, w["x"], pr)
-        out = torch.empty(N, C, DEPTH, h4, w4, device=dev, dtype=torch.float32)
+        out = None if channel_last else torch.empty(N, C, DEPTH, h4, w4, device=dev, dtype=torch.float32)
         X, Hb = w["x"], w["h"]
         for i in range(N_RES):
             _conv3d_res(X, N, DEPTH, h4, w4, C, F["res"][2 * i], None, Hb, None, pr)
-            if i < N_RES - 1:
+            if i < N_RES - 1 or channel_last:
                 _conv3d_res(Hb, N, DEPTH, h4, w4, C, F["res"][2 * i + 1], X, X, None, pr)
             else:
                 _conv3d_res(Hb, N, DEPTH, h4, w4, C, F["res"][2 * i + 1], X, None, out, pr)
-        return out
+        return X.view(N, DEPTH, h4, w4, C) if channel_last else out
+
+    @torch.no_grad()
+    def forward(self, x):
+        return self._run(x, False)
+
+    @torch.no_grad()
+    def forward_cl(self, x):
+        """forward(x) as the channel-last volume [N, 16, H / 4, W / 4, 32] (bit for bit r3d_torso_volume_to_cl of forward's result): the
+        same 16 launches, the last of which writes only its channel-last y, and no NCDHW store.  x [N, in_dim, H, W] as for forward, for
+        instance the tensor r3d_torso_seg_input assembled.  The result is the module's work buffer of this (device, stream, N, H, W): the
+        next call with that key overwrites it, so consume it on the same stream before calling again (torso_forward.py does)."""
+        return self._run(x, True)
 
     @classmethod
     def from_reference(cls, ref, precision=F32):

@@ -238,6 +238,20 @@ class Generator(nn.Module):
         return self._decode(warped, False, N, H, W, return_hid)
 
     @torch.no_grad()
+    def forward_cl(self, fs_cl, deformation, occlusion=None, return_hid=False):
+        """forward with the appearance volume already channel-last, fs_cl [N, 16, H, W, 32] (what r3d_torso_volume_to_cl makes of forward's
+        fs, for instance r3d_torso_mask_volume's masked_cl): straight to r3d_torso_warp, without the transpose and without _VOLUME_CL."""
+        cl, grid = _check_f32(fs_cl, "fs_cl", 5), _check_f32(deformation, "deformation", 5)
+        N, D, H, W, C = cl.shape
+        if C != self.input_channels or D != self.depth or tuple(grid.shape) != (N, D, H, W, 3):
+            raise ValueError("Generator: expected fs_cl [N, %d, H, W, %d] and deformation [N, %d, H, W, 3], got %s and %s"
+                             % (self.depth, self.input_channels, self.depth, tuple(cl.shape), tuple(grid.shape)))
+        warped = self._buffers_for(N, H, W, cl.device)["warp"]
+        _lib.check(_lib.load().r3d_torso_warp(_lib.ptr(cl), N, C, D, H, W, _lib.ptr(grid), D, H, W, _lib.ptr(warped), 1, _lib.stream_ptr()),
+                   "torso_warp")
+        return self._decode(warped, False, N, H, W, return_hid)
+
+    @torch.no_grad()
     def forward_with_deformed_feature(self, deformed_fs, occlusion=None, return_hid=False):
         x = _check_f32(deformed_fs, "deformed_fs", 4)
         N, C, H, W = x.shape

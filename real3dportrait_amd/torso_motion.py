@@ -181,28 +181,48 @@ class MotionFieldEstimator(nn.Module):
 
     @torch.no_grad()
     def forward(self, fs, kp_s, kp_d, Rs, Rd, tgt_head_img, tgt_head_weights):
+        return self._run(fs, False, kp_s, kp_d, Rs, Rd, None, tgt_head_img, tgt_head_weights)
+
+    @torch.no_grad()
+    def forward_cl(self, fs_cl, kp_s, kp_d, Rs, Rd, tgt_head_img, tgt_head_weights, J=None):
+        """forward with the volume already channel-last, fs_cl [N, 16, 64, 64, C] (what r3d_torso_volume_to_cl makes of forward's fs, for
+        instance r3d_torso_mask_volume's motion_cl): r3d_torso_volume_to_cl is skipped, everything after it is forward's.  J [N, 3, 3]:
+        jacobian(Rs, Rd) if the caller holds it already (Rs and Rd may then be None)."""
+        return self._run(fs_cl, True, kp_s, kp_d, Rs, Rd, J, tgt_head_img, tgt_head_weights)
+
+    def _run(self, fs, channel_last, kp_s, kp_d, Rs, Rd, J, tgt_head_img, tgt_head_weights):
         K, C, D, S = self.num_keypoints, self.input_channels, DEPTH, GRID
         fs = _check_f32(fs, "fs", 5)
         N = fs.shape[0]
         img, wts = _check_f32(tgt_head_img, "tgt_head_img", 4), _check_f32(tgt_head_weights, "tgt_head_weights", 4)
         kp_s, kp_d = _check_f32(kp_s, "kp_s", 3), _check_f32(kp_d, "kp_d", 3)
-        Rs, Rd = _check_f32(Rs, "Rs", 3), _check_f32(Rd, "Rd", 3)
-        if tuple(fs.shape) != (N, C, D, S, S) or tuple(img.shape) != (N, 3, HEAD, HEAD) or tuple(wts.shape) != (N, 1, HEAD, HEAD):
-            raise ValueError("MotionFieldEstimator: expected fs [N, %d, %d, %d, %d], tgt_head_img [N, 3, %d, %d] and tgt_head_weights "
+        want = (N, D, S, S, C) if channel_last else (N, C, D, S, S)
+        if tuple(fs.shape) != want or tuple(img.shape) != (N, 3, HEAD, HEAD) or tuple(wts.shape) != (N, 1, HEAD, HEAD):
+            raise ValueError("MotionFieldEstimator: expected fs %s, tgt_head_img [N, 3, %d, %d] and tgt_head_weights "
                              "[N, 1, %d, %d] (network2.py:220-222), got %s, %s and %s"
-                             % (C, D, S, S, HEAD, HEAD, HEAD, HEAD, tuple(fs.shape), tuple(img.shape), tuple(wts.shape)))
-        if tuple(kp_s.shape) != (N, K, 3) or tuple(kp_d.shape) != (N, K, 3) or tuple(Rs.shape) != (N, 3, 3) or tuple(Rd.shape) != (N, 3, 3):
-            raise ValueError("MotionFieldEstimator: expected kp_s, kp_d [N, %d, 3] and Rs, Rd [N, 3, 3], got %s, %s, %s and %s"
-                             % (K, tuple(kp_s.shape), tuple(kp_d.shape), tuple(Rs.shape), tuple(Rd.shape)))
+                             % (("[N, %d, %d, %d, %d]" % want[1:]), HEAD, HEAD, HEAD, HEAD, tuple(fs.shape), tuple(img.shape), tuple(wts.shape)))
+        if J is None:
+            Rs, Rd = _check_f32(Rs, "Rs", 3), _check_f32(Rd, "Rd", 3)
+            if tuple(Rs.shape) != (N, 3, 3) or tuple(Rd.shape) != (N, 3, 3):
+                raise ValueError("MotionFieldEstimator: expected Rs, Rd [N, 3, 3], got %s and %s" % (tuple(Rs.shape), tuple(Rd.shape)))
+            J = jacobian(Rs, Rd)
+        else:
+            J = _check_f32(J, "J", 3)
+            if tuple(J.shape) != (N, 3, 3):
+                raise ValueError("MotionFieldEstimator: expected J [N, 3, 3], got %s" % (tuple(J.shape),))
+        if tuple(kp_s.shape) != (N, K, 3) or tuple(kp_d.shape) != (N, K, 3):
+            raise ValueError("MotionFieldEstimator: expected kp_s, kp_d [N, %d, 3], got %s and %s" % (K, tuple(kp_s.shape), tuple(kp_d.shape)))
         dev = fs.device
         F, w = self._prepare(), self._buffers_for(N, dev)
         lib, P, st = _lib.load(), _lib.ptr, _lib.stream_ptr()
         cp, pr = _pad4(5 * (K + 1)), self.precision
         fcs = cp + 2 * HID
-        J = jacobian(Rs, Rd)
         # the hourglass input, also the first channel group of the fuser's input
-        _lib.check(lib.r3d_torso_volume_to_cl(P(fs), N, C, D, S, S, P(w["fs"]), st), "torso_volume_to_cl")
-        _lib.check(lib.r3d_torso_motion_input(P(w["fs"]), N, C, D, S, S, P(F["compress"]["w"]), P(F["compress"]["b"]), P(kp_s), P(kp_d), P(J),
+        fs_cl = fs
+        if not channel_last:
+            fs_cl = w["fs"]
+            _lib.check(lib.r3d_torso_volume_to_cl(P(fs), N, C, D, S, S, P(fs_cl), st), "torso_volume_to_cl")
+        _lib.check(lib.r3d_torso_motion_input(P(fs_cl), N, C, D, S, S, P(F["compress"]["w"]), P(F["compress"]["b"]), P(kp_s), P(kp_d), P(J),
                                               K, P(w["inp"]), cp, P(w["fuse"]), fcs, st), "torso_motion_input")
         # the hourglass; its last conv writes the second group
         x, cin, size = w["inp"], cp, S

@@ -181,7 +181,7 @@ def _reference_hparams(model):
 
 
 def patch_model(model, fuse_warp_sr=True, precision=None, secc_encoder=False, torso_generator=False, torso_motion=False, torso_precision=None,
-                torso_appearance=False):
+                torso_appearance=False, torso_forward=False):
     """Swap the hot-path operators of a constructed reference model for the HIP ones (in place).  INFERENCE ONLY: the HIP modules
     detach their inputs and build no autograd graph (the reference runs this path under torch.no_grad(), real3d_infer.py:435,479).
     precision: SR precision of the installed blocks (None = the library default 'f16mx': inside the 2e-4 of SURVEY 8(d) on every golden and heavy-tail sweep,
@@ -217,6 +217,15 @@ def patch_model(model, fuse_warp_sr=True, precision=None, secc_encoder=False, to
       every product on the fp32 matrix instruction (the exact tier, the default and the recommendation); 'bf16x3' = each operand split into
       three bf16 pieces and six piece products summed in fp32, fp32-class, no range state.  Given without torso_generator, torso_motion or
       torso_appearance it is a ValueError, as is an unknown name.
+    * torso_forward=True (opt-in; needs torso_appearance=True, torso_motion=True and torso_generator=True, anything else is a
+      ValueError): model.superresolution.torso_model.forward (facev2v_warp/model2.py:222-287) -> torso_forward.py's forward of this
+      package, with the reference's signature and `ret`: the glue of model2.py:226-236 in two HIP launches (r3d_torso_seg_input,
+      r3d_torso_mask_volume) and the appearance volume channel-last from the extractor to the estimator and the generator, 64 library
+      launches per call.  rgb_alpha or not is read from the installed extractor's input width; torso_kp_num, torso_mask_dilate_ksize and
+      mul_torso_mask from torso_model.hparams.  Still torch: the key-point index select, cat([tgt_head_img, tgt_head_weights]) inside the
+      estimator, the interpolate + cat in front of occlusion_2_predictor, and the losses.  Every call computes everything; nothing is
+      cached across calls.  If one of the three swaps was refused for this model, forward is left as it is; infer_forward_stage1 / 2
+      always are.  The reference's forward stays reachable as torso_model._r3d_reference_forward.
     Parameters are copied with strict key matching; the decoder module is left untouched (the renderer reads
     decoder.net[0|2].{weight,bias} directly)."""
     import types
@@ -224,6 +233,9 @@ def patch_model(model, fuse_warp_sr=True, precision=None, secc_encoder=False, to
     if torso_precision is not None and not (torso_generator or torso_motion or torso_appearance):
         raise ValueError("patch_model: torso_precision=%r needs torso_generator=True, torso_motion=True or torso_appearance=True" % (torso_precision,))
     torso_precision = check_precision(F32 if torso_precision is None else torso_precision, "patch_model: torso_precision")
+    if torso_forward and not (torso_appearance and torso_motion and torso_generator):
+        raise ValueError("patch_model: torso_forward=True needs torso_appearance=True, torso_motion=True and torso_generator=True (got %r, %r, %r): "
+                         "it drives the three HIP modules" % (torso_appearance, torso_motion, torso_generator))
     dev = next(model.parameters()).device
     hp = _reference_hparams(model)
     old_r = model.renderer
@@ -284,6 +296,13 @@ def patch_model(model, fuse_warp_sr=True, precision=None, secc_encoder=False, to
         tm = getattr(model.superresolution, "torso_model", None)
         if tm is not None and tap.is_reference_appearance_extractor(getattr(tm, "appearance_extractor", None)):
             tm.appearance_extractor = tap.AppearanceFeatureExtractor.from_reference(tm.appearance_extractor, torso_precision)
+    if torso_forward:
+        from . import torso_forward as tf
+        tm = getattr(model.superresolution, "torso_model", None)
+        if tm is not None and tf.supported(tm):
+            tm._r3d_torso_forward = tf.TorsoForwardState()
+            tm._r3d_reference_forward = tm.forward
+            tm.forward = types.MethodType(tf.forward, tm)
     for owner in (getattr(model, "secc_img2plane_backbone", None), getattr(model, "img2plane_backbone", None)):
         _patch_sequential(owner, "to_plane_cnn", dev)       # per-frame plane producer tail (segformer.py:691-700)
     from .superresolution import set_sr_precision
