@@ -329,9 +329,6 @@ static int launch_layernorm(const float* x, int M, int C, const float* gam, cons
 using namespace r3d;
 using namespace r3d::seg;
 
-// [a, a + na) and [b, b + nb) (counts of floats) share an element
-static bool overlap(const float* a, size_t na, const float* b, size_t nb) { return a < b + nb && b < a + na; }
-
 extern "C" int r3d_secc_embed1(const float* x, int B, int in_dim, int H, int W, const float* prenet_w, const float* prenet_b,
                                const float* w, const float* bias, const float* ln_g, const float* ln_b, float* y, r3d_stream_t stream)
 {

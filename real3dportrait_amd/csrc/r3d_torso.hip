@@ -15,10 +15,11 @@
 //                        channel-last input, 16-byte loads; otherwise one element per load (NCHW input, Cin = 65, 3, 1).
 //   torso_bf3::torso_conv<...>  the same tiles with the products on the BF16X3 tier (r3d_torso_conv_prec), and
 //   torso_bf3::torso_split      that tier's split of a plain array (r3d_torso_split_bf16x3, for the tests).
+// r3d_torso_conv / _prec describe their call and hand it, with this unit's kernel family, to the argument check, the tile table and the
+// launcher all seven torso conv entry points share (r3d_torso_launch.h).
 #include "r3d_common.h"
-#include "r3d_torso_conv.h"
+#include "r3d_torso_launch.h"
 #include <math.h>
-#include <initializer_list>
 
 namespace r3d {
 namespace torso {
@@ -113,36 +114,22 @@ __global__ void __launch_bounds__(256) torso_split(const float* x, size_t n, uin
 
 namespace torso {
 
-template <int PREC, bool VEC, int WM, int WN, int TM, int TN>
-static void launch_conv(ConvArgs g, hipStream_t st)
-{
-    constexpr int BM = WM * TM * 16, BN = WN * TN * 16;
-    g.ntn = (g.Cout + BN - 1) / BN;
-    const long long nblk = (long long)((g.M + BM - 1) / BM) * g.ntn;
-    if constexpr (PREC == tconv::BF16X3) hipLaunchKernelGGL((torso_bf3::torso_conv<VEC, WM, WN, TM, TN>), dim3((unsigned)nblk), dim3(256), 0, st, g);
-    else hipLaunchKernelGGL((torso_conv<VEC, WM, WN, TM, TN>), dim3((unsigned)nblk), dim3(256), 0, st, g);
-}
-
-// the tile follows Cout: 64 x 64 (pixels x channels) or 32 x 64, 128 x 32 up to 32 channels, 128 x 16 up to 16 (out_conv's 3, the predictor's 1)
-// (32 x 64 where 64 x 64 tiles would give the 256 CUs fewer than two blocks each: the 64^2 layers, one wave per SIMD otherwise)
-template <int PREC>
-static void dispatch_conv(const ConvArgs& g, bool vec, hipStream_t st)
-{
-    const long long big = (long long)((g.M + 63) / 64) * ((g.Cout + 63) / 64);
-    if (g.Cout > 32 && big < 512) { if (vec) launch_conv<PREC, true, 2, 2, 1, 2>(g, st); else launch_conv<PREC, false, 2, 2, 1, 2>(g, st); }
-    else if (g.Cout > 32) { if (vec) launch_conv<PREC, true, 2, 2, 2, 2>(g, st); else launch_conv<PREC, false, 2, 2, 2, 2>(g, st); }
-    else if (g.Cout > 16) { if (vec) launch_conv<PREC, true, 4, 1, 2, 2>(g, st); else launch_conv<PREC, false, 4, 1, 2, 2>(g, st); }
-    else { if (vec) launch_conv<PREC, true, 4, 1, 2, 1>(g, st); else launch_conv<PREC, false, 4, 1, 2, 1>(g, st); }
-}
+// this unit's kernel family for tlaunch::run (r3d_torso_launch.h): the 2-D body
+struct Family {
+    static constexpr bool tile64x16 = false;
+    template <int PREC, bool VEC, int WM, int WN, int TM, int TN>
+    static void (*kernel())(ConvArgs)
+    {
+        if constexpr (PREC == tconv::BF16X3) return torso_bf3::torso_conv<VEC, WM, WN, TM, TN>;
+        else return torso_conv<VEC, WM, WN, TM, TN>;
+    }
+};
 
 }  // namespace torso
 }  // namespace r3d
 
 using namespace r3d;
 using namespace r3d::torso;
-
-// [a, a + na) and [b, b + nb) (counts of floats) share an element
-static bool overlap(const float* a, size_t na, const float* b, size_t nb) { return a < b + nb && b < a + na; }
 
 extern "C" int r3d_torso_volume_to_cl(const float* fs, int N, int C, int D, int H, int W, float* out, r3d_stream_t stream)
 {
@@ -169,57 +156,21 @@ extern "C" int r3d_torso_warp(const float* fs_cl, int N, int C, int D, int H, in
     return check_launch("torso_warp");
 }
 
-static int torso_conv_impl(const float* x, int B, int Hs, int Ws, int Cin, int in_nchw, int upsample, const float* pro_scale,
-                           const float* pro_shift, float pro_slope, const float* w, const float* bias, int Cout, int ksize, int act,
-                           float act_slope, const float* residual, float* y, float* y_nchw, int precision, r3d_stream_t stream)
+extern "C" int r3d_torso_conv_prec(const float* x, int B, int Hs, int Ws, int Cin, int in_nchw, int upsample, const float* pro_scale,
+                                   const float* pro_shift, float pro_slope, const float* w, const float* bias, int Cout, int ksize, int act,
+                                   float act_slope, const float* residual, float* y, float* y_nchw, int precision, r3d_stream_t stream)
 {
-    if (precision != R3D_TORSO_F32 && precision != R3D_TORSO_BF16X3)
-        { set_error("torso_conv: precision %d is not 0 (R3D_TORSO_F32) or 1 (R3D_TORSO_BF16X3)", precision); return R3D_ERR_INVALID_ARG; }
-    if (!x || !w || (!y && !y_nchw) || (!pro_scale) != (!pro_shift)) { set_error("torso_conv: NULL pointer"); return R3D_ERR_INVALID_ARG; }
-    if (B <= 0 || Hs <= 0 || Ws <= 0 || Cin <= 0 || Cout <= 0 || Cin > 4096 || Cout > 4096)
-        { set_error("torso_conv: bad argument (B, Hs, Ws > 0, 1 <= Cin, Cout <= 4096)"); return R3D_ERR_INVALID_ARG; }
-    if (ksize != 1 && ksize != 3 && ksize != 7) { set_error("torso_conv: ksize %d is not 1, 3 or 7", ksize); return R3D_ERR_INVALID_ARG; }
-    if (upsample != 0 && upsample != 1) { set_error("torso_conv: upsample %d is not 0 or 1", upsample); return R3D_ERR_INVALID_ARG; }
-    if (act < 0 || act > 2) { set_error("torso_conv: act %d is not 0 (none), 1 (leaky) or 2 (sigmoid)", act); return R3D_ERR_INVALID_ARG; }
-    const int H = Hs << upsample, W = Ws << upsample;
-    if ((double)B * H * W > 2147483647.0 || (double)B * H * W * (Cin > Cout ? Cin : Cout) > 9.0e18)
-        { set_error("torso_conv: more than 2^31 - 1 output pixels"); return R3D_ERR_INVALID_ARG; }
-    const size_t nin = (size_t)B * Hs * Ws * Cin, nout = (size_t)B * H * W * Cout, nw = (size_t)Cout * ksize * ksize * Cin;
-    for (float* o : {y, y_nchw}) {
-        if (!o) continue;
-        if (overlap(o, nout, x, nin) || overlap(o, nout, w, nw) || (bias && overlap(o, nout, bias, Cout)) ||
-            (pro_scale && (overlap(o, nout, pro_scale, Cin) || overlap(o, nout, pro_shift, Cin))))
-            { set_error("torso_conv: an output overlaps x, w, bias or the prologue"); return R3D_ERR_INVALID_ARG; }
-        if (residual && residual != y && overlap(o, nout, residual, nout))
-            { set_error("torso_conv: an output overlaps the residual without y being the residual"); return R3D_ERR_INVALID_ARG; }
-    }
-    if (y && y_nchw && overlap(y, nout, y_nchw, nout)) { set_error("torso_conv: y and y_nchw overlap"); return R3D_ERR_INVALID_ARG; }
-    hipStream_t st = (hipStream_t)stream;
-    ConvArgs g = {};
-    g.x = x; g.B = B; g.Hs = Hs; g.Ws = Ws; g.Cin = Cin; g.H = H; g.W = W; g.up = upsample; g.in_nchw = in_nchw ? 1 : 0; g.ks = ksize;
-    g.ps = pro_scale; g.pt = pro_shift; g.pslope = pro_slope; g.w = w; g.Cout = Cout; g.bias = bias; g.act = act; g.slope = act_slope;
-    g.res = residual; g.y = y; g.y_nchw = y_nchw; g.M = B * H * W; g.K = ksize * ksize * Cin;
-    auto aligned = [](const void* p) { return p == nullptr || ((uintptr_t)p & 15) == 0; };
-    const bool vec = !in_nchw && Cin % 4 == 0 && aligned(x) && aligned(w) && aligned(pro_scale) && aligned(pro_shift);
-    if (precision == R3D_TORSO_BF16X3) dispatch_conv<tconv::BF16X3>(g, vec, st);
-    else dispatch_conv<tconv::F32>(g, vec, st);
-    return check_launch("torso_conv");
+    tlaunch::ConvCall c = tlaunch::conv_call(x, B, Hs, Ws, Cin, w, bias, Cout, ksize, act, act_slope, y, precision);
+    c.in_nchw = in_nchw; c.upsample = upsample; c.ps = pro_scale; c.pt = pro_shift; c.pslope = pro_slope; c.res = residual; c.yn = y_nchw;
+    return tlaunch::run<Family>("torso_conv", c, stream);
 }
 
 extern "C" int r3d_torso_conv(const float* x, int B, int Hs, int Ws, int Cin, int in_nchw, int upsample, const float* pro_scale,
                               const float* pro_shift, float pro_slope, const float* w, const float* bias, int Cout, int ksize, int act,
                               float act_slope, const float* residual, float* y, float* y_nchw, r3d_stream_t stream)
 {
-    return torso_conv_impl(x, B, Hs, Ws, Cin, in_nchw, upsample, pro_scale, pro_shift, pro_slope, w, bias, Cout, ksize, act, act_slope, residual,
-                           y, y_nchw, R3D_TORSO_F32, stream);
-}
-
-extern "C" int r3d_torso_conv_prec(const float* x, int B, int Hs, int Ws, int Cin, int in_nchw, int upsample, const float* pro_scale,
-                                   const float* pro_shift, float pro_slope, const float* w, const float* bias, int Cout, int ksize, int act,
-                                   float act_slope, const float* residual, float* y, float* y_nchw, int precision, r3d_stream_t stream)
-{
-    return torso_conv_impl(x, B, Hs, Ws, Cin, in_nchw, upsample, pro_scale, pro_shift, pro_slope, w, bias, Cout, ksize, act, act_slope, residual,
-                           y, y_nchw, precision, stream);
+    return r3d_torso_conv_prec(x, B, Hs, Ws, Cin, in_nchw, upsample, pro_scale, pro_shift, pro_slope, w, bias, Cout, ksize, act, act_slope,
+                               residual, y, y_nchw, R3D_TORSO_F32, stream);
 }
 
 extern "C" int r3d_torso_split_bf16x3(const float* x, size_t n, uint16_t* h, uint16_t* m, uint16_t* l, r3d_stream_t stream)

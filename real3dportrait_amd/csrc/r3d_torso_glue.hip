@@ -164,9 +164,6 @@ __global__ void __launch_bounds__(256) mask_volume(MaskArgs a)
 using namespace r3d;
 using namespace r3d::tglue;
 
-// [a, a + na) and [b, b + nb) (counts of floats) share an element
-static bool overlap(const float* a, size_t na, const float* b, size_t nb) { return a < b + nb && b < a + na; }
-
 extern "C" int r3d_torso_seg_input(const float* img, int N, int Ci, const float* segmap, int Cs, int Hs, int Ws, int c0, int c1, float* out,
                                    int OH, int OW, r3d_stream_t stream)
 {

@@ -9,8 +9,10 @@
 //   motion_deform                softmax over the K + 1 mask logits and the mask-weighted sum of the sparse motions, one thread per voxel.
 //   motion_broadcast             the 2-D head features repeated over depth into their slice of the fuser's input.
 // The sparse motions (the identity grid for k = 0, J (grid - kp_d[k]) + kp_s[k] for k >= 1) are never stored: both small kernels recompute them.
+// r3d_torso_conv3d / _prec describe their call and hand it, with this unit's kernel family, to the shared check, tile table and launcher
+// (r3d_torso_launch.h).
 #include "r3d_common.h"
-#include "r3d_torso_conv.h"
+#include "r3d_torso_launch.h"
 #include <math.h>
 
 namespace r3d {
@@ -33,28 +35,16 @@ __global__ void __launch_bounds__(256) conv3d(tconv::ConvArgs g) { tconv::conv_t
 
 namespace tmotion {
 
-template <int PREC, bool VEC, int WM, int WN, int TM, int TN>
-static void launch_conv3d(ConvArgs g, hipStream_t st)
-{
-    constexpr int BM = WM * TM * 16, BN = WN * TN * 16;
-    g.ntn = (g.Cout + BN - 1) / BN;
-    g.ntm = (g.M + BM - 1) / BM;
-    const long long nblk = (long long)g.ntm * g.ntn;
-    if constexpr (PREC == tconv::BF16X3) hipLaunchKernelGGL((tmotion_bf3::conv3d<VEC, WM, WN, TM, TN>), dim3((unsigned)nblk), dim3(256), 0, st, g);
-    else hipLaunchKernelGGL((conv3d<VEC, WM, WN, TM, TN>), dim3((unsigned)nblk), dim3(256), 0, st, g);
-}
-
-// the tile follows Cout as in r3d_torso_conv; up to 16 channels a 64 x 16 tile where 128 x 16 ones would leave most CUs without a block
-template <int PREC>
-static void dispatch_conv3d(const ConvArgs& g, bool vec, hipStream_t st)
-{
-    const long long big = (long long)((g.M + 63) / 64) * ((g.Cout + 63) / 64);
-    if (g.Cout > 32 && big < 512) { if (vec) launch_conv3d<PREC, true, 2, 2, 1, 2>(g, st); else launch_conv3d<PREC, false, 2, 2, 1, 2>(g, st); }
-    else if (g.Cout > 32) { if (vec) launch_conv3d<PREC, true, 2, 2, 2, 2>(g, st); else launch_conv3d<PREC, false, 2, 2, 2, 2>(g, st); }
-    else if (g.Cout > 16) { if (vec) launch_conv3d<PREC, true, 4, 1, 2, 2>(g, st); else launch_conv3d<PREC, false, 4, 1, 2, 2>(g, st); }
-    else if ((g.M + 127) / 128 < 256) { if (vec) launch_conv3d<PREC, true, 4, 1, 1, 1>(g, st); else launch_conv3d<PREC, false, 4, 1, 1, 1>(g, st); }
-    else { if (vec) launch_conv3d<PREC, true, 4, 1, 2, 1>(g, st); else launch_conv3d<PREC, false, 4, 1, 2, 1>(g, st); }
-}
+// this unit's kernel family for tlaunch::run (r3d_torso_launch.h): the 3-D body
+struct Family {
+    static constexpr bool tile64x16 = true;
+    template <int PREC, bool VEC, int WM, int WN, int TM, int TN>
+    static void (*kernel())(ConvArgs)
+    {
+        if constexpr (PREC == tconv::BF16X3) return tmotion_bf3::conv3d<VEC, WM, WN, TM, TN>;
+        else return conv3d<VEC, WM, WN, TM, TN>;
+    }
+};
 
 struct MotionArgs {
     const float* fs; int N, C, D, H, W;          // [N, D, H, W, C]
@@ -199,71 +189,21 @@ __global__ void __launch_bounds__(256) motion_broadcast(const float* feats, int 
 using namespace r3d;
 using namespace r3d::tmotion;
 
-// [a, a + na) and [b, b + nb) (counts of floats) share an element
-static bool overlap(const float* a, size_t na, const float* b, size_t nb) { return a < b + nb && b < a + na; }
-
-static int torso_conv3d_impl(const float* x, int B, int D, int Hs, int Ws, int Cin, int upsample, const float* w, const float* bias,
-                             int Cout, int ksize, int full_depth, int act, float act_slope, int pool, float* y, int y_cstride,
-                             int y_coffset, float* y_ncdhw, int precision, r3d_stream_t stream)
+extern "C" int r3d_torso_conv3d_prec(const float* x, int B, int D, int Hs, int Ws, int Cin, int upsample, const float* w, const float* bias,
+                                     int Cout, int ksize, int full_depth, int act, float act_slope, int pool, float* y, int y_cstride,
+                                     int y_coffset, float* y_ncdhw, int precision, r3d_stream_t stream)
 {
-    if (precision != R3D_TORSO_F32 && precision != R3D_TORSO_BF16X3)
-        { set_error("torso_conv3d: precision %d is not 0 (R3D_TORSO_F32) or 1 (R3D_TORSO_BF16X3)", precision); return R3D_ERR_INVALID_ARG; }
-    if (!x || !w || (!y && !y_ncdhw)) { set_error("torso_conv3d: NULL pointer"); return R3D_ERR_INVALID_ARG; }
-    if (B <= 0 || D <= 0 || Hs <= 0 || Ws <= 0 || Cin <= 0 || Cout <= 0 || Cin > 4096 || Cout > 4096 || D > 1024)
-        { set_error("torso_conv3d: bad argument (B, Hs, Ws > 0, 1 <= D <= 1024, 1 <= Cin, Cout <= 4096)"); return R3D_ERR_INVALID_ARG; }
-    if (ksize != 1 && ksize != 3 && ksize != 7) { set_error("torso_conv3d: ksize %d is not 1, 3 or 7", ksize); return R3D_ERR_INVALID_ARG; }
-    if (upsample != 0 && upsample != 1) { set_error("torso_conv3d: upsample %d is not 0 or 1", upsample); return R3D_ERR_INVALID_ARG; }
-    if (act < 0 || act > 2) { set_error("torso_conv3d: act %d is not 0 (none), 1 (leaky) or 2 (sigmoid)", act); return R3D_ERR_INVALID_ARG; }
-    if ((pool != 0 && pool != 1) || (full_depth != 0 && full_depth != 1))
-        { set_error("torso_conv3d: pool %d / full_depth %d is not 0 or 1", pool, full_depth); return R3D_ERR_INVALID_ARG; }
-    const int H = Hs << upsample, W = Ws << upsample, Do = full_depth ? 1 : D, kd = full_depth ? D : ksize;
-    if (pool && (H % 2 || W % 2)) { set_error("torso_conv3d: pooling an odd size (%d x %d)", H, W); return R3D_ERR_INVALID_ARG; }
-    if (pool && (y_ncdhw || !y)) { set_error("torso_conv3d: the pooled output is channel-last only (y, not y_ncdhw)"); return R3D_ERR_INVALID_ARG; }
-    if (y && (y_coffset < 0 || y_cstride < y_coffset + Cout))
-        { set_error("torso_conv3d: channel slice [%d, %d + %d) does not fit rows of %d", y_coffset, y_coffset, Cout, y_cstride); return R3D_ERR_INVALID_ARG; }
-    if ((double)B * Do * H * W > 2147483647.0 || (double)B * D * H * W * (Cin > Cout ? Cin : Cout) > 9.0e18 ||
-        (double)B * Do * H * W * (y ? y_cstride : 1) > 9.0e18)
-        { set_error("torso_conv3d: more than 2^31 - 1 output positions"); return R3D_ERR_INVALID_ARG; }
-    const size_t nin = (size_t)B * D * Hs * Ws * Cin, nw = (size_t)Cout * kd * ksize * ksize * Cin;
-    const size_t rows = (size_t)B * Do * (H >> pool) * (W >> pool), ny = rows * (size_t)(y ? y_cstride : 0), nyn = rows * Cout;
-    for (int o = 0; o < 2; ++o) {
-        const float* p = o ? y_ncdhw : y;
-        const size_t np = o ? nyn : ny;
-        if (!p) continue;
-        if (overlap(p, np, x, nin) || overlap(p, np, w, nw) || (bias && overlap(p, np, bias, Cout)))
-            { set_error("torso_conv3d: an output overlaps x, w or bias"); return R3D_ERR_INVALID_ARG; }
-    }
-    if (y && y_ncdhw && overlap(y, ny, y_ncdhw, nyn)) { set_error("torso_conv3d: y and y_ncdhw overlap"); return R3D_ERR_INVALID_ARG; }
-    hipStream_t st = (hipStream_t)stream;
-    ConvArgs g = {};
-    g.x = x; g.B = B; g.Hs = Hs; g.Ws = Ws; g.Cin = Cin; g.H = H; g.W = W; g.up = upsample; g.ks = ksize;
-    g.w = w; g.Cout = Cout; g.bias = bias; g.act = act; g.slope = act_slope; g.y = y; g.y_nchw = y_ncdhw;
-    g.D = D; g.Do = Do; g.kd = kd; g.padz = full_depth ? 0 : ksize / 2; g.pool = pool; g.ycs = y_cstride; g.yco = y_coffset;
-    g.M = B * Do * H * W; g.K = kd * ksize * ksize * Cin;
-    // fewer positions than output channels (down.4, up.0: 256 voxels under 57 MB of weights): the tiles that share a slab of weights run
-    // next to each other on one XCD, so the slab comes from HBM once
-    g.mfast = g.M < Cout;
-    auto aligned = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
-    const bool vec = Cin % 4 == 0 && aligned(x) && aligned(w);
-    if (precision == R3D_TORSO_BF16X3) dispatch_conv3d<tconv::BF16X3>(g, vec, st);
-    else dispatch_conv3d<tconv::F32>(g, vec, st);
-    return check_launch("torso_conv3d");
+    tlaunch::ConvCall c = tlaunch::conv_call(x, B, Hs, Ws, Cin, w, bias, Cout, ksize, act, act_slope, y, precision);
+    c.D = D; c.volume = true; c.upsample = upsample; c.full_depth = full_depth; c.pool = pool; c.ycs = y_cstride; c.yco = y_coffset; c.yn = y_ncdhw;
+    return tlaunch::run<Family>("torso_conv3d", c, stream);
 }
 
 extern "C" int r3d_torso_conv3d(const float* x, int B, int D, int Hs, int Ws, int Cin, int upsample, const float* w, const float* bias,
                                 int Cout, int ksize, int full_depth, int act, float act_slope, int pool, float* y, int y_cstride,
                                 int y_coffset, float* y_ncdhw, r3d_stream_t stream)
 {
-    return torso_conv3d_impl(x, B, D, Hs, Ws, Cin, upsample, w, bias, Cout, ksize, full_depth, act, act_slope, pool, y, y_cstride, y_coffset,
-                             y_ncdhw, R3D_TORSO_F32, stream);
-}
-
-extern "C" int r3d_torso_conv3d_prec(const float* x, int B, int D, int Hs, int Ws, int Cin, int upsample, const float* w, const float* bias,
-                                     int Cout, int ksize, int full_depth, int act, float act_slope, int pool, float* y, int y_cstride,
-                                     int y_coffset, float* y_ncdhw, int precision, r3d_stream_t stream)
-{
-    return torso_conv3d_impl(x, B, D, Hs, Ws, Cin, upsample, w, bias, Cout, ksize, full_depth, act, act_slope, pool, y, y_cstride, y_coffset,
-                             y_ncdhw, precision, stream);
+    return r3d_torso_conv3d_prec(x, B, D, Hs, Ws, Cin, upsample, w, bias, Cout, ksize, full_depth, act, act_slope, pool, y, y_cstride, y_coffset,
+                                 y_ncdhw, R3D_TORSO_F32, stream);
 }
 
 static int motion_common(const char* what, const float* kp_s, const float* kp_d, const float* J, int N, int D, int H, int W, int K)

@@ -19,6 +19,7 @@ import torch
 
 from . import _lib
 from .superresolution import (_BoundMeter, _f32c, _keep_tags, _tag, blend_cat, bound_of, chain_fold, const_bound, resize_bilinear)
+from .torso_layers import _Cached
 
 
 import os
@@ -56,19 +57,6 @@ def person_occlusion(alpha, torso_occlusion, head_threshold):
 def _measured(t, S):
     """Tag a (clip-constant) fp32 activation with its MEASURED max|x| (its own tensor, not a meter slot that later calls reuse)."""
     return _tag(t, _BoundMeter()(t).clone(), 0)
-
-
-class _Cached:
-    """value = fn(tensor), recomputed only when `tensor` is another object or was modified in place (the entry holds the tensor)."""
-
-    def __init__(self):
-        self._src, self._ver, self._val = None, None, None
-
-    def get(self, t, fn):
-        if self._src is not t or self._ver != t._version:
-            self._val = fn(t)
-            self._src, self._ver = t, t._version
-        return self._val
 
 
 class WarpSRState:

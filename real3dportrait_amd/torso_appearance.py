@@ -10,15 +10,15 @@ WarpBasedTorsoModelMediaPipe.forward calls the module on every frame (model2.py:
 does this one: every call computes, nothing is cached across calls.
 INFERENCE ONLY (eval semantics: BatchNorm on its running statistics, no spectral norm: use_weight_norm=False); inputs are detached and no
 autograd graph is built.  The BatchNorms are folded into the conv weights, biases and prologue vectors in fp64 once per parameter version
-(_prepare), where mid_conv's rows are also put in the depth-major order of r3d_torso_conv_split.
+(_prepare), where mid_conv's rows are also put in the depth-major order of r3d_torso_conv_split.  The building blocks, the two BatchNorm
+folds, the module base (_prepare, work buffers, from_reference) and the launch wrappers are torso_layers.py's.
 """
 import torch
 import torch.nn as nn
 
-from . import _lib
-from .torso_precision import F32, PRECISIONS, check_precision
-from .torso_generator import BN_EPS, LEAKY, NONE, _check_f32, _conv, _kernel_weight, _params_key, bn_affine64
-from .torso_motion import _ConvBlock, _kernel_weight3d
+from .torso_layers import (LEAKY, NONE, _check_f32, _conv, _conv3d_res, _conv_pool, _conv_split, _ConvBlock, _kernel_weight, _kernel_weight3d,
+                           _ResBlock, _TorsoModule, conv_layer, conv_weight64, fold_cna, fold_res_pair)
+from .torso_precision import F32
 
 C, DEPTH, DOWN, N_RES = 32, 16, (64, 128, 256), 6          # network2.py:27-30
 LAUNCHES = 16          # library launches per forward: in_conv, two pooled convs, mid_conv, twelve Conv3d (DESIGN 4.12)
@@ -30,12 +30,6 @@ class _DownBlock2D(nn.Module):
         self.layers = nn.Sequential(_ConvBlock(2, "CNA", cin, cout, 3), nn.AvgPool2d((2, 2)))
 
 
-class _ResBlock3D(nn.Module):
-    def __init__(self, c):
-        super().__init__()
-        self.layers = nn.Sequential(_ConvBlock(3, "NAC", c, c, 3), _ConvBlock(3, "NAC", c, c, 3))
-
-
 def fold_appearance(m, dtype=torch.float32):
     """The extractor's convolutions as kernel calls, folded in fp64 and rounded once to `dtype` (float64: the fold itself, for the tests).
     A dict:  in_conv: one r3d_torso_conv layer in fold_generator's format;  down: two r3d_torso_conv_pool layers (w [Cout, 3, 3, Cin], b;
@@ -43,82 +37,43 @@ def fold_appearance(m, dtype=torch.float32):
     reference's channel c 16 + d;  res: twelve r3d_torso_conv3d_res layers (w [32, 3, 3, 3, 32], b, ps / pt or None, act, res)."""
     f = lambda v: None if v is None else v.to(dtype).contiguous()
     d64 = lambda p: p.detach().double()
-    s, t = bn_affine64(m.in_conv.bn)
-    F = {"in_conv": {"w": _kernel_weight(d64(m.in_conv.conv.weight) * s[:, None, None, None], dtype), "b": f(d64(m.in_conv.conv.bias) * s + t),
-                     "ps": None, "pt": None, "k": 7, "up": 0, "act": LEAKY, "slope": 0.0, "res": False},
-         "down": [], "res": []}
+    F = {"in_conv": conv_layer(*fold_cna(m.in_conv, conv_weight64), 7, dtype, act=LEAKY), "down": [], "res": []}
     for blk in m.down:
-        cb = blk.layers[0]
-        s, t = bn_affine64(cb.bn)
-        F["down"].append({"w": _kernel_weight(d64(cb.conv.weight) * s[:, None, None, None], dtype), "b": f(d64(cb.conv.bias) * s + t)})
+        w, b = fold_cna(blk.layers[0], conv_weight64)
+        F["down"].append({"w": _kernel_weight(w, dtype), "b": f(b)})
     cin = m.mid_conv.in_channels
     F["mid"] = {"w": _kernel_weight(d64(m.mid_conv.weight).view(m.C, m.D, cin, 1, 1).transpose(0, 1).reshape(m.C * m.D, cin, 1, 1), dtype),
                 "b": f(d64(m.mid_conv.bias).view(m.C, m.D).t().reshape(-1))}
     for blk in m.res:
-        a, b = blk.layers[0], blk.layers[1]
-        s1, t1 = bn_affine64(a.bn)
-        s2, t2 = bn_affine64(b.bn)
-        # the first conv's only reader is the second block's BatchNorm + ReLU: they go into its rows, bias and epilogue
-        F["res"].append({"w": _kernel_weight3d(d64(a.conv.weight) * s2[:, None, None, None, None], dtype), "b": f(d64(a.conv.bias) * s2 + t2),
-                         "ps": f(s1), "pt": f(t1), "act": LEAKY, "res": False})
-        F["res"].append({"w": _kernel_weight3d(d64(b.conv.weight), dtype), "b": f(d64(b.conv.bias)), "ps": None, "pt": None, "act": NONE,
-                         "res": True})
+        (w1, b1, ps, pt), (w2, b2) = fold_res_pair(blk.layers[0], blk.layers[1], conv_weight64)
+        F["res"] += [{"w": _kernel_weight3d(w1, dtype), "b": f(b1), "ps": f(ps), "pt": f(pt), "act": LEAKY, "res": False},
+                     {"w": _kernel_weight3d(w2, dtype), "b": f(b2), "ps": None, "pt": None, "act": NONE, "res": True}]
     return F
 
 
-def _conv_pool(x, B, Hs, Ws, cin, L, y, precision):
-    P = _lib.ptr
-    _lib.check(_lib.load().r3d_torso_conv_pool(P(x), B, Hs, Ws, cin, 0, P(L["w"]), P(L["b"]), L["w"].shape[0], 3, LEAKY, 0.0, 1, P(y),
-                                               PRECISIONS[precision], _lib.stream_ptr()), "torso_conv_pool")
-
-
-def _conv_split(x, B, Hs, Ws, cin, L, depth, y, precision):
-    P = _lib.ptr
-    _lib.check(_lib.load().r3d_torso_conv_split(P(x), B, Hs, Ws, cin, 0, P(L["w"]), P(L["b"]), L["w"].shape[0], 1, NONE, 0.0, depth, P(y),
-                                                PRECISIONS[precision], _lib.stream_ptr()), "torso_conv_split")
-
-
-def _conv3d_res(x, B, D, Hs, Ws, cin, L, res, y, y_ncdhw, precision):
-    P = _lib.ptr
-    _lib.check(_lib.load().r3d_torso_conv3d_res(P(x), B, D, Hs, Ws, cin, P(L["ps"]), P(L["pt"]), 0.0, P(L["w"]), P(L["b"]), L["w"].shape[0], 3,
-                                                L["act"], 0.0, P(res), P(y), P(y_ncdhw), PRECISIONS[precision], _lib.stream_ptr()),
-               "torso_conv3d_res")
-
-
-class AppearanceFeatureExtractor(nn.Module):
+class AppearanceFeatureExtractor(_TorsoModule):
     """network2.py:16-45.  forward(x [N, in_dim, H, W]) -> [N, 32, 16, H / 4, W / 4] (fp32, contiguous NCDHW: what the glue of
     model2.py:231-236 consumes).  The module is fully convolutional; H and W are multiples of 4 (two 2 x 2 pools)."""
 
     def __init__(self, in_dim=3, model_scale="standard", lora_args=None, precision=F32):
-        super().__init__()
-        self.precision = check_precision(precision, "AppearanceFeatureExtractor: precision")
+        super().__init__(precision)
         if lora_args is not None:
             raise NotImplementedError("AppearanceFeatureExtractor: lora_args has no HIP implementation (got %r)" % (lora_args,))
         self.in_dim = in_dim
         self.in_conv = _ConvBlock(2, "CNA", in_dim, DOWN[0], 7)
         self.down = nn.Sequential(*[_DownBlock2D(DOWN[i], DOWN[i + 1]) for i in range(len(DOWN) - 1)])
         self.mid_conv = nn.Conv2d(DOWN[-1], C * DEPTH, 1, 1, 0)
-        self.res = nn.Sequential(*[_ResBlock3D(C) for _ in range(N_RES)])
+        self.res = nn.Sequential(*[_ResBlock(3, C) for _ in range(N_RES)])
         self.C, self.D = C, DEPTH
-        self._derived_key, self._derived = None, None
-        self._work = {}          # (device, stream, N, H, W) -> activation buffers: two streams in flight never share one
 
-    def _prepare(self):
-        key = _params_key(self)
-        if key != self._derived_key:
-            with torch.no_grad():
-                self._derived_key, self._derived = key, fold_appearance(self)
-        return self._derived
+    def _fold(self):
+        return fold_appearance(self)
 
-    def _buffers_for(self, N, H, W, dev):
-        key = (dev, _lib.stream_ptr(), N, H, W)
-        w = self._work.get(key)
-        if w is None:
-            e = lambda n: torch.empty(n, device=dev, dtype=torch.float32)
-            px = N * H * W
-            w = self._work[key] = {"a0": e(px * DOWN[0]), "a1": e(px // 4 * DOWN[1]), "a2": e(px // 16 * DOWN[2]),
-                                   "x": e(px // 16 * C * DEPTH), "h": e(px // 16 * C * DEPTH)}
-        return w
+    def _new_buffers(self, dev, N, H, W):
+        e = lambda n: torch.empty(n, device=dev, dtype=torch.float32)
+        px = N * H * W
+        return {"a0": e(px * DOWN[0]), "a1": e(px // 4 * DOWN[1]), "a2": e(px // 16 * DOWN[2]), "x": e(px // 16 * C * DEPTH),
+                "h": e(px // 16 * C * DEPTH)}
 
     def _run(self, x, channel_last):
         x = _check_f32(x, "AppearanceFeatureExtractor input", 4)
@@ -127,7 +82,7 @@ class AppearanceFeatureExtractor(nn.Module):
             raise ValueError("AppearanceFeatureExtractor: expected [N, %d, H, W] with H and W positive multiples of 4, got %s"
                              % (self.in_dim, tuple(x.shape)))
         dev = x.device
-        F, w, pr = self._prepare(), self._buffers_for(N, H, W, dev), self.precision
+        F, w, pr = self._prepare(), self._buffers_for(dev, N, H, W), self.precision
         h4, w4 = H // 4, W // 4
         _conv(x, N, H, W, cin, F["in_conv"], y=w["a0"], in_nchw=True, precision=pr)
         _conv_pool(w["a0"], N, H, W, DOWN[0], F["down"][0], w["a1"], pr)
@@ -155,12 +110,9 @@ class AppearanceFeatureExtractor(nn.Module):
         next call with that key overwrites it, so consume it on the same stream before calling again (torso_forward.py does)."""
         return self._run(x, True)
 
-    @classmethod
-    def from_reference(cls, ref, precision=F32):
-        """A HIP copy of a constructed reference AppearanceFeatureExtractor (strict key copy)."""
-        m = cls(in_dim=ref.in_conv.layers[0].in_channels, precision=precision)
-        m.load_state_dict(ref.state_dict(), strict=True)
-        return m.to(next(ref.parameters()).device).eval()
+    @staticmethod
+    def _reference_args(ref):
+        return {"in_dim": ref.in_conv.layers[0].in_channels}
 
 
 def is_reference_appearance_extractor(m):

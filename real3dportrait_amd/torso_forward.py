@@ -16,14 +16,15 @@ patch_model(model, torso_appearance=True, torso_motion=True, torso_generator=Tru
 torso model.  Every call computes everything: nothing is kept from one call to the next but work buffers and that constant.
 Still torch: the key-point index select (:238-243), cat([tgt_head_img, tgt_head_weights]) inside the estimator, the interpolate + cat in
 front of the predictor, and the losses.  The three gradient-scaling lines (:251-257, x 0.1 + x.detach() 0.9) are the identity in value up
-to one rounding and are not evaluated: INFERENCE ONLY, inputs are detached and no autograd graph is built.
+to one rounding and are not evaluated: INFERENCE ONLY, inputs are detached and no autograd graph is built.  What the modules share is
+torso_layers.py; this file uses the three through their public forward_cl only.
 """
 import torch
 import torch.nn.functional as F
 
 from . import _lib
 from .torso_appearance import LAUNCHES as EXTRACTOR_LAUNCHES
-from .torso_generator import _check_f32
+from .torso_layers import _check_f32
 from .torso_motion import jacobian
 
 SEG_CHANNELS = (2, 4)          # model2.py:227,231: the torso classes of the segmap (tasks/eg3ds/loss_utils/segment_loss/mp_segmenter.py)

@@ -10,34 +10,18 @@ torso_precision.py (the motion input, the deformation, the resizes and the folds
 names and its 129 state_dict keys, so a reference checkpoint loads with strict=True.
 INFERENCE ONLY (eval semantics: BatchNorm on its running statistics); inputs are detached and no autograd graph is built.  The BatchNorms
 are folded into the conv weights, biases and prologue vectors in fp64 once per parameter version (_prepare), where the channel groups
-are also padded to multiples of 4 and the occlusion weights permuted to the kernel's full-depth form.
+are also padded to multiples of 4 and the occlusion weights permuted to the kernel's full-depth form.  The building blocks, the two
+BatchNorm folds, the module base (_prepare, work buffers, from_reference) and the launch wrappers are torso_layers.py's.
 """
 import torch
 import torch.nn as nn
 
 from . import _lib
-from .torso_precision import F32, PRECISIONS, check_precision
-from .torso_generator import BN_EPS, LEAKY, NONE, SIGMOID, _check_f32, _conv, _kernel_weight, _params_key, bn_affine64
+from .torso_layers import (LEAKY, SIGMOID, _check_f32, _conv, _conv3d, _ConvBlock, _kernel_weight3d, _pad4, _ResBlock, _TorsoModule, conv_layer,
+                           conv_weight64, fold_cna, fold_res_pair)
+from .torso_precision import F32
 
 DEPTH, GRID, HEAD, HID = 16, 64, 256, 32          # the feature volume [N, C, 16, 64, 64], the head image 256^2, tgt_head_hid_dim
-
-
-def _pad4(c):
-    return (c + 3) // 4 * 4
-
-
-class _ConvBlock(nn.Module):
-    """ConvBlock2D / ConvBlock3D (layers.py:6-55) without weight norm and with SyncBatchNorm: `layers` holds the modules in the pattern's order."""
-
-    def __init__(self, dim, pattern, cin, cout, k):
-        super().__init__()
-        self.pattern = pattern
-        conv, norm = (nn.Conv2d, nn.BatchNorm2d) if dim == 2 else (nn.Conv3d, nn.BatchNorm3d)
-        mods = {"C": conv(cin, cout, k, 1, k // 2), "N": norm(cout if pattern.find("C") < pattern.find("N") else cin, eps=BN_EPS), "A": nn.ReLU()}
-        self.layers = nn.Sequential(*[mods[c] for c in pattern])
-
-    conv = property(lambda self: self.layers[self.pattern.index("C")])
-    bn = property(lambda self: self.layers[self.pattern.index("N")])
 
 
 class _DownBlock3D(nn.Module):
@@ -52,26 +36,6 @@ class _UpBlock3D(nn.Module):
         self.layers = nn.Sequential(nn.Upsample(scale_factor=(1, 2, 2)), _ConvBlock(3, "CNA", cin, cout, 3))
 
 
-class _ResBlock2D(nn.Module):
-    def __init__(self, c):
-        super().__init__()
-        self.layers = nn.Sequential(_ConvBlock(2, "NAC", c, c, 3), _ConvBlock(2, "NAC", c, c, 3))
-
-
-def _kernel_weight3d(w64, dtype, groups=None):
-    """[Cout, Cin, kd, kh, kw] fp64 -> the kernel's [Cout, kd, kh, kw, Cin'] in `dtype`; groups: the sizes of the input's channel groups,
-    each padded with zero columns to a multiple of 4 (default: the whole input as one group)."""
-    w = w64.permute(0, 2, 3, 4, 1)
-    parts, c0 = [], 0
-    for c in groups or [w.shape[-1]]:
-        parts.append(w[..., c0:c0 + c])
-        if _pad4(c) != c:
-            parts.append(w.new_zeros(w.shape[:-1] + (_pad4(c) - c,)))
-        c0 += c
-    assert c0 == w.shape[-1]
-    return torch.cat(parts, dim=-1).contiguous().to(dtype)
-
-
 def fold_motion(m, dtype=torch.float32):
     """The estimator's convolutions as kernel calls, folded in fp64 and rounded once to `dtype` (float64: the fold itself, for the tests).
     A dict:  compress (w [4, C], b);  enc: tgt_head_encoder as seven r3d_torso_conv layers in fold_generator's format;  down / up: five
@@ -83,25 +47,14 @@ def fold_motion(m, dtype=torch.float32):
     cm = 5 * (K + 1)
     F = {"compress": {"w": f(d64(m.compress.weight).reshape(4, -1)), "b": f(d64(m.compress.bias))}, "enc": [], "down": [], "up": []}
 
-    def layer2d(w, b, k, ps=None, pt=None, act=NONE, res=False):
-        F["enc"].append({"w": _kernel_weight(w, dtype), "b": f(b), "ps": f(ps), "pt": f(pt), "k": k, "up": 0, "act": act, "slope": 0.0, "res": res})
-
-    first = m.tgt_head_encoder[0]
-    s, t = bn_affine64(first.bn)
-    layer2d(d64(first.conv.weight) * s[:, None, None, None], d64(first.conv.bias) * s + t, 7, act=LEAKY)
+    F["enc"].append(conv_layer(*fold_cna(m.tgt_head_encoder[0], conv_weight64), 7, dtype, act=LEAKY))
     for blk in list(m.tgt_head_encoder)[1:]:
-        a, b = blk.layers[0], blk.layers[1]
-        s1, t1 = bn_affine64(a.bn)
-        s2, t2 = bn_affine64(b.bn)
-        # the first conv's only reader is the second block's BatchNorm + ReLU: they go into its rows, bias and epilogue
-        layer2d(d64(a.conv.weight) * s2[:, None, None, None], d64(a.conv.bias) * s2 + t2, 3, ps=s1, pt=t1, act=LEAKY)
-        layer2d(d64(b.conv.weight), d64(b.conv.bias), 3, res=True)
+        (w1, b1, ps, pt), (w2, b2) = fold_res_pair(blk.layers[0], blk.layers[1], conv_weight64)
+        F["enc"] += [conv_layer(w1, b1, 3, dtype, ps=ps, pt=pt, act=LEAKY), conv_layer(w2, b2, 3, dtype, res=True)]
     for name, seq, pos in (("down", m.down, 0), ("up", m.up, 1)):
         for blk in seq:
-            cb = blk.layers[pos]
-            s, t = bn_affine64(cb.bn)
-            w = d64(cb.conv.weight) * s[:, None, None, None, None]
-            F[name].append({"w": _kernel_weight3d(w, dtype), "b": f(d64(cb.conv.bias) * s + t)})
+            w, b = fold_cna(blk.layers[pos], conv_weight64)
+            F[name].append({"w": _kernel_weight3d(w, dtype), "b": f(b)})
     F["fuser"] = {"w": _kernel_weight3d(d64(m.tgt_head_fuser.weight), dtype, [cm, HID, HID]), "b": f(d64(m.tgt_head_fuser.bias))}
     F["mask"] = {"w": _kernel_weight3d(d64(m.mask_conv.weight), dtype), "b": f(d64(m.mask_conv.bias))}
     # Conv2d over x.view(N, 32 D, H, W), channel c D + d  ->  [2, D, 7, 7, 32]
@@ -119,26 +72,13 @@ def jacobian(Rs, Rd):
     return (Rs[:, :, :, None] * inv[:, None, :, :]).sum(dim=2).contiguous()
 
 
-def _conv3d(x, B, D, Hs, Ws, cin, L, k, y, ycs=None, yco=0, up=0, act=NONE, pool=0, full_depth=0, y_ncdhw=None, precision=F32):
-    """One r3d_torso_conv3d launch; a tier other than 'f32' goes through r3d_torso_conv3d_prec."""
-    P = _lib.ptr
-    cout = L["w"].shape[0]
-    args = (P(x), B, D, Hs, Ws, cin, up, P(L["w"]), P(L["b"]), cout, k, full_depth, act, 0.0, pool, P(y), cout if ycs is None else ycs, yco,
-            P(y_ncdhw))
-    if precision == F32:
-        _lib.check(_lib.load().r3d_torso_conv3d(*args, _lib.stream_ptr()), "torso_conv3d")
-    else:
-        _lib.check(_lib.load().r3d_torso_conv3d_prec(*args, PRECISIONS[precision], _lib.stream_ptr()), "torso_conv3d_prec")
-
-
-class MotionFieldEstimator(nn.Module):
+class MotionFieldEstimator(_TorsoModule):
     """network2.py:162-244.  forward(fs [N, C, 16, 64, 64], kp_s [N, K, 3], kp_d [N, K, 3], Rs [N, 3, 3], Rd [N, 3, 3], tgt_head_img
     [N, 3, 256, 256], tgt_head_weights [N, 1, 256, 256]) -> (deformation [N, 16, 64, 64, 3], occlusion [N, 1, 64, 64], occlusion_2
     [N, 1, 64, 64]).  The reference fixes these sizes (its resizes to 128^2 and 64^2, :220-222); others raise ValueError."""
 
     def __init__(self, model_scale="standard", input_channels=34, num_keypoints=4, predict_multiref_occ=True, precision=F32):
-        super().__init__()
-        self.precision = check_precision(precision, "MotionFieldEstimator: precision")
+        super().__init__(precision)
         if model_scale not in ("standard", "large") or not predict_multiref_occ:
             raise NotImplementedError("MotionFieldEstimator: only model_scale 'standard' with predict_multiref_occ has a HIP implementation "
                                       "(network2.py:177-183,232-236; got %r, predict_multiref_occ=%r)" % (model_scale, predict_multiref_occ))
@@ -148,36 +88,25 @@ class MotionFieldEstimator(nn.Module):
         self.compress = nn.Conv3d(input_channels, 4, 1, 1, 0)
         self.down = nn.Sequential(*[_DownBlock3D(down[i], down[i + 1]) for i in range(5)])
         self.up = nn.Sequential(*[_UpBlock3D(up[i], up[i + 1]) for i in range(5)])
-        self.tgt_head_encoder = nn.Sequential(_ConvBlock(2, "CNA", 4, HID, 7), *[_ResBlock2D(HID) for _ in range(3)])
+        self.tgt_head_encoder = nn.Sequential(_ConvBlock(2, "CNA", 4, HID, 7), *[_ResBlock(2, HID) for _ in range(3)])
         self.tgt_head_fuser = nn.Conv3d(HID + down[0] + up[-1], HID, 7, 1, 3)
         self.mask_conv = nn.Conv3d(HID, K + 1, 7, 1, 3)
         self.occlusion_conv = nn.Conv2d(HID * DEPTH, 1, 7, 1, 3)
         self.occlusion_conv2 = nn.Conv2d(HID * DEPTH, 1, 7, 1, 3)
         self.C, self.D = down[0] + up[-1], DEPTH
-        self._derived_key, self._derived = None, None
-        self._work = {}          # (device, stream, N) -> activation buffers: two streams in flight never share one
 
-    def _prepare(self):
-        key = _params_key(self)
-        if key != self._derived_key:
-            with torch.no_grad():
-                self._derived_key, self._derived = key, fold_motion(self)
-        return self._derived
+    def _fold(self):
+        return fold_motion(self)
 
-    def _buffers_for(self, N, dev):
-        key = (dev, _lib.stream_ptr(), N)
-        w = self._work.get(key)
-        if w is None:
-            e = lambda *n: torch.empty(*n, device=dev, dtype=torch.float32)
-            cp = _pad4(5 * (self.num_keypoints + 1))
-            vox = N * DEPTH * GRID * GRID
-            w = self._work[key] = {
-                "fs": e(vox * self.input_channels), "inp": e(vox * cp), "fuse": e(vox * (cp + 2 * HID)),
+    def _new_buffers(self, dev, N):
+        e = lambda *n: torch.empty(*n, device=dev, dtype=torch.float32)
+        cp = _pad4(5 * (self.num_keypoints + 1))
+        vox = N * DEPTH * GRID * GRID
+        return {"fs": e(vox * self.input_channels), "inp": e(vox * cp), "fuse": e(vox * (cp + 2 * HID)),
                 "down": [e(N * DEPTH * (GRID >> (i + 1)) ** 2 * c) for i, c in enumerate((64, 128, 256, 512, 1024))],
                 "up": [e(N * DEPTH * (4 << i) ** 2 * c) for i, c in enumerate((512, 256, 128, 64))],
                 "head": e(N, 4, 128, 128), "e0": e(N * 128 * 128 * HID), "e1": e(N * 128 * 128 * HID), "feats": e(N, HID, 128, 128),
                 "feats64": e(N, HID, GRID, GRID), "x": e(vox * HID), "mask": e(vox * (self.num_keypoints + 1))}
-        return w
 
     @torch.no_grad()
     def forward(self, fs, kp_s, kp_d, Rs, Rd, tgt_head_img, tgt_head_weights):
@@ -213,7 +142,7 @@ class MotionFieldEstimator(nn.Module):
         if tuple(kp_s.shape) != (N, K, 3) or tuple(kp_d.shape) != (N, K, 3):
             raise ValueError("MotionFieldEstimator: expected kp_s, kp_d [N, %d, 3], got %s and %s" % (K, tuple(kp_s.shape), tuple(kp_d.shape)))
         dev = fs.device
-        F, w = self._prepare(), self._buffers_for(N, dev)
+        F, w = self._prepare(), self._buffers_for(dev, N)
         lib, P, st = _lib.load(), _lib.ptr, _lib.stream_ptr()
         cp, pr = _pad4(5 * (K + 1)), self.precision
         fcs = cp + 2 * HID
@@ -256,12 +185,9 @@ class MotionFieldEstimator(nn.Module):
         _conv3d(w["x"], N, D, S, S, HID, F["occ"], 7, None, act=SIGMOID, full_depth=1, y_ncdhw=occ, precision=pr)
         return deformation, occ[:, 0:1].contiguous(), occ[:, 1:2].contiguous()
 
-    @classmethod
-    def from_reference(cls, ref, precision=F32):
-        """A HIP copy of a constructed reference MotionFieldEstimator at standard scale (strict key copy)."""
-        m = cls(input_channels=ref.compress.in_channels, num_keypoints=ref.mask_conv.out_channels - 1, precision=precision)
-        m.load_state_dict(ref.state_dict(), strict=True)
-        return m.to(next(ref.parameters()).device).eval()
+    @staticmethod
+    def _reference_args(ref):          # a constructed reference MotionFieldEstimator at standard scale
+        return {"input_channels": ref.compress.in_channels, "num_keypoints": ref.mask_conv.out_channels - 1}
 
 
 def is_reference_motion_estimator(m):

@@ -160,6 +160,77 @@ def test_sr_resampling_and_image_op_argument_errors():
     assert lib.r3d_person_occlusion(one, None, 0.5, 16, one, None) == -1
 
 
+def test_torso_conv_argument_errors():
+    """What the seven torso conv entry points refuse before any launch: rc -1 and a message with the entry point's name (the _prec
+    variants report the base name) and the rule.  Every call has exactly one defect; the pointers are fake, 1 TiB apart and never
+    dereferenced.  Rejected calls only: a valid one would launch (tests/test_gpu_torso_*_ops.py run those)."""
+    from real3dportrait_amd import _lib
+    lib = _lib.load()
+    X, W, BIAS, Y, YN, PS, PT, RES = (i << 40 for i in range(1, 9))
+    base = dict(x=X, B=1, D=2, Hs=4, Ws=4, Cin=8, in_nchw=0, up=0, ps=None, pt=None, w=W, bias=BIAS, Cout=8, k=3, full=0, act=1, pool=0,
+                depth=1, res=None, y=Y, ycs=None, yco=0, yn=None, prec=0)
+
+    def call(fn, **over):
+        a = dict(base, **over)
+        ycs = a["Cout"] if a["ycs"] is None else a["ycs"]
+        conv = (a["x"], a["B"], a["Hs"], a["Ws"], a["Cin"], a["in_nchw"], a["up"], a["ps"], a["pt"], 0.0, a["w"], a["bias"], a["Cout"], a["k"],
+                a["act"], 0.0, a["res"], a["y"], a["yn"])
+        conv3d = (a["x"], a["B"], a["D"], a["Hs"], a["Ws"], a["Cin"], a["up"], a["w"], a["bias"], a["Cout"], a["k"], a["full"], a["act"], 0.0,
+                  a["pool"], a["y"], ycs, a["yco"], a["yn"])
+        flat = (a["x"], a["B"], a["Hs"], a["Ws"], a["Cin"], a["in_nchw"], a["w"], a["bias"], a["Cout"], a["k"], a["act"], 0.0)
+        args = {"conv": conv + (None,), "conv_prec": conv + (a["prec"], None), "conv3d": conv3d + (None,), "conv3d_prec": conv3d + (a["prec"], None),
+                "conv_pool": flat + (a["pool"], a["y"], a["prec"], None), "conv_split": flat + (a["depth"], a["y"], a["prec"], None),
+                "conv3d_res": (a["x"], a["B"], a["D"], a["Hs"], a["Ws"], a["Cin"], a["ps"], a["pt"], 0.0, a["w"], a["bias"], a["Cout"], a["k"],
+                               a["act"], 0.0, a["res"], a["y"], a["yn"], a["prec"], None)}[fn]
+        rc = getattr(lib, "r3d_torso_" + fn)(*args)
+        return rc, lib.r3d_last_error()
+
+    def refused(fns, quote, **over):
+        for fn in fns.split():
+            rc, msg = call(fn, **over)
+            name = ("torso_" + fn[:-5] if fn.endswith("_prec") else "torso_" + fn).encode()
+            assert rc == -1 and name + b":" in msg and quote in msg, (fn, over, rc, msg)
+        return msg
+
+    ALL = "conv conv_prec conv3d conv3d_prec conv_pool conv_split conv3d_res"
+    TWO_OUT, D3, PREC = "conv conv_prec conv3d conv3d_prec conv3d_res", "conv3d conv3d_prec conv3d_res", "conv_prec conv3d_prec conv_pool conv_split conv3d_res"
+    refused(ALL, b"NULL pointer", x=None)
+    refused(ALL, b"NULL pointer", w=None)
+    refused(ALL, b"NULL pointer", y=None)                                       # no output pointer at all
+    refused("conv conv_prec conv3d_res", b"NULL pointer", ps=PS)                # pro_scale without pro_shift
+    refused("conv conv_prec conv3d_res", b"NULL pointer", pt=PT)
+    refused(ALL, b"bad argument", B=0)
+    refused(ALL, b"bad argument", Cin=0)
+    refused(ALL, b"bad argument", Cout=4097)
+    refused(D3, b"bad argument", D=1025)
+    refused(ALL, b"ksize 5", k=5)
+    refused("conv conv_prec conv3d conv3d_prec", b"upsample 2", up=2)
+    refused(ALL, b"act 3", act=3)
+    refused(PREC, b"precision 2", prec=2)
+    refused("conv3d conv3d_prec conv_pool", b"pool", pool=2)
+    refused("conv3d conv3d_prec", b"pool", full=2)
+    refused("conv3d conv3d_prec conv_pool", b"odd size", pool=1, Hs=3)          # a 3 x 4 grid
+    refused("conv3d conv3d_prec", b"channel-last only", pool=1, yn=YN)
+    refused("conv3d conv3d_prec", b"channel-last only", pool=1, y=None, yn=YN)
+    refused("conv3d conv3d_prec", b"channel slice", yco=-1)
+    refused("conv3d conv3d_prec", b"channel slice", ycs=11, yco=4)
+    refused("conv_split", b"multiple of depth", Cout=10, depth=4)
+    refused("conv_split", b"multiple of depth", depth=0)
+    refused(ALL, b"2^31", B=32768, D=1, Hs=256, Ws=256, Cin=1, Cout=1)          # 2^31 output positions
+    refused(ALL, b"overlap", y=X)
+    refused(ALL, b"overlap", y=W)
+    refused(TWO_OUT, b"overlap", yn=Y + 4)
+    refused(TWO_OUT, b"overlap", y=None, yn=X)
+    refused("conv conv_prec conv3d_res", b"residual", res=Y + 4)                # overlaps y without being y
+    # a rule that does not apply to an entry point stays not applying: the call is refused for its one defect, which is checked later
+    refused("conv conv_prec conv_pool conv_split", b"act 3", Hs=1025, D=1025, act=3)            # the 2-D entry points have no D to limit
+    refused("conv_split", b"act 3", Cout=2050, depth=1025, act=3)                               # nor does the split's depth have that limit
+    refused("conv3d conv3d_prec conv_pool", b"overlap", pool=0, Hs=3, y=X)                     # odd sizes are fine without the pool
+    refused("conv3d conv3d_prec", b"overlap", y=None, yco=-1, yn=X)                             # no y: no channel slice
+    assert b"residual" not in refused("conv conv_prec conv3d_res", b"overlap", res=Y, yn=Y + 4)  # the residual may be y itself
+    refused("conv3d conv3d_prec", b"overlap", full=1, D=1024, y=None, yn=X)                     # full depth: D depth taps, one output depth
+
+
 def test_product_has_no_oracle_dependency():
     """The oracle is test infrastructure: nothing under real3dportrait_amd/ may import or load it."""
     pkg = os.path.join(ROOT, "real3dportrait_amd")
