@@ -17,7 +17,7 @@
 //  * the stride-2 transposed conv runs as 4 output phases with 4/2/2/1 taps (9 tap-GEMMs per 4 output
 //    pixels: no multiply-by-zero work), followed by a fused FIR4x4 + bias + lrelu kernel;
 //  * modulation/demodulation is a per-forward packing kernel (no host sync, any ws), not a grouped conv.
-#include "r3d_sr_common.h"
+#include "r3d_sr_launch.h"
 
 namespace r3d {
 
@@ -657,10 +657,7 @@ extern "C" int r3d_sr_block_forward(const void* prepacked, const void* styles, i
         set_error("sr_block_forward: bad argument"); return R3D_ERR_INVALID_ARG;
     }
     if (!up && precision == R3D_SR_F32) { set_error("sr_block_forward: up=0 (SynthesisBlockNoUp) needs R3D_SR_F16X3"); return R3D_ERR_INVALID_ARG; }
-    {   // the kernels index one sample's activation with 32 bits
-        const size_t ohw = (size_t)(up ? 4 : 1) * Hin * Win, cmax = (size_t)(Cin > Cout ? Cin : Cout);
-        if (cmax * ohw >= ((size_t)1 << 32)) { set_error("sr_block_forward: activation of %zu elements per sample exceeds the 32-bit index range", cmax * ohw); return R3D_ERR_INVALID_ARG; }
-    }
+    if (int rc = r3d::check_index32("sr_block_forward", (size_t)(Cin > Cout ? Cin : Cout), (size_t)(up ? 2 : 1) * Hin, (size_t)(up ? 2 : 1) * Win)) return rc;
     if (!workspace || workspace_bytes < r3d_sr_block_workspace_bytes(N, Cin, Cout, Hin, Win)) {
         set_error("sr_block_forward: workspace too small"); return R3D_ERR_WORKSPACE;
     }
@@ -832,27 +829,11 @@ extern "C" int r3d_conv_forward(const void* prepacked, const void* scales, const
                                 void* workspace, size_t workspace_bytes, r3d_stream_t stream)
 {
     using namespace r3d;
-    if (!prepacked || !scales || !x || !y || N <= 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0 || (ksize != 1 && ksize != 3)) {
-        set_error("conv_forward: bad argument"); return R3D_ERR_INVALID_ARG;
-    }
-    if (x_format < R3D_FMT_NCHW || x_format > R3D_FMT_SPLIT_MX || y_format < R3D_FMT_NCHW || y_format > R3D_FMT_SPLIT_MX ||
-        (y_format == R3D_FMT_SPLIT_MX && (Cout & 15)) || (x_format == R3D_FMT_SPLIT_MX && (ksize != 3 || (Cin & 15)))) {           // (SPLIT_MX out: fp8 records for an f16mx SR block that consumes y; 16-channel groups)
-        set_error("conv_forward: unsupported activation format (x %d, y %d)", x_format, y_format); return R3D_ERR_INVALID_ARG;
-    }
-    if (Cout & 3) { set_error("conv_forward: Cout = %d must be a multiple of 4", Cout); return R3D_ERR_INVALID_ARG; }
-    {   // the kernels index one sample's activation with 32 bits (Cout padded to the 128-cout block)
-        const size_t cmax = (size_t)((Cin > Cout ? Cin : Cout) + BLOCK_M);
-        if (cmax * H * W >= ((size_t)1 << 32)) { set_error("conv_forward: activation of %zu elements per sample exceeds the 32-bit index range", cmax * H * W); return R3D_ERR_INVALID_ARG; }
-    }
-    if ((x_format != R3D_FMT_NCHW && (Cin & 15)) || (y_format != R3D_FMT_NCHW && (Cout & 7))) {
-        set_error("conv_forward: blocked formats need Cin %% 16 == 0 and Cout %% 8 == 0 (Cin %d, Cout %d)", Cin, Cout); return R3D_ERR_INVALID_ARG;
-    }
-    if (x_format < R3D_FMT_SPLIT && (!workspace || workspace_bytes < r3d_conv_workspace_bytes(N, Cin, H, W))) {
-        set_error("conv_forward: workspace too small"); return R3D_ERR_WORKSPACE;
-    }
-    return conv_forward_f16x3(prepacked, reinterpret_cast<const float*>(scales), bias, N, Cin, Cout, H, W, ksize, x, x_format,
-                              act, act_slope, act_gain, clamp, y, y_format, next_scale, next_scale_stride, y_absmax,
-                              workspace, (hipStream_t)stream);
+    SrConvCall c = sr_conv_call("conv_forward", N, Cin, Cout, H, W, ksize, act, act_slope, act_gain, clamp, y, y_format, next_scale, next_scale_stride,
+                                y_absmax, (hipStream_t)stream);
+    c.prepacked = prepacked; c.scales = scales; c.bias = bias; c.x = x; c.x_format = x_format; c.workspace = workspace; c.workspace_bytes = workspace_bytes;
+    if (int rc = check(c)) return rc;
+    return conv_forward_f16x3(c);
 }
 
 extern "C" int r3d_conv_forward_cat(const void* prepacked, const void* scales, const float* bias,
@@ -863,28 +844,13 @@ extern "C" int r3d_conv_forward_cat(const void* prepacked, const void* scales, c
                                     void* workspace, size_t workspace_bytes, r3d_stream_t stream)
 {
     using namespace r3d;
-    if (!prepacked || !scales || !x || !y_cat || !mask || N <= 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0) {
-        set_error("conv_forward_cat: bad argument"); return R3D_ERR_INVALID_ARG;
-    }
-    if (ksize != 1) { set_error("conv_forward_cat: ksize %d: only the 1x1 conv kernel carries the concatenation epilogue", ksize); return R3D_ERR_INVALID_ARG; }
-    if (y_format != R3D_FMT_SPLIT && y_format != R3D_FMT_SPLIT_MX) { set_error("conv_forward_cat: y_format %d must be SPLIT or SPLIT_MX", y_format); return R3D_ERR_INVALID_ARG; }
-    if ((Cout & 15) || (chan_off & 15) || (C_total & 15) || chan_off < 0 || chan_off + Cout > C_total) {
-        set_error("conv_forward_cat: Cout %d, chan_off %d, C_total %d must be multiples of 16 with chan_off + Cout <= C_total", Cout, chan_off, C_total); return R3D_ERR_INVALID_ARG;
-    }
-    if (x_format < R3D_FMT_NCHW || x_format > R3D_FMT_SPLIT_MX || (x_format == R3D_FMT_SPLIT_MX && (ksize != 3 || (Cin & 15))) || (x_format != R3D_FMT_NCHW && (Cin & 15))) {
-        set_error("conv_forward_cat: unsupported input (format %d, Cin %d)", x_format, Cin); return R3D_ERR_INVALID_ARG;
-    }
-    {
-        const size_t cmax = (size_t)((Cin > C_total ? Cin : C_total) + BLOCK_M);
-        if (cmax * H * W >= ((size_t)1 << 32)) { set_error("conv_forward_cat: activation of %zu elements per sample exceeds the 32-bit index range", cmax * H * W); return R3D_ERR_INVALID_ARG; }
-    }
-    if (x_format < R3D_FMT_SPLIT && (!workspace || workspace_bytes < r3d_conv_workspace_bytes(N, Cin, H, W))) {
-        set_error("conv_forward_cat: workspace too small"); return R3D_ERR_WORKSPACE;
-    }
     const ConvCat cat = {mask, mask_invert ? 1 : 0, C_total, chan_off};
-    return conv_forward_f16x3(prepacked, reinterpret_cast<const float*>(scales), bias, N, Cin, Cout, H, W, ksize, x, x_format,
-                              act, act_slope, act_gain, clamp, y_cat, y_format, next_scale, next_scale_stride, nullptr,
-                              workspace, (hipStream_t)stream, &cat);
+    SrConvCall c = sr_conv_call("conv_forward_cat", N, Cin, Cout, H, W, ksize, act, act_slope, act_gain, clamp, y_cat, y_format, next_scale, next_scale_stride,
+                                nullptr, (hipStream_t)stream);
+    c.prepacked = prepacked; c.scales = scales; c.bias = bias; c.x = x; c.x_format = x_format; c.workspace = workspace; c.workspace_bytes = workspace_bytes;
+    c.cat = &cat;
+    if (int rc = check(c)) return rc;
+    return conv_forward_f16x3(c);
 }
 
 extern "C" int r3d_conv_forward_blend(const void* prepacked, const void* scales, const float* bias,
@@ -894,21 +860,12 @@ extern "C" int r3d_conv_forward_blend(const void* prepacked, const void* scales,
                                       void* y, int y_format, const float* next_scale, size_t next_scale_stride, float* y_absmax, r3d_stream_t stream)
 {
     using namespace r3d;
-    if (!prepacked || !scales || !a || !b || !mask || !y || N <= 0 || Ca <= 0 || Cb <= 0 || Cout <= 0 || H <= 0 || W <= 0) {
-        set_error("conv_forward_blend: bad argument"); return R3D_ERR_INVALID_ARG;
-    }
-    if ((Ca & 7) || (Cb & 7) || ((Ca + Cb) & 63)) {
-        set_error("conv_forward_blend: Ca %d and Cb %d must be multiples of 8 and their sum a multiple of 64", Ca, Cb); return R3D_ERR_INVALID_ARG;
-    }
-    if (y_format < R3D_FMT_NCHW || y_format > R3D_FMT_SPLIT_MX || (y_format == R3D_FMT_SPLIT_MX && (Cout & 15)) || (y_format != R3D_FMT_NCHW && (Cout & 7)) || (Cout & 3)) {
-        set_error("conv_forward_blend: unsupported output (format %d, Cout %d)", y_format, Cout); return R3D_ERR_INVALID_ARG;
-    }
-    {
-        const size_t cmax = (size_t)((Ca + Cb > Cout ? Ca + Cb : Cout) + BLOCK_M);
-        if (cmax * H * W >= ((size_t)1 << 32)) { set_error("conv_forward_blend: activation of %zu elements per sample exceeds the 32-bit index range", cmax * H * W); return R3D_ERR_INVALID_ARG; }
-    }
-    return conv_forward_blend_f16x3(prepacked, reinterpret_cast<const float*>(scales), bias, N, Ca, Cb, Cout, H, W, a, b, mask,
-                                    act, act_slope, act_gain, clamp, y, y_format, next_scale, next_scale_stride, y_absmax, (hipStream_t)stream);
+    SrConvCall c = sr_conv_call("conv_forward_blend", N, Ca + Cb, Cout, H, W, 1, act, act_slope, act_gain, clamp, y, y_format,
+                                next_scale, next_scale_stride, y_absmax, (hipStream_t)stream);
+    c.prepacked = prepacked; c.scales = scales; c.bias = bias;
+    c.blend = true; c.bl_a = a; c.bl_b = b; c.bl_mask = mask; c.Ca = Ca; c.Cb = Cb;
+    if (int rc = check(c)) return rc;
+    return conv_forward_blend_f16x3(c);
 }
 
 extern "C" int r3d_upsample2x_bilinear(const float* x_cb8, int N, int C, int H, int W, void* y, int y_format,

@@ -163,16 +163,7 @@ int conv_prepack_f16x3(const float* w, int Cin, int Cout, int ksize, void* prepa
 size_t conv_workspace_bytes_f16x3(int N, int Cin, int H, int W);
 // the conv's SPLIT output as one part of a channel concatenation (r3d_conv_forward_cat): channels [chan_off, chan_off + Cout) of C_total, times mask or 1 - mask per pixel
 struct ConvCat { const float* mask; int mask_invert; int C_total; int chan_off; };
-int conv_forward_f16x3(const void* prepacked, const float* scales, const float* bias,
-                       int N, int Cin, int Cout, int H, int W, int ksize,
-                       const void* x, int x_format, int act, float slope, float gain, float clamp,
-                       void* y, int y_format, const float* next_scale, size_t next_scale_stride, float* y_absmax,
-                       void* workspace, hipStream_t st, const ConvCat* cat = nullptr);
-
-int conv_forward_blend_f16x3(const void* prepacked, const float* scales, const float* bias,
-                             int N, int Ca, int Cb, int Cout, int H, int W, const float* xa, const float* xb, const float* mask,
-                             int act, float slope, float gain, float clamp,
-                             void* y, int y_format, const float* next_scale, size_t next_scale_stride, float* y_absmax, hipStream_t st);
+// (conv_forward_f16x3 / conv_forward_blend_f16x3 take the call description: r3d_sr_launch.h)
 
 int upsample2x_bilinear_f16x3(const float* x_cb8, int N, int C, int H, int W, void* y, int y_format,
                               const float* next_scale, size_t next_scale_stride, hipStream_t st);

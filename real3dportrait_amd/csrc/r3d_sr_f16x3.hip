@@ -23,7 +23,7 @@
 // modules/eg3ds/torch_utils/ops/{conv2d_resample.py:116-133, upfirdn2d.py:171-215,317-354, bias_act.py:93-122}.
 #include <stdlib.h>
 
-#include "r3d_sr_common.h"
+#include "r3d_sr_launch.h"
 #include "r3d_stamps.h"
 
 namespace r3d {
@@ -1732,12 +1732,16 @@ int upsample2x_bilinear_f16x3(const float* x_cb8, int N, int C, int H, int W, vo
 
 // ---- host ------------------------------------------------------------------------------------------------------
 // A/B switch of the Winograd F(2,3) conv (r3d_sr_wino.h): R3D_CONV_WINO=0 keeps every plain 3x3 conv on the direct kernels
+static constexpr float kSqrt2 = 1.4142135623730951f;   // the lrelu gain of the SR blocks
 static int wino_mode() { static const int v = getenv("R3D_CONV_WINO") ? atoi(getenv("R3D_CONV_WINO")) : 3; return v; }   // 0 off, 1 both precisions, 2 f16mx only, 3 f16x3 only
-// ... and the shapes it takes: whole 16 x 16-pixel tiles, 16-channel stages, 128-cout blocks
-static bool wino_shape_ok(int Cin, int Cout, int H, int W)
+// ... and when a plain 3x3 conv over a plain SPLIT operand takes it (mx: the layer's precision is f16mx): the mode allows the precision, and the
+// shape is whole 16 x 16-pixel tiles, 16-channel stages, 128-cout blocks
+static bool use_wino(int Cin, int Cout, int H, int W, bool mx)
 {
+    const int m = wino_mode();
     // (the kernel addresses one sample's SPLIT activation and the weight pack through 32-bit buffer offsets)
-    return wino_mode() && (H & 15) == 0 && (W & 15) == 0 && (Cin & 15) == 0 && (Cout % BLOCK_M) == 0 && (size_t)Cin * H * W * 4 < ((size_t)1 << 31) && (size_t)48 * Cin * Cout < ((size_t)1 << 31);
+    return (m == 1 || (m == 2 && mx) || (m == 3 && !mx)) && (H & 15) == 0 && (W & 15) == 0 && (Cin & 15) == 0 && (Cout % BLOCK_M) == 0 &&
+           (size_t)Cin * H * W * 4 < ((size_t)1 << 31) && (size_t)48 * Cin * Cout < ((size_t)1 << 31);
 }
 
 // prepacked: SrPackLayout (r3d_sr_common.h)
@@ -1805,16 +1809,14 @@ static void launch_conv2(Conv2Args& a, int tiles, int N, hipStream_t st, bool mx
 
 static int tiles_of(int H, int W) { return ((W + F_TILE_W - 1) / F_TILE_W) * ((H + F_TILE_H - 1) / F_TILE_H); }
 
-// where a conv's epilogue writes y [N][Cout][H][W] in y_format (R3D_FMT_NONE: nowhere); the SPLIT formats are multiplied by next_scale
-static void conv_set_output(Conv2Args& a, void* y, int y_format, int Cout, int H, int W, const float* next_scale, size_t next_scale_stride)
+// A conv's operand as SPLIT: a SPLIT | SPLIT_MX input where it is, an NCHW | CB8 one converted into `xin` times the layer's in-multiplier (Ci: Cin padded to 16)
+static const uint4* split_input(const void* x, int x_format, const float* in_scale, size_t in_scale_stride, void* xin, int Ci, int Cin, int N, int H, int W, hipStream_t st)
 {
-    if (y_format == R3D_FMT_CB8) { a.y_f32 = reinterpret_cast<float*>(y); a.y_f32_stride_n = (size_t)Cout * H * W; }
-    else if (y_format == R3D_FMT_NCHW) { a.y_nchw = reinterpret_cast<float*>(y); a.y_nchw_stride_n = (size_t)Cout * H * W; }
-    else if (y_format == R3D_FMT_SPLIT || y_format == R3D_FMT_SPLIT_MX) {
-        a.y_split = reinterpret_cast<uint4*>(y); a.y_split_stride_n = (size_t)Cout / 8 * H * W * 2;
-        a.next_scale = next_scale; a.next_scale_stride_n = next_scale_stride;
-        a.y_split_mx = y_format == R3D_FMT_SPLIT_MX ? 1 : 0;
-    }
+    if (x_format == R3D_FMT_SPLIT || x_format == R3D_FMT_SPLIT_MX) return reinterpret_cast<const uint4*>(x);
+    ProfScope ps(R3D_PROF_LAYOUT, st);
+    hipLaunchKernelGGL(to_split_kernel, dim3((H * W + 255) / 256, Ci / 8, N), dim3(256), 0, st,
+                       reinterpret_cast<const float*>(x), x_format == R3D_FMT_CB8 ? 1 : 0, in_scale, in_scale_stride, reinterpret_cast<uint4*>(xin), Ci, Cin, H * W);
+    return reinterpret_cast<const uint4*>(xin);
 }
 
 // upconv_fir_f16x3_kernel<CLAMP, MX, MXIN>: clamp compiled in | the epilogue writes conv1's fp8 records | the input carries fp8 records
@@ -1834,20 +1836,13 @@ int sr_block_forward_f16x3(const void* prepacked, const void* styles, int N, int
     const int OH = up ? 2 * Hin : Hin, OW = up ? 2 * Win : Win;
     const SrWorkspaceLayout WS = sr_workspace_layout(N, Cin, Cout, Hin, Win);     // (the T and xo slots serve R3D_SR_F32 only)
     char* wsb = reinterpret_cast<char*>(workspace);
-    uint4* xin = reinterpret_cast<uint4*>(wsb + WS.xin);
     uint4* y0 = reinterpret_cast<uint4*>(wsb + WS.y0);
     float* rgbp = reinterpret_cast<float*>(wsb + WS.rgbp);
 
-    const uint4* xs = reinterpret_cast<const uint4*>(x);
     const bool mx_in = x_format == R3D_FMT_SPLIT_MX;          // (validated by the caller: up = 1, R3D_SR_F16MX)
-    if (x_format != R3D_FMT_SPLIT && !mx_in) {
-        ProfScope ps(R3D_PROF_LAYOUT, st);
-        hipLaunchKernelGGL(to_split_kernel, dim3((Hin * Win + 255) / 256, Cin / 8, N), dim3(256), 0, st,
-                           reinterpret_cast<const float*>(x), x_format == R3D_FMT_CB8 ? 1 : 0, pk + L.s0f, L.total, xin, Cin, Cin, Hin * Win);
-        xs = xin;
-    }
+    const uint4* xs = split_input(x, x_format, pk + L.s0f, L.total, wsb + WS.xin, Cin, Cin, N, Hin, Win, st);
     // conv1 on the Winograd F(2,3) kernel: its operand is transformed in fp32 inside the kernel, so conv0 hands over plain SPLIT (no fp8 records)
-    const bool wino1 = wino_shape_ok(Cout, Cout, OH, OW) && (wino_mode() == 1 || (wino_mode() == 2 && mx) || (wino_mode() == 3 && !mx));
+    const bool wino1 = use_wino(Cout, Cout, OH, OW, mx);
     const bool mx0 = mx && !wino1;                            // does conv0's epilogue write the fp8 records of conv1's operand?
     if (up) {
         // ---- conv0: fused transposed conv + FIR + bias + lrelu -> SPLIT (one kernel, T stays on chip) ----------------
@@ -1867,31 +1862,26 @@ int sr_block_forward_f16x3(const void* prepacked, const void* styles, int N, int
         hipLaunchKernelGGL(kUpconv[clamp >= 0.f][mx0][mx_in], ugrid, dim3(256), 0, st, u);
     } else {
         // ---- conv0 of SynthesisBlockNoUp (superresolution.py:159-258): plain modulated 3x3 conv -> SPLIT for conv1 ----
+        SrConvCall c0 = sr_conv_call("sr_block_forward", N, Cin, Cout, OH, OW, 3, 1, 0.2f, kSqrt2, clamp, y0, mx0 ? R3D_FMT_SPLIT_MX : R3D_FMT_SPLIT,
+                                     pk + L.s1f, L.total, nullptr, st);      // f16mx: conv1 reads fp8 records (the Winograd kernel: plain SPLIT)
+        c0.bias = pk + L.b0;
         Conv2Args a = {};
+        c0.fill(a, Cin, Cout, pk + L.d0f, L.total, L.total);
         a.x = xs; a.x_stride_n = (size_t)Cin / 8 * Hin * Win * 2;
         a.wp = reinterpret_cast<const uint4*>(wpk + (mx_in ? P.c0_mx : P.c0));
-        a.out_scale = pk + L.d0f; a.out_scale_stride_n = L.total; a.bias = pk + L.b0; a.bias_stride_n = L.total;
-        a.OH = OH; a.OW = OW;
-        conv_set_output(a, y0, mx0 ? R3D_FMT_SPLIT_MX : R3D_FMT_SPLIT, Cout, OH, OW, pk + L.s1f, L.total);      // f16mx: conv1 reads fp8 records (the Winograd kernel: plain SPLIT)
-        a.Cin = Cin; a.Cout = Cout; a.CoutReal = Cout; a.H = Hin; a.W = Win; a.nphase = 1;
-        a.act = 1; a.act_slope = 0.2f; a.act_gain = 1.4142135623730951f; a.clamp = clamp;
-        sr_fill_conv3x3_phase(a.ph, OH, OW);
         ProfScope ps(R3D_PROF_CONV, st);
         launch_conv2(a, tiles_of(OH, OW), N, st, mx_in);
     }
     // ---- conv1 (3x3) + bias/lrelu + toRGB partials (+ optional x outputs) ------------------------------------------
     {
+        SrConvCall c1 = sr_conv_call("sr_block_forward", N, Cout, Cout, OH, OW, 3, 1, 0.2f, kSqrt2, clamp, x_out, x_out ? x_out_format : R3D_FMT_NONE,
+                                     next_scale, next_scale_stride, x_absmax, st);
+        c1.bias = pk + L.b1;
         Conv2Args a = {};
+        c1.fill(a, Cout, Cout, pk + L.d1f, L.total, L.total);
         a.x = y0; a.x_stride_n = (size_t)Cout / 8 * OH * OW * 2;
         a.wp = reinterpret_cast<const uint4*>(wpk + (wino1 ? P.c1_wino : P.c1));
-        a.out_scale = pk + L.d1f; a.out_scale_stride_n = L.total; a.bias = pk + L.b1; a.bias_stride_n = L.total;
-        a.OH = OH; a.OW = OW;
-        if (x_out) conv_set_output(a, x_out, x_out_format, Cout, OH, OW, next_scale, next_scale_stride);
-        a.y_absmax = reinterpret_cast<unsigned*>(x_absmax);
         a.wrgb = pk + L.wrgb; a.wrgb_stride_n = L.total; a.rgb_partial = rgbp; a.rgbp_stride_n = (size_t)(Cout / 64) * 3 * OH * OW;
-        a.Cin = Cout; a.Cout = Cout; a.CoutReal = Cout; a.H = OH; a.W = OW; a.nphase = 1;
-        a.act = 1; a.act_slope = 0.2f; a.act_gain = 1.4142135623730951f; a.clamp = clamp;
-        sr_fill_conv3x3_phase(a.ph, OH, OW);
         ProfScope ps(R3D_PROF_CONV, st);
         launch_conv2(a, tiles_of(OH, OW), N, st, mx, wino1);
     }
@@ -1933,69 +1923,42 @@ int conv_prepack_f16x3(const float* w, int Cin, int Cout, int ksize, void* prepa
 size_t conv_workspace_bytes_f16x3(int N, int Cin, int H, int W) { return align256((size_t)N * conv_pack_layout(Cin, 1, 1).Ci * H * W * 4) + 256; }
 
 // scales: per-sample ConvScales vectors (stride S.total) written by r3d_conv_chain_scales (in_vec: multiplier of the fp32 -> SPLIT input
-// conversion; out_vec: epilogue multiplier 2^-kw[co] * 2^-e_in); bias [Cout] shared by the batch (or null)
-int conv_forward_f16x3(const void* prepacked, const float* scales, const float* bias,
-                       int N, int Cin, int Cout, int H, int W, int ksize,
-                       const void* x, int x_format, int act, float slope, float gain, float clamp,
-                       void* y, int y_format, const float* next_scale, size_t next_scale_stride, float* y_absmax,
-                       void* workspace, hipStream_t st, const ConvCat* cat)
+// conversion; out_vec: epilogue multiplier 2^-kw[co] * 2^-e_in); bias [Cout] shared by the batch (or null).  The caller has check()ed c.
+int conv_forward_f16x3(const SrConvCall& c)
 {
-    const ConvPackLayout P = conv_pack_layout(Cin, Cout, ksize);
-    const int Ci = P.Ci, Co = P.Co;
-    const ConvScales S = conv_scales_layout(Ci, Co);
-    const uint4* xs = reinterpret_cast<const uint4*>(x);
-    const bool mx_in = x_format == R3D_FMT_SPLIT_MX;          // (validated by the caller: ksize 3, Cin % 16 == 0): the f16mx main loop
-    if (x_format != R3D_FMT_SPLIT && !mx_in) {
-        uint4* xin = reinterpret_cast<uint4*>(workspace);
-        ProfScope ps(R3D_PROF_LAYOUT, st);
-        hipLaunchKernelGGL(to_split_kernel, dim3((H * W + 255) / 256, Ci / 8, N), dim3(256), 0, st,
-                           reinterpret_cast<const float*>(x), x_format == R3D_FMT_CB8 ? 1 : 0, scales + S.in_vec, S.total, xin, Ci, Cin, H * W);
-        xs = xin;
-    }
+    const ConvPackLayout P = conv_pack_layout(c.Cin, c.Cout, c.ksize);
+    const ConvScales S = conv_scales_layout(P.Ci, P.Co);
+    const float* scales = reinterpret_cast<const float*>(c.scales);
+    const bool mx_in = c.x_format == R3D_FMT_SPLIT_MX;        // the f16mx main loop
     Conv2Args a = {};
-    a.x = xs; a.x_stride_n = (size_t)Ci / 8 * H * W * 2;
-    a.out_scale = scales + S.out_vec; a.out_scale_stride_n = S.total; a.bias = bias; a.bias_stride_n = 0;
-    a.OH = H; a.OW = W;
-    conv_set_output(a, y, y_format, Cout, H, W, next_scale, next_scale_stride);
-    if (cat) {      // (SPLIT | SPLIT_MX) y is the whole concatenated tensor [N][hi|lo][C_total / 8][H][W][8]; next_scale the consumer's whole in-multiplier vector
-        a.y_split_stride_n = (size_t)cat->C_total / 8 * H * W * 2; a.y_cat_chunks = cat->C_total / 8; a.y_cat_off = cat->chan_off / 8;
+    c.fill(a, P.Ci, P.Co, scales + S.out_vec, S.total, 0);
+    a.x = split_input(c.x, c.x_format, scales + S.in_vec, S.total, c.workspace, P.Ci, c.Cin, c.N, c.H, c.W, c.stream);
+    a.x_stride_n = (size_t)P.Ci / 8 * c.H * c.W * 2;
+    if (const ConvCat* cat = c.cat) {   // (SPLIT | SPLIT_MX) y is the whole concatenated tensor [N][hi|lo][C_total / 8][H][W][8]; next_scale the consumer's whole in-multiplier vector
+        a.y_split_stride_n = (size_t)cat->C_total / 8 * c.H * c.W * 2; a.y_cat_chunks = cat->C_total / 8; a.y_cat_off = cat->chan_off / 8;
         a.y_mask = cat->mask; a.y_mask_invert = cat->mask_invert;
-        if (next_scale) a.next_scale = next_scale + cat->chan_off;
+        if (c.next_scale) a.next_scale = c.next_scale + cat->chan_off;
     }
-    a.y_absmax = reinterpret_cast<unsigned*>(y_absmax);
-    a.Cin = Ci; a.Cout = Co; a.CoutReal = Cout; a.H = H; a.W = W; a.nphase = 1;
-    a.act = act; a.act_slope = slope; a.act_gain = gain; a.clamp = clamp;
-    if (ksize == 3) sr_fill_conv3x3_phase(a.ph, H, W);
-    else sr_fill_conv1x1_phase(a.ph, H, W);
     // a plain SPLIT operand (the f16x3 precision, or a producer that does not write records): Winograd F(2,3) when the shape allows it
-    const bool wino = ksize == 3 && !mx_in && wino_shape_ok(Ci, Co, H, W) && (wino_mode() == 1 || wino_mode() == 3);
-    a.wp = reinterpret_cast<const uint4*>(reinterpret_cast<const float*>(prepacked) + (mx_in ? P.w_mx : wino ? P.w_wino : P.w));
-    ProfScope ps(R3D_PROF_CONV, st);
-    launch_conv2(a, tiles_of(H, W), N, st, mx_in, wino);
+    const bool wino = c.ksize == 3 && !mx_in && use_wino(P.Ci, P.Co, c.H, c.W, false);
+    a.wp = reinterpret_cast<const uint4*>(reinterpret_cast<const float*>(c.prepacked) + (mx_in ? P.w_mx : wino ? P.w_wino : P.w));
+    ProfScope ps(R3D_PROF_CONV, c.stream);
+    launch_conv2(a, tiles_of(c.H, c.W), c.N, c.stream, mx_in, wino);
     return check_launch("conv_forward");
 }
 
-// cat([a * mask, b * (1 - mask)]) -> 1x1 conv in one kernel (conv1x1_blend_f16x3_kernel); the caller validated: ksize 1, a / b CB8, Ca % 8 == Cb % 8 == 0, (Ca + Cb) % 64 == 0
-int conv_forward_blend_f16x3(const void* prepacked, const float* scales, const float* bias,
-                             int N, int Ca, int Cb, int Cout, int H, int W, const float* xa, const float* xb, const float* mask,
-                             int act, float slope, float gain, float clamp,
-                             void* y, int y_format, const float* next_scale, size_t next_scale_stride, float* y_absmax, hipStream_t st)
+// cat([a * mask, b * (1 - mask)]) -> 1x1 conv in one kernel (conv1x1_blend_f16x3_kernel); the caller has check()ed c: ksize 1, a / b CB8, Ca % 8 == Cb % 8 == 0, (Ca + Cb) % 64 == 0
+int conv_forward_blend_f16x3(const SrConvCall& c)
 {
-    const ConvPackLayout P = conv_pack_layout(Ca + Cb, Cout, 1);
-    const int Ci = P.Ci, Co = P.Co;
-    const ConvScales S = conv_scales_layout(Ci, Co);
+    const ConvPackLayout P = conv_pack_layout(c.Cin, c.Cout, 1);
+    const ConvScales S = conv_scales_layout(P.Ci, P.Co);
+    const float* scales = reinterpret_cast<const float*>(c.scales);
     Conv2Args a = {};
-    a.wp = reinterpret_cast<const uint4*>(reinterpret_cast<const float*>(prepacked) + P.w);
-    a.bl_a = xa; a.bl_b = xb; a.bl_mask = mask; a.bl_scale = scales + S.in_vec; a.bl_scale_stride_n = S.total; a.bl_Ca = Ca;
-    a.out_scale = scales + S.out_vec; a.out_scale_stride_n = S.total; a.bias = bias; a.bias_stride_n = 0;
-    a.OH = H; a.OW = W;
-    conv_set_output(a, y, y_format, Cout, H, W, next_scale, next_scale_stride);
-    a.y_absmax = reinterpret_cast<unsigned*>(y_absmax);
-    a.Cin = Ci; a.Cout = Co; a.CoutReal = Cout; a.H = H; a.W = W; a.nphase = 1;
-    a.act = act; a.act_slope = slope; a.act_gain = gain; a.clamp = clamp;
-    sr_fill_conv1x1_phase(a.ph, H, W);
-    ProfScope ps(R3D_PROF_CONV, st);
-    hipLaunchKernelGGL(conv1x1_blend_f16x3_kernel, dim3(tiles_of(H, W), Co / BLOCK_M, N), dim3(512), 0, st, a);
+    c.fill(a, P.Ci, P.Co, scales + S.out_vec, S.total, 0);
+    a.wp = reinterpret_cast<const uint4*>(reinterpret_cast<const float*>(c.prepacked) + P.w);
+    a.bl_a = c.bl_a; a.bl_b = c.bl_b; a.bl_mask = c.bl_mask; a.bl_scale = scales + S.in_vec; a.bl_scale_stride_n = S.total; a.bl_Ca = c.Ca;
+    ProfScope ps(R3D_PROF_CONV, c.stream);
+    hipLaunchKernelGGL(conv1x1_blend_f16x3_kernel, dim3(tiles_of(c.H, c.W), P.Co / BLOCK_M, c.N), dim3(512), 0, c.stream, a);
     return check_launch("conv_forward_blend");
 }
 

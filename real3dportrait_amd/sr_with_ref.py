@@ -18,7 +18,8 @@ The face-vid2vid warp network `torso_model` is a cold-ish PyTorch encoder and is
 import torch
 
 from . import _lib
-from .superresolution import (_BoundMeter, _f32c, _keep_tags, _tag, blend_cat, bound_of, chain_fold, const_bound, resize_bilinear)
+from .sr_activation import _tag, as_input, bound_of, empty, fmt_of, logical_shape, tag_split
+from .superresolution import _BoundMeter, _f32c, blend_cat, chain_fold, const_bound, resize_bilinear
 from .torso_layers import _Cached
 
 
@@ -115,15 +116,7 @@ def forward_v2(self, rgb, x, ws, ref_torso_rgb, ref_bg_rgb, weights_img, segmap,
             raise NotImplementedError("the fused SuperresolutionHybrid8XDC_Warp forward needs SR precision 'f16x3' (got 'f32')")
         return ref_forward(rgb, x, ws, ref_torso_rgb, ref_bg_rgb, weights_img, segmap, kp_s, kp_d, target_torso_mask=target_torso_mask,
                            **block_kwargs)
-    # block0 / head_torso_block / block1 are shared with the reference's other entry points (infer_forward_stage1/2,
-    # sr_with_ref.py:165-214, call self.block0(x, rgb, ws) and expect NCHW x): the hand-off formats are set for this call only
-    b0, b1, hb = self.block0, self.block1, self.head_torso_block
-    saved = [(m, m.out_format, m.return_x) for m in (b0, hb, b1)]
-    try:
-        return _forward_v2(self, S, rgb, x, ws, ref_torso_rgb, ref_bg_rgb, weights_img, segmap, kp_s, kp_d, target_torso_mask, block_kwargs)
-    finally:
-        for m, fmt, rx in saved:
-            m.out_format, m.return_x = fmt, rx
+    return _forward_v2(self, S, rgb, x, ws, ref_torso_rgb, ref_bg_rgb, weights_img, segmap, kp_s, kp_d, target_torso_mask, block_kwargs)
 
 
 def _forward_v1(self, rgb, x, ws, ref_torso_rgb, ref_bg_rgb, weights_img, segmap, kp_s, kp_d, target_torso_mask, block_kwargs):
@@ -141,29 +134,23 @@ def _forward_v1(self, rgb, x, ws, ref_torso_rgb, ref_bg_rgb, weights_img, segmap
     ref_bg_rgb_256 = resize_bilinear(ref_bg_rgb, (256, 256), aa)
     kw = dict(block_kwargs)
     kw.setdefault("noise_mode", "none")
-    b0, b1 = self.block0, self.block1
-    saved = [(m, m.out_format, m.return_x) for m in (b0, b1)]
-    try:
-        b0.out_format, b0.return_x, b1.out_format, b1.return_x = "nchw", True, "nchw", True
-        x, rgb = b0(x, rgb, ws3, **kw)                                                                  # :83
-        if hp.get("torso_model_version", "v1") == "v1":
-            rgb_torso, ret = self.torso_model.forward(ref_torso_rgb_256, segmap, kp_s, kp_d, rgb_256.detach(), cal_loss=True,
-                                                      target_torso_mask=target_torso_mask)
-        else:
-            rgb_torso, ret = self.torso_model.forward(ref_torso_rgb_256, segmap, kp_s, kp_d, rgb_256.detach(), weights_256.detach(),
-                                                      cal_loss=True, target_torso_mask=target_torso_mask)
-        x_torso = self.torso_encoder(ret["deformed_torso_hid"])                                         # :88
-        x_bg = self.bg_encoder(ref_bg_rgb_256)                                                          # :90
-        rgb = blend(rgb, rgb_torso, weights_256)                                                        # :94
-        x = blend(x, x_torso, weights_256)                                                              # :95
-        torso_occ = resize_bilinear(ret["occlusion_2"], (256, 256), aa)                                 # :99
-        pocc = person_occlusion(weights_256, torso_occ, hp["htbsr_head_threshold"])                     # :96-100
-        rgb = blend(rgb, ref_bg_rgb_256, pocc)                                                          # :101
-        x = self.fuse_fg_bg_convs(blend_cat(x, x_bg, pocc, self.fuse_fg_bg_convs))                      # :102-103
-        _, rgb = b1(x, rgb, ws3, **kw)                                                                  # :104
-    finally:
-        for m, fmt, rx in saved:
-            m.out_format, m.return_x = fmt, rx
+    kw.update(_out_format="nchw", _return_x=True)         # the blocks are shared with the fused forward: the reference layout for these calls only
+    x, rgb = self.block0(x, rgb, ws3, **kw)                                                             # :83
+    if hp.get("torso_model_version", "v1") == "v1":
+        rgb_torso, ret = self.torso_model.forward(ref_torso_rgb_256, segmap, kp_s, kp_d, rgb_256.detach(), cal_loss=True,
+                                                  target_torso_mask=target_torso_mask)
+    else:
+        rgb_torso, ret = self.torso_model.forward(ref_torso_rgb_256, segmap, kp_s, kp_d, rgb_256.detach(), weights_256.detach(),
+                                                  cal_loss=True, target_torso_mask=target_torso_mask)
+    x_torso = self.torso_encoder(ret["deformed_torso_hid"])                                             # :88
+    x_bg = self.bg_encoder(ref_bg_rgb_256)                                                              # :90
+    rgb = blend(rgb, rgb_torso, weights_256)                                                            # :94
+    x = blend(x, x_torso, weights_256)                                                                  # :95
+    torso_occ = resize_bilinear(ret["occlusion_2"], (256, 256), aa)                                     # :99
+    pocc = person_occlusion(weights_256, torso_occ, hp["htbsr_head_threshold"])                         # :96-100
+    rgb = blend(rgb, ref_bg_rgb_256, pocc)                                                              # :101
+    x = self.fuse_fg_bg_convs(blend_cat(x, x_bg, pocc, self.fuse_fg_bg_convs))                          # :102-103
+    _, rgb = self.block1(x, rgb, ws3, **kw)                                                             # :104
     return rgb, ret
 
 
@@ -173,7 +160,7 @@ def _forward_v2(self, S, rgb, x, ws, ref_torso_rgb, ref_bg_rgb, weights_img, seg
     weights_img = weights_img.detach()
     N, dev = rgb.shape[0], rgb.device
     ws3 = S.c_ws3.get(ws, lambda w: w[:, -1:, :].expand(N, 3, -1).contiguous())                      # :69
-    if getattr(x, "_r3d_fmt", None) != "split" and x.shape[-1] != self.input_resolution:               # :71-75, cold
+    if fmt_of(x) != "split" and x.shape[-1] != self.input_resolution:                                   # :71-75, cold
         sz = (self.input_resolution, self.input_resolution)
         x, rgb = resize_bilinear(x, sz, aa), resize_bilinear(rgb, sz, aa)
     rgb_256 = resize_bilinear(rgb, (256, 256), aa)                                                      # :77
@@ -189,18 +176,17 @@ def _forward_v2(self, S, rgb, x, ws, ref_torso_rgb, ref_bg_rgb, weights_img, seg
 
     # ---- block0: 128^2 head features -> 256^2 (:83); its conv1 epilogue measures max|x0| ------------------------------------------
     prep0 = b0.prepare(ws3, dev, ws_key=ws)
-    if getattr(x, "_r3d_fmt", None) == "split":
-        # the ray kernel wrote block0's first operand itself (split_input_spec below folded for it before the render launch)
-        if getattr(x, "_r3d_for", None) is not b0 or not S.split_fold_pending:
-            raise RuntimeError("SPLIT feature image without a pending split_input_spec() fold of this module")
-        S.split_fold_pending = False
-    else:
-        S.split_fold_pending = False
-        x = _keep_tags(x)
+    x, _, presplit = as_input(x, b0)
+    if presplit and not S.split_fold_pending:
+        # (the ray kernel wrote block0's first operand itself: split_input_spec above folded for it before the render launch)
+        raise RuntimeError("SPLIT feature image without a pending split_input_spec() fold of this module")
+    S.split_fold_pending = False
+    if not presplit:
         bx, _ = bound_of(x, S.meter_x, layers=2)
         chain_fold([b0.chain_op(-1)], N, [bx], zero=[m_x0])
-    b0.out_format, b0.return_x = "cb8", True
-    x0, rgb0 = b0(x, rgb, ws3, _prepared=prep0, _folded=True, _x_absmax=m_x0, **kw)
+    # block0 / head_torso_block / block1 are shared with the reference's other entry points (infer_forward_stage1/2, sr_with_ref.py:165-214, call
+    # self.block0(x, rgb, ws) and expect NCHW x): the hand-off formats are per call
+    x0, rgb0 = b0(x, rgb, ws3, _prepared=prep0, _folded=True, _x_absmax=m_x0, _out_format="cb8", _return_x=True, **kw)
 
     # ---- warp-based torso branch (PyTorch, untouched) (:84-87) ---------------------------------------------------------------------
     if hp.get("torso_model_version", "v1") == "v1":
@@ -211,8 +197,9 @@ def _forward_v2(self, S, rgb, x, ws, ref_torso_rgb, ref_bg_rgb, weights_img, seg
                                                   cal_loss=True, target_torso_mask=target_torso_mask)
     hid = ret["deformed_torso_hid"]
     te = self.torso_encoder._plan() if _FUSE_TORSO_CAT else ()
-    fuse_cat = len(te) == 1 and te[0][0].kernel_size[0] == 1 and te[0][0].out_channels % 16 == 0 and getattr(x0, "_r3d_fmt", None) == "cb8" \
-        and x0.shape[1] % 2 == 0 and getattr(hid, "_r3d_fmt", "nchw") == "nchw"
+    _, Ca, H0, W0 = logical_shape(x0)
+    fuse_cat = len(te) == 1 and te[0][0].kernel_size[0] == 1 and te[0][0].out_channels % 16 == 0 and fmt_of(x0) == "cb8" \
+        and Ca % 16 == 0 and fmt_of(hid) == "nchw"
     if not fuse_cat:
         x_torso = self.torso_encoder(hid, out_format="cb8")                                            # :88 (1x1 conv, measured input)
     x_bg = S.c_xbg.get(ref_bg_rgb, lambda _: _measured(self.bg_encoder(ref_bg_rgb_256, out_format="cb8"), S))   # :90 (clip constant)
@@ -226,16 +213,15 @@ def _forward_v2(self, S, rgb, x, ws, ref_torso_rgb, ref_bg_rgb, weights_img, seg
         # split -- the fp32 x_torso (67 MB written, 67 MB read back by blend_cat) does not exist.  The consumer's fold therefore runs BEFORE the producer, in one
         # chain with it: op 0 = torso_encoder (bound of its output = what its tag carried), op 1.. = the fusion stack reading (max|x0|, op 0).  Same bits.
         tconv, tslope, _ = te[0]
-        hid = _keep_tags(hid)
+        hid, _, _ = as_input(hid, tconv)
         tconv.prepare(N, dev)
         bh, dh = bound_of(hid, S.meter_hid, 1)
         tconv._depth_in = dh
         ops, head, last = fuse_ht.chain_ops(N, dev, -2, 0, base=1)
         chain_fold([tconv.chain_op(-1, negative_slope=tslope)] + ops + [hb.chain_op(last)], N, [bh, m_x0], zero=[m_y] if _HB_TAIL_FOLD else [m_x2])
         fmt = "split_mx" if head.wants_mx() else "split"
-        Ca, Cb = x0.shape[1] * 8, tconv.out_channels
-        xs = torch.empty(N, 2, (Ca + Cb) // 8, x0.shape[2], x0.shape[3], 8, device=dev, dtype=torch.float16)
-        xs._r3d_fmt, xs._r3d_for = fmt, head
+        Cb = tconv.out_channels
+        xs = tag_split(empty(fmt, N, Ca + Cb, H0, W0, dev), fmt, head)
         tconv.forward_cat(hid, xs, Ca, alpha, True, head, negative_slope=tslope)
         blend_cat(x0, None, alpha, fuse_ht, _folded_head=head, _b_channels=Cb, _dst=xs)
     else:
@@ -246,8 +232,7 @@ def _forward_v2(self, S, rgb, x, ws, ref_torso_rgb, ref_bg_rgb, weights_img, seg
     y = fuse_ht(xs, out_format="split_mx" if hb.wants_mx() else "split", _next=hb, _y_absmax=m_y if _HB_TAIL_FOLD else None)       # :105
     if _HB_TAIL_FOLD:
         chain_fold([hb.chain_op(-1, tail=True)], N, [m_y], zero=[m_x2])
-    hb.out_format, hb.return_x = "cb8", True
-    x2, rgb2 = hb(y, rgb1, ws3, _prepared=preph, _folded=True, _x_absmax=m_x2, **kw)                   # :106
+    x2, rgb2 = hb(y, rgb1, ws3, _prepared=preph, _folded=True, _x_absmax=m_x2, _out_format="cb8", _return_x=True, **kw)      # :106
 
     # ---- person / background fusion (:107-115) ----------------------------------------------------------------------------------------
     torso_occ = resize_bilinear(ret["occlusion_2"], (256, 256), aa)                                     # :110
@@ -265,8 +250,7 @@ def _forward_v2(self, S, rgb, x, ws, ref_torso_rgb, ref_bg_rgb, weights_img, seg
         xs2 = blend_cat(x2, x_bg, pocc, fuse_fg, _folded_head=head)                                     # :113
         z = fuse_fg(xs2, out_format=zfmt, _next=b1, _y_absmax=m_z)                                      # :114
     chain_fold([b1.chain_op(-1, tail=True)], N, [m_z])
-    b1.return_x = False
-    _, rgb_out = b1(z, rgb3, ws3, _prepared=prep1, _folded=True, **kw)                                 # :115
+    _, rgb_out = b1(z, rgb3, ws3, _prepared=prep1, _folded=True, _return_x=False, **kw)                # :115
     return rgb_out, ret
 
 
@@ -287,13 +271,7 @@ def infer_forward_stage1(self, rgb, x, ws, ref_torso_rgb, ref_bg_rgb, weights_im
     ref_bg_rgb_256 = resize_bilinear(ref_bg_rgb, (256, 256), aa)
     kw = dict(block_kwargs)
     kw.setdefault("noise_mode", "none")
-    b0 = self.block0
-    saved = (b0.out_format, b0.return_x)
-    try:
-        b0.out_format, b0.return_x = "nchw", True
-        x, rgb = b0(x, rgb, ws3, **kw)                                                                  # :180
-    finally:
-        b0.out_format, b0.return_x = saved
+    x, rgb = self.block0(x, rgb, ws3, _out_format="nchw", _return_x=True, **kw)                         # :180
     ret = self.torso_model.infer_forward_stage1(ref_torso_rgb_256, segmap, kp_s, kp_d, rgb_256.detach(), cal_loss=True)      # :182
     ret["ref_bg_rgb_256"], ret["weights_256"], ret["x"], ret["ws"], ret["rgb"] = ref_bg_rgb_256, weights_256, x, ws3, rgb
     return ret
@@ -311,23 +289,16 @@ def infer_forward_stage2(self, facev2v_ret, **block_kwargs):
     x_bg = self.bg_encoder(ref_bg_rgb_256)                                                              # :198
     kw = dict(block_kwargs)
     kw.setdefault("noise_mode", "none")
-    b1 = self.block1
-    saved = (b1.out_format, b1.return_x)
-    try:
-        b1.out_format, b1.return_x = "nchw", True
-        if hp.get("weight_fuse", True):
-            rgb = blend(rgb, rgb_torso, weights_256)                                                    # :201
-            x = blend(x, x_torso, weights_256)                                                          # :202
-            torso_occ = resize_bilinear(facev2v_ret["occlusion_2"], (256, 256), self.sr_antialias)     # :206
-            pocc = person_occlusion(weights_256, torso_occ, 0.5)                                        # :204-207
-            rgb = blend(rgb, ref_bg_rgb_256, pocc)                                                      # :209
-            x = self.fuse_fg_bg_convs(blend_cat(x, x_bg, pocc, self.fuse_fg_bg_convs))                  # :210-211
-            x, rgb = b1(x, rgb, ws3, **kw)                                                              # :212
-        else:
-            raise NotImplementedError("weight_fuse=False: block1 is called with img=None there (sr_with_ref.py:214-216), which the HIP "
-                                      "SynthesisBlock does not build")
-    finally:
-        b1.out_format, b1.return_x = saved
+    if not hp.get("weight_fuse", True):
+        raise NotImplementedError("weight_fuse=False: block1 is called with img=None there (sr_with_ref.py:214-216), which the HIP "
+                                  "SynthesisBlock does not build")
+    rgb = blend(rgb, rgb_torso, weights_256)                                                            # :201
+    x = blend(x, x_torso, weights_256)                                                                  # :202
+    torso_occ = resize_bilinear(facev2v_ret["occlusion_2"], (256, 256), self.sr_antialias)             # :206
+    pocc = person_occlusion(weights_256, torso_occ, 0.5)                                                # :204-207
+    rgb = blend(rgb, ref_bg_rgb_256, pocc)                                                              # :209
+    x = self.fuse_fg_bg_convs(blend_cat(x, x_bg, pocc, self.fuse_fg_bg_convs))                          # :210-211
+    x, rgb = self.block1(x, rgb, ws3, _out_format="nchw", _return_x=True, **kw)                         # :212
     return rgb, facev2v_ret
 
 

@@ -28,6 +28,8 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from .sr_activation import (FMT, MAX_DEPTH, SPLIT_FORMATS, _keep_tags, _tag, as_input, bound_of, empty, fmt_of, logical_shape, out_target,  # noqa: F401
+                            tag_bound, tag_split)          # (_tag, _keep_tags, bound_of, MAX_DEPTH: imported from here by tests and scripts)
 from .volumetric_rendering import _FC, _f32c
 
 _SQRT2 = float(np.sqrt(2.0))
@@ -109,44 +111,11 @@ def set_sr_precision(module, precision):
                 m.precision = precision
     return module
 
-MAX_DEPTH = 3      # a stored fp16 operand may be at most this many conv layers away from a measured / known max|x|
-
-
 # f16mx main loops only within this many layers of a measured bound (ConvStack.forward).  Round 4: 2 -- the e4m3 records carried one exponent
 # per tensor and went subnormal three propagated bounds (~15 binades) from a measurement.  Round 5: the e5m2 records have the fp16 hi plane's own
 # exponent range, so an MX operand is usable wherever a SPLIT operand is (MAX_DEPTH), including the hand-offs between a stack and a block
 # (fuse_fg_bg_convs -> block1: depth 3); measured at depth 3: to_plane_cnn 2.9e-5 (2.2e-5 at depth 2), torso frame 4.0e-5 of max|ref|.
 MX_MAX_DEPTH = int(os.environ.get("R3D_MX_MAX_DEPTH", str(MAX_DEPTH)))
-
-
-def bound_of(x, meter, layers=1):
-    """(bound, depth) of an fp32 activation that is about to enter a chain of `layers` conv layers folded together.  The propagated
-    bound loosens ~5 binades per layer and the fp16 window has ~16, so a tag (`_r3d_bound`, `_r3d_depth` = layers since the last
-    measurement) is only trusted while the deepest operand of the chain stays within MAX_DEPTH layers of a measurement; otherwise
-    max|x| is measured on the device (depth 0)."""
-    b = getattr(x, "_r3d_bound", None)
-    d = int(getattr(x, "_r3d_depth", 0))
-    if b is not None and d + layers - 1 <= MAX_DEPTH:
-        return b, d
-    return meter(x), 0
-
-
-def _tag(y, bound, depth):
-    y._r3d_bound, y._r3d_depth = bound, depth
-    return y
-
-
-def _keep_tags(x):
-    """_f32c (detach) drops python attributes: carry the range tags over."""
-    y = _f32c(x)
-    if y is not x:
-        b = getattr(x, "_r3d_bound", None)
-        if b is not None:
-            _tag(y, b, int(getattr(x, "_r3d_depth", 0)))
-        fmt = getattr(x, "_r3d_fmt", None)
-        if fmt is not None:
-            y._r3d_fmt = fmt
-    return y
 
 
 def chain_fold(ops, N, ext, zero=()):
@@ -161,6 +130,17 @@ def chain_fold(ops, N, ext, zero=()):
     zptrs = (ctypes.c_void_p * max(1, len(zero)))(*[t.data_ptr() for t in zero])
     _lib.check(lib.r3d_chain_fold(ctypes.cast(arr, ctypes.c_void_p), len(ops), N, ctypes.cast(ptrs, ctypes.c_void_p), len(ext),
                                   ctypes.cast(zptrs, ctypes.c_void_p), len(zero), _lib.stream_ptr()), "chain_fold")
+
+
+class _DeviceBuffers:
+    """`_buf(name, nbytes, dev)`: the uint8 device buffer kept in attribute `name`, grown (or moved) when it does not hold nbytes on dev."""
+
+    def _buf(self, name, nbytes, dev):
+        t = getattr(self, name)
+        if t is None or t.numel() < nbytes or t.device != dev:
+            t = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+            setattr(self, name, t)
+        return t
 
 
 class SynthesisLayer(nn.Module):
@@ -194,7 +174,7 @@ class ToRGBLayer(nn.Module):
         self.weight_gain = 1 / np.sqrt(in_channels * (kernel_size ** 2))
 
 
-class SynthesisBlock(nn.Module):
+class SynthesisBlock(_DeviceBuffers, nn.Module):
     """networks_stylegan2.py:377-476 for the configuration the SR path instantiates: in_channels != 0,
     architecture 'skip', up=2 conv0 + conv1 + toRGB, fp32.
 
@@ -246,14 +226,7 @@ class SynthesisBlock(nn.Module):
         self._depth_in = 0             # layers between the last measurement and this block's input (set by whoever folds it)
         self._fold_epoch = 0           # bumped by every chain_op(): lets a caller see that nobody re-folded the block since its own fold
 
-    def _buf(self, name, nbytes, dev):
-        t = getattr(self, name)
-        if t is None or t.numel() < nbytes or t.device != dev:
-            t = torch.empty(nbytes, device=dev, dtype=torch.uint8)
-            setattr(self, name, t)
-        return t
-
-    _FMT = {"none": -1, "nchw": 0, "cb8": 1, "split": 2, "split_mx": 3}      # split_mx: SPLIT with fp8 records in the lo plane (f16mx hand-off between up blocks)
+    _FMT = FMT
     _PREC = {"f32": 0, "f16x3": 1, "f16mx": 2}
 
     def _prec(self):
@@ -321,7 +294,9 @@ class SynthesisBlock(nn.Module):
         return self._styles.view(torch.float32).as_strided((N,), (self.styles_stride(),), off).contiguous()
 
     def forward(self, x, img, ws, force_fp32=False, fused_modconv=None, update_emas=False, noise_mode="random",
-                _prepared=None, _next=None, _folded=False, _u8_out=None, _need_img=True, _x_absmax=None, **layer_kwargs):
+                _prepared=None, _next=None, _folded=False, _u8_out=None, _need_img=True, _x_absmax=None, _out_format=None, _return_x=None,
+                **layer_kwargs):
+        """_out_format / _return_x: `self.out_format` / `self.return_x` for this call only (None: the attribute)."""
         lib = _lib.load()
         if noise_mode == "random" or (noise_mode == "const" and
                                       (float(self.conv0.noise_strength) != 0 or float(self.conv1.noise_strength) != 0)):
@@ -329,14 +304,8 @@ class SynthesisBlock(nn.Module):
                                       "(img2plane_baseline.py:113)" % noise_mode)
         if img is None:
             raise NotImplementedError("img=None (first block of a synthesis network) is not on the SR path")
-        x_fmt = getattr(x, "_r3d_fmt", "nchw")
-        if x_fmt in ("split", "split_mx"):
-            if getattr(x, "_r3d_for", None) is not self:
-                raise RuntimeError("SPLIT activation was scaled for a different consumer")
-            _folded = True
-            x = x.contiguous()
-        else:
-            x = _keep_tags(x)
+        x, x_fmt, presplit = as_input(x, self)
+        _folded = _folded or presplit
         img = _f32c(img)
         N = img.shape[0]
         Hin, Win = img.shape[-2], img.shape[-1]
@@ -353,34 +322,26 @@ class SynthesisBlock(nn.Module):
         work = self._buf("_workspace", need, dev)
         OH, OW = (2 * Hin, 2 * Win) if self._UP else (Hin, Win)
         img_out = torch.empty(N, 3, OH, OW, device=dev, dtype=torch.float32) if (_need_img or _u8_out is None) else None
-        out_fmt = self.out_format if self.return_x else "none"
-        next_scale, next_stride = None, 0
-        if out_fmt == "none":
-            x_out = None
-        elif out_fmt in ("split", "split_mx"):
-            if _next is None:
-                raise RuntimeError("out_format=%r needs the consumer (`_next`: its folded in-multiplier)" % out_fmt)
-            if out_fmt == "split_mx" and not (prec == 2 and _next.wants_mx()):
-                # mixed per-module precision: only an f16mx block writes the fp8 records, and only an f16mx consumer reads them
-                out_fmt = "split"
-            next_scale, next_stride = _next.in_scale()
-            x_out = torch.empty(N, 2, Cout // 8, OH, OW, 8, device=dev, dtype=torch.float16)
-        elif out_fmt == "cb8":
-            x_out = torch.empty(N, Cout // 8, OH, OW, 8, device=dev, dtype=torch.float32)
-        else:
-            x_out = torch.empty(N, Cout, OH, OW, device=dev, dtype=torch.float32)
+        want_x = self.return_x if _return_x is None else _return_x
+        # mixed per-module precision: only an f16mx block writes the fp8 records, and only an f16mx consumer reads them
+        out_fmt, next_scale, next_stride = out_target((self.out_format if _out_format is None else _out_format) if want_x else "none", prec == 2, _next)
+        x_out = None if out_fmt == "none" else empty(out_fmt, N, Cout, OH, OW, dev)
         _lib.check(lib.r3d_sr_block_forward(_lib.ptr(pre), _lib.ptr(styles), N, Cin, Cout, Hin, Win, self._UP,
-                                            _lib.ptr(x), self._FMT[x_fmt], _lib.ptr(img), self._clamp(), _lib.ptr(x_out), self._FMT[out_fmt],
+                                            _lib.ptr(x), FMT[x_fmt], _lib.ptr(img), self._clamp(), _lib.ptr(x_out), FMT[out_fmt],
                                             _lib.ptr(next_scale), next_stride, _lib.ptr(img_out), _lib.ptr(_u8_out), _lib.ptr(_x_absmax), prec,
                                             _lib.ptr(work), need, st), "sr_block_forward")
-        if x_out is not None:
-            if out_fmt != "nchw":
-                x_out._r3d_fmt = out_fmt
-            if out_fmt in ("split", "split_mx"):
-                x_out._r3d_for = _next
-            elif prec >= 1:
-                _tag(x_out, self.bound_out(N), self._depth_in + 2)
+        if out_fmt in SPLIT_FORMATS:
+            tag_split(x_out, out_fmt, _next)
+        elif x_out is not None and prec >= 1:
+            tag_bound(x_out, self.bound_out(N), self._depth_in + 2)
         return x_out, img_out
+
+    def num_layers(self):
+        return 2
+
+    def fold_for_input(self, N, dev, bounds, ws=None, depth=0):
+        assert ws is not None, "folding a SynthesisBlock needs its ws"
+        return _fold_single(self, N, dev, bounds, ws=ws, depth=depth)
 
 
 class SynthesisBlockNoUp(SynthesisBlock):
@@ -391,7 +352,7 @@ class SynthesisBlockNoUp(SynthesisBlock):
     _UP = 0
 
 
-class Conv2d(nn.Module):
+class Conv2d(_DeviceBuffers, nn.Module):
     """torch.nn.Conv2d(in_channels, out_channels, k, 1, padding=k//2) on the HIP conv kernel (r3d_conv_forward), with
     torch's parameter names/shapes so the reference's state_dict loads unchanged.  Covers what the torso / background
     fusion stacks of sr_with_ref.py:24-63 use: k in {1, 3}, stride 1, 'same' zero padding, bias."""
@@ -420,9 +381,6 @@ class Conv2d(nn.Module):
         # block-scaled 8-bit MFMA; the PRODUCER of the input asks `wants_mx()` and writes the records | 'f16x3' (fp32-class).  'f32' = 'f16x3'
         # here (the plain convs have no exact-f32 kernel).  R3D_SR_PRECISION / set_sr_precision() as for the SR blocks.
         self.precision = os.environ.get("R3D_SR_PRECISION", DEFAULT_SR_PRECISION)
-
-    _buf = SynthesisBlock._buf
-    _FMT = SynthesisBlock._FMT
 
     def wants_mx(self):
         return self.precision == "f16mx" and self.kernel_size[0] == 3 and self.in_channels % 16 == 0
@@ -455,18 +413,10 @@ class Conv2d(nn.Module):
         off = int(lib.r3d_conv_scales_bound_offset(self.in_channels, self.out_channels))
         return self._scales.view(torch.float32).as_strided((N,), (self.in_scale()[1],), off).contiguous()     # dense float[N] (a copy for N > 1)
 
-    @staticmethod
-    def _shape(x, x_fmt):
-        if x_fmt == "nchw":
-            return x.shape
-        if x_fmt == "cb8":
-            return x.shape[0], x.shape[1] * 8, x.shape[2], x.shape[3]
-        return x.shape[0], x.shape[2] * 8, x.shape[3], x.shape[4]
-
     def can_blend(self, a, b):
         """May `cat([a * m, b * (1 - m)])` be fused into this conv (r3d_conv_forward_blend)?  1x1, both sources channel-blocked fp32, Cin % 64 == 0."""
-        return (self.kernel_size[0] == 1 and getattr(a, "_r3d_fmt", None) == "cb8" and getattr(b, "_r3d_fmt", None) == "cb8"
-                and (a.shape[1] + b.shape[1]) * 8 == self.in_channels and self.in_channels % 64 == 0)
+        return (self.kernel_size[0] == 1 and fmt_of(a) == "cb8" and fmt_of(b) == "cb8"
+                and logical_shape(a)[1] + logical_shape(b)[1] == self.in_channels and self.in_channels % 64 == 0)
 
     def forward(self, x, negative_slope=None, out_format="nchw", _next=None, _folded=False, _y_absmax=None, _blend=None):
         """negative_slope: fuse a following torch.nn.LeakyReLU(negative_slope); out_format 'nchw' | 'cb8' | 'split'
@@ -477,26 +427,21 @@ class Conv2d(nn.Module):
         if _blend is not None:
             a, b, mask = _blend
             assert _folded and self.can_blend(a, b), "fused blend: a folded 1x1 conv over two 'cb8' sources"
+            (N, Ca, H, W), (Nb, Cb, Hb, Wb) = logical_shape(a), logical_shape(b)
             a, b, mask = a.contiguous(), b.contiguous(), _f32c(mask)
-            N, H, W = a.shape[0], a.shape[2], a.shape[3]
-            assert tuple(b.shape[:1] + b.shape[2:4]) == (N, H, W) and tuple(mask.shape) == (N, 1, H, W), (a.shape, b.shape, mask.shape)
-            y, next_scale, next_stride = self._alloc_out(N, H, W, out_format, _next, a.device)
-            _lib.check(lib.r3d_conv_forward_blend(_lib.ptr(self._prepacked), _lib.ptr(self._scales), _lib.ptr(self._bias32), N, a.shape[1] * 8, b.shape[1] * 8,
+            assert (Nb, Hb, Wb) == (N, H, W) and tuple(mask.shape) == (N, 1, H, W), (a.shape, b.shape, mask.shape)
+            out_format, next_scale, next_stride = out_target(out_format, True, _next)
+            y = empty(out_format, N, self.out_channels, H, W, a.device)
+            _lib.check(lib.r3d_conv_forward_blend(_lib.ptr(self._prepacked), _lib.ptr(self._scales), _lib.ptr(self._bias32), N, Ca, Cb,
                                                   self.out_channels, H, W, _lib.ptr(a), _lib.ptr(b), _lib.ptr(mask),
                                                   0 if negative_slope is None else 1, float(negative_slope or 0.0), 1.0, -1.0,
-                                                  _lib.ptr(y), self._FMT[out_format], _lib.ptr(next_scale), next_stride, _lib.ptr(_y_absmax), _lib.stream_ptr()),
+                                                  _lib.ptr(y), FMT[out_format], _lib.ptr(next_scale), next_stride, _lib.ptr(_y_absmax), _lib.stream_ptr()),
                        "conv_forward_blend")
-            return self._tag_out(y, out_format, _next, N)
-        x_fmt = getattr(x, "_r3d_fmt", "nchw")
-        if x_fmt in ("split", "split_mx"):
-            if getattr(x, "_r3d_for", None) is not self:
-                raise RuntimeError("SPLIT activation was scaled for a different consumer")
-            _folded = True
-            x = x.contiguous()
-        else:
-            x = _keep_tags(x)
+            return self._tagged(y, out_format, _next, N)
+        N, C, H, W = logical_shape(x)
+        x, x_fmt, presplit = as_input(x, self)
+        _folded = _folded or presplit
         Cin, Cout, k = self.in_channels, self.out_channels, self.kernel_size[0]
-        N, C, H, W = self._shape(x, x_fmt)
         if C != Cin:
             raise RuntimeError("Conv2d: expected input with %d channels, got %d" % (Cin, C))
         dev = x.device
@@ -506,79 +451,64 @@ class Conv2d(nn.Module):
             bx, self._depth_in = bound_of(x, self._meter, layers=1)
             chain_fold([self.chain_op(-1, negative_slope=negative_slope)], N, [bx])
         need = int(lib.r3d_conv_workspace_bytes(N, Cin, H, W))
-        work = self._buf("_workspace", need, dev) if x_fmt not in ("split", "split_mx") else None
-        y, next_scale, next_stride = self._alloc_out(N, H, W, out_format, _next, dev)
+        work = self._buf("_workspace", need, dev) if not presplit else None
+        out_format, next_scale, next_stride = out_target(out_format, True, _next)
+        y = empty(out_format, N, Cout, H, W, dev)
         act = 0 if negative_slope is None else 1
         _lib.check(lib.r3d_conv_forward(_lib.ptr(self._prepacked), _lib.ptr(self._scales), _lib.ptr(self._bias32), N, Cin, Cout, H, W, k,
-                                        _lib.ptr(x), self._FMT[x_fmt], act, float(negative_slope or 0.0), 1.0, -1.0,
-                                        _lib.ptr(y), self._FMT[out_format], _lib.ptr(next_scale), next_stride, _lib.ptr(_y_absmax),
+                                        _lib.ptr(x), FMT[x_fmt], act, float(negative_slope or 0.0), 1.0, -1.0,
+                                        _lib.ptr(y), FMT[out_format], _lib.ptr(next_scale), next_stride, _lib.ptr(_y_absmax),
                                         _lib.ptr(work), need if work is not None else 0, st), "conv_forward")
-        return self._tag_out(y, out_format, _next, N)
+        return self._tagged(y, out_format, _next, N)
+
+    def _tagged(self, y, out_format, _next, N):
+        if out_format in SPLIT_FORMATS:
+            return tag_split(y, out_format, _next)
+        return tag_bound(y, self.bound_out(N), self._depth_in + 1)
+
+    def num_layers(self):
+        return 1
+
+    def fold_for_input(self, N, dev, bounds, ws=None, depth=0):
+        return _fold_single(self, N, dev, bounds, depth=depth)
 
     def forward_cat(self, x, dst, chan_off, mask, mask_invert, _next, negative_slope=None):
         """This (already folded) 1x1 conv's output as channels [chan_off, chan_off + out_channels) of the concatenated SPLIT / SPLIT_MX tensor `dst`
         ([N, 2, C_total / 8, H, W, 8] halfs, tagged `_r3d_fmt`), times mask (or 1 - mask) per pixel and the in-multiplier of `_next`, the consumer of
         `dst` (r3d_conv_forward_cat): `x_torso = torso_encoder(hid)` + its half of `cat([x * a, x_torso * (1 - a)])` (sr_with_ref.py:88,104)."""
         lib = _lib.load()
-        x_fmt = getattr(x, "_r3d_fmt", "nchw")
+        x_fmt = fmt_of(x)
         assert x_fmt in ("nchw", "cb8") and self.kernel_size[0] == 1, "forward_cat: a 1x1 conv over an fp32 input"
+        N, C, H, W = logical_shape(x)
         x = _f32c(x)
-        N, C, H, W = self._shape(x, x_fmt)
-        assert C == self.in_channels and tuple(dst.shape[:2]) == (N, 2) and tuple(dst.shape[3:]) == (H, W, 8) and tuple(mask.shape) == (N, 1, H, W)
+        Nd, C_total, Hd, Wd = logical_shape(dst)
+        assert C == self.in_channels and fmt_of(dst) in SPLIT_FORMATS and (Nd, Hd, Wd) == (N, H, W) and tuple(mask.shape) == (N, 1, H, W)
         need = int(lib.r3d_conv_workspace_bytes(N, C, H, W))
         work = self._buf("_workspace", need, x.device)
         ns, stride = _next.in_scale()
         _lib.check(lib.r3d_conv_forward_cat(_lib.ptr(self._prepacked), _lib.ptr(self._scales), _lib.ptr(self._bias32), N, C, self.out_channels, H, W, 1,
-                                            _lib.ptr(x), self._FMT[x_fmt], 0 if negative_slope is None else 1, float(negative_slope or 0.0), 1.0, -1.0,
-                                            _lib.ptr(dst), self._FMT[dst._r3d_fmt], dst.shape[2] * 8, chan_off, _lib.ptr(_f32c(mask)), int(bool(mask_invert)),
+                                            _lib.ptr(x), FMT[x_fmt], 0 if negative_slope is None else 1, float(negative_slope or 0.0), 1.0, -1.0,
+                                            _lib.ptr(dst), FMT[fmt_of(dst)], C_total, chan_off, _lib.ptr(_f32c(mask)), int(bool(mask_invert)),
                                             _lib.ptr(ns), stride, _lib.ptr(work), need, _lib.stream_ptr()), "conv_forward_cat")
         return dst
-
-    def _alloc_out(self, N, H, W, out_format, _next, dev):
-        Cout = self.out_channels
-        next_scale, next_stride = None, 0
-        if out_format in ("split", "split_mx"):      # split_mx: fp8 records in the lo plane, for an f16mx SynthesisBlock that consumes y
-            assert _next is not None, "out_format='split' needs the consumer (its folded in-multiplier)"
-            next_scale, next_stride = _next.in_scale()
-            y = torch.empty(N, 2, Cout // 8, H, W, 8, device=dev, dtype=torch.float16)
-        elif out_format == "cb8":
-            y = torch.empty(N, Cout // 8, H, W, 8, device=dev, dtype=torch.float32)
-        else:
-            y = torch.empty(N, Cout, H, W, device=dev, dtype=torch.float32)
-        return y, next_scale, next_stride
-
-    def _tag_out(self, y, out_format, _next, N):
-        if out_format != "nchw":
-            y._r3d_fmt = out_format
-        if out_format in ("split", "split_mx"):
-            y._r3d_for = _next
-        else:
-            _tag(y, self.bound_out(N), self._depth_in + 1)
-        return y
 
 
 def upsample2x_bilinear(x, out_format="split", _next=None):
     """torch.nn.UpsamplingBilinear2d(scale_factor=2.) (align_corners=True) on a channel-blocked fp32 activation
     (r3d_upsample2x_bilinear); output 'split' / 'split_mx' (input of the conv `_next`, already folded) or 'cb8'."""
     lib = _lib.load()
-    assert getattr(x, "_r3d_fmt", None) == "cb8", "upsample2x_bilinear takes the 'cb8' output of a Conv2d"
+    assert fmt_of(x) == "cb8", "upsample2x_bilinear takes the 'cb8' output of a Conv2d"
     bx, dx = getattr(x, "_r3d_bound", None), int(getattr(x, "_r3d_depth", 0))
+    N, C, H, W = logical_shape(x)
     x = x.contiguous()
-    N, C8, H, W, _ = x.shape
-    next_scale, next_stride = None, 0
-    if out_format in ("split", "split_mx"):
-        assert _next is not None
-        next_scale, next_stride = _next.in_scale()
-        y = torch.empty(N, 2, C8, 2 * H, 2 * W, 8, device=x.device, dtype=torch.float16)
-    else:
-        y = torch.empty(N, C8, 2 * H, 2 * W, 8, device=x.device, dtype=torch.float32)
-    _lib.check(lib.r3d_upsample2x_bilinear(_lib.ptr(x), N, C8 * 8, H, W, _lib.ptr(y), SynthesisBlock._FMT[out_format],
+    out_format, next_scale, next_stride = out_target(out_format, True, _next)
+    y = empty(out_format, N, C, 2 * H, 2 * W, x.device)
+    _lib.check(lib.r3d_upsample2x_bilinear(_lib.ptr(x), N, C, H, W, _lib.ptr(y), FMT[out_format],
                                            _lib.ptr(next_scale), next_stride, _lib.stream_ptr()), "upsample2x_bilinear")
-    y._r3d_fmt = out_format
-    if out_format in ("split", "split_mx"):
-        y._r3d_for = _next
+    if out_format in SPLIT_FORMATS:
+        tag_split(y, out_format, _next)
     elif bx is not None:
-        _tag(y, bx, dx)            # a convex combination does not raise the bound
+        tag_bound(y, bx, dx)       # a convex combination does not raise the bound
     return y
 
 
@@ -606,19 +536,16 @@ def blend_cat(a, b, mask, consumer, ws=None, _folded_head=None, _b_channels=None
     already folded it (inside a larger chain)."""
     lib = _lib.load()
 
-    def desc(t):
-        fmt = getattr(t, "_r3d_fmt", "nchw")
-        assert fmt in ("nchw", "cb8"), fmt
-        t = _keep_tags(t)
-        if fmt == "nchw":
-            return t, 0, t.shape[1], t.shape[0], t.shape[2], t.shape[3]
-        return t, 1, t.shape[1] * 8, t.shape[0], t.shape[2], t.shape[3]
-    a, fa, Ca, N, H, W = desc(a)
+    fa, fb = fmt_of(a), fmt_of(b)           # (b = None: 'nchw')
+    assert fa in ("nchw", "cb8") and fb in ("nchw", "cb8"), (fa, fb)
+    a = _keep_tags(a)
+    N, Ca, H, W = logical_shape(a)
     if b is None:
         assert _folded_head is not None and _b_channels
-        fb, Cb, Nb, Hb, Wb = 0, int(_b_channels), N, H, W
+        Nb, Cb, Hb, Wb = N, int(_b_channels), H, W
     else:
-        b, fb, Cb, Nb, Hb, Wb = desc(b)
+        b = _keep_tags(b)
+        Nb, Cb, Hb, Wb = logical_shape(b)
     mask = _f32c(mask)
     assert (N, H, W) == (Nb, Hb, Wb) and tuple(mask.shape) == (N, 1, H, W), (a.shape, b.shape, mask.shape)
     if _folded_head is not None:
@@ -629,14 +556,12 @@ def blend_cat(a, b, mask, consumer, ws=None, _folded_head=None, _b_channels=None
         (ba, da), (bb, db) = bound_of(a, meters[0], L), bound_of(b, meters[1], L)
         head = consumer.fold_for_input(N, a.device, [ba, bb], ws=ws, depth=max(da, db))
     ns, stride = head.in_scale()
-    y = _dst if _dst is not None else torch.empty(N, 2, (Ca + Cb) // 8, H, W, 8, device=a.device, dtype=torch.float16)
-    assert tuple(y.shape) == (N, 2, (Ca + Cb) // 8, H, W, 8) and y.is_contiguous()
     fmt = "split_mx" if head.wants_mx() else "split"       # an f16mx consumer: fp8 records in the lo plane
-    _lib.check(lib.r3d_blend_cat_to_split(_lib.ptr(a), fa, Ca, _lib.ptr(b), fb, Cb, _lib.ptr(mask), N, H, W, _lib.ptr(y), SynthesisBlock._FMT[fmt],
+    y = _dst if _dst is not None else empty(fmt, N, Ca + Cb, H, W, a.device)
+    assert tuple(y.shape) == (N, 2, (Ca + Cb) // 8, H, W, 8) and y.is_contiguous()
+    _lib.check(lib.r3d_blend_cat_to_split(_lib.ptr(a), FMT[fa], Ca, _lib.ptr(b), FMT[fb], Cb, _lib.ptr(mask), N, H, W, _lib.ptr(y), FMT[fmt],
                                           _lib.ptr(ns), stride, _lib.stream_ptr()), "blend_cat_to_split")
-    y._r3d_fmt = fmt
-    y._r3d_for = head
-    return y
+    return tag_split(y, fmt, head)
 
 
 def _fold_single(module, N, dev, bounds, ws=None, negative_slope=None, depth=0):
@@ -650,15 +575,6 @@ def _fold_single(module, N, dev, bounds, ws=None, negative_slope=None, depth=0):
         op = module.chain_op(-1, -2 if len(bounds) > 1 else _lib.CHAIN_SRC_NONE, negative_slope=negative_slope)
     chain_fold([op], N, bounds)
     return module
-
-
-def _block_fold_for_input(self, N, dev, bounds, ws=None, depth=0):
-    assert ws is not None, "folding a SynthesisBlock needs its ws"
-    return _fold_single(self, N, dev, bounds, ws=ws, depth=depth)
-
-
-SynthesisBlock.fold_for_input = _block_fold_for_input
-SynthesisBlock.num_layers = lambda self: 2
 
 
 class ConvStack(nn.Sequential):
@@ -733,20 +649,16 @@ class ConvStack(nn.Sequential):
         _blend = (a, b, mask) with x = None: the stack's input is cat([a * mask, b * (1 - mask)]) and its first conv computes it (Conv2d.can_blend;
         the caller has folded the stack for the two sources, as for blend_cat(_folded_head=...))."""
         plan = self._plan()
-        x_fmt = getattr(x, "_r3d_fmt", "nchw")
-        dx = int(getattr(x, "_r3d_depth", 0))
+        dx = 0                # a SPLIT input (untagged), as the fused blend: the caller folded the stack from the sources' bounds
         if _blend is not None:
             assert x is None
-            dx = 0            # as for blend_cat's untagged SPLIT output: the caller folded the stack from the sources' bounds
-        elif x_fmt in ("split", "split_mx"):
-            if getattr(x, "_r3d_for", None) is not plan[0][0]:
-                raise RuntimeError("SPLIT activation was scaled for a different consumer")
         else:
-            if not hasattr(self, "_meter_obj"):
-                object.__setattr__(self, "_meter_obj", _BoundMeter())
-            x = _keep_tags(x)
-            bx, dx = bound_of(x, self._meter_obj, len(plan))
-            self.fold_for_input(x.shape[0], x.device, [bx], depth=dx)
+            x, _, presplit = as_input(x, plan[0][0])
+            if not presplit:
+                if not hasattr(self, "_meter_obj"):
+                    object.__setattr__(self, "_meter_obj", _BoundMeter())
+                bx, dx = bound_of(x, self._meter_obj, len(plan))
+                self.fold_for_input(x.shape[0], x.device, [bx], depth=dx)
         for k, (m, slope, up) in enumerate(plan):
             nxt = plan[k + 1][0] if k + 1 < len(plan) else None
             # The fp8 records carry ONE exponent per tensor (the fold's bound), and a bound propagated through the layers' L1 norms loosens by
@@ -764,14 +676,6 @@ class ConvStack(nn.Sequential):
             else:
                 x = m(x, negative_slope=slope, out_format=out_format, _next=_next, _folded=True, _y_absmax=_y_absmax, _blend=bl)
         return x
-
-
-def _conv_fold_for_input(self, N, dev, bounds, ws=None, depth=0):
-    return _fold_single(self, N, dev, bounds, depth=depth)
-
-
-Conv2d.fold_for_input = _conv_fold_for_input
-Conv2d.num_layers = lambda self: 1
 
 
 class SuperresolutionHybrid8XDC(nn.Module):
@@ -855,7 +759,7 @@ class SuperresolutionHybrid8XDC(nn.Module):
         _need_img=False the fp32 image is not materialised and None is returned.
         x may be the renderer's SPLIT copy of the feature image (produced for `split_input_spec`): no conversion launch then."""
         b0, b1 = self.block0, self.block1
-        x_is_split = getattr(x, "_r3d_fmt", None) == "split"
+        x_is_split = fmt_of(x) == "split"
         if x_is_split:
             N, dev = x.shape[0], x.device
             bx, dx = const_bound(self.FEATURE_BOUND, N, dev), 0          # the bound split_input_spec folded for
@@ -872,10 +776,10 @@ class SuperresolutionHybrid8XDC(nn.Module):
         mx = x_absmax is not None              # (f16mx with R3D_MX_TAIL_FOLD=1)
         if b0.precision in ("f16x3", "f16mx"):
             # f16mx: block0's conv1 epilogue leaves fp8 records in the lo plane and block1's up-sampling conv runs its cross products on them
-            b0.out_format, nxt = ("split_mx" if b1.wants_mx() else "split"), b1
+            fmt0, nxt = ("split_mx" if b1.wants_mx() else "split"), b1
         else:
-            b0.out_format, nxt = "cb8", None
-        x, rgb = b0(x, rgb, ws3, _prepared=prep0, _next=nxt, _folded=True, _x_absmax=x_absmax, **block_kwargs)
+            fmt0, nxt = "cb8", None
+        x, rgb = b0(x, rgb, ws3, _prepared=prep0, _next=nxt, _folded=True, _x_absmax=x_absmax, _out_format=fmt0, **block_kwargs)
         if mx:
             # tail fold: block1's conv1 operand from the MEASURED max|x0|; clears the slot for the next frame (the kernel reads its
             # bounds before it zeroes) -- our own fold, so the main fold's signature stays valid

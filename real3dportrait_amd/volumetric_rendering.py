@@ -17,7 +17,7 @@ import ctypes
 import torch
 import torch.nn as nn
 
-from . import _lib
+from . import _lib, sr_activation
 
 
 def _f32c(t):
@@ -248,7 +248,7 @@ class ImportanceRenderer(nn.Module):
             sp_scale, sp_stride, consumer = _split_for
             R = int(round(M ** 0.5))
             assert R * R == M, "the SPLIT copy is an image: M must be a square"
-            x_split = torch.empty(N, 2, 4, R, R, 8, device=dev, dtype=torch.float16)
+            x_split = sr_activation.tag_split(sr_activation.empty("split", N, 32, R, R, dev), "split", consumer)
         _lib.check(lib.r3d_render_forward(
             _lib.ptr(planes_nhwc), N, H, W, D, _lib.ptr(w1), _lib.ptr(b1), _lib.ptr(w2), _lib.ptr(b2),
             _lib.ptr(o), _lib.ptr(d), M, Nc, Nf, float(rendering_options["box_warp"]),
@@ -259,7 +259,6 @@ class ImportanceRenderer(nn.Module):
             _lib.ptr(x_split), None if sp_scale is None else sp_scale.data_ptr(), int(sp_stride),
             _lib.ptr(self._workspace), need, _lib.stream_ptr()), "render_forward")
         if x_split is not None:
-            x_split._r3d_fmt, x_split._r3d_for = "split", consumer
             rgb._r3d_split = x_split
         return rgb, depth, wsum, valid
 

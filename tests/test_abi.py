@@ -231,6 +231,131 @@ def test_torso_conv_argument_errors():
     refused("conv3d conv3d_prec", b"overlap", full=1, D=1024, y=None, yn=X)                     # full depth: D depth taps, one output depth
 
 
+def test_sr_conv_argument_errors():
+    """What r3d_conv_forward / _cat / _blend and r3d_sr_block_forward refuse before any launch: rc -1 (-2 for the workspace) and a message with the
+    entry point's name and the rule.  Every call has exactly one defect unless its comment says otherwise; the pointers are fake, 1 TiB apart and
+    never dereferenced.  Rejected calls only: a valid one would launch (tests/test_gpu_blend_conv.py, test_gpu_sr_ops.py, test_gpu_raw_abi.py
+    run those), which is also why "no workspace is asked for a SPLIT input" cannot be shown here -- the workspace is the last rule."""
+    from real3dportrait_amd import _lib
+    lib = _lib.load()
+    PRE, SC, X, Y, MASK, A, B, NS, WS, IMG, IMGO, U8, AM = (i << 40 for i in range(1, 14))
+    NCHW, CB8, SPLIT, SPLIT_MX, BIG = 0, 1, 2, 3, 1 << 60
+    base = {
+        "conv_forward": dict(pre=PRE, sc=SC, N=1, Cin=64, Cout=128, H=16, W=16, k=3, x=X, xf=NCHW, y=Y, yf=NCHW, ns=None, ws=WS, wsb=BIG),
+        "conv_forward_cat": dict(pre=PRE, sc=SC, N=1, Cin=64, Cout=128, H=16, W=16, k=1, x=X, xf=NCHW, y=Y, yf=SPLIT, Ct=256, off=128, mask=MASK,
+                                 ns=NS, ws=WS, wsb=BIG),
+        "conv_forward_blend": dict(pre=PRE, sc=SC, N=1, Ca=32, Cb=32, Cout=128, H=16, W=16, a=A, b=B, mask=MASK, y=Y, yf=NCHW, ns=None),
+        "sr_block_forward": dict(pre=PRE, sc=SC, N=1, Cin=16, Cout=128, H=8, W=8, up=1, x=X, xf=NCHW, img=IMG, y=Y, yf=NCHW, ns=None, imgo=IMGO,
+                                 u8=None, am=None, prec=1, ws=WS, wsb=BIG)}
+
+    def call(fn, **over):
+        assert set(over) <= set(base[fn]), (fn, over)          # an override the entry point has no argument for would leave a valid call
+        a = dict(base[fn], **over)
+        args = {"conv_forward": lambda: (a["pre"], a["sc"], None, a["N"], a["Cin"], a["Cout"], a["H"], a["W"], a["k"], a["x"], a["xf"], 0, 0.0, 1.0, -1.0,
+                                         a["y"], a["yf"], a["ns"], 0, None, a["ws"], a["wsb"], None),
+                "conv_forward_cat": lambda: (a["pre"], a["sc"], None, a["N"], a["Cin"], a["Cout"], a["H"], a["W"], a["k"], a["x"], a["xf"], 0, 0.0, 1.0, -1.0,
+                                             a["y"], a["yf"], a["Ct"], a["off"], a["mask"], 1, a["ns"], 0, a["ws"], a["wsb"], None),
+                "conv_forward_blend": lambda: (a["pre"], a["sc"], None, a["N"], a["Ca"], a["Cb"], a["Cout"], a["H"], a["W"], a["a"], a["b"], a["mask"],
+                                               0, 0.0, 1.0, -1.0, a["y"], a["yf"], a["ns"], 0, None, None),
+                "sr_block_forward": lambda: (a["pre"], a["sc"], a["N"], a["Cin"], a["Cout"], a["H"], a["W"], a["up"], a["x"], a["xf"], a["img"], -1.0,
+                                             a["y"], a["yf"], a["ns"], 0, a["imgo"], a["u8"], a["am"], a["prec"], a["ws"], a["wsb"], None)}[fn]()
+        rc = getattr(lib, "r3d_" + fn)(*args)
+        return rc, lib.r3d_last_error()
+
+    def refused(fns, quote, rc=-1, **over):
+        for fn in fns.split():
+            got, msg = call(fn, **over)
+            assert got == rc and fn.encode() + b":" in msg and quote in msg, (fn, over, got, msg)
+
+    CONV, CAT, BLEND, BLOCK = "conv_forward", "conv_forward_cat", "conv_forward_blend", "sr_block_forward"
+    PLAIN, LAYERS = CONV + " " + CAT, " ".join((CONV, CAT, BLEND))
+    EVERY = LAYERS + " " + BLOCK
+    # ---- NULL pointers and non-positive sizes ---------------------------------------------------------------------------------------------
+    for key in ("pre", "sc"):
+        refused(EVERY, b"bad argument", **{key: None})
+    refused(PLAIN + " " + BLOCK, b"bad argument", x=None)
+    refused(LAYERS, b"bad argument", y=None)
+    refused(CAT + " " + BLEND, b"bad argument", mask=None)
+    refused(BLEND, b"bad argument", a=None)
+    refused(BLEND, b"bad argument", b=None)
+    refused(BLOCK, b"bad argument", img=None)
+    refused(BLOCK, b"bad argument", imgo=None)                                  # neither the fp32 nor the uint8 image
+    for key in ("N", "H", "W"):
+        refused(EVERY, b"bad argument", **{key: 0})
+        refused(EVERY, b"bad argument", **{key: -1})
+    refused(LAYERS, b"bad argument", Cout=0)
+    refused(PLAIN, b"bad argument", Cin=0)
+    refused(BLEND, b"bad argument", Ca=0)
+    refused(BLEND, b"bad argument", Cb=-8)
+    refused(BLOCK, b"bad argument", Cin=24)                                     # the block: Cin % 16, Cout % 128, up 0 | 1
+    refused(BLOCK, b"bad argument", Cout=64)
+    refused(BLOCK, b"bad argument", up=2)
+    # ---- kernel size ------------------------------------------------------------------------------------------------------------------------
+    for k in (0, 2, 5):
+        refused(CONV, b"bad argument", k=k)
+    refused(CAT, b"1x1", k=3)
+    # ---- activation formats -----------------------------------------------------------------------------------------------------------------
+    for f in (-1, 4):
+        refused(CONV, b"unsupported", xf=f)
+        refused(CONV, b"unsupported", yf=f)
+        refused(CAT, b"unsupported input", xf=f)
+        refused(BLEND, b"unsupported output", yf=f)
+        refused(BLOCK, b"unsupported activation format", xf=f)
+    for f in (NCHW, CB8, -1, 4):
+        refused(CAT, b"must be SPLIT or SPLIT_MX", yf=f)
+    refused(BLOCK, b"unsupported activation format", yf=4)
+    refused(BLOCK, b"unsupported activation format", yf=-2)
+    refused(CONV, b"unsupported", xf=SPLIT_MX, k=1)                             # fp8 records: the 3x3 kernels only
+    refused(CAT, b"unsupported input", xf=SPLIT_MX)                             # (so never for the 1x1 conv of _cat)
+    refused(CONV, b"unsupported", xf=SPLIT_MX, Cin=24)                          # ... in whole 16-channel groups
+    refused(CONV, b"unsupported", yf=SPLIT_MX, Cout=24)
+    refused(BLEND, b"unsupported output", yf=SPLIT_MX, Cout=24)
+    for f in (CB8, SPLIT):
+        refused(CONV, b"blocked formats", xf=f, Cin=24)
+        refused(CAT, b"unsupported input", xf=f, Cin=24)
+        refused(CONV, b"blocked formats", yf=f, Cout=12)
+        refused(BLEND, b"unsupported output", yf=f, Cout=12)
+    refused(CONV, b"multiple of 4", Cout=30)
+    refused(BLEND, b"unsupported output", Cout=30)                              # Cout % 4 for an NCHW output too
+    # ---- the concatenation part and the blend operand -----------------------------------------------------------------------------------------
+    refused(CAT, b"multiples of 16", Cout=24)
+    refused(CAT, b"multiples of 16", off=120)
+    refused(CAT, b"multiples of 16", Ct=264)
+    refused(CAT, b"chan_off + Cout <= C_total", off=-16)
+    refused(CAT, b"chan_off + Cout <= C_total", off=144)
+    refused(CAT, b"chan_off + Cout <= C_total", Ct=240)
+    refused(BLEND, b"multiples of 8", Ca=36, Cb=28)
+    refused(BLEND, b"multiples of 8", Ca=28, Cb=36)
+    refused(BLEND, b"multiple of 64", Ca=8, Cb=40)
+    # ---- 2^32 elements per sample, through each entry point's own channel term; one channel group less passes (two defects: the workspace is next) ----
+    refused(CONV, b"32-bit index", H=4096, W=4096)                              # (max(Cin, Cout) + 128) H W = 2^32
+    refused(CONV, b"workspace", rc=-2, H=4096, W=4096, Cout=124, wsb=8)
+    refused(CONV, b"32-bit index", H=4096, W=4096, Cin=128, Cout=4)             # ... through Cin
+    refused(CAT, b"32-bit index", H=2048, W=2048, Ct=896, off=0)                # (max(Cin, C_total) + 128) H W = 2^32; Cout + 128 stays at 2^30
+    refused(CAT, b"workspace", rc=-2, H=2048, W=2048, Ct=880, off=0, wsb=8)
+    refused(BLEND, b"32-bit index", H=2048, W=2048, Ca=448, Cb=448, Cout=64)    # (max(Ca + Cb, Cout) + 128) H W = 2^32
+    refused(BLOCK, b"32-bit index", H=2048, W=2048, Cout=256)                   # max(Cin, Cout) (up ? 4 : 1) H W = 2^32
+    refused(BLOCK, b"workspace", rc=-2, H=2048, W=2048, Cout=256, up=0, wsb=8)
+    # ---- workspace ------------------------------------------------------------------------------------------------------------------------------
+    for f in (NCHW, CB8):
+        refused(PLAIN, b"workspace too small", rc=-2, xf=f, wsb=8)
+        refused(PLAIN, b"workspace too small", rc=-2, xf=f, ws=None)
+    refused(BLOCK, b"workspace too small", rc=-2, wsb=8)
+    refused(BLOCK, b"workspace too small", rc=-2, ws=None)
+    # ---- the block's precisions ---------------------------------------------------------------------------------------------------------------
+    refused(BLOCK, b"unknown precision", prec=3)
+    refused(BLOCK, b"unknown precision", prec=-1)
+    refused(BLOCK, b"uint8", prec=0, u8=U8)                                     # R3D_SR_F32: no fused uint8 image, no max|x|, no up = 0, no SPLIT
+    refused(BLOCK, b"x_absmax", prec=0, am=AM)
+    refused(BLOCK, b"up=0", prec=0, up=0)
+    refused(BLOCK, b"unsupported activation format", prec=0, xf=SPLIT)
+    refused(BLOCK, b"unsupported activation format", prec=0, yf=SPLIT, ns=NS)
+    refused(BLOCK, b"unsupported activation format", prec=1, xf=SPLIT_MX)        # fp8 records: R3D_SR_F16MX only
+    refused(BLOCK, b"unsupported activation format", prec=1, yf=SPLIT_MX, ns=NS)
+    for prec, f in ((1, SPLIT), (2, SPLIT), (2, SPLIT_MX)):
+        refused(BLOCK, b"unsupported activation format", prec=prec, yf=f)       # a SPLIT output without next_scale
+
+
 def test_product_has_no_oracle_dependency():
     """The oracle is test infrastructure: nothing under real3dportrait_amd/ may import or load it."""
     pkg = os.path.join(ROOT, "real3dportrait_amd")

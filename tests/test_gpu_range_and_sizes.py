@@ -307,6 +307,44 @@ def test_bounds_are_upper_bounds_and_stored_operands_fit_fp16(torch_cuda):
     assert float(blk.bound_out(1)[0]) >= float(xo.abs().max())
 
 
+@pytest.mark.parametrize("precision", ["f16x3", "f16mx"])
+@pytest.mark.parametrize("up", [True, False])
+def test_block_output_format_per_call_equals_the_attributes(torch_cuda, precision, up):
+    """block(..., _out_format=f, _return_x=True) is bit-identical in x and img to setting block.out_format = f / block.return_x = True and calling,
+    for the fp32 formats and for SPLIT scaled for a folded consumer; the per-call arguments win over the attributes and leave them as they were.
+    The smallest block the kernels accept."""
+    torch = torch_cuda
+    from real3dportrait_amd import synth
+    from real3dportrait_amd.superresolution import SynthesisBlock, SynthesisBlockNoUp, _BoundMeter, chain_fold
+    N, Cin, Cout, H = 2, 16, 128, 8
+    OH = 2 * H if up else H
+    blk = (SynthesisBlock if up else SynthesisBlockNoUp)(Cin, Cout, w_dim=512, resolution=OH, img_channels=3, is_last=False, conv_clamp=None).cuda()
+    load_block(torch, blk, synth.synth_sr_block(91, Cin, Cout, 512, 700))
+    nxt = SynthesisBlock(Cout, 128, w_dim=512, resolution=2 * OH, img_channels=3, is_last=True, conv_clamp=None).cuda()
+    load_block(torch, nxt, synth.synth_sr_block(92, Cout, 128, 512, 700))
+    blk.precision = nxt.precision = precision
+    x = T(torch, synth.hash_unitvar(93, (N, Cin, H, H), stream=1))
+    img = T(torch, synth.hash_unitvar(93, (N, 3, H, H), stream=2) * np.float32(0.5))
+    ws = T(torch, np.ones((N, 3, 512), np.float32) + synth.hash_unitvar(93, (N, 3, 512), stream=3) * np.float32(0.2))
+    for f in ("nchw", "cb8", "split"):
+        kw = {}
+        if f == "split":        # one fold for both calls: the block and the consumer its SPLIT output is scaled for
+            blk.prepare(ws, x.device); nxt.prepare(ws, x.device)
+            chain_fold([blk.chain_op(-1), nxt.chain_op(0)], N, [_BoundMeter()(x).clone()])
+            kw = dict(_next=nxt, _folded=True)
+        blk.out_format, blk.return_x = f, True
+        xa, ia = blk(x, img, ws, noise_mode="none", **kw)
+        blk.out_format, blk.return_x = "nchw", False
+        xb, ib = blk(x, img, ws, noise_mode="none", _out_format=f, _return_x=True, **kw)
+        assert (blk.out_format, blk.return_x) == ("nchw", False)
+        assert getattr(xa, "_r3d_fmt", "nchw") == getattr(xb, "_r3d_fmt", "nchw") == f and xa.dtype == xb.dtype and xa.shape == xb.shape
+        assert getattr(xb, "_r3d_for", None) is (nxt if f == "split" else None)
+        assert torch.equal(xa, xb) and torch.equal(ia, ib), (precision, up, f)
+        assert torch.isfinite(ia).all() and float(ia.abs().max()) > 0
+    none, _ = blk(x, img, ws, noise_mode="none")         # the attributes are the default
+    assert none is None
+
+
 # ------------------------------------------------------------------------------------------------
 # output side
 # ------------------------------------------------------------------------------------------------
