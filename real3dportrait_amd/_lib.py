@@ -93,7 +93,7 @@ SIGNATURES = {
 
 
 # test hooks outside the C ABI of include/r3d_hip.h: bound when the library exports them, absent otherwise (nothing in the product calls
-# them, and a library built from older sources -- the packed-f32 A/B partner of an earlier tree, say -- must keep loading)
+# them, and a library built from older sources -- the other side of a scripts/gpu_lib_ab.sh comparison, say -- must keep loading)
 OPTIONAL_SIGNATURES = {
     "r3d_debug_merge_fallbacks": (c_int, [ctypes.POINTER(ctypes.c_ulonglong), c_int]),
 }

@@ -491,27 +491,21 @@ __device__ __forceinline__ void conv_epilogue(const Conv2Args& a, const ConvPhas
 // One block: 128 couts x 16x16 pixels, WN x 2 waves; wave (wm, wn) owns couts [64wm, +64) and pixel rows
 // [2*NT*wn, +2*NT) as 2 x NT MFMA tiles (WN=2,NT=4: 4 waves x 128 accumulators; WN=4,NT=2: 8 waves x 64 accumulators
 // = 4 waves/SIMD at 2 blocks/CU).  Per stage = 16 input channels (two 8-channel blocks = one K=16 MFMA step per tap):
-// the halo patch (B operand, hi+lo) sits in LDS for all taps of the stage; the weights (A operand) go through LDS in
-// sub-stages of SUB taps.  All global loads are register-prefetched one (sub-)stage ahead, and the weight loads are
-// issued BEFORE the patch loads, so the compiler's counted s_waitcnt vmcnt(N) at the weight ds_write leaves the slow
-// (MALL/HBM) patch loads in flight under the MFMAs.
-// Only the 1x1 conv (NTAPS = 1, WN = 4, NT = 2) runs on this routine now: the 3x3 convs moved to conv3x3_dma_block, the transposed-conv phases
-// (NTAPS 4 / 2) and the 4-wave shape were retired (DESIGN "Retired experiment switches").  It stays generic in NTAPS: written out for one tap, hipcc
-// orders a few independent moves of the packed-f32 partner build's epilogue differently (profiles/switch_retirement/kernel_text_diff.txt).
-template <int NTAPS, int WN, int NT>
+// the patch (B operand, hi+lo; in the 18 x 18 layout of the 3x3 convs) and the weights (A operand) of the stage sit in LDS.  The patch loads are
+// register-prefetched one stage ahead, the weights come by LDS-DMA one stage ahead, issued BEFORE the patch loads.
+// One tap: only the 1x1 conv (WN = 4, NT = 2) runs on this routine; the 3x3 convs are conv3x3_dma_block's.
+template <int WN, int NT>
 __device__ __forceinline__ void conv2_block(const Conv2Args& a, const ConvPhase& ph, int n, uint4* lds)
 {
     static_assert(WN * NT == 8, "16 pixel rows per block");
     constexpr int NTHR = 128 * WN;
-    constexpr int SUB = NTAPS >= 9 ? 3 : (NTAPS >= 2 ? 2 : 1);        // taps per weight sub-stage
-    constexpr int NSUB = (NTAPS + SUB - 1) / SUB;                     // sub-stages per stage
     constexpr int B_ELEMS = 2 * 2 * F_PATCH_PIX;                      // uint4: planes x chunks x pixels = 1296
     constexpr int NPF = (B_ELEMS + NTHR - 1) / NTHR;
-    constexpr int A_ELEMS = SUB * 2 * 256;                            // uint4 per sub-stage: (tap, half-chunk) x (cout, hi|lo)
-    constexpr int A_BUF = 3 * 2 * 256;                                // uint4 per weight buffer (sized for SUB = 3)
+    constexpr int A_ELEMS = 2 * 256;                                  // uint4 of weights per stage: half-chunk x (cout, hi|lo)
+    constexpr int A_BUF = 3 * 2 * 256;                                // uint4 between the two weight buffers (the stage fills a third)
     constexpr int NAR = A_ELEMS / NTHR;
     uint4* patchB = lds;                                              // [plane][chunk][324]
-    uint4* bufA = lds + B_ELEMS;                                      // 2 x [SUB][2 chunks][hi|lo][128 couts], filled by LDS-DMA
+    uint4* bufA = lds + B_ELEMS;                                      // 2 x [2 chunks][hi|lo][128 couts], filled by LDS-DMA
     const int tiles_x = (ph.outW + F_TILE_W - 1) / F_TILE_W;
     const int tile = blockIdx.x;
     const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
@@ -540,7 +534,7 @@ __device__ __forceinline__ void conv2_block(const Conv2Args& a, const ConvPhase&
     int boff[NT];
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) boff[nt] = (row0 + nt * 2 + prow + 1) * F_PATCH_W + (pcol + 1) + h * F_PATCH_PIX;
-    const int aoff = h * 256 + 64 * wm + li;                          // [ts][hc = h][hi|lo][128 couts]: + ts*512 + mt*32 (+128 for lo)
+    const int aoff = h * 256 + 64 * wm + li;                          // [hc = h][hi|lo][128 couts]: + mt*32 (+128 for lo)
 
     const int chunk_stride = a.H * a.W;
     uint4 pf[NPF];
@@ -574,88 +568,74 @@ __device__ __forceinline__ void conv2_block(const Conv2Args& a, const ConvPhase&
         }
     };
     // weights: global -> LDS by DMA (global_load_lds_dwordx4: LDS address = wave-uniform base + lane*16; the
-    // sub-stage image is linear in e = tid + NTHR*k, so a wave's 64 lanes fill one contiguous KB); no VGPRs, no ds_write
+    // stage image is linear in e = tid + NTHR*k, so a wave's 64 lanes fill one contiguous KB); no VGPRs, no ds_write
     const int tid_seg = __builtin_amdgcn_readfirstlane(threadIdx.x >> 7);      // 128-cout segment of this wave
     const int wave_u = __builtin_amdgcn_readfirstlane(wave);
     const unsigned tid_lo = threadIdx.x & 127;
-    auto dma_weights = [&](int c0, int sub, uint4* dstA) {
+    auto dma_weights = [&](int c0, uint4* dstA) {
 #pragma unroll
         for (int k = 0; k < NAR; ++k) {
-            const int seg = (NTHR >> 7) * k + tid_seg, t = sub * SUB + (seg >> 2), hc = (seg >> 1) & 1, hl = seg & 1;   // wave-uniform
-            if (t < NTAPS) {
-                const uint4* src = WP + (((size_t)ph.widx[t] * nchunks + (c0 + hc)) * 2 + hl) * a.Cout + m0;     // uniform
-                // inline asm: hipcc would otherwise put s_waitcnt vmcnt(0) in front of every ds_read while an LDS-DMA it
-                // knows about is in flight (no alias info inside one LDS array); waits for these DMAs are the explicit
-                // counted s_waitcnt vmcnt below (cdna_hip_programming.md section 5.7)
-                const unsigned lds_dst = __builtin_amdgcn_readfirstlane(
-                    (unsigned)(size_t)(__attribute__((address_space(3))) uint4*)(dstA + NTHR * k + 64 * wave_u));
-                const uint4* gsrc = src + tid_lo;
-                unsigned keep;
-                asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                             : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-            }
+            const int seg = (NTHR >> 7) * k + tid_seg, t = seg >> 2, hc = (seg >> 1) & 1, hl = seg & 1;   // wave-uniform
+            // seg < 4, so t is 0: hipcc does not see that through the readfirstlane and emits the test and the indexed widx load; written
+            // with a literal 0 the kernel's instructions change, and this routine's device code is kept as it is
+            if (t >= 1) continue;
+            const uint4* src = WP + (((size_t)ph.widx[t] * nchunks + (c0 + hc)) * 2 + hl) * a.Cout + m0;     // uniform
+            // inline asm: hipcc would otherwise put s_waitcnt vmcnt(0) in front of every ds_read while an LDS-DMA it
+            // knows about is in flight (no alias info inside one LDS array); waits for these DMAs are the explicit
+            // s_waitcnt vmcnt below (cdna_hip_programming.md section 5.7)
+            const unsigned lds_dst = __builtin_amdgcn_readfirstlane(
+                (unsigned)(size_t)(__attribute__((address_space(3))) uint4*)(dstA + NTHR * k + 64 * wave_u));
+            const uint4* gsrc = src + tid_lo;
+            unsigned keep;
+            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
+                         : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
         }
     };
 
-    int g = 0;                                                        // global sub-stage counter (weight buffer parity)
-    dma_weights(0, 0, bufA);
+    dma_weights(0, bufA);
     load_patch(0);
-    for (int c0 = 0; c0 < nchunks; c0 += 2) {
+    int g = 0;                                                        // stage counter (weight buffer parity)
+    for (int c0 = 0; c0 < nchunks; c0 += 2, ++g) {
+        __syncthreads();                                               // previous stage's patch reads are done
 #pragma unroll
-        for (int sub = 0; sub < NSUB; ++sub, ++g) {
-            if (sub == 0) {
-                __syncthreads();                                       // previous stage's patch reads are done
+        for (int k = 0; k < NPF; ++k) {
+            const int e = threadIdx.x + NTHR * k;
+            if (e < B_ELEMS) patchB[e] = pf[k];
+        }
+        // weights of this stage have landed (own DMAs) -> barrier -> everybody's have
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+        const uint4* curA = bufA + (g & 1) * A_BUF;
+        uint4* nxtA = bufA + ((g + 1) & 1) * A_BUF;
+        // next weights first, then the next patch: in-order vmcnt lets the weights be waited for while the slow patch loads are still in flight
+        if (c0 + 2 < nchunks) {
+            dma_weights(c0 + 2, nxtA);
+            load_patch(c0 + 2);
+        }
+        h8 ah[2], al[2];
 #pragma unroll
-                for (int k = 0; k < NPF; ++k) {
-                    const int e = threadIdx.x + NTHR * k;
-                    if (e < B_ELEMS) patchB[e] = pf[k];
-                }
-            }
-            // weights of this sub-stage have landed (own DMAs) -> barrier -> everybody's have
-            // (the NPF patch loads of the next stage were issued AFTER these DMAs during sub-stage 0: leave them in flight)
-            if (NSUB > 1 && sub == 1 && c0 + 2 < nchunks) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NPF) : "memory");
-            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-            asm volatile("" ::: "memory");
-            const uint4* curA = bufA + (g & 1) * A_BUF;
-            uint4* nxtA = bufA + ((g + 1) & 1) * A_BUF;
-            // next weights first, then (once per stage) the next patch: in-order vmcnt lets the weights be waited for
-            // while the slow patch loads are still in flight
-            {
-            if (sub + 1 < NSUB) dma_weights(c0, sub + 1, nxtA);
-            else if (c0 + 2 < nchunks) dma_weights(c0 + 2, 0, nxtA);
-            if (sub == 0 && c0 + 2 < nchunks) load_patch(c0 + 2);
-            }
+        for (int mt = 0; mt < 2; ++mt) {
+            uint4 q0 = curA[aoff + mt * 32], q1 = curA[aoff + mt * 32 + 128];
+            ah[mt] = *reinterpret_cast<h8*>(&q0); al[mt] = *reinterpret_cast<h8*>(&q1);
+        }
+        const int toff = ph.dy[0] * F_PATCH_W + ph.dx[0];
 #pragma unroll
-            for (int ts = 0; ts < SUB; ++ts) {
-                const int t = sub * SUB + ts;
-                if (t < NTAPS) {
-                    h8 ah[2], al[2];
+        for (int nt = 0; nt < NT; ++nt) {
+            uint4 r0 = patchB[boff[nt] + toff];
+            uint4 r1 = patchB[boff[nt] + toff + 2 * F_PATCH_PIX];
+            const h8 bh = *reinterpret_cast<h8*>(&r0), bl = *reinterpret_cast<h8*>(&r1);
 #pragma unroll
-                    for (int mt = 0; mt < 2; ++mt) {
-                        uint4 q0 = curA[ts * 512 + aoff + mt * 32], q1 = curA[ts * 512 + aoff + mt * 32 + 128];
-                        ah[mt] = *reinterpret_cast<h8*>(&q0); al[mt] = *reinterpret_cast<h8*>(&q1);
-                    }
-                    const int toff = ph.dy[t] * F_PATCH_W + ph.dx[t];
-#pragma unroll
-                    for (int nt = 0; nt < NT; ++nt) {
-                        uint4 r0 = patchB[boff[nt] + toff];
-                        uint4 r1 = patchB[boff[nt] + toff + 2 * F_PATCH_PIX];
-                        const h8 bh = *reinterpret_cast<h8*>(&r0), bl = *reinterpret_cast<h8*>(&r1);
-#pragma unroll
-                        for (int mt = 0; mt < 2; ++mt) {
-                            acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[mt], bh, acc[mt][nt], 0, 0, 0);
-                            acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[mt], bl, acc[mt][nt], 0, 0, 0);
-                            acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[mt], bh, acc[mt][nt], 0, 0, 0);
-                        }
-                    }
-                }
+            for (int mt = 0; mt < 2; ++mt) {
+                acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[mt], bh, acc[mt][nt], 0, 0, 0);
+                acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[mt], bl, acc[mt][nt], 0, 0, 0);
+                acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[mt], bh, acc[mt][nt], 0, 0, 0);
             }
         }
     }
     __syncthreads();
-    conv_epilogue<WN, NT, false, NTAPS == 1>(a, ph, n, acc, i0, j0, m0, reinterpret_cast<float*>(lds));
+    conv_epilogue<WN, NT, false, true>(a, ph, n, acc, i0, j0, m0, reinterpret_cast<float*>(lds));
 }
 
 // ---- plain 3x3 conv, LDS-DMA pipeline ------------------------------------------------------------------------------
@@ -943,7 +923,7 @@ template <int WN, int NT, int OCC>
 __global__ __launch_bounds__(128 * WN, OCC) void conv1x1_mfma_f16x3_kernel(Conv2Args a)
 {
     __shared__ uint4 lds[F_LDS_UINT4];
-    conv2_block<1, WN, NT>(a, a.ph[0], blockIdx.z, lds);
+    conv2_block<WN, NT>(a, a.ph[0], blockIdx.z, lds);
 }
 
 // ---- 1x1 conv with the alpha / occlusion blend + channel concatenation of its operand fused in (round 6) ------------------------------------------------------

@@ -1,9 +1,9 @@
 """What one build of the library computes -- the head frame (both SR precisions), ray-kernel shapes, the torso frame -- so that two builds can be
-compared.  `R3D_LIB` selects the build (default: the shipped library).  Used by tests/test_gpu_coresidency.py::test_build_without_packed_f32_agrees
-with `make NOPK=1` (no packed-f32 instruction in the code objects) against the product build (packed-f32 forms rewritten by
-csrc/tools/pk_opsel_fix.py).  The two compilations contract different mul + add pairs into fmas (fp-contract=fast around the SLP vectoriser), so the
-comparison is a tight tolerance, not a digest: fp32 ray-kernel outputs within 1e-5, uint8 frames within one count in < 0.2 % of the bytes, the torso frame's fp32 image within 3e-4 of its maximum -- an op_sel mix-up
-puts the wrong operand into a quarter of the lanes and is off by the operand's magnitude.
+compared.  `R3D_LIB` selects the build (default: the shipped library).  How a kernel change compares the outputs of the library of an older
+commit, or of one built with other flags, with the current one's (scripts/gpu_lib_ab.sh compares their timing).  Two compilations may contract different mul + add pairs into fmas (fp-contract=fast around the SLP
+vectoriser), so the comparison is a tight tolerance, not a digest: fp32 ray-kernel outputs within 1e-5, uint8 frames within one count in < 0.2 % of the
+bytes, the torso frame's fp32 image within 3e-4 of its maximum -- a wrong operand in a quarter of the lanes (the packed-f32 op_sel erratum, DESIGN 4.1a,
+which these tolerances were set for) is off by the operand's magnitude.
 usage: gpu_build_ab.py OUT.npz         compute with the build R3D_LIB names, save the arrays
        gpu_build_ab.py A.so B.so       run both as children and compare"""
 import hashlib, os, subprocess, sys, time

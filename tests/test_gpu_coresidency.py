@@ -1,11 +1,11 @@
 """GPU: results must not depend on what else is resident on the CUs.
 
 Round 3 found why round 2's experiment kernels sometimes did: on gfx950 a packed-f32 instruction whose src1 / src2 op_sel bit is set
-returns a wrong low half in lanes 48-63 while another wave of the SIMD executes MFMAs.  The build rewrites those forms
-(csrc/tools/pk_opsel_fix.py; tests/test_abi.py checks the shipped code objects).  These tests keep the hardware facts the rewrite relies
-on, and the end-to-end guarantees, honest:
-  * the stand-alone probe (scripts/probes/coexec_probe.hip): every pattern is exact when it runs alone, and the forms the rewriter EMITS
-    stay exact next to an MFMA load;
+returns a wrong low half in lanes 48-63 while another wave of the SIMD executes MFMAs.  The library is built without
+packed-f32 instructions (csrc/Makefile refuses them; tests/test_abi.py checks the shipped code objects).  These tests keep the hardware
+facts, and the end-to-end guarantees, honest:
+  * the stand-alone probe (scripts/probes/coexec_probe.hip): every pattern is exact when it runs alone, and the forms with a crossed src0,
+    a broadcast or a swapped SGPR stay exact next to an MFMA load;
   * the ray kernel (which now shares bilinear taps inside lane quads -- the variant that exposed the erratum) next to a synthetic MFMA
     load that made the unfixed variant differ in more than half of its frames;
   * the soak of scripts/gpu_soak_pipeline.py reduced to test size, for both SR precisions that run MFMAs next to packed-f32 epilogues.
@@ -56,15 +56,15 @@ def test_probe_rewritten_forms_are_exact_next_to_mfma_load():
         print("  pattern %d %-62s alone %d, next to MFMA load %d" % (k, r["name"], r["alone"], r["load"]))
     for k in (39, 40, 41, 42, 43, 44, 45, 46, 48, 49, 50):
         assert res[k]["alone"] == 0, (k, res[k])                    # every form is exact when nothing else runs
-    for k in (43, 44, 45, 49, 50):                                   # src0-crossed / broadcast / swapped-SGPR forms: what pk_opsel_fix.py emits or leaves
-        assert res[k]["load"] == 0, "form relied on by the build is not exact next to MFMAs: %r" % (res[k],)
+    for k in (43, 44, 45, 49, 50):                                   # src0-crossed / broadcast / swapped-SGPR forms: exact on the hardware
+        assert res[k]["load"] == 0, "form known as exact is not exact next to MFMAs: %r" % (res[k],)
     if res[39]["load"] == 0 and res[48]["load"] == 0:
         print("  NOTE: the erratum (patterns 39, 48) did not show on this device / firmware")
 
 
 def test_stand_alone_erratum_reproducer():
     """scripts/probes/pk_opsel_erratum_repro.hip (84 lines, no library; expected output profiles/r04/pk_opsel_erratum_repro.txt): the form
-    the build emits (src0 crossed) is exact alone and next to the conv-shaped MFMA load -- its exit code; the hazardous form (src1
+    with src0 crossed is exact alone and next to the conv-shaped MFMA load -- its exit code; the hazardous form (src1
     crossed) is exact alone.  That the hazardous form DOES miscompute next to the load is printed, not asserted: a fixed part would be
     good news, not a test failure."""
     import subprocess
@@ -163,22 +163,3 @@ def test_pipelined_frames_equal_sequential_soak(torch_cuda, precision):
         bad += int((ring != ref).flatten(1).any(dim=1).sum())
     assert bad == 0, "%d of %d pipelined frames differ from the sequential render" % (bad, passes * n)
 
-
-def test_build_with_packed_f32_agrees():
-    """The product is compiled without packed-f32 instructions (round 5: they buy nothing next to MFMAs and one of their forms is hazardous on gfx950,
-    DESIGN 4.1a).  Its A/B partner is the same source WITH them, every translation unit through the op_sel rewriter (`make PK=1`, built by
-    __graft_entry__.build_test_helpers(); the product build of rounds 3-4).  The two compilations contract different mul + add pairs
-    (fp-contract=fast around the SLP vectoriser), so the comparison is a tight tolerance -- fp32 ray-kernel outputs within 1e-5, uint8 frames within
-    one count in < 0.2 % of the bytes, the torso frame's fp32 image within 3e-4 of its maximum (nine f16mx convolutions deep) -- where a wrong
-    operand in a quarter of the lanes is off by the operand's magnitude: head frames (both SR precisions), four ray-kernel shapes, the torso frame."""
-    import subprocess
-    import sys
-    pk = os.path.join(ROOT, "tests", "_build", "libr3d_hip_pk.so")
-    assert os.path.exists(pk), "tests/_build/libr3d_hip_pk.so is missing: __graft_entry__.build() builds it"
-    listing = open(os.path.join(ROOT, "tests", "_build", "obj_pk", "r3d_render.fix.s")).read()
-    assert "v_pk_fma_f32" in listing and "v_pk_mul_f32" in listing                      # it really is the build with them
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "scripts", "gpu_build_ab.py"), "default", "tests/_build/libr3d_hip_pk.so"],
-                       capture_output=True, text=True, timeout=900, cwd=ROOT)
-    print(r.stdout)
-    assert r.returncode == 0 and "\nAGREE" in r.stdout, (r.stdout[-3000:], r.stderr[-1500:])
-    assert r.stdout.count("compare ") >= 3 + 4 * 3 and " BAD" not in r.stdout
