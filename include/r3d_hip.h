@@ -47,7 +47,8 @@ const char* r3d_last_error(void);
  * torch.flip calls SegFormerSECC2PlaneBackbone.forward applies to its conv output (modules/real3d/segformer.py:722-728:
  * planes 0,1 along H, plane 2 along H and W = 0b110101 = 53) when `add` is the raw to_plane_cnn output; 0 = none.
  * depth > 1: tri-grids (triplane_feature_type 'trigrid' / 'trigrid_v2', renderer.py:78-89): planes_nchw is
- * [N,3,C*depth,H,W] with channel c*depth + d (the reference's .view(N*3, C, D, H, W)) -> [N,3,depth,H,W,C]. */
+ * [N,3,C*depth,H,W] with channel c*depth + d (the reference's .view(N*3, C, D, H, W)) -> [N,3,depth,H,W,C].
+ * Limit: H * W <= 2^31 - 1 (the kernels index a plane with an int); larger planes are refused with R3D_ERR_INVALID_ARG. */
 #define R3D_SECC_PLANE_FLIPS 53
 int r3d_planes_to_nhwc(const float* planes_nchw, const float* add_nchw, float* planes_nhwc,
                        int N, int C, int H, int W, int depth, int add_flip, float* absmax_partials, int* n_partials,
@@ -59,7 +60,8 @@ size_t r3d_planes_absmax_partials(int N, int C, int H, int W, int depth);
 
 /* --- A1 ray generation --------------------------------------------------------------------------
  * Replaces RaySampler.forward(cam2world[N,4,4], intrinsics[N,3,3], resolution)
- * (modules/eg3ds/volumetric_rendering/ray_sampler.py:24-63).  origins/dirs: [N, R*R, 3]. */
+ * (modules/eg3ds/volumetric_rendering/ray_sampler.py:24-63).  origins/dirs: [N, R*R, 3].
+ * Limit: R * R <= 2^31 - 1 (R <= 46340); a larger image is refused with R3D_ERR_INVALID_ARG. */
 int r3d_raygen(const float* c2w, const float* intrinsics, int N, int R,
                float* origins, float* dirs, r3d_stream_t stream);
 
@@ -99,6 +101,8 @@ int r3d_raygen(const float* c2w, const float* intrinsics, int N, int R,
  *                exceeds 48 AND Nf > 0 (the kernel shapes with more than three 16-sample tiles per pass and a fine pass) also 24 KB per wave of the
  *                launch's grid (min(512, rays / 4 rounded up to 8) blocks x 4 waves: 48 MB for a full grid), in which a wave parks the colours of the
  *                ray it is rendering between the decode and the composite (ABI 0.5.0: they do not fit the register file; 0.6.0: sized from the grid).
+ * Limits, refused with R3D_ERR_INVALID_ARG: 3 * triplane_depth * H * W * 128 < 2^32 (the taps are 32-bit byte offsets into one image's planes) and
+ * N * M <= 2^31 - 1 (the kernels carry the ray index in an int).
  */
 size_t r3d_render_workspace_bytes(int N, int M, int Nc, int Nf);
 int r3d_render_forward(const float* planes_nhwc, int N, int H, int W, int triplane_depth,
@@ -120,7 +124,9 @@ int r3d_render_forward(const float* planes_nhwc, int N, int H, int W, int tripla
 
 /* Replaces ImportanceRenderer.run_model(planes, decoder, sample_coordinates, sample_directions, options)
  * (renderer.py:169-188; inference branches) -- the point-query used by .sample() (triplane.py:140-148).
- * coords [N,npts,3] -> rgb [N,npts,32], sigma [N,npts]. */
+ * coords [N,npts,3] -> rgb [N,npts,32], sigma [N,npts].
+ * Limits, refused with R3D_ERR_INVALID_ARG: 3 * triplane_depth * H * W * 8 < 2^31 (the gather indexes one image's planes with an int in 16-byte
+ * units) and H, W < 2^24 (24-bit row products). */
 int r3d_run_model(const float* planes_nhwc, int N, int H, int W, int triplane_depth,
                   const float* w1, const float* b1, const float* w2, const float* b2,
                   const float* coords, int npts, float box_warp,

@@ -18,6 +18,7 @@
 // Behaviour restated from (upstream repo paths): modules/eg3ds/volumetric_rendering/renderer.py:118-297,
 // ray_marcher.py:25-57, math_utils.py:46-118, ray_sampler.py:24-63, modules/eg3ds/models/triplane.py:177-189.
 
+#include <algorithm>
 #include "r3d_common.h"
 #include "r3d_stamps.h"
 
@@ -36,6 +37,7 @@ static constexpr int kWavesPerBlock = 4;
 // depth D > 1 (tri-grids, renderer.py:78-89): source channel c*D + d of plane p goes to slice d: [N*3][D][H*W][C]
 // absmax_part (may be NULL): one float per block = max |value written| of the block (no atomics, no init); the decoder fold
 // (decoder_fold_kernel) reduces them to the bound the fp16 split of the gathered features is scaled with.
+// HW = H * W is an int in both layout kernels: H * W <= 2^31 - 1 (host check in r3d_planes_to_nhwc).
 __device__ __forceinline__ void block_absmax_store(float m, float* __restrict__ absmax_part, int block_linear, float* red)
 {
 #pragma unroll
@@ -164,7 +166,7 @@ __global__ void raygen_kernel(const float* __restrict__ c2w, const float* __rest
 {
     const int n = blockIdx.y;
     const int m = blockIdx.x * blockDim.x + threadIdx.x;
-    const int M = R * R;
+    const int M = R * R;                            // R * R <= 2^31 - 1 (host check in r3d_raygen)
     if (m >= M) return;
     float o3[3], d3[3];
     make_ray(c2w + 16 * n, K + 9 * n, R, m, o3, d3);
@@ -457,7 +459,7 @@ __device__ __forceinline__ void plane_taps(float u, float v, int H, int W, int p
     const bool vy0 = okc && y0 >= 0 && y0 < H, vy1 = okc && y0 + 1 >= 0 && y0 + 1 < H;
     const int xa = min(max(x0, 0), W - 1), xb = min(max(x0 + 1, 0), W - 1);
     const int ya = min(max(y0, 0), H - 1), yb = min(max(y0 + 1, 0), H - 1);
-    const int ra = __mul24(ya, W), rb = __mul24(yb, W);  // 24-bit multiply (full rate; v_mul_lo_u32 is quarter rate): H, W < 2^24 (host check)
+    const int ra = __mul24(ya, W), rb = __mul24(yb, W);  // 24-bit multiply (full rate; v_mul_lo_u32 is quarter rate): H, W < 2^24 (host check: planes_fit)
     t[0].idx = plane_base4 + (ra + xa) * 8; t[0].w = (vx0 && vy0) ? fx0 * fy0 : 0.0f;
     t[1].idx = plane_base4 + (ra + xb) * 8; t[1].w = (vx1 && vy0) ? fx1 * fy0 : 0.0f;
     t[2].idx = plane_base4 + (rb + xa) * 8; t[2].w = (vx0 && vy1) ? fx0 * fy1 : 0.0f;
@@ -469,7 +471,7 @@ __device__ __forceinline__ void gather_sample(const float4* __restrict__ planes4
                                               float px, float py, float pz, float scale, float xs3, float x[8], int D = 1)
 {
     const float qx = px * scale, qy = py * scale, qz = pz * scale;
-    const int HW8 = H * W * 8;
+    const int HW8 = H * W * 8;                           // tap indices are ints in float4 units: 3 * D * H * W * 8 < 2^31 per image (host check: kGatherLimit)
     const float us[3] = {qx, qx, qz}, vs[3] = {qy, qz, qx};
     if constexpr (TRI) {
         // tri-grid (sample_from_trigrids, renderer.py:78-89): each plane is a [C, D, H, W] volume sampled tri-linearly; the
@@ -945,6 +947,11 @@ __device__ __forceinline__ void march(const float* T, const float* S, float* wv,
     dsum = wave_sum(ds);
 }
 
+// Which shapes <NTC, NTF> of render_kernel park a ray's colours in the workspace, and how many 64-lane f32x4 tiles a wave of such a shape parks there.
+// The kernel's GPARK and slot stride, the host's park_g and the room r3d_render_workspace_bytes asks for (kRenderParkTilesMax) all come from these two.
+constexpr bool render_shape_parks(int ntc, int ntf) { return ntf > 0 && ntc > 3; }
+constexpr int render_park_tiles(int ntc, int ntf) { return render_shape_parks(ntc, ntf) ? 2 * (ntc + ntf) : 0; }
+
 struct RenderArgs {
     const float4* planes4; int N, H, W, M, D;      // D: tri-grid depth (1 = tri-plane)
     const float* w1; const float* b1; const float* w2; const float* b2;
@@ -994,7 +1001,7 @@ struct RayIter {
     {
         if (strips) { if (n >= N) return false; img = n; ray = n * M + row * R + col0 + c; return true; }
         if (lin >= nrays) return false;
-        ray = (int)lin; img = ray / M; return true;
+        ray = (int)lin; img = ray / M; return true;          // N * M <= 2^31 - 1 (host check in r3d_render_forward)
     }
     __device__ __forceinline__ void advance()
     {
@@ -1023,7 +1030,7 @@ __global__ __launch_bounds__(256, OCC) void render_kernel(RenderArgs a, int R)
     // Round 5: the bigger shapes park ALL colours of a ray -- coarse and fine, tile by tile as the decode produces them -- in the workspace (2 (NTC +
     // NTF) KB per wave, each 16 B per lane written once and read once per ray, served by L2) instead of leaving 96 live registers to the allocator
     // (built without packed-f32 instructions <6,6> spilled 131 registers and BASELINE config 5's render took 15.0 instead of 12.5 ms).
-    constexpr bool GPARK = NTF > 0 && NTC > 3;
+    constexpr bool GPARK = render_shape_parks(NTC, NTF);
     __shared__ __attribute__((aligned(16))) f32x4 park[PARK ? kWavesPerBlock : 1][PARK ? 2 * NTC : 1][64];
 
     stage_decoder(dec, a.w1, a.b1, a.w2, a.b2, a.fold);
@@ -1098,7 +1105,7 @@ __global__ __launch_bounds__(256, OCC) void render_kernel(RenderArgs a, int R)
         f32x4 colc[2][NTC];
         float sigc[NTC];
         f32x4* gpark = nullptr;                         // GPARK: this wave's [2 (NTC + NTF)][64] f32x4 slots of the workspace
-        if constexpr (GPARK) gpark = A.park_g + ((size_t)(blockIdx.x * kWavesPerBlock + wave) * (2 * (NTC + NTF))) * 64 + lane;
+        if constexpr (GPARK) gpark = A.park_g + ((size_t)(blockIdx.x * kWavesPerBlock + wave) * render_park_tiles(NTC, NTF)) * 64 + lane;
         {
             // the depths go to the ray's LDS record first (the march reads them there anyway): the pass fetches the depth of the sample a lane
             // gathers for (lane gs of the per-sample mapping: q = 0, s = gs) per tile, as the fine pass does, instead of holding NTC shuffled
@@ -1469,45 +1476,125 @@ __global__ __launch_bounds__(256, 2) void run_model_kernel(const float4* __restr
 // -------------------------------------------------------------------------------------------------
 // host side
 // -------------------------------------------------------------------------------------------------
-// workspace: gstate header (8 ints) + 3 ints per ray_limits block, then ray_start[nrays], ray_end[nrays]
-static inline size_t render_state_bytes(size_t nrays) { return ((kStateHeader + 3 * ((nrays + kLimitsBlock - 1) / kLimitsBlock)) * sizeof(int) + 63) & ~(size_t)63; }
-// decoder fold record (64 bytes) + room for the partials of plane_absmax_kernel (when the caller passes none)
-static constexpr size_t kFoldBytes = 64 + kAbsmaxBlocks * sizeof(float);
 static constexpr int kMaxGrid = 512;          // blocks of a render launch: 2 per CU
+static inline size_t align64(size_t v) { return (v + 63) & ~(size_t)63; }
 
-// launches (plane_absmax_kernel if needed +) decoder_fold_kernel; returns the device address of the DecFold record
-static const DecFold* launch_decoder_fold(const float* planes_nhwc, size_t plane_floats, const float* plane_absmax, int n_plane_absmax,
-                                          const float* w1, const float* b1, const float* w2, void* fold_mem, hipStream_t st)
-{
-    DecFold* fold = reinterpret_cast<DecFold*>(fold_mem);
-    float* part = reinterpret_cast<float*>(reinterpret_cast<char*>(fold_mem) + 64);
-    if (!plane_absmax || n_plane_absmax <= 0) {
-        hipLaunchKernelGGL(plane_absmax_kernel, dim3(kAbsmaxBlocks), dim3(256), 0, st, reinterpret_cast<const float4*>(planes_nhwc), plane_floats / 4, part);
-        plane_absmax = part; n_plane_absmax = kAbsmaxBlocks;
-    }
-    hipLaunchKernelGGL(decoder_fold_kernel, dim3(1), dim3(256), 0, st, plane_absmax, n_plane_absmax, w1, b1, w2, fold);
-    return fold;
-}
-
-template <int NTC, int NTF>
-static void launch_render(const RenderArgs& a, int R, int grid, hipStream_t st)
-{
-    // <OCC = 2 waves/SIMD, one plane (8 loads) in flight>: no scratch for every shape up to 64+64 samples (232 VGPRs at REF).
-    // Measured at REF with the quad-coalesced gather: <2,1> 0.229 ms, <2,3> (24 loads in flight, 8 spilled registers) 0.232,
-    // <3,1> (168-VGPR cap, 64 spilled) 0.353, <3,3> 0.423.  (Before the gather change <2,3> led <2,1> by 5 %: the loads were the limiter.)
-    hipLaunchKernelGGL((render_kernel<NTC, NTF, 2, 1>), dim3(grid), dim3(256), 0, st, a, R);
-}
-
+// ---- the shape table --------------------------------------------------------------------------------------------------------------------
+// The instantiated shapes <NTC, NTF> of render_kernel, listed once.  Every shape runs at <OCC = 2 waves/SIMD>.
+// Tri-planes, one plane (8 loads) in flight: no scratch for every shape up to 64+64 samples (232 VGPRs at REF).
+// Measured at REF with the quad-coalesced gather: <2,1> 0.229 ms, <2,3> (24 loads in flight, 8 spilled registers) 0.232,
+// <3,1> (168-VGPR cap, 64 spilled) 0.353, <3,3> 0.423.  (Before the gather change <2,3> led <2,1> by 5 %: the loads were the limiter.)
+#define R3D_RENDER_PLANE_SHAPES(X) X(1, 0) X(1, 1) X(2, 0) X(2, 1) X(2, 2) X(3, 0) X(3, 1) X(3, 2) X(3, 3) X(4, 0) X(6, 0) X(4, 4) X(6, 6)
+// Tri-grids: only the three covering shapes (a secondary configuration).
+#define R3D_RENDER_TRI_SHAPES(X) X(6, 0) X(3, 3) X(6, 6)
 // The shapes whose working set does not fit 256 registers (64+64 samples and up, the tri-grids) run at two waves per SIMD like the others: <4,4>, <6,6>
-// and the tri-grid <6,6> park their colours in the workspace (GPARK), and what still does not fit (the tri-grids) spills to scratch.  At ONE wave per SIMD (the wave owns the SIMD's 512 registers, the same values
-// live in AGPRs, no scratch in any shape) config 5's render went 12.9 -> 16.3 ms and the tri-grids 0.331 -> 0.383 ms: the second wave's latency hiding is worth
-// more than the scratch traffic costs (profiles/r05/ray_big_shapes_one_wave_per_simd.txt; DESIGN "Retired experiment switches").
+// and the tri-grid <6,6> park their colours in the workspace (render_shape_parks), and what still does not fit (the tri-grids) spills to scratch.  At ONE
+// wave per SIMD (the wave owns the SIMD's 512 registers, the same values live in AGPRs, no scratch in any shape) config 5's render went 12.9 -> 16.3 ms
+// and the tri-grids 0.331 -> 0.383 ms: the second wave's latency hiding is worth more than the scratch traffic costs
+// (profiles/r05/ray_big_shapes_one_wave_per_simd.txt; DESIGN "Retired experiment switches").
 
-// tri-grid variants: only the three covering shapes are instantiated (a secondary configuration)
-template <int NTC, int NTF>
-static void launch_render_tri(const RenderArgs& a, int R, int grid, hipStream_t st)
+struct RenderShape {
+    int ntc, ntf; bool tri;
+    void (*kernel)(RenderArgs, int);
+    bool parks() const { return render_shape_parks(ntc, ntf); }
+};
+static const RenderShape kRenderShapes[] = {
+#define R3D_SHAPE(C_, F_) {C_, F_, false, render_kernel<C_, F_, 2, 1>},
+    R3D_RENDER_PLANE_SHAPES(R3D_SHAPE)
+#undef R3D_SHAPE
+#define R3D_SHAPE(C_, F_) {C_, F_, true, render_kernel<C_, F_, 2, 3, true>},
+    R3D_RENDER_TRI_SHAPES(R3D_SHAPE)
+#undef R3D_SHAPE
+};
+// The most tiles a wave of any shape in the table parks: r3d_render_workspace_bytes has no depth argument, so every call that parks gets this much room
+// per wave (<4,4> uses 16 of them).  The sizes the query returns are published: a new shape that parks more is an ABI change.
+#define R3D_SHAPE(C_, F_) render_park_tiles(C_, F_),
+static constexpr int kRenderParkTilesMax = std::max({R3D_RENDER_PLANE_SHAPES(R3D_SHAPE) R3D_RENDER_TRI_SHAPES(R3D_SHAPE)});
+#undef R3D_SHAPE
+static_assert(kRenderParkTilesMax == 24, "r3d_render_workspace_bytes: the parking room per wave is 24 tiles of 64 f32x4");
+
+static const RenderShape* find_render_shape(bool tri, int ntc, int ntf)
 {
-    hipLaunchKernelGGL((render_kernel<NTC, NTF, 2, 3, true>), dim3(grid), dim3(256), 0, st, a, R);
+    for (const RenderShape& s : kRenderShapes)
+        if (s.tri == tri && s.ntc == ntc && s.ntf == ntf) return &s;
+    return nullptr;
+}
+
+// The shape a call runs: the one with its own tile counts where the table has it; otherwise the first of <6,0>, <3,3>, <4,4> that the table has for this
+// kind of plane and that covers the call (a coarse-only call: only a coarse-only shape); otherwise <6,6>, which covers every legal call.
+// NOT the smallest cover: <1,2> runs <3,3>, not <2,2>.
+static const RenderShape& pick_render_shape(int Nc, int Nf, int triplane_depth)
+{
+    const int ntc = (Nc + 15) / 16, ntf = (Nf + 15) / 16;
+    const bool tri = triplane_depth > 1;
+    if (const RenderShape* s = find_render_shape(tri, ntc, ntf)) return *s;
+    static const int cover[3][2] = {{6, 0}, {3, 3}, {4, 4}};
+    for (const int* c : cover)
+        if (ntc <= c[0] && ntf <= c[1] && (ntf == 0) == (c[1] == 0))
+            if (const RenderShape* s = find_render_shape(tri, c[0], c[1])) return *s;
+    return *find_render_shape(tri, 6, 6);
+}
+
+// ---- the workspace ------------------------------------------------------------------------------------------------------------------------
+// The grid r3d_render_forward launches for nrays rays: <= 2 blocks per CU on 256 CUs, a multiple of 8 (XCD strips)
+static int render_grid(size_t nrays)
+{
+    const size_t max_blocks = ((nrays + kWavesPerBlock - 1) / kWavesPerBlock + 7) / 8 * 8;
+    return max_blocks < (size_t)kMaxGrid ? (int)max_blocks : kMaxGrid;
+}
+// Parking room of a call: per wave of its grid, when the shape it runs parks -- as tri-planes or as tri-grids, the query is not told which
+static size_t render_park_bytes(size_t nrays, int Nc, int Nf)
+{
+    const bool parks = pick_render_shape(Nc, Nf, 1).parks() || pick_render_shape(Nc, Nf, 2).parks();
+    return parks ? (size_t)render_grid(nrays) * kWavesPerBlock * kRenderParkTilesMax * 64 * sizeof(f32x4) : 0;
+}
+
+// Byte offsets of the workspace of r3d_render_forward (rays = true) and of r3d_run_model (rays = false: the fold record and its partials alone)
+static_assert(sizeof(DecFold) <= 64, "the fold record's slot is 64 bytes");
+struct RenderWorkspaceLayout { size_t gstate, ray_start, ray_end, fold, partials, park, total; };
+static RenderWorkspaceLayout render_workspace_layout(bool rays, size_t nrays, size_t park_bytes)
+{
+    RenderWorkspaceLayout L;
+    size_t o = 0;
+    L.gstate = o; if (rays) o += align64((kStateHeader + 3 * ((nrays + kLimitsBlock - 1) / kLimitsBlock)) * sizeof(int));   // header + 3 ints per ray_limits block
+    L.ray_start = o; if (rays) o += nrays * sizeof(float);
+    L.ray_end = o; if (rays) o += nrays * sizeof(float);
+    const size_t rays_end = o;
+    L.fold = o = align64(o); o += 64;                                   // the DecFold record
+    L.partials = o; o += kAbsmaxBlocks * sizeof(float);                 // of plane_absmax_kernel, when the caller passed none (plane_bound)
+    L.park = o; o += park_bytes;                                        // [wave of the grid][kRenderParkTilesMax][64] f32x4; a shape's own slot stride is render_park_tiles
+    L.total = rays_end + (rays ? 64 : 0) + (o - L.fold);                // a published size: a whole 64 bytes for the rounding in front of the fold record
+    return L;
+}
+
+// The |max| partials the decoder fold reads: the caller's, or -- when it passed none -- the ones plane_absmax_kernel writes behind the fold record here
+struct PlaneBound { const float* partials; int count; };
+static PlaneBound plane_bound(const float* plane_absmax, int n_plane_absmax, const float* planes_nhwc, size_t plane_floats, float* own, hipStream_t st)
+{
+    if (plane_absmax && n_plane_absmax > 0) return {plane_absmax, n_plane_absmax};
+    hipLaunchKernelGGL(plane_absmax_kernel, dim3(kAbsmaxBlocks), dim3(256), 0, st, reinterpret_cast<const float4*>(planes_nhwc), plane_floats / 4, own);
+    return {own, kAbsmaxBlocks};
+}
+
+// ---- argument rules -----------------------------------------------------------------------------------------------------------------------
+static constexpr long long kIntMax = 2147483647;
+// How far each path can index an image's planes [3][depth][H][W][32]: the ray kernel's taps are 32-bit BYTE offsets (128 bytes per texel); the gather of
+// r3d_run_model (gather_sample<3, TRI>, plane_taps) is an int in float4 units (8 per texel).  Both multiply rows with __mul24: H, W < 2^24.
+static constexpr size_t kTapByteLimit = (size_t)1 << 32, kGatherLimit = (size_t)1 << 31;
+static bool planes_fit(int H, int W, int depth, size_t texel_units, size_t limit)        // H, W first: the product then cannot wrap
+{
+    return H < (1 << 24) && W < (1 << 24) && (size_t)H * W * 3 * depth * texel_units < limit;
+}
+
+// what r3d_render_forward and r3d_run_model both ask of the planes, the decoder and the box
+static int check_planes_decoder(const char* what, const float* planes_nhwc, int N, int H, int W, int triplane_depth,
+                                const float* w1, const float* b1, const float* w2, const float* b2, float box_warp)
+{
+    if (!planes_nhwc || !w1 || !b1 || !w2 || !b2) { set_error("%s: NULL pointer (planes_nhwc, w1, b1, w2, b2)", what); return R3D_ERR_INVALID_ARG; }
+    if (N <= 0 || H <= 1 || W <= 1 || triplane_depth < 1 || triplane_depth > 16 || !(box_warp > 0.f)) {
+        set_error("%s: bad shape (N > 0, H, W > 1, 1 <= triplane_depth <= 16, box_warp > 0)", what); return R3D_ERR_INVALID_ARG;
+    }
+    return R3D_OK;
 }
 
 }  // namespace r3d
@@ -1538,6 +1625,7 @@ extern "C" int r3d_planes_to_nhwc(const float* planes_nchw, const float* add_nch
     if (!planes_nchw || !planes_nhwc || N <= 0 || C <= 0 || H <= 0 || W <= 0 || depth < 1 || depth > 16 || add_flip < 0 || add_flip > 63) {
         set_error("planes_to_nhwc: bad argument"); return R3D_ERR_INVALID_ARG;
     }
+    if ((long long)H * W > kIntMax) { set_error("planes_to_nhwc: H * W = %lld exceeds 2^31 - 1 (the kernels index a plane with an int)", (long long)H * W); return R3D_ERR_INVALID_ARG; }
     const int HW = H * W;
     dim3 grid((HW + 31) / 32, (C + 31) / 32, N * 3 * depth), block(32, 8);
     ProfScope ps(R3D_PROF_LAYOUT, (hipStream_t)stream);
@@ -1555,28 +1643,17 @@ extern "C" int r3d_raygen(const float* c2w, const float* intrinsics, int N, int 
                           float* origins, float* dirs, r3d_stream_t stream)
 {
     if (!c2w || !intrinsics || !origins || !dirs || N <= 0 || R <= 0) { set_error("raygen: bad argument"); return R3D_ERR_INVALID_ARG; }
+    if ((long long)R * R > kIntMax) { set_error("raygen: R * R = %lld exceeds 2^31 - 1 (the kernel indexes an image's rays with an int)", (long long)R * R); return R3D_ERR_INVALID_ARG; }
     dim3 grid((R * R + 255) / 256, N);
     ProfScope ps(R3D_PROF_MISC, (hipStream_t)stream);
     hipLaunchKernelGGL(raygen_kernel, grid, dim3(256), 0, (hipStream_t)stream, c2w, intrinsics, R, origins, dirs);
     return check_launch("raygen");
 }
 
-// The grid r3d_render_forward launches for nrays rays, and whether the shape it dispatches parks a ray's colours in the workspace (one helper for the size
-// query and the launch, so that the two cannot drift apart; ADVICE r5: the query used to add a fixed 48 MB whenever Nc or Nf exceeded 48, also for Nf = 0
-// -- <4,0> / <6,0> never park -- and for small launches whose grid is a fraction of kMaxGrid).
-static int render_grid(size_t nrays)
-{
-    const size_t max_blocks = ((nrays + kWavesPerBlock - 1) / kWavesPerBlock + 7) / 8 * 8;
-    return max_blocks < (size_t)kMaxGrid ? (int)max_blocks : kMaxGrid;
-}
-static bool render_parks(int Nc, int Nf) { return (Nc > 48 || Nf > 48) && Nf > 0; }
-// per wave of the grid: 2 (NTC + NTF) tiles of 64 f32x4; 24 covers <6,6> and its tri-grid twin (a tri-grid call with 49..64 samples runs <6,6> too)
-static size_t render_park_bytes(size_t nrays, int Nc, int Nf) { return render_parks(Nc, Nf) ? (size_t)render_grid(nrays) * kWavesPerBlock * 24 * 64 * sizeof(f32x4) : 0; }
-
 extern "C" size_t r3d_render_workspace_bytes(int N, int M, int Nc, int Nf)
 {
     const size_t nrays = (size_t)N * M;
-    return render_state_bytes(nrays) + 2 * nrays * sizeof(float) + 64 + kFoldBytes + render_park_bytes(nrays, Nc, Nf);
+    return render_workspace_layout(true, nrays, render_park_bytes(nrays, Nc, Nf)).total;
 }
 
 // Test hook, not part of the C ABI of include/r3d_hip.h (like the stamp readers of experiment builds): *count = rays of the current device
@@ -1592,7 +1669,7 @@ extern "C" int r3d_debug_merge_fallbacks(unsigned long long* count, int reset)
     return R3D_OK;
 }
 
-extern "C" size_t r3d_run_model_workspace_bytes(void) { return kFoldBytes; }
+extern "C" size_t r3d_run_model_workspace_bytes(void) { return render_workspace_layout(false, 0, 0).total; }
 
 extern "C" int r3d_render_forward(const float* planes_nhwc, int N, int H, int W, int triplane_depth,
                                   const float* w1, const float* b1, const float* w2, const float* b2,
@@ -1608,80 +1685,60 @@ extern "C" int r3d_render_forward(const float* planes_nhwc, int N, int H, int W,
     if (split_out && (!split_scale || ((uintptr_t)split_out & 15) || ((uintptr_t)split_scale & 15) || (split_scale_stride & 3))) {
         set_error("render_forward: split_out needs a 16-byte aligned split_scale [N][32] (stride a multiple of 4 floats)"); return R3D_ERR_INVALID_ARG;
     }
+    if (int rc = check_planes_decoder("render_forward", planes_nhwc, N, H, W, triplane_depth, w1, b1, w2, b2, box_warp)) return rc;
     const bool cam = origins == nullptr && dirs == nullptr && cam2world != nullptr && intrinsics != nullptr;
-    if (!planes_nhwc || !w1 || !b1 || !w2 || !b2 || (!cam && (!origins || !dirs)) || !rgb || !wsum || !valid) {
+    if ((!cam && (!origins || !dirs)) || !rgb || !wsum || !valid) {
         set_error("render_forward: NULL pointer (rays: origins + dirs, or cam2world + intrinsics with origins = dirs = NULL)"); return R3D_ERR_INVALID_ARG;
     }
-    if (N <= 0 || M <= 0 || H <= 1 || W <= 1 || triplane_depth < 1 || triplane_depth > 16 || !(box_warp > 0.f)) { set_error("render_forward: bad shape"); return R3D_ERR_INVALID_ARG; }
+    if (M <= 0) { set_error("render_forward: bad shape (M > 0)"); return R3D_ERR_INVALID_ARG; }
     if (Nc < 4 || Nc > 96 || Nf < 0 || Nf > 96) {
         set_error("render_forward: depth_resolution %d / importance %d outside [4,96] / [0,96]", Nc, Nf);
         return R3D_ERR_INVALID_ARG;
     }
-    if ((size_t)H * W * 3 * triplane_depth * 128 >= ((size_t)1 << 32)) { set_error("render_forward: planes too large for 32-bit tap offsets (3 * depth * H * W * 128 bytes per image must stay below 4 GiB)"); return R3D_ERR_INVALID_ARG; }
-    if (!workspace || workspace_bytes < r3d_render_workspace_bytes(N, M, Nc, Nf)) { set_error("render_forward: workspace too small"); return R3D_ERR_WORKSPACE; }
-    hipStream_t st = (hipStream_t)stream;
+    if (!planes_fit(H, W, triplane_depth, 128, kTapByteLimit)) { set_error("render_forward: planes too large for 32-bit tap offsets (3 * depth * H * W * 128 bytes per image must stay below 4 GiB)"); return R3D_ERR_INVALID_ARG; }
+    if ((long long)N * M > kIntMax) { set_error("render_forward: N * M = %lld rays exceed 2^31 - 1 (the kernels carry the ray index in an int)", (long long)N * M); return R3D_ERR_INVALID_ARG; }
     const int nrays = N * M;
-    int* gstate = reinterpret_cast<int*>(workspace);
-    float* ray_start = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + render_state_bytes(nrays));
-    float* ray_end = ray_start + nrays;
-    void* fold_mem = reinterpret_cast<char*>(workspace) + ((render_state_bytes(nrays) + 2 * (size_t)nrays * sizeof(float) + 63) & ~(size_t)63);
-    f32x4* park_g = reinterpret_cast<f32x4*>(reinterpret_cast<char*>(fold_mem) + kFoldBytes);      // (64-byte aligned: kFoldBytes is a multiple of 64)
-
+    const RenderShape& shape = pick_render_shape(Nc, Nf, triplane_depth);
+    const RenderWorkspaceLayout L = render_workspace_layout(true, (size_t)nrays, render_park_bytes((size_t)nrays, Nc, Nf));
+    if (!workspace || workspace_bytes < L.total) { set_error("render_forward: workspace too small"); return R3D_ERR_WORKSPACE; }
     int R = 0;                                        // square image -> XCD strip order of the rays; otherwise linear order
-    for (int r = 1; r * r <= M; ++r) if (r * r == M) R = r;
+    for (int r = 1; (long long)r * r <= M; ++r) if (r * r == M) R = r;
     if (cam && R == 0) { set_error("render_forward: camera mode needs M = R * R rays (got %d)", M); return R3D_ERR_INVALID_ARG; }
+
+    hipStream_t st = (hipStream_t)stream;
+    char* ws = reinterpret_cast<char*>(workspace);
     RenderArgs a;
+    a.gstate = reinterpret_cast<int*>(ws + L.gstate); a.nlimit_blocks = (nrays + kLimitsBlock - 1) / kLimitsBlock;
+    float* ray_start = reinterpret_cast<float*>(ws + L.ray_start);
+    float* ray_end = reinterpret_cast<float*>(ws + L.ray_end);
+    DecFold* fold = reinterpret_cast<DecFold*>(ws + L.fold);
     {
         ProfScope ps(R3D_PROF_MISC, st);
         // the decoder's range fold rides as the last block of the ray-limits launch (planes without |max| partials are measured first)
-        DecFold* fold = reinterpret_cast<DecFold*>(fold_mem);
-        if (!plane_absmax || n_plane_absmax <= 0) {
-            float* part = reinterpret_cast<float*>(reinterpret_cast<char*>(fold_mem) + 64);
-            hipLaunchKernelGGL(plane_absmax_kernel, dim3(kAbsmaxBlocks), dim3(256), 0, st, reinterpret_cast<const float4*>(planes_nhwc),
-                               (size_t)N * 3 * triplane_depth * H * W * kC / 4, part);
-            plane_absmax = part; n_plane_absmax = kAbsmaxBlocks;
-        }
-        hipLaunchKernelGGL(ray_limits_kernel, dim3((nrays + kLimitsBlock - 1) / kLimitsBlock + 1), dim3(kLimitsBlock), 0, st, origins, dirs, nrays,
-                           box_warp * 0.5f, ray_start, ray_end, valid, gstate, plane_absmax, n_plane_absmax, w1, b1, w2, fold,
+        const PlaneBound pb = plane_bound(plane_absmax, n_plane_absmax, planes_nhwc, (size_t)N * 3 * triplane_depth * H * W * kC,
+                                          reinterpret_cast<float*>(ws + L.partials), st);
+        hipLaunchKernelGGL(ray_limits_kernel, dim3(a.nlimit_blocks + 1), dim3(kLimitsBlock), 0, st, origins, dirs, nrays,
+                           box_warp * 0.5f, ray_start, ray_end, valid, a.gstate, pb.partials, pb.count, w1, b1, w2, fold,
                            cam ? cam2world : nullptr, cam ? intrinsics : nullptr, R);
-        a.fold = fold;
     }
+    a.fold = fold;
     a.planes4 = reinterpret_cast<const float4*>(planes_nhwc); a.N = N; a.H = H; a.W = W; a.M = M; a.D = triplane_depth;
     a.w1 = w1; a.b1 = b1; a.w2 = w2; a.b2 = b2;
     a.split_out = reinterpret_cast<uint2*>(split_out); a.split_scale = split_scale; a.split_scale_stride = split_scale_stride;
     a.cam_c2w = cam ? cam2world : nullptr; a.cam_K = cam ? intrinsics : nullptr; a.cam_R = R;
     a.origins = origins; a.dirs = dirs; a.ray_start = ray_start; a.ray_end = ray_end; a.valid = valid;
-    a.gstate = gstate; a.nlimit_blocks = (nrays + kLimitsBlock - 1) / kLimitsBlock; a.Nc = Nc; a.Nf = Nf; a.scale = 2.0f / box_warp; a.white_back = white_back;
+    a.Nc = Nc; a.Nf = Nf; a.scale = 2.0f / box_warp; a.white_back = white_back;
     a.noise_c = noise_c; a.u_f = u_f; a.seed = seed;
     a.rgb = rgb; a.depth = depth; a.wsum = wsum; a.rgb_cm = rgb_channel_major ? 1 : 0;
     a.clk = prof_clock_slot(R3D_PROF_RENDER);
-    a.park_g = render_parks(Nc, Nf) ? park_g : nullptr;      // (exactly the calls the dispatch below sends to a parking shape: <4,4>, <6,6> and the tri-grid <6,6>)
-
-    // (R computed above: square image -> XCD strip order; otherwise linear order)
-    const int waves_needed = nrays;
-    const int grid = render_grid((size_t)waves_needed);      // <= 2 blocks per CU on 256 CUs, multiple of 8 (XCD strips)
-
-    const int ntc = (Nc + 15) / 16, ntf = (Nf + 15) / 16;
+    a.park_g = shape.parks() ? reinterpret_cast<f32x4*>(ws + L.park) : nullptr;
     {
-    ProfScope ps(R3D_PROF_RENDER, st);
-#define R3D_CASE(C_, F_) else if (ntc == C_ && ntf == F_) launch_render<C_, F_>(a, R, grid, st)
-    if (triplane_depth > 1) {
-        if (ntf == 0) launch_render_tri<6, 0>(a, R, grid, st);
-        else if (ntc <= 3 && ntf <= 3) launch_render_tri<3, 3>(a, R, grid, st);
-        else launch_render_tri<6, 6>(a, R, grid, st);
-    }
-    R3D_CASE(1, 0); R3D_CASE(1, 1); R3D_CASE(2, 0); R3D_CASE(2, 1); R3D_CASE(2, 2);
-    R3D_CASE(3, 0); R3D_CASE(3, 1); R3D_CASE(3, 2); R3D_CASE(3, 3);
-    R3D_CASE(4, 0); R3D_CASE(6, 0);
-    else if (ntf == 0 && ntc <= 6) launch_render<6, 0>(a, R, grid, st);
-    else if (ntc <= 3 && ntf <= 3) launch_render<3, 3>(a, R, grid, st);
-    else if (ntc <= 4 && ntf <= 4) launch_render<4, 4>(a, R, grid, st);
-    else launch_render<6, 6>(a, R, grid, st);
-#undef R3D_CASE
+        ProfScope ps(R3D_PROF_RENDER, st);
+        hipLaunchKernelGGL(shape.kernel, dim3(render_grid((size_t)nrays)), dim3(256), 0, st, a, R);      // one wave per ray
     }
     if (depth) {
         ProfScope ps2(R3D_PROF_MISC, st);
-        hipLaunchKernelGGL(depth_clamp_kernel, dim3((nrays + 255) / 256), dim3(256), 0, st, depth, nrays, gstate);
+        hipLaunchKernelGGL(depth_clamp_kernel, dim3((nrays + 255) / 256), dim3(256), 0, st, depth, nrays, a.gstate);
     }
     return check_launch("render_forward");
 }
@@ -1692,23 +1749,25 @@ extern "C" int r3d_run_model(const float* planes_nhwc, int N, int H, int W, int 
                              float* rgb, float* sigma, const float* plane_absmax, int n_plane_absmax,
                              void* workspace, size_t workspace_bytes, r3d_stream_t stream)
 {
-    if (!planes_nhwc || !w1 || !b1 || !w2 || !b2 || !coords || !rgb || !sigma || N <= 0 || npts <= 0 || triplane_depth < 1 || triplane_depth > 16 || !(box_warp > 0.f)) {
-        set_error("run_model: bad argument"); return R3D_ERR_INVALID_ARG;
+    if (!coords || !rgb || !sigma || npts <= 0) { set_error("run_model: bad argument (coords, rgb, sigma, npts > 0)"); return R3D_ERR_INVALID_ARG; }
+    if (int rc = check_planes_decoder("run_model", planes_nhwc, N, H, W, triplane_depth, w1, b1, w2, b2, box_warp)) return rc;
+    if (!planes_fit(H, W, triplane_depth, 8, kGatherLimit)) {
+        set_error("run_model: planes too large for the gather's int offsets (3 * depth * H * W * 8 must stay below 2^31, H and W below 2^24)"); return R3D_ERR_INVALID_ARG;
     }
-    if (!workspace || workspace_bytes < kFoldBytes || ((uintptr_t)workspace & 15)) { set_error("run_model: workspace too small (r3d_run_model_workspace_bytes) or unaligned"); return R3D_ERR_WORKSPACE; }
-    if (H <= 1 || W <= 1) { set_error("run_model: bad shape"); return R3D_ERR_INVALID_ARG; }
+    const RenderWorkspaceLayout L = render_workspace_layout(false, 0, 0);
+    if (!workspace || workspace_bytes < L.total || ((uintptr_t)workspace & 15)) { set_error("run_model: workspace too small (r3d_run_model_workspace_bytes) or unaligned"); return R3D_ERR_WORKSPACE; }
+    hipStream_t st = (hipStream_t)stream;
+    char* ws = reinterpret_cast<char*>(workspace);
     const long long chunks = ((long long)N * npts + 63) / 64;
     int grid = (int)((chunks + kWavesPerBlock - 1) / kWavesPerBlock);
     if (grid > 1024) grid = 1024;
-    const DecFold* fold = launch_decoder_fold(planes_nhwc, (size_t)N * 3 * triplane_depth * H * W * kC, plane_absmax, n_plane_absmax, w1, b1, w2, workspace, (hipStream_t)stream);
-    ProfScope ps(R3D_PROF_RENDER, (hipStream_t)stream);
-    if (triplane_depth > 1)
-        hipLaunchKernelGGL(run_model_kernel<true>, dim3(grid), dim3(256), 0, (hipStream_t)stream,
-                           reinterpret_cast<const float4*>(planes_nhwc), N, H, W, triplane_depth, w1, b1, w2, b2, coords, npts,
-                           2.0f / box_warp, rgb, sigma, fold);
-    else
-        hipLaunchKernelGGL(run_model_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream,
-                           reinterpret_cast<const float4*>(planes_nhwc), N, H, W, triplane_depth, w1, b1, w2, b2, coords, npts,
-                           2.0f / box_warp, rgb, sigma, fold);
+    DecFold* fold = reinterpret_cast<DecFold*>(ws + L.fold);
+    const PlaneBound pb = plane_bound(plane_absmax, n_plane_absmax, planes_nhwc, (size_t)N * 3 * triplane_depth * H * W * kC,
+                                      reinterpret_cast<float*>(ws + L.partials), st);
+    hipLaunchKernelGGL(decoder_fold_kernel, dim3(1), dim3(256), 0, st, pb.partials, pb.count, w1, b1, w2, fold);
+    ProfScope ps(R3D_PROF_RENDER, st);
+    auto kernel = triplane_depth > 1 ? run_model_kernel<true> : run_model_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, st, reinterpret_cast<const float4*>(planes_nhwc), N, H, W, triplane_depth, w1, b1, w2, b2, coords, npts,
+                       2.0f / box_warp, rgb, sigma, static_cast<const DecFold*>(fold));
     return check_launch("run_model");
 }

@@ -175,6 +175,13 @@ class ImportanceRenderer(nn.Module):
         self._plane_cache = (planes, planes._version, out)
         return out
 
+    def _ensure_workspace(self, need, dev):
+        """Make self._workspace hold at least `need` bytes on `dev` (it only ever grows on one device); returns int(need)."""
+        need = int(need)
+        if self._workspace is None or self._workspace.numel() < need or self._workspace.device != dev:
+            self._workspace = torch.empty(need, device=dev, dtype=torch.uint8)
+        return need
+
     def _check_options(self, opts):
         if self.triplane_feature_type not in ("triplane", "trigrid", "trigrid_v2"):
             raise NotImplementedError("triplane_feature_type=%r (3dgrid) is not built" % self.triplane_feature_type)
@@ -239,9 +246,7 @@ class ImportanceRenderer(nn.Module):
         depth = torch.empty(N, M, 1, device=dev, dtype=torch.float32) if self.need_depth else None
         wsum = torch.empty(N, M, 1, device=dev, dtype=torch.float32)
         valid = torch.empty(N, M, 1, device=dev, dtype=torch.bool)
-        need = int(lib.r3d_render_workspace_bytes(N, M, Nc, Nf))
-        if self._workspace is None or self._workspace.numel() < need or self._workspace.device != dev:
-            self._workspace = torch.empty(need, device=dev, dtype=torch.uint8)
+        need = self._ensure_workspace(lib.r3d_render_workspace_bytes(N, M, Nc, Nf), dev)
         part, npart = self._absmax_of(planes_nhwc)        # None (caller's own layout, or updated in place since): measured inside the call
         x_split, sp_scale, sp_stride = None, None, 0
         if _split_for is not None:
@@ -277,9 +282,7 @@ class ImportanceRenderer(nn.Module):
         w1, b1, w2, b2 = decoder_params(decoder)
         rgb = torch.empty(N, npts, 32, device=coords.device, dtype=torch.float32)
         sigma = torch.empty(N, npts, 1, device=coords.device, dtype=torch.float32)
-        need = int(lib.r3d_run_model_workspace_bytes())
-        if self._workspace is None or self._workspace.numel() < need or self._workspace.device != coords.device:
-            self._workspace = torch.empty(need, device=coords.device, dtype=torch.uint8)
+        need = self._ensure_workspace(lib.r3d_run_model_workspace_bytes(), coords.device)
         part, npart = self._absmax_of(planes_nhwc)
         _lib.check(lib.r3d_run_model(_lib.ptr(planes_nhwc), N, H, W, D, _lib.ptr(w1), _lib.ptr(b1), _lib.ptr(w2),
                                      _lib.ptr(b2), _lib.ptr(coords), npts, float(options["box_warp"]),

@@ -601,3 +601,59 @@ def test_run_model_range_sweep(torch_cuda, oracle, k):
     e_rgb, e_s = np.abs(out["rgb"].cpu().numpy() - ref[0]).max(), np.abs(out["sigma"].cpu().numpy().reshape(ref[1].shape) - ref[1]).max()
     print("run_model k=%+d: rgb %.2e sigma %.2e" % (k, e_rgb, e_s))
     assert e_rgb <= 2e-5 and e_s <= 2e-4
+
+
+# ------------------------------------------------------------------------------------------------
+# the render workspace: r3d_render_workspace_bytes is exactly enough
+# ------------------------------------------------------------------------------------------------
+WS_PATTERN, WS_FRONT = 0xA5, 512 << 10
+
+
+@pytest.mark.parametrize("N,M,Nc,Nf,D,camera", [
+    (1, 1, 4, 0, 1, False),            # <1,0>, one ray, one block of the limits pass
+    (2, 1000, 16, 16, 1, False),       # <1,1>, not a square: linear ray order; the ray arrays end off a 64-byte boundary
+    (1, 64, 64, 20, 1, True),          # <4,4> parks 16 tiles per wave in room sized for 24; camera mode, 8 x 8
+    (1, 64, 96, 0, 1, False),          # <6,0> never parks
+    (1, 64, 52, 20, 2, False),         # tri-grid <6,6> parks 24 tiles per wave
+])
+def test_render_workspace_is_exactly_enough(torch_cuda, N, M, Nc, Nf, D, camera):
+    """r3d_render_forward through the raw ABI on a workspace that is a window of exactly r3d_render_workspace_bytes(N, M, Nc, Nf) bytes, with
+    workspace_bytes saying so, inside ONE allocation whose rest (512 KB in front, the window's size + 512 KB behind) holds a pattern: a region
+    of the layout or a parking slot that ran past the total lands in the pattern (a failed assertion, never a fault).  The planes' |max| is
+    measured inside the call, so the partials behind the fold record are written too.  Hash noise, fixed seed: the outputs must equal, bit
+    for bit, those of the same call on a workspace of twice the size."""
+    torch = torch_cuda
+    from real3dportrait_amd import _lib, synth
+    lib = _lib.load()
+    H = W = 16
+    dev = "cuda"
+    planes = T(torch, synth.hash_unitvar(601, (N, 3, D, H, W, 32), stream=1))
+    w1, b1, w2, b2 = (T(torch, a) for a in synth.synth_decoder(602, sigma_bias=3.0))
+    c2w = K = o = d = None
+    if camera:
+        cams = synth.camera_sweep(N, -0.2, 0.2)
+        c2w, K = T(torch, cams[:, :16]), T(torch, cams[:, 16:])
+    else:
+        target = (synth.synth_noise(603, (N, M, 3)) - 0.5).astype(np.float32) * np.float32(0.8)        # every ray crosses the unit box
+        origin = np.tile(np.array([0.1, 0.05, 2.7], np.float32), (N, M, 1))
+        dirs = target - origin
+        o, d = T(torch, origin), T(torch, dirs / np.linalg.norm(dirs, axis=-1, keepdims=True))
+    need = int(lib.r3d_render_workspace_bytes(N, M, Nc, Nf))
+
+    def run(ws, nbytes):
+        rgb = torch.full((N, 32, M), float("nan"), device=dev); depth = torch.full((N, M), float("nan"), device=dev)
+        wsum = torch.full((N, M), float("nan"), device=dev); valid = torch.full((N, M), 7, dtype=torch.uint8, device=dev)
+        _lib.check(lib.r3d_render_forward(_lib.ptr(planes), N, H, W, D, _lib.ptr(w1), _lib.ptr(b1), _lib.ptr(w2), _lib.ptr(b2), _lib.ptr(o), _lib.ptr(d), M,
+                                          Nc, Nf, 1.0, 0, None, None, 20240607, _lib.ptr(rgb), 1, _lib.ptr(depth), _lib.ptr(wsum), _lib.ptr(valid), None, 0,
+                                          _lib.ptr(c2w), _lib.ptr(K), None, None, 0, _lib.ptr(ws), nbytes, _lib.stream_ptr()), "render_forward")
+        torch.cuda.synchronize()
+        return [t.view(torch.int32) if t.dtype == torch.float32 else t for t in (rgb, depth, wsum, valid)]
+
+    buf = torch.full((WS_FRONT + 2 * need + WS_FRONT,), WS_PATTERN, dtype=torch.uint8, device=dev)
+    got = run(buf[WS_FRONT:WS_FRONT + need], need)
+    assert bool((buf[:WS_FRONT] == WS_PATTERN).all()), "r3d_render_forward wrote in front of its workspace"
+    assert bool((buf[WS_FRONT + need:] == WS_PATTERN).all()), "r3d_render_forward wrote past r3d_render_workspace_bytes"
+    ref = run(torch.full((2 * need,), WS_PATTERN, dtype=torch.uint8, device=dev), 2 * need)
+    assert bool(got[3].bool().any()) and not bool(torch.isnan(got[0].view(torch.float32)).any())          # rays that hit, colours that were written
+    for name, g, r in zip(("rgb", "depth", "wsum", "valid"), got, ref):
+        assert torch.equal(g, r), "%s differs between the exact workspace and one of twice the size" % name
