@@ -322,6 +322,19 @@ int r3d_conv_forward_blend(const void* prepacked, const void* scales, const floa
                            int act, float act_slope, float act_gain, float clamp,
                            void* y, int y_format, const float* next_scale, size_t next_scale_stride, float* y_absmax, r3d_stream_t stream);
 
+/* Test hooks (added under ABI 0.8.0): which kernel variant, grid and block order the host picks for a conv layer call, without launching anything
+ * (no GPU needed).  The launchers dispatch on the same structs these report (csrc/r3d_sr_launch.h sr_conv_variant / sr_block_variants), the
+ * R3D_CONV_WINO mode of the process included.  A record is 6 ints {variant, bits, order, grid x, grid y, grid z}:
+ *   variant  0 / 1 conv_mfma_f16x3_kernel<4,2,4> plain / MX (3x3, 16 x 16 tiles)    2 / 3 conv_mfma_f16x3_rows8_kernel plain / MX (8-row tiles)
+ *            4 / 5 conv_wino_f16x3_kernel plain / MX    6 conv1x1_mfma_f16x3_kernel    7 conv1x1_blend_f16x3_kernel    8 upconv_fir_f16x3_kernel
+ *   bits     variant 8: 4 CLAMP | 2 MX (the epilogue writes conv1's fp8 records) | 1 MXIN (the input carries fp8 records); else 0
+ *   order    2: the XCD-aware block order, 0: grid order
+ * r3d_debug_conv_variant: r3d_conv_forward / _cat (blend = 0; Cin, Cout unpadded, as passed there) or r3d_conv_forward_blend (blend = 1, Cin = Ca + Cb,
+ *   ksize 1); out[6].  r3d_debug_sr_block_variants: r3d_sr_block_forward at R3D_SR_F16X3 | R3D_SR_F16MX; out[12] = conv0's record, conv1's record.
+ * Both return R3D_ERR_INVALID_ARG for a call the entry point would refuse for its shape, formats or precision. */
+int r3d_debug_conv_variant(int N, int Cin, int Cout, int H, int W, int ksize, int x_format, int blend, int* out);
+int r3d_debug_sr_block_variants(int N, int Cin, int Cout, int Hin, int Win, int up, int x_format, int precision, float clamp, int* out);
+
 /* torch.nn.UpsamplingBilinear2d(scale_factor=2) (align_corners=True), the resampling step inside to_plane_cnn
  * (modules/real3d/segformer.py:691-700), between two r3d_conv_forward layers: x fp32 channel-blocked [N,C/8,H,W,8] ->
  * y at 2H x 2W in R3D_FMT_CB8, R3D_FMT_SPLIT or R3D_FMT_SPLIT_MX (scaled by next_scale, NULL = 1; SPLIT_MX -- the consumer runs the f16mx

@@ -51,6 +51,8 @@ SIGNATURES = {
     "r3d_conv_prepack": (c_int, [P, c_int, c_int, c_int, P, P]),
     "r3d_conv_forward": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, c_int,
                                  c_int, c_float, c_float, c_float, P, c_int, P, c_size_t, P, P, c_size_t, P]),
+    "r3d_debug_conv_variant": (c_int, [c_int] * 8 + [ctypes.POINTER(c_int)]),
+    "r3d_debug_sr_block_variants": (c_int, [c_int] * 8 + [c_float, ctypes.POINTER(c_int)]),
     "r3d_frames_to_u8": (c_int, [P, c_int, c_int, c_int, P, P]),
     "r3d_resize_bilinear": (c_int, [P, c_int, c_int, c_int, P, c_int, c_int, c_int, P]),
     "r3d_blend": (c_int, [P, P, P, c_int, c_int, c_int, c_int, P, P]),

@@ -868,6 +868,38 @@ extern "C" int r3d_conv_forward_blend(const void* prepacked, const void* scales,
     return conv_forward_blend_f16x3(c);
 }
 
+// ---- test hooks: what the launchers of r3d_sr_f16x3.hip would run for a call (nothing is launched; include/r3d_hip.h) ----------------------
+static void put_variant(const r3d::SrVariantChoice& v, int* out)
+{
+    out[0] = v.variant; out[1] = v.bits; out[2] = v.order; out[3] = (int)v.gx; out[4] = (int)v.gy; out[5] = (int)v.gz;
+}
+
+extern "C" int r3d_debug_conv_variant(int N, int Cin, int Cout, int H, int W, int ksize, int x_format, int blend, int* out)
+{
+    using namespace r3d;
+    if (!out || N <= 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0 || (ksize != 1 && ksize != 3) || (blend && ksize != 1) ||
+        x_format < R3D_FMT_NCHW || x_format > R3D_FMT_SPLIT_MX || (x_format != R3D_FMT_NCHW && (Cin & 15)) || (x_format == R3D_FMT_SPLIT_MX && ksize != 3)) {
+        set_error("debug_conv_variant: bad argument"); return R3D_ERR_INVALID_ARG;
+    }
+    const ConvPackLayout P = conv_pack_layout(Cin, Cout, ksize);
+    put_variant(blend ? sr_blend_variant(P.Co, H, W, N) : sr_conv_variant(ksize, P.Ci, P.Co, H, W, N, x_format == R3D_FMT_SPLIT_MX, false, sr_wino_mode()), out);
+    return R3D_OK;
+}
+
+extern "C" int r3d_debug_sr_block_variants(int N, int Cin, int Cout, int Hin, int Win, int up, int x_format, int precision, float clamp, int* out)
+{
+    using namespace r3d;
+    if (!out || N <= 0 || Hin <= 0 || Win <= 0 || (Cin & 15) || Cin <= 0 || Cout <= 0 || (Cout % BLOCK_M) || (up != 0 && up != 1) ||
+        (precision != R3D_SR_F16X3 && precision != R3D_SR_F16MX) || x_format < R3D_FMT_NCHW || x_format > R3D_FMT_SPLIT_MX ||
+        (x_format == R3D_FMT_SPLIT_MX && precision != R3D_SR_F16MX)) {
+        set_error("debug_sr_block_variants: bad argument"); return R3D_ERR_INVALID_ARG;
+    }
+    SrVariantChoice v[2];
+    sr_block_variants(N, Cin, Cout, Hin, Win, up, x_format, precision == R3D_SR_F16MX, clamp, sr_wino_mode(), v);
+    put_variant(v[0], out); put_variant(v[1], out + 6);
+    return R3D_OK;
+}
+
 extern "C" int r3d_upsample2x_bilinear(const float* x_cb8, int N, int C, int H, int W, void* y, int y_format,
                                        const float* next_scale, size_t next_scale_stride, r3d_stream_t stream)
 {

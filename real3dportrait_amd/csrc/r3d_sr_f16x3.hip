@@ -745,9 +745,13 @@ __device__ __forceinline__ void conv3x3_dma_block(const Conv2Args& a, const Conv
         for (int k = 0; k < KMAX; ++k) {
             pmask[k] = __ballot((pf_valid >> k) & 1u);
             pf_boff[k] = pf_off[k] * 16u;
-            if ((k < KMAX - 1 || three) && !((pf_valid >> k) & 1u)) {
-                pbuf[64 * (8 * k + wave_u) + lane] = make_uint4(0, 0, 0, 0);
-                pbuf[PBUF + 64 * (8 * k + wave_u) + lane] = make_uint4(0, 0, 0, 0);
+            if (k < KMAX - 1 || three) {
+                const bool outside = !((pf_valid >> k) & 1u);
+                if (outside) pbuf[64 * (8 * k + wave_u) + lane] = make_uint4(0, 0, 0, 0);
+                // A single stage (Cin = 16) never fills the second buffer, and the fp8 pair-MFMA of its last sub-stage reads that buffer's records for
+                // the tap that does not exist: its weight rows are zero (dma_weights2), but e5m2 has Inf / NaN encodings and 0 x NaN is NaN, so
+                // whatever an earlier kernel left in LDS reached the output.  More stages leave a real stage's (finite) records there.
+                if (outside || nst == 1) pbuf[PBUF + 64 * (8 * k + wave_u) + lane] = make_uint4(0, 0, 0, 0);
             }
         }
         __syncthreads();                                              // zero fill done before any DMA is in flight
@@ -1711,18 +1715,8 @@ int upsample2x_bilinear_f16x3(const float* x_cb8, int N, int C, int H, int W, vo
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------
-// A/B switch of the Winograd F(2,3) conv (r3d_sr_wino.h): R3D_CONV_WINO=0 keeps every plain 3x3 conv on the direct kernels
 static constexpr float kSqrt2 = 1.4142135623730951f;   // the lrelu gain of the SR blocks
-static int wino_mode() { static const int v = getenv("R3D_CONV_WINO") ? atoi(getenv("R3D_CONV_WINO")) : 3; return v; }   // 0 off, 1 both precisions, 2 f16mx only, 3 f16x3 only
-// ... and when a plain 3x3 conv over a plain SPLIT operand takes it (mx: the layer's precision is f16mx): the mode allows the precision, and the
-// shape is whole 16 x 16-pixel tiles, 16-channel stages, 128-cout blocks
-static bool use_wino(int Cin, int Cout, int H, int W, bool mx)
-{
-    const int m = wino_mode();
-    // (the kernel addresses one sample's SPLIT activation and the weight pack through 32-bit buffer offsets)
-    return (m == 1 || (m == 2 && mx) || (m == 3 && !mx)) && (H & 15) == 0 && (W & 15) == 0 && (Cin & 15) == 0 && (Cout % BLOCK_M) == 0 &&
-           (size_t)Cin * H * W * 4 < ((size_t)1 << 31) && (size_t)48 * Cin * Cout < ((size_t)1 << 31);
-}
+// (which kernel a layer runs on, R3D_CONV_WINO included: sr_conv_variant / sr_block_variants, r3d_sr_launch.h)
 
 // prepacked: SrPackLayout (r3d_sr_common.h)
 int sr_prepack_f16x3(int Cin, int Cout, const float* c0_w, const float* c1_w, void* prepacked, hipStream_t st, bool mx)
@@ -1762,32 +1756,24 @@ int sr_prepack_f16x3(int Cin, int Cout, const float* c0_w, const float* c1_w, vo
     return check_launch("sr_block_prepack");
 }
 
-// wino: a.wp is a Winograd pack (sr_prepack_wino_kernel), a.x plain SPLIT; mx selects the f16mx main loop
-static void launch_conv2(Conv2Args& a, int tiles, int N, hipStream_t st, bool mx = false, bool wino = false)
+static_assert(SR_TILE == F_TILE_H && SR_TILE == F_TILE_W && SR_UP_TILE == U_TILE, "sr_conv_variant / sr_block_variants (r3d_sr_launch.h) size the grids by these tiles");
+
+// v: what sr_conv_variant chose for this layer (a Winograd variant: a.wp is a Winograd pack (sr_prepack_wino_kernel), a.x plain SPLIT; an MX one: the f16mx main loop)
+static void launch_conv2(Conv2Args& a, const SrVariantChoice& v, hipStream_t st)
 {
     a.clk = prof_clock_slot(R3D_PROF_CONV);
-    dim3 grid(tiles, a.Cout / BLOCK_M, N);
-    a.order = (tiles & 7) == 0 ? 2 : 0;                                 // XCD-aware block order whenever the tiles divide over the 8 XCDs
-    if (wino) {
-        if (mx) hipLaunchKernelGGL(conv_wino_f16x3_kernel<true>, grid, dim3(512), 0, st, a);
-        else hipLaunchKernelGGL(conv_wino_f16x3_kernel<false>, grid, dim3(512), 0, st, a);
-        return;
+    a.order = v.order;
+    const dim3 grid(v.gx, v.gy, v.gz);
+    switch (v.variant) {
+    case SR_VAR_WINO: hipLaunchKernelGGL(conv_wino_f16x3_kernel<false>, grid, dim3(512), 0, st, a); break;
+    case SR_VAR_WINO_MX: hipLaunchKernelGGL(conv_wino_f16x3_kernel<true>, grid, dim3(512), 0, st, a); break;
+    case SR_VAR_ROWS8: hipLaunchKernelGGL(conv_mfma_f16x3_rows8_kernel<false>, grid, dim3(512), 0, st, a); break;
+    case SR_VAR_ROWS8_MX: hipLaunchKernelGGL(conv_mfma_f16x3_rows8_kernel<true>, grid, dim3(512), 0, st, a); break;     // (round 4: to_plane_cnn's 128^2 layers on MX)
+    case SR_VAR_CONV1X1: hipLaunchKernelGGL((conv1x1_mfma_f16x3_kernel<4, 2, 4>), grid, dim3(512), 0, st, a); break;
+    case SR_VAR_DIRECT16_MX: hipLaunchKernelGGL((conv_mfma_f16x3_kernel<4, 2, 4, true>), grid, dim3(512), 0, st, a); break;
+    default: hipLaunchKernelGGL((conv_mfma_f16x3_kernel<4, 2, 4>), grid, dim3(512), 0, st, a); break;                   // SR_VAR_DIRECT16
     }
-    if (a.ph[0].ntaps == 9 && (size_t)tiles * grid.y * grid.z <= 256) {
-        // under-filled launch (<= half of the 512 block slots): 8x16-pixel tiles, twice the blocks (bit-identical results)
-        const int t8 = ((a.ph[0].outW + F_TILE_W - 1) / F_TILE_W) * ((a.ph[0].outH + 7) / 8);
-        a.order = (t8 & 7) == 0 ? 2 : 0;
-        if (mx) hipLaunchKernelGGL(conv_mfma_f16x3_rows8_kernel<true>, dim3(t8, grid.y, grid.z), dim3(512), 0, st, a);     // (round 4: to_plane_cnn's 128^2 layers on MX)
-        else hipLaunchKernelGGL(conv_mfma_f16x3_rows8_kernel<false>, dim3(t8, grid.y, grid.z), dim3(512), 0, st, a);
-        return;
-    }
-    // 8 waves x (64 couts x 64 px): 4 waves/SIMD at 2 blocks/CU
-    if (a.ph[0].ntaps == 1) hipLaunchKernelGGL((conv1x1_mfma_f16x3_kernel<4, 2, 4>), grid, dim3(512), 0, st, a);
-    else if (mx) hipLaunchKernelGGL((conv_mfma_f16x3_kernel<4, 2, 4, true>), grid, dim3(512), 0, st, a);
-    else hipLaunchKernelGGL((conv_mfma_f16x3_kernel<4, 2, 4>), grid, dim3(512), 0, st, a);
 }
-
-static int tiles_of(int H, int W) { return ((W + F_TILE_W - 1) / F_TILE_W) * ((H + F_TILE_H - 1) / F_TILE_H); }
 
 // A conv's operand as SPLIT: a SPLIT | SPLIT_MX input where it is, an NCHW | CB8 one converted into `xin` times the layer's in-multiplier (Ci: Cin padded to 16)
 static const uint4* split_input(const void* x, int x_format, const float* in_scale, size_t in_scale_stride, void* xin, int Ci, int Cin, int N, int H, int W, hipStream_t st)
@@ -1822,7 +1808,9 @@ int sr_block_forward_f16x3(const void* prepacked, const void* styles, int N, int
     const bool mx_in = x_format == R3D_FMT_SPLIT_MX;          // (validated by the caller: up = 1, R3D_SR_F16MX)
     const uint4* xs = split_input(x, x_format, pk + L.s0f, L.total, wsb + WS.xin, Cin, Cin, N, Hin, Win, st);
     // conv1 on the Winograd F(2,3) kernel: its operand is transformed in fp32 inside the kernel, so conv0 hands over plain SPLIT (no fp8 records)
-    const bool wino1 = use_wino(Cout, Cout, OH, OW, mx);
+    SrVariantChoice v[2];
+    sr_block_variants(N, Cin, Cout, Hin, Win, up, x_format, mx, clamp, sr_wino_mode(), v);
+    const bool wino1 = v[1].wino();
     const bool mx0 = mx && !wino1;                            // does conv0's epilogue write the fp8 records of conv1's operand?
     if (up) {
         // ---- conv0: fused transposed conv + FIR + bias + lrelu -> SPLIT (one kernel, T stays on chip) ----------------
@@ -1833,13 +1821,13 @@ int sr_block_forward_f16x3(const void* prepacked, const void* styles, int N, int
         u.y = y0; u.y_stride_n = (size_t)Cout / 8 * OH * OW * 2;
         u.Cin = Cin; u.Cout = Cout; u.H = Hin; u.W = Win;
         u.tiles_x = (Win + U_TILE - 1) / U_TILE;
-        u.ntiles = u.tiles_x * ((Hin + U_TILE - 1) / U_TILE);
+        u.ntiles = v[0].tiles;
         u.tiles_per_xcd = (u.ntiles + 7) / 8;
         u.clamp = clamp;
         u.clk = prof_clock_slot(R3D_PROF_UPCONV);
         ProfScope ps(R3D_PROF_UPCONV, st);
-        const dim3 ugrid(8 * u.tiles_per_xcd * (Cout / 32), N);
-        hipLaunchKernelGGL(kUpconv[clamp >= 0.f][mx0][mx_in], ugrid, dim3(256), 0, st, u);
+        const dim3 ugrid(v[0].gx, v[0].gy);
+        hipLaunchKernelGGL(kUpconv[(v[0].bits & SR_UP_CLAMP) != 0][(v[0].bits & SR_UP_MX) != 0][(v[0].bits & SR_UP_MXIN) != 0], ugrid, dim3(256), 0, st, u);
     } else {
         // ---- conv0 of SynthesisBlockNoUp (superresolution.py:159-258): plain modulated 3x3 conv -> SPLIT for conv1 ----
         SrConvCall c0 = sr_conv_call("sr_block_forward", N, Cin, Cout, OH, OW, 3, 1, 0.2f, kSqrt2, clamp, y0, mx0 ? R3D_FMT_SPLIT_MX : R3D_FMT_SPLIT,
@@ -1850,7 +1838,7 @@ int sr_block_forward_f16x3(const void* prepacked, const void* styles, int N, int
         a.x = xs; a.x_stride_n = (size_t)Cin / 8 * Hin * Win * 2;
         a.wp = reinterpret_cast<const uint4*>(wpk + (mx_in ? P.c0_mx : P.c0));
         ProfScope ps(R3D_PROF_CONV, st);
-        launch_conv2(a, tiles_of(OH, OW), N, st, mx_in);
+        launch_conv2(a, v[0], st);
     }
     // ---- conv1 (3x3) + bias/lrelu + toRGB partials (+ optional x outputs) ------------------------------------------
     {
@@ -1863,7 +1851,7 @@ int sr_block_forward_f16x3(const void* prepacked, const void* styles, int N, int
         a.wp = reinterpret_cast<const uint4*>(wpk + (wino1 ? P.c1_wino : P.c1));
         a.wrgb = pk + L.wrgb; a.wrgb_stride_n = L.total; a.rgb_partial = rgbp; a.rgbp_stride_n = (size_t)(Cout / 64) * 3 * OH * OW;
         ProfScope ps(R3D_PROF_CONV, st);
-        launch_conv2(a, tiles_of(OH, OW), N, st, mx, wino1);
+        launch_conv2(a, v[1], st);
     }
     {
         ProfScope ps(R3D_PROF_TORGB, st);
@@ -1920,10 +1908,10 @@ int conv_forward_f16x3(const SrConvCall& c)
         if (c.next_scale) a.next_scale = c.next_scale + cat->chan_off;
     }
     // a plain SPLIT operand (the f16x3 precision, or a producer that does not write records): Winograd F(2,3) when the shape allows it
-    const bool wino = c.ksize == 3 && !mx_in && use_wino(P.Ci, P.Co, c.H, c.W, false);
-    a.wp = reinterpret_cast<const uint4*>(reinterpret_cast<const float*>(c.prepacked) + (mx_in ? P.w_mx : wino ? P.w_wino : P.w));
+    const SrVariantChoice v = sr_conv_variant(c.ksize, P.Ci, P.Co, c.H, c.W, c.N, mx_in, false, sr_wino_mode());
+    a.wp = reinterpret_cast<const uint4*>(reinterpret_cast<const float*>(c.prepacked) + (mx_in ? P.w_mx : v.wino() ? P.w_wino : P.w));
     ProfScope ps(R3D_PROF_CONV, c.stream);
-    launch_conv2(a, tiles_of(c.H, c.W), c.N, c.stream, mx_in, wino);
+    launch_conv2(a, v, c.stream);
     return check_launch("conv_forward");
 }
 
@@ -1938,7 +1926,8 @@ int conv_forward_blend_f16x3(const SrConvCall& c)
     a.wp = reinterpret_cast<const uint4*>(reinterpret_cast<const float*>(c.prepacked) + P.w);
     a.bl_a = c.bl_a; a.bl_b = c.bl_b; a.bl_mask = c.bl_mask; a.bl_scale = scales + S.in_vec; a.bl_scale_stride_n = S.total; a.bl_Ca = c.Ca;
     ProfScope ps(R3D_PROF_CONV, c.stream);
-    hipLaunchKernelGGL(conv1x1_blend_f16x3_kernel, dim3(tiles_of(c.H, c.W), P.Co / BLOCK_M, c.N), dim3(512), 0, c.stream, a);
+    const SrVariantChoice v = sr_blend_variant(P.Co, c.H, c.W, c.N);
+    hipLaunchKernelGGL(conv1x1_blend_f16x3_kernel, dim3(v.gx, v.gy, v.gz), dim3(512), 0, c.stream, a);
     return check_launch("conv_forward_blend");
 }
 

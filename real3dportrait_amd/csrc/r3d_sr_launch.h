@@ -99,6 +99,99 @@ inline int check(const SrConvCall& c)
     return R3D_OK;
 }
 
+// ---- which kernel a conv layer runs on ---------------------------------------------------------------------------------------------------
+// The nine kernel variants behind r3d_conv_forward / _cat / _blend and the two convs of an SR block, and the one place that picks among them: the
+// launchers of r3d_sr_f16x3.hip dispatch on what sr_conv_variant / sr_blend_variant / sr_block_variants return, and the test hooks
+// r3d_debug_conv_variant / r3d_debug_sr_block_variants (include/r3d_hip.h) return the same structs, so what a test is told is what was launched.
+enum SrVariant {
+    SR_VAR_DIRECT16 = 0,        // conv_mfma_f16x3_kernel<4,2,4>: 3x3, 16 x 16-pixel tiles
+    SR_VAR_DIRECT16_MX = 1,     // ... <4,2,4,true>: the f16mx main loop over a SPLIT_MX operand
+    SR_VAR_ROWS8 = 2,           // conv_mfma_f16x3_rows8_kernel<false>: 3x3, 8-row tiles, an under-filled launch
+    SR_VAR_ROWS8_MX = 3,        // ... <true>
+    SR_VAR_WINO = 4,            // conv_wino_f16x3_kernel<false>: Winograd F(2,3) over a plain SPLIT operand
+    SR_VAR_WINO_MX = 5,         // ... <true>: conv1 of an f16mx block under R3D_CONV_WINO = 1 | 2
+    SR_VAR_CONV1X1 = 6,         // conv1x1_mfma_f16x3_kernel<4,2,4> (with the concatenation epilogue)
+    SR_VAR_BLEND1X1 = 7,        // conv1x1_blend_f16x3_kernel (r3d_conv_forward_blend)
+    SR_VAR_UPCONV = 8,          // upconv_fir_f16x3_kernel<CLAMP, MX, MXIN>: conv0 of an up-sampling block; `bits` names the instantiation
+};
+enum { SR_UP_CLAMP = 4, SR_UP_MX = 2, SR_UP_MXIN = 1 };     // SrVariantChoice::bits of SR_VAR_UPCONV
+
+// the tile sizes the grids follow (static_asserted against the kernels' own constants in r3d_sr_f16x3.hip)
+static constexpr int SR_TILE = 16, SR_TILE_ROWS8 = 8, SR_UP_TILE = 14, SR_UP_COUTS = 32;
+static constexpr size_t SR_ROWS8_MAX_BLOCKS = 256;          // a 3x3 launch of at most this many 16-row blocks (half of the 512 block slots) takes 8-row tiles
+
+struct SrVariantChoice {
+    int variant = -1, bits = 0;
+    int order = 0;                                          // Conv2Args::order: 2 = the XCD-aware block order, whenever the tile count divides over the 8 XCDs
+    unsigned gx = 0, gy = 0, gz = 1;                        // the grid
+    int tiles = 0;                                          // pixel tiles of one sample and one cout tile (SR_VAR_UPCONV: gx counts 8 tiles_per_xcd slots, the rest idle)
+    bool wino() const { return variant == SR_VAR_WINO || variant == SR_VAR_WINO_MX; }
+};
+
+// R3D_CONV_WINO, the A/B switch of the Winograd F(2,3) conv (r3d_sr_wino.h), read once per process: 0 keeps every plain 3x3 conv on the direct
+// kernels, 1 both precisions, 2 f16mx only, 3 (default) f16x3 only
+inline int sr_wino_mode() { static const int v = getenv("R3D_CONV_WINO") ? atoi(getenv("R3D_CONV_WINO")) : 3; return v; }
+
+// ... and when a plain 3x3 conv over a plain SPLIT operand takes it (mx: the layer's precision is f16mx): the mode allows the precision, and the
+// shape is whole 16 x 16-pixel tiles, 16-channel stages, 128-cout blocks
+inline bool sr_use_wino(int wino_mode, int Ci, int Co, int H, int W, bool mx)
+{
+    const int m = wino_mode;
+    // (the kernel addresses one sample's SPLIT activation and the weight pack through 32-bit buffer offsets)
+    return (m == 1 || (m == 2 && mx) || (m == 3 && !mx)) && (H & 15) == 0 && (W & 15) == 0 && (Ci & 15) == 0 && (Co % BLOCK_M) == 0 &&
+           (size_t)Ci * H * W * 4 < ((size_t)1 << 31) && (size_t)48 * Ci * Co < ((size_t)1 << 31);
+}
+
+inline int sr_tiles_of(int H, int W, int rows = SR_TILE) { return ((W + SR_TILE - 1) / SR_TILE) * ((H + rows - 1) / rows); }
+
+// One conv layer of ksize 1 | 3 over a SPLIT operand.  Ci / Co: the padded channel counts; operand_mx: the operand carries fp8 records (SPLIT_MX);
+// layer_mx: the layer's precision is f16mx (it matters to the Winograd kernel alone, whose operand is always plain SPLIT); wino_mode:
+// sr_wino_mode(), or 0 for a layer that has no Winograd weight pack.
+inline SrVariantChoice sr_conv_variant(int ksize, int Ci, int Co, int H, int W, int N, bool operand_mx, bool layer_mx, int wino_mode)
+{
+    SrVariantChoice c;
+    c.tiles = sr_tiles_of(H, W);
+    c.gy = (unsigned)(Co / BLOCK_M); c.gz = (unsigned)N;
+    if (ksize == 3 && !operand_mx && sr_use_wino(wino_mode, Ci, Co, H, W, layer_mx)) c.variant = layer_mx ? SR_VAR_WINO_MX : SR_VAR_WINO;
+    else if (ksize == 3 && (size_t)c.tiles * c.gy * c.gz <= SR_ROWS8_MAX_BLOCKS) {
+        // under-filled launch: 8 x 16-pixel tiles, twice the blocks (bit-identical results)
+        c.variant = operand_mx ? SR_VAR_ROWS8_MX : SR_VAR_ROWS8;
+        c.tiles = sr_tiles_of(H, W, SR_TILE_ROWS8);
+    }
+    // 8 waves x (64 couts x 64 px): 4 waves/SIMD at 2 blocks/CU
+    else c.variant = ksize == 1 ? SR_VAR_CONV1X1 : operand_mx ? SR_VAR_DIRECT16_MX : SR_VAR_DIRECT16;
+    c.gx = (unsigned)c.tiles;
+    c.order = (c.tiles & 7) == 0 ? 2 : 0;
+    return c;
+}
+
+// cat([a * mask, b * (1 - mask)]) -> 1x1 conv (r3d_conv_forward_blend): one kernel, blocks in grid order
+inline SrVariantChoice sr_blend_variant(int Co, int H, int W, int N)
+{
+    SrVariantChoice c;
+    c.variant = SR_VAR_BLEND1X1; c.tiles = sr_tiles_of(H, W);
+    c.gx = (unsigned)c.tiles; c.gy = (unsigned)(Co / BLOCK_M); c.gz = (unsigned)N;
+    return c;
+}
+
+// The two convs of an SR block at precision f16x3 | f16mx (mx), input [N][Cin][Hin][Win] in x_format: v[0] conv0 (the fused up-sampling conv, or the
+// plain 3x3 conv of SynthesisBlockNoUp, which has no Winograd pack), v[1] conv1.  conv1 on the Winograd kernel transforms its operand in fp32, so
+// conv0 then hands over plain SPLIT: its epilogue writes conv1's fp8 records only when conv1 stays on the direct f16mx kernels.
+inline void sr_block_variants(int N, int Cin, int Cout, int Hin, int Win, int up, int x_format, bool mx, float clamp, int wino_mode, SrVariantChoice v[2])
+{
+    const int OH = up ? 2 * Hin : Hin, OW = up ? 2 * Win : Win;
+    const bool mx_in = x_format == R3D_FMT_SPLIT_MX;
+    v[1] = sr_conv_variant(3, Cout, Cout, OH, OW, N, mx && !sr_use_wino(wino_mode, Cout, Cout, OH, OW, mx), mx, wino_mode);
+    const bool mx0 = mx && !v[1].wino();
+    if (!up) { v[0] = sr_conv_variant(3, Cin, Cout, OH, OW, N, mx_in, mx, 0); return; }
+    SrVariantChoice c;
+    c.variant = SR_VAR_UPCONV;
+    c.bits = (clamp >= 0.f ? SR_UP_CLAMP : 0) | (mx0 ? SR_UP_MX : 0) | (mx_in ? SR_UP_MXIN : 0);
+    c.tiles = ((Win + SR_UP_TILE - 1) / SR_UP_TILE) * ((Hin + SR_UP_TILE - 1) / SR_UP_TILE);
+    c.gx = (unsigned)(8 * ((c.tiles + 7) / 8) * (Cout / SR_UP_COUTS)); c.gy = (unsigned)N;      // 8 XCDs x tiles_per_xcd slots x 32-cout groups
+    v[0] = c;
+}
+
 // f16x3 implementation (r3d_sr_f16x3.hip)
 int conv_forward_f16x3(const SrConvCall& c);
 int conv_forward_blend_f16x3(const SrConvCall& c);

@@ -281,8 +281,9 @@ def conv_ref(c, x, slope, dt=torch.float64):
     return y if slope is None else F.leaky_relu(y, slope)
 
 
-def conv_run(c, x, x_fmt, N, H, W, slope, y_fmt, nxt=None):
-    """r3d_conv_forward of the (prepared, folded) layer c into a guarded window; nxt: the folded consumer of a SPLIT / SPLIT_MX output."""
+def conv_run(c, x, x_fmt, N, H, W, slope, y_fmt, nxt=None, y_absmax=None):
+    """r3d_conv_forward of the (prepared, folded) layer c into a guarded window; nxt: the folded consumer of a SPLIT / SPLIT_MX output; y_absmax: a zeroed
+    device float[N] the epilogue maxes |y| into."""
     lib = _lib.load()
     Cin, Cout, k = c.in_channels, c.out_channels, c.kernel_size[0]
     need = int(lib.r3d_conv_workspace_bytes(N, Cin, H, W))
@@ -293,7 +294,7 @@ def conv_run(c, x, x_fmt, N, H, W, slope, y_fmt, nxt=None):
     else:
         y = Out((N, Cout // 8, H, W, 8) if y_fmt == CB8 else (N, Cout, H, W))
     call("conv_forward", c._prepacked, c._scales, c._bias32, N, Cin, Cout, H, W, k, x, x_fmt, 0 if slope is None else 1, float(slope or 0.0), 1.0, -1.0,
-         y.t, y_fmt, ns, stride, None, work, need if work is not None else 0)
+         y.t, y_fmt, ns, stride, y_absmax, work, need if work is not None else 0)
     return y
 
 
@@ -313,8 +314,9 @@ def make_block(g, Cin, Cout, up, clamp=None, precision="f16x3"):
     return blk, p
 
 
-def block_run(blk, prep, x, x_fmt, img, N, Hin, Win, out_fmt, nxt=None):
-    """r3d_sr_block_forward of the (prepared, folded) block into guarded windows: (x_out, img_out)."""
+def block_run(blk, prep, x, x_fmt, img, N, Hin, Win, out_fmt, nxt=None, x_absmax=None):
+    """r3d_sr_block_forward of the (prepared, folded) block into guarded windows: (x_out, img_out); x_absmax: a zeroed device float[N] conv1's epilogue
+    maxes |x_out| into."""
     lib = _lib.load()
     Cin, Cout = blk.in_channels, blk.out_channels
     need = int(lib.r3d_sr_block_workspace_bytes(N, Cin, Cout, Hin, Win))
@@ -324,7 +326,7 @@ def block_run(blk, prep, x, x_fmt, img, N, Hin, Win, out_fmt, nxt=None):
     x_out = Out((N, 2, Cout // 8, OH, OW, 8), torch.float16) if out_fmt >= SPLIT else Out((N, Cout, OH, OW))
     img_out = Out((N, 3, OH, OW))
     call("sr_block_forward", prep[0], prep[1], N, Cin, Cout, Hin, Win, blk._UP, x, x_fmt, img, blk._clamp(), x_out.t, out_fmt, ns, stride,
-         img_out.t, None, None, blk._prec(), work, need)
+         img_out.t, None, x_absmax, blk._prec(), work, need)
     return x_out, img_out
 
 
