@@ -618,6 +618,38 @@ int r3d_torso_seg_input(const float* img, int N, int Ci, const float* segmap, in
 int r3d_torso_mask_volume(const float* feats_cl, int N, int D, int H, int W, int C, const float* segmap, int Cs, int Hs, int Ws, int c0,
                           int c1, int ksize, int mul_mask, float* masked_cl, float* motion_cl, r3d_stream_t stream);
 
+/* --- mesh rasteriser: the SECC map's z-buffer rasterisation and attribute interpolation, inference (added under ABI 0.8.0) -------------
+ * MeshRenderer.forward (deep_3drecon/util/mesh_renderer.py:53-130) as SECC_Renderer configures it: pytorch3d's rasteriser with
+ * image_size = S, blur_radius = 0, faces_per_pixel = 1, cull_backfaces = False under FoVPerspectiveCameras(fov, znear, zfar), identity
+ * pose, aspect 1.  The rule is restated from pytorch3d's naive rasteriser (tests/raster_ref64.py is the fp64 restatement);
+ * equality with pytorch3d rests on that restatement and has not been measured.  fp32.
+ *   vertex [B, N, 3] camera space, read only (negate_x != 0: x is negated on the fly, as mesh_renderer.py:69-71 does on its copy);
+ *   tri [M, 3] (tri_batched = 0) or [B, M, 3] (tri_batched != 0), int32; feat [B, N, C], 1 <= C <= 4, or NULL together with image.
+ *   Projection x_ndc = s x / z, y_ndc = s y / z, s = 1 / tan(fov / 2); pixel (row i from the top, column j from the left) has
+ *   y_ndc = -1 + (2 (S - 1 - i) + 1) / S and x_ndc = -1 + (2 (S - 1 - j) + 1) / S.  A pixel is covered by a face iff its three
+ *   barycentrics (areas over area + 1e-8, faces with |area| <= 1e-8 skipped) are STRICTLY positive, either winding; the depth is the
+ *   perspective-corrected camera-space z, the smallest wins, the lower face index on an exact tie: deterministic, run to run and stream
+ *   to stream.
+ *   pix_to_face [B, S, S] int64 (may be NULL): the packed index b M + f, or -1.
+ *   mask [B, 1, S, S] = pix_to_face > 0 with first_face_is_background != 0 -- the reference's own test (mesh_renderer.py:116), which
+ *     turns face 0 of the batch's first mesh into background -- or pix_to_face >= 0 with 0.
+ *   depth [B, 1, S, S] = mask pz; image [B, C, S, S] = (mask sum_k b_k feat[tri[f, k]]) out_scale + out_shift with the
+ *   perspective-corrected barycentrics b_k (1, 0: the reference; 2, -1: SECC_Renderer's (x - 0.5) / 0.5 of secc_renderer.py:52 folded
+ *   in).  Empty pixels are -1 / 0 / 0 / out_shift.  The barycentrics themselves are not stored.
+ * Difference from pytorch3d, on input SECC_Renderer cannot produce (faces at z = 10 +- 1.5, znear = 5): a face with a vertex at
+ * z < znear / 2 (or z <= 0) is DROPPED where pytorch3d clips it, as is a face with a non-finite vertex or projection or an index
+ * outside [0, N); nothing is read out of bounds on such input.
+ * Limits, refused with R3D_ERR_INVALID_ARG before any launch: NULL vertex / tri / mask / depth, feat without image or the reverse,
+ * S outside 1 .. 16384, C outside 1 .. 4, B M >= 2^31, B S S >= 2^31, fov_deg not finite or not in (0, 180); R3D_ERR_WORKSPACE: a
+ * workspace that is NULL, not 8-byte aligned or smaller than r3d_raster_workspace_bytes(B, S, M) (0 for sizes the call refuses).  The
+ * workspace needs no initialisation and carries nothing between calls (one async memset per call clears the keys); two calls in
+ * flight on different streams need a workspace each. */
+size_t r3d_raster_workspace_bytes(int B, int S, int M);
+int r3d_raster_forward(const float* vertex, const float* feat, const int32_t* tri, int tri_batched, int B, int N, int M, int C, int S,
+                       float fov_deg, float znear, int negate_x, int first_face_is_background, float out_scale, float out_shift,
+                       int64_t* pix_to_face, float* mask, float* depth, float* image, void* workspace, size_t workspace_bytes,
+                       r3d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

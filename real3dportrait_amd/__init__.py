@@ -10,6 +10,7 @@ Operators keep the reference's names and signatures (see each module's docstring
     TorsoMotionFieldEstimator                            (torso_motion.py: the torso network's per-frame MotionFieldEstimator)
     TorsoAppearanceFeatureExtractor                      (torso_appearance.py: the torso network's AppearanceFeatureExtractor)
     torso_model_forward, torso_seg_input, torso_mask_volume (torso_forward.py: the torso model's forward over the three, its two glue kernels)
+    MeshRenderer, rasterize, patch_secc_renderer         (mesh_renderer.py: the SECC map's z-buffer rasteriser, without pytorch3d)
     render_clip_sharded                                  (frames.py: frame sharding + RCCL gather)
 All compute goes through libr3d_hip.so (include/r3d_hip.h); there is no eager/CPU fallback.
 """
@@ -42,6 +43,9 @@ def __getattr__(name):      # lazy: importing the package (e.g. for synth) must 
         import importlib
         m = importlib.import_module(".torso_forward", __name__)          # the submodule's name is not an attribute this function serves
         return getattr(m, {"torso_model_forward": "forward", "torso_seg_input": "seg_input", "torso_mask_volume": "mask_volume"}[name])
+    if name in ("MeshRenderer", "rasterize", "patch_secc_renderer"):
+        import importlib
+        return getattr(importlib.import_module(".mesh_renderer", __name__), name)
     if name in ("render_clip_sharded", "shard_frames"):
         from . import frames as m
         return getattr(m, name)

@@ -91,6 +91,9 @@ SIGNATURES = {
     "r3d_torso_conv3d_res": (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, P, c_float, P, P, c_int, c_int, c_int, c_float, P, P, P, c_int, P]),
     "r3d_torso_seg_input": (c_int, [P, c_int, c_int, P, c_int, c_int, c_int, c_int, c_int, P, c_int, c_int, P]),
     "r3d_torso_mask_volume": (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P]),
+    "r3d_raster_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "r3d_raster_forward": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_int, c_int, c_float, c_float,
+                                   P, P, P, P, P, c_size_t, P]),
 }
 
 
@@ -98,6 +101,9 @@ SIGNATURES = {
 # them, and a library built from older sources -- the other side of a scripts/gpu_lib_ab.sh comparison, say -- must keep loading)
 OPTIONAL_SIGNATURES = {
     "r3d_debug_merge_fallbacks": (c_int, [ctypes.POINTER(ctypes.c_ulonglong), c_int]),
+    # r3d_raster_forward with the large-face threshold and a stage mask (1 clear, 2 scatter, 4 large_faces, 8 resolve) in front of the stream
+    "r3d_debug_raster_forward": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_int, c_int, c_float, c_float,
+                                         P, P, P, P, P, c_size_t, c_int, c_int, P]),
 }
 
 

@@ -580,3 +580,28 @@ def synth_torso_onehot_segmap(seed, N=1, Cs=6, Hs=512, Ws=512, centres=10, speck
         for c in range(Cs):
             seg[n, c] = label == c
     return seg
+
+
+BFM_FOV_DEG = 2.0 * math.degrees(math.atan(112.0 / 1015.0))     # SECC_Renderer's camera (deep_3drecon/secc_renderer.py:14: centre 112, focal 1015)
+
+
+def synth_face_mesh(G, seed, C=3):
+    """A face-like mesh for the rasteriser (real3dportrait_amd/mesh_renderer.py): a (G + 1)^2 grid over [-1.05, 1.05]^2 with sigma = 0.01
+    jitter in x and y and z = 10 - 0.9 cos(1.3 u) cos(1.1 v) + 0.05 noise, split into 2 G^2 triangles, plus a second copy with x and y
+    scaled by 0.35 and z - 0.4: a nearer layer, so that the depth test decides pixels.  About 95 % of the image at BFM_FOV_DEG.
+    Returns vertex [N, 3] float32 (camera space), tri [M, 3] int64 and feat [N, C] float32 in [0, 1); N = 2 (G + 1)^2, M = 4 G^2."""
+    n = (G + 1) * (G + 1)
+    lin = np.linspace(-1.05, 1.05, G + 1)
+    v, u = np.meshgrid(lin, lin, indexing="ij")
+    u, v = u.reshape(-1), v.reshape(-1)
+    jit = hash_unitvar(seed, (3, n), stream=40).astype(np.float64)
+    x, y = u + 0.01 * jit[0], v + 0.01 * jit[1]
+    z = 10.0 - 0.9 * np.cos(1.3 * u) * np.cos(1.1 * v) + 0.05 * jit[2]
+    layer = np.stack([x, y, z], axis=1)
+    near = np.stack([0.35 * x, 0.35 * y, z - 0.4], axis=1)
+    r, c = np.meshgrid(np.arange(G), np.arange(G), indexing="ij")
+    i00 = (r * (G + 1) + c).reshape(-1)
+    i01, i10, i11 = i00 + 1, i00 + G + 1, i00 + G + 2
+    tri = np.concatenate([np.stack([i00, i01, i11], axis=1), np.stack([i00, i11, i10], axis=1)], axis=0).astype(np.int64)
+    return {"vertex": np.concatenate([layer, near], axis=0).astype(np.float32), "tri": np.concatenate([tri, tri + n], axis=0),
+            "feat": hash_uniform(seed, 2 * n * C, stream=41).reshape(2 * n, C)}
