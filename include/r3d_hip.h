@@ -650,6 +650,32 @@ int r3d_raster_forward(const float* vertex, const float* feat, const int32_t* tr
                        int64_t* pix_to_face, float* mask, float* depth, float* image, void* workspace, size_t workspace_bytes,
                        r3d_stream_t stream);
 
+/* --- blink edit of SECC maps, inference (added under ABI 0.8.0) --------------------------------------------------------------------------
+ * blink_eye_for_secc (inference/edit_secc.py:47-129) for F selected frames of a clip secc [T, 3, H, W] fp32 in [-1, 1], as the blink loop
+ * of inference/real3d_infer.py:411-426 applies it, on the device: no host round trip and no kd-tree (DESIGN 4.15 states the rule;
+ * tests/blink_ref.py is its NumPy restatement).  Per listed frame k: map frame_idx[k] with close_eye_percent percent[k] is quantised to
+ * 8 bits, q = trunc(((x + 1) / 2) 255), and comes back as q / 127.5 - 1; for percent > 0 the eye holes found in the two prior regions are
+ * closed from above and below by copying, to each pixel to close, the colour of the nearest face pixel that lies more than 5 pixels away
+ * from every hole pixel.
+ *   Differences from the reference: (1) on a distance tie the face pixel with the lowest (row, column) is taken, where the reference
+ *   takes whatever its kd-tree returns (3 to 16 % of the edited pixels on the test maps; everywhere else the result is bit-identical);
+ *   (2) NaN and values outside [-1, 1] quantise to 0 .. 255 by clamping; (3) maps on which the reference raises ValueError come back
+ *   quantised only, with a status.
+ *   frame_idx [F] int32, percent [F] double, status [F] int32: DEVICE arrays.  status[k] = 0 done; 1 no eye pixel in one of the prior
+ *   regions; 2 no face pixel left around the eyes; 3 frame_idx[k] outside [0, T) or percent[k] outside [0, 1] (NaN included): that
+ *   frame is neither read nor written.
+ *   out [T, 3, H, W] may be secc itself (in place).  Only the listed frames are written, in place or not: with out != secc the caller
+ *   copies whatever else out should hold.  Listing a frame twice is the caller's error (the result of that frame is then undefined,
+ *   nothing is accessed out of bounds).
+ * The result is a pure function of the input: run to run and stream to stream bit-identical.  No host synchronisation and no allocation.
+ * Refused before any launch, R3D_ERR_INVALID_ARG: a NULL pointer, H or W outside 16 .. 4096, T < 1, F < 1, F > T, F > 65535;
+ * R3D_ERR_WORKSPACE: a workspace that is NULL, not 8-byte aligned or smaller than r3d_secc_blink_workspace_bytes(F, H, W) (0 for sizes
+ * the call refuses).  The workspace needs no initialisation and carries nothing between calls; two calls in flight on different
+ * streams need a workspace each. */
+size_t r3d_secc_blink_workspace_bytes(int F, int H, int W);
+int r3d_secc_blink(const float* secc, int T, int H, int W, const int32_t* frame_idx, const double* percent, int F, float* out,
+                   int32_t* status, void* workspace, size_t workspace_bytes, r3d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

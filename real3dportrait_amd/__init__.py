@@ -11,6 +11,7 @@ Operators keep the reference's names and signatures (see each module's docstring
     TorsoAppearanceFeatureExtractor                      (torso_appearance.py: the torso network's AppearanceFeatureExtractor)
     torso_model_forward, torso_seg_input, torso_mask_volume (torso_forward.py: the torso model's forward over the three, its two glue kernels)
     MeshRenderer, rasterize, patch_secc_renderer         (mesh_renderer.py: the SECC map's z-buffer rasteriser, without pytorch3d)
+    blink_eye_for_secc, blink_frames, apply_periodic_blink, blink_schedule, patch_blink (edit_secc.py: the driving maps' blink edit)
     render_clip_sharded                                  (frames.py: frame sharding + RCCL gather)
 All compute goes through libr3d_hip.so (include/r3d_hip.h); there is no eager/CPU fallback.
 """
@@ -46,6 +47,9 @@ def __getattr__(name):      # lazy: importing the package (e.g. for synth) must 
     if name in ("MeshRenderer", "rasterize", "patch_secc_renderer"):
         import importlib
         return getattr(importlib.import_module(".mesh_renderer", __name__), name)
+    if name in ("blink_eye_for_secc", "blink_frames", "blink_schedule", "apply_periodic_blink", "patch_blink"):
+        import importlib
+        return getattr(importlib.import_module(".edit_secc", __name__), name)
     if name in ("render_clip_sharded", "shard_frames"):
         from . import frames as m
         return getattr(m, name)

@@ -94,6 +94,8 @@ SIGNATURES = {
     "r3d_raster_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "r3d_raster_forward": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_int, c_int, c_float, c_float,
                                    P, P, P, P, P, c_size_t, P]),
+    "r3d_secc_blink_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "r3d_secc_blink": (c_int, [P, c_int, c_int, c_int, P, P, c_int, P, P, P, c_size_t, P]),
 }
 
 
@@ -104,6 +106,8 @@ OPTIONAL_SIGNATURES = {
     # r3d_raster_forward with the large-face threshold and a stage mask (1 clear, 2 scatter, 4 large_faces, 8 resolve) in front of the stream
     "r3d_debug_raster_forward": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_int, c_int, c_float, c_float,
                                          P, P, P, P, P, c_size_t, c_int, c_int, P]),
+    # r3d_secc_blink with a stage mask (1 clear, 2 quantise_bounds, 4 erode, 8 columns, 16 fill) in front of the stream
+    "r3d_debug_secc_blink": (c_int, [P, c_int, c_int, c_int, P, P, c_int, P, P, P, c_size_t, c_int, P]),
 }
 
 

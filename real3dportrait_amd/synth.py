@@ -605,3 +605,29 @@ def synth_face_mesh(G, seed, C=3):
     tri = np.concatenate([np.stack([i00, i01, i11], axis=1), np.stack([i00, i11, i10], axis=1)], axis=0).astype(np.int64)
     return {"vertex": np.concatenate([layer, near], axis=0).astype(np.float32), "tri": np.concatenate([tri, tri + n], axis=0),
             "feat": hash_uniform(seed, 2 * n * C, stream=41).reshape(2 * n, C)}
+
+
+def synth_secc_eyes(H, W, seed, crossing=False, zero_channel=0, right_hole=True):
+    """A SECC-like map [3, H, W] float32 in [-1, 1] for the blink edit (real3dportrait_amd/edit_secc.py): an elliptical face
+    ((u - .5) / .42)^2 + ((v - .52) / .47)^2 < 1 (u, v the pixel centres in [0, 1]) over a background of -1, smooth colours 2 x - 1 with
+    x in [0.02, 1] (a colour never quantises to 0) plus sigma = 0.01 noise, and two elliptical eye holes of -1 at u = 0.37 and 0.63,
+    v = 0.385 (the right one 0.013 lower), half-axes 0.065 x 0.028.  crossing: the right hole sits at u = 0.56 with a half-axis of 0.09, so it
+    crosses the middle column into the left prior region.  zero_channel = n: n face pixels get one channel at x = 0.001, which quantises
+    to 0 (the reference then counts the pixel as non-face).  right_hole=False leaves the right prior region without an eye pixel."""
+    v, u = np.meshgrid((np.arange(H) + 0.5) / H, (np.arange(W) + 0.5) / W, indexing="ij")
+    face = ((u - 0.5) / 0.42) ** 2 + ((v - 0.52) / 0.47) ** 2 < 1.0
+    noise = 0.01 * hash_unitvar(seed, (3, H, W), stream=50).astype(np.float64)
+    x = np.stack([0.5 + 0.4 * np.sin(3.1 * u + 0.3 * seed) * np.cos(2.3 * v), 0.5 + 0.4 * np.cos(2.7 * u * v + 0.2 * seed),
+                  0.5 + 0.35 * np.sin(4.0 * (u - v)) + 0.1 * v]) + noise
+    x = np.clip(x, 0.02, 1.0)
+    ru, rw = (0.56, 0.09) if crossing else (0.63, 0.065)
+    hole = ((u - 0.37) / 0.065) ** 2 + ((v - 0.385) / 0.028) ** 2 < 1.0
+    if right_hole:
+        hole |= ((u - ru) / rw) ** 2 + ((v - 0.398) / 0.028) ** 2 < 1.0
+    if zero_channel:
+        ys, xs = np.nonzero(face & ~hole)
+        pick = (hash_uniform(seed, 2 * zero_channel, stream=51).reshape(2, -1) * np.array([[len(ys)], [3]])).astype(np.int64)
+        x[pick[1], ys[pick[0]], xs[pick[0]]] = 0.001
+    img = 2.0 * x - 1.0
+    img[:, ~face | hole] = -1.0
+    return img.astype(np.float32)
