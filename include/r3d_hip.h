@@ -676,6 +676,35 @@ size_t r3d_secc_blink_workspace_bytes(int F, int H, int W);
 int r3d_secc_blink(const float* secc, int T, int H, int W, const int32_t* frame_idx, const double* percent, int F, float* out,
                    int32_t* status, void* workspace, size_t workspace_bytes, r3d_stream_t stream);
 
+/* --- morphable face model: the vertices of the SECC meshes and the 2D landmarks, inference (added under ABI 0.8.0) ----------------------
+ * r3d_face_vertex is ParametricFaceModel.compute_face_vertex (deep_3drecon/deep_3drecon_models/bfm.py:332-347), r3d_face_landmarks is
+ * Face3DHelper.reconstruct_lm2d (data_util/face3d_helper.py:132-169): the same arithmetic on the L key rows plus the projection.  fp32
+ * (tests/face_model_ref64.py is the fp64 restatement).  Arrays in the reference's own layouts, nothing is repacked:
+ *   mean [3 N]; id_base [3 N, Ki] and exp_base [3 N, Ke] row-major (row 3 n + c is component c of vertex n); id [T, Ki], exp [T, Ke],
+ *   euler [T, 3] in radians, trans [T, 3]; vertex [T, N, 3], the layout r3d_raster_forward reads; lm2d [T, L, 2].
+ * Per frame t and vertex n:
+ *   p = mean[3 n ..] + id_base[3 n .., :] . id[t] + exp_base[3 n .., :] . exp[t], one chain of fused multiply-adds per row, in this
+ *       order: the mean, then k = 0 .. Ki - 1 of the identity, then k = 0 .. Ke - 1 of the expression;
+ *   q = M p + trans[t] with M = Rz Ry Rx of compute_rotation (bfm.py:204-238; the reference writes p @ (Rz Ry Rx)^T);
+ *   q.z = camera_distance - q.z when to_camera != 0.
+ * The landmarks continue with the projection of perspective_projection(focal, center): x' = (focal q.x + center q.z) / q.z, likewise
+ * y', then y' = image_size - y', and both are divided by image_size (the reference: 1015, 112, 224, camera_distance 10).
+ *   exp, euler or trans may be NULL, meaning zeros: the result is bit-identical to passing arrays of +0.0f.  Ke = 0 is allowed (exp_base
+ *   and exp are then ignored).
+ * A frame's result depends on that frame's inputs only: not on T, not on the other frames of the call.  A frame computed alone and as
+ * frame 37 of 51 is bit-identical, so a clip does not depend on how it is cut into chunks.  Run to run and stream to stream
+ * bit-identical; no allocation, no workspace, no host synchronisation.  Inputs are never written.  Any 4-byte-aligned pointer and any
+ * Ki, Ke are accepted; 16-byte loads are used for a base whose pointer is 16-byte aligned and whose K is a multiple of 4.
+ * Refused before any launch with R3D_ERR_INVALID_ARG: NULL mean / id_base / id / output; exp_base NULL while Ke > 0; N (L) or T < 1;
+ * Ki < 1, Ke < 0 or Ki + Ke > 512; 3 N T >= 2^31; camera_distance not finite; for the landmarks focal, center or image_size not
+ * finite, focal <= 0 or image_size <= 0; an output that overlaps an input. */
+int r3d_face_vertex(const float* mean, const float* id_base, const float* exp_base, int N, int Ki, int Ke, const float* id,
+                    const float* exp, const float* euler, const float* trans, int T, float camera_distance, int to_camera,
+                    float* vertex, r3d_stream_t stream);
+int r3d_face_landmarks(const float* key_mean, const float* key_id_base, const float* key_exp_base, int L, int Ki, int Ke,
+                       const float* id, const float* exp, const float* euler, const float* trans, int T, float camera_distance,
+                       int to_camera, float focal, float center, float image_size, float* lm2d, r3d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,6 +12,8 @@ Operators keep the reference's names and signatures (see each module's docstring
     torso_model_forward, torso_seg_input, torso_mask_volume (torso_forward.py: the torso model's forward over the three, its two glue kernels)
     MeshRenderer, rasterize, patch_secc_renderer         (mesh_renderer.py: the SECC map's z-buffer rasteriser, without pytorch3d)
     blink_eye_for_secc, blink_frames, apply_periodic_blink, blink_schedule, patch_blink (edit_secc.py: the driving maps' blink edit)
+    compute_face_vertex, reconstruct_lm2d, patch_face_model, patch_face3d_helper (face_model.py: the morphable model's vertices and landmarks)
+    get_driving_motion, patch_driving_motion             (driving_motion.py: face model -> rasteriser -> blink -> landmarks on the device)
     render_clip_sharded                                  (frames.py: frame sharding + RCCL gather)
 All compute goes through libr3d_hip.so (include/r3d_hip.h); there is no eager/CPU fallback.
 """
@@ -50,6 +52,12 @@ def __getattr__(name):      # lazy: importing the package (e.g. for synth) must 
     if name in ("blink_eye_for_secc", "blink_frames", "blink_schedule", "apply_periodic_blink", "patch_blink"):
         import importlib
         return getattr(importlib.import_module(".edit_secc", __name__), name)
+    if name in ("compute_face_vertex", "reconstruct_lm2d", "patch_face_model", "patch_face3d_helper"):
+        import importlib
+        return getattr(importlib.import_module(".face_model", __name__), name)
+    if name in ("get_driving_motion", "patch_driving_motion"):
+        import importlib
+        return getattr(importlib.import_module(".driving_motion", __name__), name)
     if name in ("render_clip_sharded", "shard_frames"):
         from . import frames as m
         return getattr(m, name)

@@ -96,6 +96,8 @@ SIGNATURES = {
                                    P, P, P, P, P, c_size_t, P]),
     "r3d_secc_blink_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "r3d_secc_blink": (c_int, [P, c_int, c_int, c_int, P, P, c_int, P, P, P, c_size_t, P]),
+    "r3d_face_vertex": (c_int, [P, P, P, c_int, c_int, c_int, P, P, P, P, c_int, c_float, c_int, P, P]),
+    "r3d_face_landmarks": (c_int, [P, P, P, c_int, c_int, c_int, P, P, P, P, c_int, c_float, c_int, c_float, c_float, c_float, P, P]),
 }
 
 

@@ -110,6 +110,26 @@ def rasterize(vertex, tri, S, fov, znear, feat=None, negate_x=True, first_face_i
     return p2f, mask, depth, image
 
 
+@torch.no_grad()
+def _rasterize_into(vertex, tri, S, fov, znear, feat, image, mask, depth, out_scale=1.0, out_shift=0.0):
+    """rasterize's call with every output given (driving_motion.py): vertex [B, N, 3], feat [B, N, C] and the outputs image [B, C, S, S],
+    mask and depth [B, 1, S, S] are contiguous fp32 tensors on one GPU, tri [M, 3] or [B, M, 3] integer; the reference's settings
+    (x negated, face 0 of the first mesh is background), no pix_to_face.  The same launches as rasterize, so the same bits."""
+    B, N = vertex.shape[:2]
+    M, S = tri.shape[-2], int(S)
+    C = feat.shape[2]
+    for t, shape, what in ((vertex, (B, N, 3), "vertex"), (feat, (B, N, C), "feat"), (image, (B, C, S, S), "image"),
+                           (mask, (B, 1, S, S), "mask"), (depth, (B, 1, S, S), "depth")):
+        if tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_contiguous() or t.device != vertex.device:
+            raise ValueError("_rasterize_into: %s must be a contiguous float32 %s tensor on %s" % (what, shape, vertex.device))
+    t32 = _checked_tri(tri, N)
+    ws = _workspace(vertex.device, B, S, M)
+    rc = _lib.load().r3d_raster_forward(_lib.ptr(vertex), _lib.ptr(feat), _lib.ptr(t32), int(tri.dim() == 3), B, N, M, C, S, float(fov),
+                                        float(znear), 1, 1, float(out_scale), float(out_shift), None, _lib.ptr(mask), _lib.ptr(depth),
+                                        _lib.ptr(image), _lib.ptr(ws), ws.numel(), _lib.stream_ptr())
+    _lib.check(rc, "raster_forward")
+
+
 class MeshRenderer(nn.Module):
     """deep_3drecon/util/mesh_renderer.py:35-130 on the HIP rasteriser: the same constructor, forward(vertex, tri, feat=None) ->
     (mask [B, 1, S, S], depth [B, 1, S, S], image [B, C, S, S] or None), fp32, x negated as the reference negates it (on its copy, never

@@ -631,3 +631,65 @@ def synth_secc_eyes(H, W, seed, crossing=False, zero_channel=0, right_hole=True)
     img = 2.0 * x - 1.0
     img[:, ~face | hole] = -1.0
     return img.astype(np.float32)
+
+
+SECC_EYES = ((0.37, 0.385), (0.63, 0.398))          # (u, v) of synth_secc_eyes' two holes, half-axes 0.065 x 0.028 of the image
+
+
+def synth_face_model(G, seed, Ki=80, Ke=64):
+    """A morphable face model for real3dportrait_amd/face_model.py and driving_motion.py, with the attributes the reference's
+    ParametricFaceModel, SECC_Renderer and Face3DHelper carry (BFM data exists on no machine this project is built on):
+
+        mean_shape [3 N, 1]   a single-layer (G + 1)^2 grid like synth_face_mesh's: x, y over [-1.05, 1.05]^2 with a jitter of sigma = a tenth of a cell, model
+                              z = 0.9 cos(1.3 u) cos(1.1 v), so that camera z = camera_distance - z = 10 - 0.9 cos cos
+        id_base [3 N, Ki], exp_base [3 N, Ke]   smooth displacement fields of amplitude 0.004 per unit coefficient: column k is
+                              sin(a_k u + p_k) sin(b_k v + q_k) times a fixed unit direction d_k, a_k, b_k in [0.5, 3): the gradient of a
+                              unit-variance sum of all columns stays near 0.05, so no triangle flips
+        tri [M, 3] int64      2 G^2 triangles minus those whose centre projects (mean shape, BFM_FOV_DEG, x negated as the renderer does)
+                              into one of two ellipses at SECC_EYES, as SECC_Renderer removes the eye faces; the blink edit accepts the
+                              rendered map.  Face 0 is the zero-area triangle (0, 0, 0): the reference's mask, pix_to_face > 0, turns face 0
+                              of the FIRST mesh of every batch into background, and with a face that covers nothing a map cannot depend on
+                              where its frame falls in a chunk
+        feat [N, 3]           in [0.02, 1]: a colour never quantises to 0
+        keypoints [68] int64, key_mean_shape [68, 3], key_id_base [204, Ki], key_exp_base [204, Ke]   as Face3DHelper.load_3dmm cuts them
+        camera_distance 10.0
+
+    float32 throughout, every number from hash_*: the same (G, seed, Ki, Ke) gives the same model everywhere."""
+    n = (G + 1) * (G + 1)
+    lin = np.linspace(-1.05, 1.05, G + 1)
+    v, u = np.meshgrid(lin, lin, indexing="ij")
+    u, v = u.reshape(-1), v.reshape(-1)
+    jit = hash_unitvar(seed, (2, n), stream=70).astype(np.float64)
+    sigma = 0.1 * 2.1 / G                    # |jitter| <= 3.47 sigma: two neighbours never cross
+    x, y, z = u + sigma * jit[0], v + sigma * jit[1], 0.9 * np.cos(1.3 * u) * np.cos(1.1 * v)
+    mean = np.stack([x, y, z], axis=1)
+
+    def basis(K, stream):
+        if K == 0:
+            return np.zeros((3 * n, 0), np.float32)
+        par = hash_uniform(seed, 4 * K, stream).reshape(4, K).astype(np.float64)
+        d = hash_unitvar(seed, (K, 3), stream + 1).astype(np.float64) + 1e-3
+        d /= np.linalg.norm(d, axis=1, keepdims=True)
+        a, b, p, q = 0.5 + 2.5 * par[0], 0.5 + 2.5 * par[1], 2 * math.pi * par[2], 2 * math.pi * par[3]
+        field = np.sin(u[:, None] * a + p) * np.sin(v[:, None] * b + q)                    # [n, K]
+        return (0.004 * field[:, None, :] * d.T[None]).reshape(3 * n, K).astype(np.float32)
+
+    r, c = np.meshgrid(np.arange(G), np.arange(G), indexing="ij")
+    i00 = (r * (G + 1) + c).reshape(-1)
+    i01, i10, i11 = i00 + 1, i00 + G + 1, i00 + G + 2
+    tri = np.concatenate([np.stack([i00, i01, i11], axis=1), np.stack([i00, i11, i10], axis=1)], axis=0).astype(np.int64)
+    centre = mean[tri].mean(axis=1)
+    s = 1015.0 / 112.0                                                                    # 1 / tan(BFM_FOV_DEG / 2)
+    cz = 10.0 - centre[:, 2]
+    pu, pv = 0.5 * (1.0 + s * centre[:, 0] / cz), 0.5 * (1.0 - s * centre[:, 1] / cz)      # x_ndc = s (-x) / z = 1 - 2 u; y_ndc = 1 - 2 v
+    eye = np.zeros(len(tri), bool)
+    for eu, ev in SECC_EYES:
+        eye |= ((pu - eu) / 0.065) ** 2 + ((pv - ev) / 0.028) ** 2 < 1.0
+    tri = np.concatenate([np.zeros((1, 3), np.int64), tri[~eye]], axis=0)
+    key = (np.arange(68) * n) // 68 + (hash_uniform(seed, 68, stream=75) * (n // 68)).astype(np.int64)
+    id_base, exp_base = basis(Ki, 71), basis(Ke, 73)
+    mean32 = mean.astype(np.float32)
+    return {"mean_shape": mean32.reshape(-1, 1), "id_base": id_base, "exp_base": exp_base, "tri": tri,
+            "feat": (0.02 + 0.98 * hash_uniform(seed, 3 * n, stream=76).reshape(n, 3)).astype(np.float32), "keypoints": key,
+            "key_mean_shape": mean32[key], "key_id_base": id_base.reshape(n, 3, Ki)[key].reshape(3 * 68, Ki),
+            "key_exp_base": exp_base.reshape(n, 3, Ke)[key].reshape(3 * 68, Ke), "camera_distance": 10.0}

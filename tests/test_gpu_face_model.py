@@ -1,0 +1,202 @@
+"""GPU: the HIP face model (r3d_face_vertex / r3d_face_landmarks, real3dportrait_amd/face_model.py) against the fp64
+restatement tests/face_model_ref64.py and the reference's recorded fp32 outputs, and its bit-exact properties.
+
+Tolerance: the largest absolute error against fp64 may be at most 4 x the error the REFERENCE's own fp32 evaluation has against fp64 on
+the fixture of that quantity (ref_err_vs_fp64: 6.5e-7 for vertices at |v| <= 12, 1.9e-7 for landmarks with to_camera, 2.7e-7 for landmarks
+without it, the reconstruct_lm2d_nerf path, whose values reach 1.7 at depth 6 instead of 10); 4 covers another summation order over 144
+terms and the device's sinf / cosf, both routes being fp32 accumulations.  In any case below the 2e-4 of SURVEY 8(d)."""
+import numpy as np
+import pytest
+import torch
+
+from conftest import load_golden
+import face_model_ref64 as F64
+from real3dportrait_amd import synth
+from test_face_model_host import fixture_model, fixture_to_camera
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+VERT_TOL = 4.0 * float(load_golden("face_model_b_n625_t51")["ref_err_vs_fp64"])
+LM_TOL = {True: 4.0 * float(load_golden("face_model_c_lm68_t51")["ref_err_vs_fp64"]),                # by to_camera
+          False: 4.0 * float(load_golden("face_model_d_lm68_t51_world")["ref_err_vs_fp64"])}
+_MODELS = {}
+
+
+def model(Ki, Ke):
+    if (Ki, Ke) not in _MODELS:
+        _MODELS[(Ki, Ke)] = synth.synth_face_model(24, 0, Ki, Ke)
+    return _MODELS[(Ki, Ke)]
+
+
+def dev(a):
+    return None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+
+
+def offset_by_one_float(a):
+    """a on the device as a contiguous view that starts one float into its buffer: 4-byte aligned, not 16."""
+    buf = torch.empty(a.size + 1, device=DEV, dtype=torch.float32)
+    view = buf[1:].view(*a.shape)
+    view.copy_(torch.from_numpy(np.ascontiguousarray(a)))
+    assert (a.size == 0 or view.data_ptr() % 16 == 4) and view.is_contiguous()          # an empty tensor (Ke = 0) has no address
+    return view
+
+
+def vertex_arrays(N, Ki, Ke, misaligned):
+    m = model(Ki, Ke)
+    host = m["mean_shape"].reshape(-1)[:3 * N], m["id_base"][:3 * N], m["exp_base"][:3 * N]
+    put = offset_by_one_float if misaligned else dev
+    return host, (dev(host[0]), put(host[1]), put(host[2]))
+
+
+@pytest.mark.parametrize("Ki,Ke", [(80, 64), (7, 5), (80, 0)])
+@pytest.mark.parametrize("T", [1, 3, 50, 51])
+@pytest.mark.parametrize("N", [1, 37, 625])
+def test_vertices_against_fp64(N, T, Ki, Ke):
+    from real3dportrait_amd import face_model as FM
+    host, arrays = vertex_arrays(N, Ki, Ke, misaligned=True)
+    _, aligned = vertex_arrays(N, Ki, Ke, misaligned=False)
+    idc, expc, euler, trans = F64.coefficients(100 + N + T, T, Ki, Ke)
+    worst = 0.0
+    for pose in (False, True):
+        for to_camera in (True, False):
+            eu, tr = (euler, trans) if pose else (None, None)
+            got = FM.face_vertex(arrays, dev(idc), dev(expc), dev(eu), dev(tr), camera_distance=10.0, to_camera=to_camera)
+            assert got.shape == (T, N, 3) and got.dtype == torch.float32
+            ref = F64.face_vertex(*host, idc, expc, eu, tr, 10.0, to_camera)
+            e = float(np.abs(got.cpu().numpy().astype(np.float64) - ref).max())
+            worst = max(worst, e)
+            assert e <= VERT_TOL and e < 2e-4, (pose, to_camera, e, VERT_TOL)
+            # 16-byte loads (aligned bases, K % 4 == 0) and 4-byte loads fill the same tile
+            assert torch.equal(got, FM.face_vertex(aligned, dev(idc), dev(expc), dev(eu), dev(tr), camera_distance=10.0, to_camera=to_camera))
+    print("vertices N %d T %d K %d+%d: max |err| against fp64 %.3e (bound %.3e)" % (N, T, Ki, Ke, worst, VERT_TOL))
+
+
+@pytest.mark.parametrize("T", [1, 51])
+@pytest.mark.parametrize("L", [1, 68])
+def test_landmarks_against_fp64(L, T):
+    from real3dportrait_amd import face_model as FM
+    m = model(80, 64)
+    host = m["key_mean_shape"].reshape(-1)[:3 * L], m["key_id_base"][:3 * L], m["key_exp_base"][:3 * L]
+    arrays = (dev(host[0]), offset_by_one_float(host[1]), offset_by_one_float(host[2]))
+    idc, expc, euler, trans = F64.coefficients(200 + L + T, T)
+    away = trans.copy()
+    away[:, 2] += 6.0                    # without to_camera the model's own z (0 .. 0.9) is the depth: move it off the projection's pole, as the fixture does
+    for to_camera, tr in ((True, trans), (False, away)):
+        got = FM.face_landmarks(arrays, dev(idc), dev(expc), dev(euler), dev(tr), to_camera=to_camera)
+        assert got.shape == (T, L, 2)
+        ref = F64.landmarks(*host, idc, expc, euler, tr, to_camera=to_camera)
+        e = float(np.abs(got.cpu().numpy().astype(np.float64) - ref).max())
+        print("landmarks L %d T %d to_camera %d: max |err| against fp64 %.3e (bound %.3e), largest |value| %.2f"
+              % (L, T, to_camera, e, LM_TOL[to_camera], float(np.abs(ref).max())))
+        assert e <= LM_TOL[to_camera] and e < 2e-4, (to_camera, e, LM_TOL[to_camera])
+
+
+@pytest.mark.parametrize("name", ["face_model_a_n37_t5", "face_model_b_n625_t51", "face_model_c_lm68_t51", "face_model_d_lm68_t51_world"])
+def test_agreement_with_the_reference_outputs(name):
+    from real3dportrait_amd import face_model as FM
+    g = load_golden(name)
+    arrays = tuple(dev(a) for a in fixture_model(g))
+    args = tuple(dev(g[k]) for k in ("id", "exp", "euler", "trans"))
+    if "lm2d" in g:
+        to_camera = fixture_to_camera(g)
+        got, rec, tol = FM.face_landmarks(arrays, *args, to_camera=to_camera), g["lm2d"], LM_TOL[to_camera]
+    else:
+        got, rec, tol = FM.face_vertex(arrays, *args), g["vertex"], VERT_TOL
+    e = float(np.abs(got.cpu().numpy().astype(np.float64) - rec.astype(np.float64)).max())
+    print("%s: max |HIP - reference fp32| %.3e (bound %.3e)" % (name, e, tol))
+    assert e <= tol
+
+
+def test_frames_are_independent_of_the_call():
+    """T = 51 in one call against 51 calls of T = 1, and against chunks of 7: bit-identical."""
+    from real3dportrait_amd import face_model as FM
+    host, arrays = vertex_arrays(625, 80, 64, misaligned=False)
+    idc, expc, euler, trans = (dev(a) for a in F64.coefficients(31, 51))
+    whole = FM.face_vertex(arrays, idc, expc, euler, trans)
+    single = torch.cat([FM.face_vertex(arrays, idc[t:t + 1], expc[t:t + 1], euler[t:t + 1], trans[t:t + 1]) for t in range(51)])
+    assert torch.equal(whole, single)
+    chunks = torch.cat([FM.face_vertex(arrays, idc[t:t + 7], expc[t:t + 7], euler[t:t + 7], trans[t:t + 7]) for t in range(0, 51, 7)])
+    assert torch.equal(whole, chunks)
+    m = model(80, 64)
+    keys = tuple(dev(a) for a in (m["key_mean_shape"].reshape(-1), m["key_id_base"], m["key_exp_base"]))
+    lm = FM.face_landmarks(keys, idc, expc, euler, trans)
+    lm1 = torch.cat([FM.face_landmarks(keys, idc[t:t + 1], expc[t:t + 1], euler[t:t + 1], trans[t:t + 1]) for t in range(51)])
+    assert torch.equal(lm, lm1)
+
+
+def test_null_means_zeros_bit_for_bit():
+    from real3dportrait_amd import face_model as FM
+    host, arrays = vertex_arrays(625, 80, 64, misaligned=False)
+    T = 11
+    idc, expc, euler, trans = (dev(a) for a in F64.coefficients(32, T))
+    z3, ze = torch.zeros(T, 3, device=DEV), torch.zeros(T, 64, device=DEV)
+    assert torch.equal(FM.face_vertex(arrays, idc, expc, None, None), FM.face_vertex(arrays, idc, expc, z3, z3))
+    assert torch.equal(FM.face_vertex(arrays, idc, None, euler, trans), FM.face_vertex(arrays, idc, ze, euler, trans))
+    assert torch.equal(FM.face_vertex(arrays, idc, expc, None, trans), FM.face_vertex(arrays, idc, expc, z3, trans))
+    assert torch.equal(FM.face_vertex(arrays, idc, expc, euler, None), FM.face_vertex(arrays, idc, expc, euler, z3))
+    m = model(80, 64)
+    keys = tuple(dev(a) for a in (m["key_mean_shape"].reshape(-1), m["key_id_base"], m["key_exp_base"]))
+    assert torch.equal(FM.face_landmarks(keys, idc, None, None, None), FM.face_landmarks(keys, idc, ze, z3, z3))
+
+
+def test_deterministic_on_any_stream_and_inputs_unwritten():
+    from real3dportrait_amd import face_model as FM
+    host, arrays = vertex_arrays(625, 80, 64, misaligned=False)
+    args = tuple(dev(a) for a in F64.coefficients(33, 51))
+    before = [t.clone() for t in arrays + args]
+    a = FM.face_vertex(arrays, *args)
+    b = FM.face_vertex(arrays, *args)
+    side = torch.cuda.Stream(device=DEV)
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        c = FM.face_vertex(arrays, *args)
+    side.synchronize()
+    assert torch.equal(a, b) and torch.equal(a, c)
+    assert all(torch.equal(x, y) for x, y in zip(before, arrays + args))
+    out = torch.full((51, 625, 3), float("nan"), device=DEV)
+    assert FM.face_vertex(arrays, *args, out=out) is out and torch.equal(out, a)
+
+
+class _FaceModel:
+    """The attributes of ParametricFaceModel that compute_face_vertex reads, as numpy arrays (the reference's state before .to())."""
+
+    def __init__(self, m):
+        self.mean_shape, self.id_base, self.exp_base, self.camera_distance = m["mean_shape"], m["id_base"], m["exp_base"], m["camera_distance"]
+
+    def compute_face_vertex(self, id, exp, angle, trans):
+        return "reference"
+
+
+class _Helper(torch.nn.Module):
+    def __init__(self, m):
+        super().__init__()
+        for k in ("key_mean_shape", "key_id_base", "key_exp_base"):
+            self.register_buffer(k, torch.from_numpy(m[k]))
+
+    def reconstruct_lm2d(self, id_coeff, exp_coeff, euler, trans, to_camera=True):
+        return "reference"
+
+
+def test_patched_objects():
+    from real3dportrait_amd import patch_face3d_helper, patch_face_model
+    m = model(80, 64)
+    idc, expc, euler, trans = F64.coefficients(34, 6)
+    fm = _FaceModel(m)
+    assert patch_face_model(fm) is fm and fm._r3d_reference_compute_face_vertex(None, None, None, None) == "reference"
+    v = fm.compute_face_vertex(dev(idc), dev(expc), dev(euler), dev(trans))
+    ref = F64.face_vertex(m["mean_shape"], m["id_base"], m["exp_base"], idc, expc, euler, trans)
+    assert v.shape == (6, 625, 3) and v.device == torch.device(DEV)
+    assert float(np.abs(v.cpu().numpy() - ref).max()) <= VERT_TOL
+    assert fm.compute_face_vertex(dev(idc), dev(expc), dev(euler), dev(trans)).equal(v)          # the cached upload
+    assert patch_face_model(fm) is fm and fm._r3d_reference_compute_face_vertex(None, None, None, None) == "reference"
+    from real3dportrait_amd import face_model as FM
+    assert FM.model_arrays(fm, torch.device("cuda"))[1] is FM.model_arrays(fm, torch.device(DEV))[1]          # one upload per device
+    h = _Helper(m).to(DEV)
+    assert patch_face3d_helper(h) is h and h._r3d_reference_reconstruct_lm2d(None, None, None, None) == "reference"
+    lm = h.reconstruct_lm2d(dev(idc), dev(expc), dev(euler), dev(trans))
+    lref = F64.landmarks(m["key_mean_shape"], m["key_id_base"], m["key_exp_base"], idc, expc, euler, trans)
+    assert lm.shape == (6, 68, 2) and float(np.abs(lm.cpu().numpy() - lref).max()) <= LM_TOL[True]
+    btc = h.reconstruct_lm2d(*(dev(a).reshape(2, 3, -1) for a in (idc, expc, euler, trans)))
+    assert btc.shape == (2, 3, 68, 2) and torch.equal(btc.reshape(6, 68, 2), lm)
+    host_coeffs = h.reconstruct_lm2d(*(torch.from_numpy(a) for a in (idc, expc, euler, trans)))          # the reference moves them too
+    assert host_coeffs.is_cuda and torch.equal(host_coeffs, lm)
