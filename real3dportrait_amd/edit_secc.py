@@ -29,10 +29,10 @@ _STATUS_TEXT = {1: "no eye pixel in one of the two prior regions (the reference 
 
 
 def _workspace(dev, F, H, W):
-    key = (dev, _lib.stream_ptr(), F, H, W)
+    key = (dev, torch.cuda.current_stream().cuda_stream, F, H, W)
     ws = _WORKSPACE.get(key)
     if ws is None:
-        nbytes = _lib.load().r3d_secc_blink_workspace_bytes(F, H, W)
+        nbytes = _lib.call("r3d_secc_blink_workspace_bytes", F, H, W)
         if nbytes == 0:
             raise ValueError("blink: F = %d frames of %d x %d are outside what r3d_secc_blink accepts" % (F, H, W))
         if len(_WORKSPACE) >= 8:          # a clip uses one or two shapes; do not collect every shape a long-lived process ever saw
@@ -85,9 +85,7 @@ def blink_frames(drv_secc, frame_idx, percents, out=None):
         d_idx = torch.tensor(idx, dtype=torch.int32).to(dev, non_blocking=True)
         d_pct = torch.tensor(pct, dtype=torch.float64).to(dev, non_blocking=True)
         status = torch.empty(F, dtype=torch.int32, device=dev)
-        rc = _lib.load().r3d_secc_blink(_lib.ptr(target), T, H, W, _lib.ptr(d_idx), _lib.ptr(d_pct), F, _lib.ptr(target), _lib.ptr(status),
-                                        _lib.ptr(ws), ws.numel(), _lib.stream_ptr())
-    _lib.check(rc, "secc_blink")
+        _lib.call("r3d_secc_blink", target, T, H, W, d_idx, d_pct, F, target, status, ws, ws.numel())
     return status
 
 

@@ -83,10 +83,8 @@ def face_vertex(arrays, id, exp=None, euler=None, trans=None, camera_distance=CA
     elif out.shape != (T, N, 3) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev:
         raise ValueError("face_vertex: out must be a contiguous float32 [%d, %d, 3] tensor on %s" % (T, N, dev))
     with torch.cuda.device(dev):
-        rc = _lib.load().r3d_face_vertex(_lib.ptr(mean), _lib.ptr(idb), _lib.ptr(expb) if Ke else None, N, Ki, Ke, _lib.ptr(idc),
-                                         _lib.ptr(expc) if Ke else None, _lib.ptr(eu), _lib.ptr(tr), T, float(camera_distance),
-                                         int(bool(to_camera)), _lib.ptr(out), _lib.stream_ptr())
-    _lib.check(rc, "face_vertex")
+        _lib.call("r3d_face_vertex", mean, idb, expb if Ke else None, N, Ki, Ke, idc, expc if Ke else None, eu, tr, T, float(camera_distance),
+                  int(bool(to_camera)), out)
     return out
 
 
@@ -101,11 +99,8 @@ def face_landmarks(arrays, id, exp=None, euler=None, trans=None, camera_distance
     eu, tr = _coeff(euler, "euler", T, 3, dev), _coeff(trans, "trans", T, 3, dev)
     out = torch.empty(T, L, 2, device=dev, dtype=torch.float32)
     with torch.cuda.device(dev):
-        rc = _lib.load().r3d_face_landmarks(_lib.ptr(mean), _lib.ptr(idb), _lib.ptr(expb) if Ke else None, L, Ki, Ke, _lib.ptr(idc),
-                                            _lib.ptr(expc) if Ke else None, _lib.ptr(eu), _lib.ptr(tr), T, float(camera_distance),
-                                            int(bool(to_camera)), float(focal), float(center), float(image_size), _lib.ptr(out),
-                                            _lib.stream_ptr())
-    _lib.check(rc, "face_landmarks")
+        _lib.call("r3d_face_landmarks", mean, idb, expb if Ke else None, L, Ki, Ke, idc, expc if Ke else None, eu, tr, T, float(camera_distance),
+                  int(bool(to_camera)), float(focal), float(center), float(image_size), out)
     return out
 
 

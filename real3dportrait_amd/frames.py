@@ -47,15 +47,14 @@ class ClipGatherer:
             import ctypes
             from . import _lib
             self._lib = _lib
-            lib = _lib.load()
             uid = (ctypes.c_char * 128)()
             if self.rank == 0:
-                _lib.check(lib.r3d_comm_unique_id(ctypes.cast(uid, ctypes.c_void_p)), "comm_unique_id")
+                _lib.call("r3d_comm_unique_id", ctypes.cast(uid, ctypes.c_void_p))
             box = [bytes(uid.raw)]
             dist.broadcast_object_list(box, src=0, group=group)
             uid = (ctypes.c_char * 128).from_buffer_copy(box[0])
             comm = ctypes.c_void_p()
-            _lib.check(lib.r3d_comm_init(ctypes.cast(uid, ctypes.c_void_p), self.rank, self.world, ctypes.byref(comm)), "comm_init")
+            _lib.call("r3d_comm_init", ctypes.cast(uid, ctypes.c_void_p), self.rank, self.world, ctypes.byref(comm))
             self._comm = comm
         elif backend != "torch":
             raise ValueError("backend must be 'r3d' or 'torch'")
@@ -67,10 +66,7 @@ class ClipGatherer:
         if not self.dist:
             return local[:num_frames]
         if self.backend == "r3d":
-            lib = self._lib.load()
-            self._lib.check(lib.r3d_gather_frames(self._comm, local.data_ptr(), local.numel(),
-                                                  None if self.root_buf is None else self.root_buf.data_ptr(), 0, self._lib.stream_ptr()),
-                            "gather_frames")
+            self._lib.call("r3d_gather_frames", self._comm, local, local.numel(), self.root_buf, 0)
         else:
             dist.gather(local, [self.root_buf[r] for r in range(self.world)] if self.rank == 0 else None, dst=0, group=self.group)
         if self.rank != 0:
@@ -79,7 +75,7 @@ class ClipGatherer:
 
     def close(self):
         if self._comm is not None:
-            self._lib.load().r3d_comm_destroy(self._comm)
+            self._lib.call("r3d_comm_destroy", self._comm)
             self._comm = None
 
 
@@ -211,7 +207,6 @@ class ClipRenderer:
     def render_u8(self, t, out=None):
         """Frame t as uint8 [H,W,3] (into `out` [1,H,W,3] if given).  With the f16x3 SR the clamp -> uint8 conversion of
         real3d_infer.py:472,518-522 is fused into the last block's toRGB kernel (no fp32 image round trip)."""
-        lib = self._lib.load()
         fimg = self._features(t)
         sr = self.G.superresolution
         if out is None:
@@ -222,8 +217,7 @@ class ClipRenderer:
         else:
             img = sr(fimg[:, :3], x, self.ws, noise_mode="none").contiguous()
             N, _, H, W = img.shape
-            self._lib.check(lib.r3d_frames_to_u8(self._lib.ptr(img), N, H, W, self._lib.ptr(out), self._lib.stream_ptr()),
-                            "frames_to_u8")
+            self._lib.call("r3d_frames_to_u8", img, N, H, W, out)
         return out[0] if out.dim() == 4 else out
 
 

@@ -46,10 +46,10 @@ def _checked_tri(tri, N):
 
 
 def _workspace(dev, B, S, M):
-    key = (dev, _lib.stream_ptr(), B, S, M)
+    key = (dev, torch.cuda.current_stream().cuda_stream, B, S, M)
     ws = _WORKSPACE.get(key)
     if ws is None:
-        nbytes = _lib.load().r3d_raster_workspace_bytes(B, S, M)
+        nbytes = _lib.call("r3d_raster_workspace_bytes", B, S, M)
         if nbytes == 0:
             raise ValueError("rasterize: B = %d meshes of M = %d faces at S = %d are outside what r3d_raster_forward accepts" % (B, M, S))
         if len(_WORKSPACE) >= 8:          # a clip uses one or two shapes; do not collect every shape a long-lived process ever saw
@@ -98,15 +98,12 @@ def rasterize(vertex, tri, S, fov, znear, feat=None, negate_x=True, first_face_i
     e = lambda c: torch.empty(B, c, S, S, device=v.device, dtype=torch.float32)
     p2f = torch.empty(B, S, S, device=v.device, dtype=torch.int64) if want_pix_to_face else None
     mask, depth, image = e(1), e(1), (e(C) if feat is not None else None)
-    lib = _lib.load()
-    args = (_lib.ptr(v), _lib.ptr(feat), _lib.ptr(t32), int(tri.dim() == 3), B, N, M, C, S, float(fov), float(znear), int(bool(negate_x)),
-            int(bool(first_face_is_background)), float(out_scale), float(out_shift), _lib.ptr(p2f), _lib.ptr(mask), _lib.ptr(depth),
-            _lib.ptr(image), _lib.ptr(ws), ws.numel())
+    args = (v, feat, t32, int(tri.dim() == 3), B, N, M, C, S, float(fov), float(znear), int(bool(negate_x)), int(bool(first_face_is_background)),
+            float(out_scale), float(out_shift), p2f, mask, depth, image, ws, ws.numel())
     if _large_box is None:
-        rc = lib.r3d_raster_forward(*args, _lib.stream_ptr())
+        _lib.call("r3d_raster_forward", *args)
     else:
-        rc = lib.r3d_debug_raster_forward(*args, int(_large_box), 15, _lib.stream_ptr())
-    _lib.check(rc, "raster_forward")
+        _lib.call("r3d_debug_raster_forward", *args, int(_large_box), 15)
     return p2f, mask, depth, image
 
 
@@ -124,10 +121,8 @@ def _rasterize_into(vertex, tri, S, fov, znear, feat, image, mask, depth, out_sc
             raise ValueError("_rasterize_into: %s must be a contiguous float32 %s tensor on %s" % (what, shape, vertex.device))
     t32 = _checked_tri(tri, N)
     ws = _workspace(vertex.device, B, S, M)
-    rc = _lib.load().r3d_raster_forward(_lib.ptr(vertex), _lib.ptr(feat), _lib.ptr(t32), int(tri.dim() == 3), B, N, M, C, S, float(fov),
-                                        float(znear), 1, 1, float(out_scale), float(out_shift), None, _lib.ptr(mask), _lib.ptr(depth),
-                                        _lib.ptr(image), _lib.ptr(ws), ws.numel(), _lib.stream_ptr())
-    _lib.check(rc, "raster_forward")
+    _lib.call("r3d_raster_forward", vertex, feat, t32, int(tri.dim() == 3), B, N, M, C, S, float(fov), float(znear), 1, 1, float(out_scale),
+              float(out_shift), None, mask, depth, image, ws, ws.numel())
 
 
 class MeshRenderer(nn.Module):

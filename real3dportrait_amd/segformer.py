@@ -151,7 +151,7 @@ class SegFormerSECC2PlaneBackbone(nn.Module):
         return d
 
     def _buffers_for(self, B, H, W, dev):
-        key = (dev, _lib.stream_ptr(), B, H, W)
+        key = (dev, torch.cuda.current_stream().cuda_stream, B, H, W)
         w = self._work.get(key)
         if w is None:
             n1 = B * (H // 4) * (W // 4)
@@ -179,48 +179,41 @@ class SegFormerSECC2PlaneBackbone(nn.Module):
         """Runs prenet + mix_vit; returns (buffers, B, H, W, params).  Stage outputs c1..c4 stay in the stream's buffers [B, h, w, C]."""
         B, H, W = self._check_input(x)
         x = x.detach().float().contiguous()
-        lib, P, st = _lib.load(), _lib.ptr, _lib.stream_ptr()
+        st = torch.cuda.current_stream().cuda_stream
         d = self._prepare()
         w = self._buffers_for(B, H, W, x.device)
         mv = self.mix_vit
         X, T, Q, O, H1, H2, SR, KV = w["x"], w["t"], w["q"], w["o"], w["h1"], w["h2"], w["sr"], w["kv"]
         h, wd = H // 4, W // 4
         pe = mv.patch_embed1
-        _lib.check(lib.r3d_secc_embed1(P(x), B, self.in_dim, H, W, P(self.prenet.weight), P(self.prenet.bias), P(d["conv"]["pe1"]),
-                                       P(pe.proj.bias), P(pe.norm.weight), P(pe.norm.bias), P(X), st), "secc_embed1")
+        _lib.call("r3d_secc_embed1", x, B, self.in_dim, H, W, self.prenet.weight, self.prenet.bias, d["conv"]["pe1"], pe.proj.bias, pe.norm.weight,
+                  pe.norm.bias, X, st)
         for s, (C, heads, sr) in enumerate(zip(SECC_DIMS, SECC_HEADS, SECC_SR), 1):
             if s > 1:
                 pe, prev = getattr(mv, "patch_embed%d" % s), w["c"][s - 2]
-                _lib.check(lib.r3d_secc_conv(P(prev), B, h, wd, SECC_DIMS[s - 2], P(d["conv"]["pe%d" % s]), P(pe.proj.bias), C, 3, 2, 1,
-                                             P(pe.norm.weight), P(pe.norm.bias), pe.norm.eps, P(X), st), "secc_conv")
+                _lib.call("r3d_secc_conv", prev, B, h, wd, SECC_DIMS[s - 2], d["conv"]["pe%d" % s], pe.proj.bias, C, 3, 2, 1, pe.norm.weight,
+                          pe.norm.bias, pe.norm.eps, X, st)
                 h, wd = h // 2, wd // 2
             M, L = B * h * wd, (h // sr) * (wd // sr)
             for j, blk in enumerate(getattr(mv, "block%d" % s)):
                 a, n1 = blk.attn, blk.norm1
                 if sr > 1:
-                    _lib.check(lib.r3d_secc_layernorm(P(X), M, C, P(n1.weight), P(n1.bias), n1.eps, P(T), st), "secc_layernorm")
-                    _lib.check(lib.r3d_secc_linear(P(T), M, C, None, None, 0.0, P(a.q.weight), P(a.q.bias), C, 0, None, P(Q), st), "secc_linear")
-                    _lib.check(lib.r3d_secc_conv(P(T), B, h, wd, C, P(d["conv"]["sr%d.%d" % (s, j)]), P(a.sr.bias), C, sr, sr, 0,
-                                                 None, None, 0.0, P(SR), st), "secc_conv")
-                    _lib.check(lib.r3d_secc_linear(P(SR), B * L, C, P(a.norm.weight), P(a.norm.bias), a.norm.eps, P(a.kv.weight),
-                                                   P(a.kv.bias), 2 * C, 0, None, P(KV), st), "secc_linear")
+                    _lib.call("r3d_secc_layernorm", X, M, C, n1.weight, n1.bias, n1.eps, T, st)
+                    _lib.call("r3d_secc_linear", T, M, C, None, None, 0.0, a.q.weight, a.q.bias, C, 0, None, Q, st)
+                    _lib.call("r3d_secc_conv", T, B, h, wd, C, d["conv"]["sr%d.%d" % (s, j)], a.sr.bias, C, sr, sr, 0, None, None, 0.0, SR, st)
+                    _lib.call("r3d_secc_linear", SR, B * L, C, a.norm.weight, a.norm.bias, a.norm.eps, a.kv.weight, a.kv.bias, 2 * C, 0, None, KV, st)
                 else:
-                    _lib.check(lib.r3d_secc_linear(P(X), M, C, P(n1.weight), P(n1.bias), n1.eps, P(a.q.weight), P(a.q.bias), C, 0, None,
-                                                   P(Q), st), "secc_linear")
-                    _lib.check(lib.r3d_secc_linear(P(X), M, C, P(n1.weight), P(n1.bias), n1.eps, P(a.kv.weight), P(a.kv.bias), 2 * C, 0,
-                                                   None, P(KV), st), "secc_linear")
-                _lib.check(lib.r3d_secc_attention(P(Q), P(KV), B, h * wd, L, C, heads, (C // heads) ** -0.5, P(O), st), "secc_attention")
-                _lib.check(lib.r3d_secc_linear(P(O), M, C, None, None, 0.0, P(a.proj.weight), P(a.proj.bias), C, 0, P(X), P(X), st),
-                           "secc_linear")
+                    _lib.call("r3d_secc_linear", X, M, C, n1.weight, n1.bias, n1.eps, a.q.weight, a.q.bias, C, 0, None, Q, st)
+                    _lib.call("r3d_secc_linear", X, M, C, n1.weight, n1.bias, n1.eps, a.kv.weight, a.kv.bias, 2 * C, 0, None, KV, st)
+                _lib.call("r3d_secc_attention", Q, KV, B, h * wd, L, C, heads, (C // heads) ** -0.5, O, st)
+                _lib.call("r3d_secc_linear", O, M, C, None, None, 0.0, a.proj.weight, a.proj.bias, C, 0, X, X, st)
                 mlp, n2 = blk.mlp, blk.norm2
-                _lib.check(lib.r3d_secc_linear(P(X), M, C, P(n2.weight), P(n2.bias), n2.eps, P(mlp.fc1.weight), P(mlp.fc1.bias), 4 * C, 0,
-                                               None, P(H1), st), "secc_linear")
+                _lib.call("r3d_secc_linear", X, M, C, n2.weight, n2.bias, n2.eps, mlp.fc1.weight, mlp.fc1.bias, 4 * C, 0, None, H1, st)
                 dw = mlp.dwconv.dwconv
-                _lib.check(lib.r3d_secc_dwconv_gelu(P(H1), B, h, wd, 4 * C, P(dw.weight), P(dw.bias), P(H2), st), "secc_dwconv_gelu")
-                _lib.check(lib.r3d_secc_linear(P(H2), M, 4 * C, None, None, 0.0, P(mlp.fc2.weight), P(mlp.fc2.bias), C, 0, P(X), P(X), st),
-                           "secc_linear")
+                _lib.call("r3d_secc_dwconv_gelu", H1, B, h, wd, 4 * C, dw.weight, dw.bias, H2, st)
+                _lib.call("r3d_secc_linear", H2, M, 4 * C, None, None, 0.0, mlp.fc2.weight, mlp.fc2.bias, C, 0, X, X, st)
             nrm = getattr(mv, "norm%d" % s)
-            _lib.check(lib.r3d_secc_layernorm(P(X), M, C, P(nrm.weight), P(nrm.bias), nrm.eps, P(w["c"][s - 1]), st), "secc_layernorm")
+            _lib.call("r3d_secc_layernorm", X, M, C, nrm.weight, nrm.bias, nrm.eps, w["c"][s - 1], st)
         return w, B, H, W, d
 
     @torch.no_grad()
@@ -237,14 +230,13 @@ class SegFormerSECC2PlaneBackbone(nn.Module):
     def forward_features(self, x):
         """fuse_head(mix_vit(prenet(x))): [B, 256, H/4, W/4] NCHW fp32."""
         w, B, H, W, d = self._encode(x)
-        lib, P, st = _lib.load(), _lib.ptr, _lib.stream_ptr()
+        st = torch.cuda.current_stream().cuda_stream
         for s in (2, 3, 4):
             n = B * (H // 2 ** (s + 1)) * (W // 2 ** (s + 1))
-            _lib.check(lib.r3d_secc_linear(P(w["c"][s - 1]), n, SECC_DIMS[s - 1], None, None, 0.0, P(d["wfold%d" % s]), None, 256, 0, None,
-                                           P(w["f"][s - 1]), st), "secc_linear")
+            _lib.call("r3d_secc_linear", w["c"][s - 1], n, SECC_DIMS[s - 1], None, None, 0.0, d["wfold%d" % s], None, 256, 0, None, w["f"][s - 1], st)
         out = torch.empty(B, 256, H // 4, W // 4, device=x.device, dtype=torch.float32)
-        _lib.check(lib.r3d_secc_head(P(w["c"][0]), B, H // 4, W // 4, P(d["wfold1"]), P(w["f"][1]), P(w["f"][2]), P(w["f"][3]),
-                                     P(d["hconst"]), P(d["bn_scale"]), P(d["bn_shift"]), P(out), st), "secc_head")
+        _lib.call("r3d_secc_head", w["c"][0], B, H // 4, W // 4, d["wfold1"], w["f"][1], w["f"][2], w["f"][3], d["hconst"], d["bn_scale"],
+                  d["bn_shift"], out, st)
         return out
 
     @torch.no_grad()

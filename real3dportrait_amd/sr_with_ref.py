@@ -35,23 +35,20 @@ _FUSE_TORSO_CAT = os.environ.get("R3D_FUSE_TORSO_CAT", "1") != "0"
 
 def blend(a, b, mask):
     """a * mask + b * (1 - mask)   (sr_with_ref.py:103,113)."""
-    lib = _lib.load()
     a, b, mask = _f32c(a), _f32c(b), _f32c(mask)
     N, C, H, W = a.shape
     assert b.shape == a.shape and tuple(mask.shape) == (N, 1, H, W)
     out = torch.empty_like(a)
-    _lib.check(lib.r3d_blend(_lib.ptr(a), _lib.ptr(b), _lib.ptr(mask), N, C, H, W, _lib.ptr(out), _lib.stream_ptr()), "blend")
+    _lib.call("r3d_blend", a, b, mask, N, C, H, W, out)
     return out
 
 
 def person_occlusion(alpha, torso_occlusion, head_threshold):
     """clamp(torso_occlusion + where(alpha > thr, 1, alpha), 0, 1)   (sr_with_ref.py:117-122)."""
-    lib = _lib.load()
     alpha, torso_occlusion = _f32c(alpha), _f32c(torso_occlusion)
     assert alpha.shape == torso_occlusion.shape
     out = torch.empty_like(alpha)
-    _lib.check(lib.r3d_person_occlusion(_lib.ptr(alpha), _lib.ptr(torso_occlusion), float(head_threshold), alpha.numel(), _lib.ptr(out),
-                                        _lib.stream_ptr()), "person_occlusion")
+    _lib.call("r3d_person_occlusion", alpha, torso_occlusion, float(head_threshold), alpha.numel(), out)
     return out
 
 

@@ -53,14 +53,13 @@ class _BoundMeter:
         self._k = 0
 
     def __call__(self, x):
-        lib = _lib.load()
         N = x.shape[0]
         if self._slots is None or self._slots.shape[1] != N or self._slots.device != x.device:
             self._slots = torch.zeros(2, N, device=x.device, dtype=torch.float32)
             self._k = 0
         cur, nxt = self._slots[self._k & 1], self._slots[(self._k + 1) & 1]
         self._k += 1
-        _lib.check(lib.r3d_absmax(_lib.ptr(x), x.numel() // N, N, cur.data_ptr(), nxt.data_ptr(), _lib.stream_ptr()), "absmax")
+        _lib.call("r3d_absmax", x, x.numel() // N, N, cur, nxt)
         return cur
 
 
@@ -121,15 +120,14 @@ MX_MAX_DEPTH = int(os.environ.get("R3D_MX_MAX_DEPTH", str(MAX_DEPTH)))
 def chain_fold(ops, N, ext, zero=()):
     """One r3d_chain_fold launch: ops = list of _lib.ChainOp, ext = list of device float[N] bound tensors, zero = absmax slots
     (device float[N]) that kernels launched after this fold will measure into (`_x_absmax` / `_y_absmax`)."""
-    lib = _lib.load()
     assert 1 <= len(ops) <= _lib.CHAIN_MAX_OPS and len(ext) <= _lib.CHAIN_MAX_EXT and len(zero) <= _lib.CHAIN_MAX_ZERO
     arr = (_lib.ChainOp * len(ops))(*ops)
     for t in list(ext) + list(zero):
         assert t.is_cuda and t.dtype == torch.float32 and t.numel() >= N and t.is_contiguous()
     ptrs = (ctypes.c_void_p * max(1, len(ext)))(*[t.data_ptr() for t in ext])
     zptrs = (ctypes.c_void_p * max(1, len(zero)))(*[t.data_ptr() for t in zero])
-    _lib.check(lib.r3d_chain_fold(ctypes.cast(arr, ctypes.c_void_p), len(ops), N, ctypes.cast(ptrs, ctypes.c_void_p), len(ext),
-                                  ctypes.cast(zptrs, ctypes.c_void_p), len(zero), _lib.stream_ptr()), "chain_fold")
+    _lib.call("r3d_chain_fold", ctypes.cast(arr, ctypes.c_void_p), len(ops), N, ctypes.cast(ptrs, ctypes.c_void_p), len(ext),
+              ctypes.cast(zptrs, ctypes.c_void_p), len(zero))
 
 
 class _DeviceBuffers:
@@ -245,9 +243,7 @@ class SynthesisBlock(_DeviceBuffers, nn.Module):
         `ws` [N,3,w_dim] (cached on the identity + version of `ws_key`, default `ws` itself, and the parameter versions:
         a clip renders every frame with the same ws).  Returns (prepacked, styles) device buffers.  The FOLDED vectors the
         f16x3 kernels read are written by `fold()` / chain_fold, every forward."""
-        lib = _lib.load()
         Cin, Cout = self.in_channels, self.out_channels
-        st = _lib.stream_ptr()
         c0, c1, tr = self.conv0, self.conv1, self.torgb
         params = (c0.weight, c0.bias, c0.affine.weight, c0.affine.bias, c1.weight, c1.bias, c1.affine.weight, c1.affine.bias,
                   tr.weight, tr.bias, tr.affine.weight, tr.affine.bias)
@@ -256,9 +252,8 @@ class SynthesisBlock(_DeviceBuffers, nn.Module):
         prec = self._prec()
         key = (keep[0].data_ptr(), c0.weight._version, keep[4].data_ptr(), c1.weight._version, str(dev), prec)
         if self._prepack_key != key:
-            pre = self._buf("_prepacked", int(lib.r3d_sr_block_prepacked_bytes(Cin, Cout)), dev)
-            _lib.check(lib.r3d_sr_block_prepack(Cin, Cout, _lib.ptr(keep[0]), _lib.ptr(keep[4]), _lib.ptr(pre), prec, st),
-                       "sr_block_prepack")
+            pre = self._buf("_prepacked", _lib.call("r3d_sr_block_prepacked_bytes", Cin, Cout), dev)
+            _lib.call("r3d_sr_block_prepack", Cin, Cout, keep[0], keep[4], pre, prec)
             self._prepack_key = key
         src = ws if ws_key is None else ws_key
         N = ws.shape[0]
@@ -266,14 +261,13 @@ class SynthesisBlock(_DeviceBuffers, nn.Module):
         if self._styles_key != skey or self._styles_ws is not src:
             ws = _f32c(ws)
             assert ws.shape[1] == self.num_conv + self.num_torgb and ws.shape[2] == self.w_dim, ws.shape
-            styles = self._buf("_styles", int(lib.r3d_sr_block_styles_bytes(N, Cin, Cout)), dev)
-            _lib.check(lib.r3d_sr_block_styles(_lib.ptr(ws), N, self.w_dim, Cin, Cout, *[_lib.ptr(t) for t in keep],
-                                               _lib.ptr(styles), st), "sr_block_styles")
+            styles = self._buf("_styles", _lib.call("r3d_sr_block_styles_bytes", N, Cin, Cout), dev)
+            _lib.call("r3d_sr_block_styles", ws, N, self.w_dim, Cin, Cout, *keep, styles)
             self._styles_key, self._styles_ws = skey, src
         return self._prepacked, self._styles
 
     def styles_stride(self):
-        return int(_lib.load().r3d_sr_block_styles_bytes(1, self.in_channels, self.out_channels)) // 4
+        return _lib.call("r3d_sr_block_styles_bytes", 1, self.in_channels, self.out_channels) // 4
 
     def in_scale(self):
         """(device float view, per-sample stride): the folded conv0 style vector = what a producer of this block's SPLIT
@@ -288,8 +282,7 @@ class SynthesisBlock(_DeviceBuffers, nn.Module):
 
     def bound_out(self, N):
         """Device view [N] of the bound on this block's output x written by the last fold (valid until the next fold)."""
-        lib = _lib.load()
-        off = int(lib.r3d_sr_block_bound_offset(self.in_channels, self.out_channels))
+        off = _lib.call("r3d_sr_block_bound_offset", self.in_channels, self.out_channels)
         # N > 1: the per-sample bounds sit one styles record apart; consumers (r3d_chain_fold ext bounds) read a dense float[N]
         return self._styles.view(torch.float32).as_strided((N,), (self.styles_stride(),), off).contiguous()
 
@@ -297,7 +290,6 @@ class SynthesisBlock(_DeviceBuffers, nn.Module):
                 _prepared=None, _next=None, _folded=False, _u8_out=None, _need_img=True, _x_absmax=None, _out_format=None, _return_x=None,
                 **layer_kwargs):
         """_out_format / _return_x: `self.out_format` / `self.return_x` for this call only (None: the attribute)."""
-        lib = _lib.load()
         if noise_mode == "random" or (noise_mode == "const" and
                                       (float(self.conv0.noise_strength) != 0 or float(self.conv1.noise_strength) != 0)):
             raise NotImplementedError("noise_mode=%r: the inference path uses 'none' "
@@ -311,14 +303,13 @@ class SynthesisBlock(_DeviceBuffers, nn.Module):
         Hin, Win = img.shape[-2], img.shape[-1]
         Cin, Cout = self.in_channels, self.out_channels
         dev = img.device
-        st = _lib.stream_ptr()
         prec = self._prec()
         pre, styles = _prepared if _prepared is not None else self.prepare(ws, dev)
         if prec >= 1 and not _folded:
             # f16mx wants the conv1 operand within one layer of a measurement: only a measured / known input bound will do
             bx, self._depth_in = bound_of(x, self._meter, layers=2 if prec == 1 else MAX_DEPTH + 1)
             chain_fold([self.chain_op(-1)], N, [bx])
-        need = int(lib.r3d_sr_block_workspace_bytes(N, Cin, Cout, Hin, Win))
+        need = _lib.call("r3d_sr_block_workspace_bytes", N, Cin, Cout, Hin, Win)
         work = self._buf("_workspace", need, dev)
         OH, OW = (2 * Hin, 2 * Win) if self._UP else (Hin, Win)
         img_out = torch.empty(N, 3, OH, OW, device=dev, dtype=torch.float32) if (_need_img or _u8_out is None) else None
@@ -326,10 +317,8 @@ class SynthesisBlock(_DeviceBuffers, nn.Module):
         # mixed per-module precision: only an f16mx block writes the fp8 records, and only an f16mx consumer reads them
         out_fmt, next_scale, next_stride = out_target((self.out_format if _out_format is None else _out_format) if want_x else "none", prec == 2, _next)
         x_out = None if out_fmt == "none" else empty(out_fmt, N, Cout, OH, OW, dev)
-        _lib.check(lib.r3d_sr_block_forward(_lib.ptr(pre), _lib.ptr(styles), N, Cin, Cout, Hin, Win, self._UP,
-                                            _lib.ptr(x), FMT[x_fmt], _lib.ptr(img), self._clamp(), _lib.ptr(x_out), FMT[out_fmt],
-                                            _lib.ptr(next_scale), next_stride, _lib.ptr(img_out), _lib.ptr(_u8_out), _lib.ptr(_x_absmax), prec,
-                                            _lib.ptr(work), need, st), "sr_block_forward")
+        _lib.call("r3d_sr_block_forward", pre, styles, N, Cin, Cout, Hin, Win, self._UP, x, FMT[x_fmt], img, self._clamp(), x_out, FMT[out_fmt],
+                  next_scale, next_stride, img_out, _u8_out, _x_absmax, prec, work, need)
         if out_fmt in SPLIT_FORMATS:
             tag_split(x_out, out_fmt, _next)
         elif x_out is not None and prec >= 1:
@@ -387,19 +376,18 @@ class Conv2d(_DeviceBuffers, nn.Module):
 
     def prepare(self, N, dev):
         """Static weight re-layout (cached on the parameter version) and this call's scales buffer."""
-        lib = _lib.load()
         Cin, Cout, k = self.in_channels, self.out_channels, self.kernel_size[0]
         w = _f32c(self.weight)
         key = (w.data_ptr(), self.weight._version, str(dev))
         if self._prepack_key != key:
-            pre = self._buf("_prepacked", int(lib.r3d_conv_prepacked_bytes(Cin, Cout, k)), dev)
-            _lib.check(lib.r3d_conv_prepack(_lib.ptr(w), Cin, Cout, k, _lib.ptr(pre), _lib.stream_ptr()), "conv_prepack")
+            pre = self._buf("_prepacked", _lib.call("r3d_conv_prepacked_bytes", Cin, Cout, k), dev)
+            _lib.call("r3d_conv_prepack", w, Cin, Cout, k, pre)
             self._prepack_key = key
         self._bias32 = _f32c(self.bias) if self.bias is not None else None
-        self._buf("_scales", int(lib.r3d_conv_scales_bytes(N, Cin, Cout)), dev)
+        self._buf("_scales", _lib.call("r3d_conv_scales_bytes", N, Cin, Cout), dev)
 
     def in_scale(self):
-        N1 = int(_lib.load().r3d_conv_scales_bytes(1, self.in_channels, self.out_channels)) // 4
+        N1 = _lib.call("r3d_conv_scales_bytes", 1, self.in_channels, self.out_channels) // 4
         return self._scales.view(torch.float32), N1
 
     def chain_op(self, src_a=-1, src_b=_lib.CHAIN_SRC_NONE, negative_slope=None):
@@ -409,8 +397,7 @@ class Conv2d(_DeviceBuffers, nn.Module):
                             bias=None if self._bias32 is None else self._bias32.data_ptr())
 
     def bound_out(self, N):
-        lib = _lib.load()
-        off = int(lib.r3d_conv_scales_bound_offset(self.in_channels, self.out_channels))
+        off = _lib.call("r3d_conv_scales_bound_offset", self.in_channels, self.out_channels)
         return self._scales.view(torch.float32).as_strided((N,), (self.in_scale()[1],), off).contiguous()     # dense float[N] (a copy for N > 1)
 
     def can_blend(self, a, b):
@@ -423,7 +410,6 @@ class Conv2d(_DeviceBuffers, nn.Module):
         ('split' needs `_next`, the consumer module, folded by the caller in the same chain).
         _blend = (a, b, mask) instead of x: the input is cat([a * mask, b * (1 - mask)], dim=1) (sr_with_ref.py:113-114), computed inside the
         kernel (see can_blend; the caller has folded this layer for max(bound(a), bound(b)))."""
-        lib = _lib.load()
         if _blend is not None:
             a, b, mask = _blend
             assert _folded and self.can_blend(a, b), "fused blend: a folded 1x1 conv over two 'cb8' sources"
@@ -432,11 +418,9 @@ class Conv2d(_DeviceBuffers, nn.Module):
             assert (Nb, Hb, Wb) == (N, H, W) and tuple(mask.shape) == (N, 1, H, W), (a.shape, b.shape, mask.shape)
             out_format, next_scale, next_stride = out_target(out_format, True, _next)
             y = empty(out_format, N, self.out_channels, H, W, a.device)
-            _lib.check(lib.r3d_conv_forward_blend(_lib.ptr(self._prepacked), _lib.ptr(self._scales), _lib.ptr(self._bias32), N, Ca, Cb,
-                                                  self.out_channels, H, W, _lib.ptr(a), _lib.ptr(b), _lib.ptr(mask),
-                                                  0 if negative_slope is None else 1, float(negative_slope or 0.0), 1.0, -1.0,
-                                                  _lib.ptr(y), FMT[out_format], _lib.ptr(next_scale), next_stride, _lib.ptr(_y_absmax), _lib.stream_ptr()),
-                       "conv_forward_blend")
+            _lib.call("r3d_conv_forward_blend", self._prepacked, self._scales, self._bias32, N, Ca, Cb, self.out_channels, H, W, a, b, mask,
+                      0 if negative_slope is None else 1, float(negative_slope or 0.0), 1.0, -1.0, y, FMT[out_format], next_scale, next_stride,
+                      _y_absmax)
             return self._tagged(y, out_format, _next, N)
         N, C, H, W = logical_shape(x)
         x, x_fmt, presplit = as_input(x, self)
@@ -445,20 +429,18 @@ class Conv2d(_DeviceBuffers, nn.Module):
         if C != Cin:
             raise RuntimeError("Conv2d: expected input with %d channels, got %d" % (Cin, C))
         dev = x.device
-        st = _lib.stream_ptr()
         if not _folded:
             self.prepare(N, dev)
             bx, self._depth_in = bound_of(x, self._meter, layers=1)
             chain_fold([self.chain_op(-1, negative_slope=negative_slope)], N, [bx])
-        need = int(lib.r3d_conv_workspace_bytes(N, Cin, H, W))
+        need = _lib.call("r3d_conv_workspace_bytes", N, Cin, H, W)
         work = self._buf("_workspace", need, dev) if not presplit else None
         out_format, next_scale, next_stride = out_target(out_format, True, _next)
         y = empty(out_format, N, Cout, H, W, dev)
         act = 0 if negative_slope is None else 1
-        _lib.check(lib.r3d_conv_forward(_lib.ptr(self._prepacked), _lib.ptr(self._scales), _lib.ptr(self._bias32), N, Cin, Cout, H, W, k,
-                                        _lib.ptr(x), FMT[x_fmt], act, float(negative_slope or 0.0), 1.0, -1.0,
-                                        _lib.ptr(y), FMT[out_format], _lib.ptr(next_scale), next_stride, _lib.ptr(_y_absmax),
-                                        _lib.ptr(work), need if work is not None else 0, st), "conv_forward")
+        _lib.call("r3d_conv_forward", self._prepacked, self._scales, self._bias32, N, Cin, Cout, H, W, k, x, FMT[x_fmt], act,
+                  float(negative_slope or 0.0), 1.0, -1.0, y, FMT[out_format], next_scale, next_stride, _y_absmax,
+                  work, need if work is not None else 0)
         return self._tagged(y, out_format, _next, N)
 
     def _tagged(self, y, out_format, _next, N):
@@ -476,35 +458,31 @@ class Conv2d(_DeviceBuffers, nn.Module):
         """This (already folded) 1x1 conv's output as channels [chan_off, chan_off + out_channels) of the concatenated SPLIT / SPLIT_MX tensor `dst`
         ([N, 2, C_total / 8, H, W, 8] halfs, tagged `_r3d_fmt`), times mask (or 1 - mask) per pixel and the in-multiplier of `_next`, the consumer of
         `dst` (r3d_conv_forward_cat): `x_torso = torso_encoder(hid)` + its half of `cat([x * a, x_torso * (1 - a)])` (sr_with_ref.py:88,104)."""
-        lib = _lib.load()
         x_fmt = fmt_of(x)
         assert x_fmt in ("nchw", "cb8") and self.kernel_size[0] == 1, "forward_cat: a 1x1 conv over an fp32 input"
         N, C, H, W = logical_shape(x)
         x = _f32c(x)
         Nd, C_total, Hd, Wd = logical_shape(dst)
         assert C == self.in_channels and fmt_of(dst) in SPLIT_FORMATS and (Nd, Hd, Wd) == (N, H, W) and tuple(mask.shape) == (N, 1, H, W)
-        need = int(lib.r3d_conv_workspace_bytes(N, C, H, W))
+        need = _lib.call("r3d_conv_workspace_bytes", N, C, H, W)
         work = self._buf("_workspace", need, x.device)
         ns, stride = _next.in_scale()
-        _lib.check(lib.r3d_conv_forward_cat(_lib.ptr(self._prepacked), _lib.ptr(self._scales), _lib.ptr(self._bias32), N, C, self.out_channels, H, W, 1,
-                                            _lib.ptr(x), FMT[x_fmt], 0 if negative_slope is None else 1, float(negative_slope or 0.0), 1.0, -1.0,
-                                            _lib.ptr(dst), FMT[fmt_of(dst)], C_total, chan_off, _lib.ptr(_f32c(mask)), int(bool(mask_invert)),
-                                            _lib.ptr(ns), stride, _lib.ptr(work), need, _lib.stream_ptr()), "conv_forward_cat")
+        _lib.call("r3d_conv_forward_cat", self._prepacked, self._scales, self._bias32, N, C, self.out_channels, H, W, 1, x, FMT[x_fmt],
+                  0 if negative_slope is None else 1, float(negative_slope or 0.0), 1.0, -1.0, dst, FMT[fmt_of(dst)], C_total, chan_off,
+                  _f32c(mask), int(bool(mask_invert)), ns, stride, work, need)
         return dst
 
 
 def upsample2x_bilinear(x, out_format="split", _next=None):
     """torch.nn.UpsamplingBilinear2d(scale_factor=2.) (align_corners=True) on a channel-blocked fp32 activation
     (r3d_upsample2x_bilinear); output 'split' / 'split_mx' (input of the conv `_next`, already folded) or 'cb8'."""
-    lib = _lib.load()
     assert fmt_of(x) == "cb8", "upsample2x_bilinear takes the 'cb8' output of a Conv2d"
     bx, dx = getattr(x, "_r3d_bound", None), int(getattr(x, "_r3d_depth", 0))
     N, C, H, W = logical_shape(x)
     x = x.contiguous()
     out_format, next_scale, next_stride = out_target(out_format, True, _next)
     y = empty(out_format, N, C, 2 * H, 2 * W, x.device)
-    _lib.check(lib.r3d_upsample2x_bilinear(_lib.ptr(x), N, C, H, W, _lib.ptr(y), FMT[out_format],
-                                           _lib.ptr(next_scale), next_stride, _lib.stream_ptr()), "upsample2x_bilinear")
+    _lib.call("r3d_upsample2x_bilinear", x, N, C, H, W, y, FMT[out_format], next_scale, next_stride)
     if out_format in SPLIT_FORMATS:
         tag_split(y, out_format, _next)
     elif bx is not None:
@@ -515,12 +493,11 @@ def upsample2x_bilinear(x, out_format="split", _next=None):
 def resize_bilinear(x, size, antialias=True):
     """F.interpolate(x, size=size, mode='bilinear', align_corners=False, antialias=antialias) on the HIP kernel (ATen's separable
     antialiased weights; superresolution.py:351-355, sr_with_ref.py:71-82,110)."""
-    lib = _lib.load()
     x = _f32c(x)
     N, C, H, W = x.shape
     OH, OW = size
     y = torch.empty(N, C, OH, OW, device=x.device, dtype=torch.float32)
-    _lib.check(lib.r3d_resize_bilinear(_lib.ptr(x), N * C, H, W, _lib.ptr(y), OH, OW, int(bool(antialias)), _lib.stream_ptr()), "resize_bilinear")
+    _lib.call("r3d_resize_bilinear", x, N * C, H, W, y, OH, OW, int(bool(antialias)))
     return y
 
 
@@ -534,8 +511,6 @@ def blend_cat(a, b, mask, consumer, ws=None, _folded_head=None, _b_channels=None
     here from max(bound(a), bound(b)) (mask in [0,1]), then r3d_blend_cat_to_split multiplies by its in-multiplier.
     a, b: NCHW fp32 or 'cb8'-tagged tensors; mask [N,1,H,W].  _folded_head: the consumer's first module when the caller has
     already folded it (inside a larger chain)."""
-    lib = _lib.load()
-
     fa, fb = fmt_of(a), fmt_of(b)           # (b = None: 'nchw')
     assert fa in ("nchw", "cb8") and fb in ("nchw", "cb8"), (fa, fb)
     a = _keep_tags(a)
@@ -559,8 +534,7 @@ def blend_cat(a, b, mask, consumer, ws=None, _folded_head=None, _b_channels=None
     fmt = "split_mx" if head.wants_mx() else "split"       # an f16mx consumer: fp8 records in the lo plane
     y = _dst if _dst is not None else empty(fmt, N, Ca + Cb, H, W, a.device)
     assert tuple(y.shape) == (N, 2, (Ca + Cb) // 8, H, W, 8) and y.is_contiguous()
-    _lib.check(lib.r3d_blend_cat_to_split(_lib.ptr(a), FMT[fa], Ca, _lib.ptr(b), FMT[fb], Cb, _lib.ptr(mask), N, H, W, _lib.ptr(y), FMT[fmt],
-                                          _lib.ptr(ns), stride, _lib.stream_ptr()), "blend_cat_to_split")
+    _lib.call("r3d_blend_cat_to_split", a, FMT[fa], Ca, b, FMT[fb], Cb, mask, N, H, W, y, FMT[fmt], ns, stride)
     return tag_split(y, fmt, head)
 
 

@@ -49,8 +49,7 @@ def seg_input(img, segmap, c0=SEG_CHANNELS[0], c1=SEG_CHANNELS[1], size=None, ou
             raise ValueError("seg_input: img %s and segmap %s differ in N" % (tuple(img.shape), tuple(seg.shape)))
     if out is None:
         out = torch.empty(N, Ci + 2, OH, OW, device=seg.device, dtype=torch.float32)
-    _lib.check(_lib.load().r3d_torso_seg_input(_lib.ptr(img), N, Ci, _lib.ptr(seg), Cs, Hs, Ws, c0, c1, _lib.ptr(out), OH, OW, _lib.stream_ptr()),
-               "torso_seg_input")
+    _lib.call("r3d_torso_seg_input", img, N, Ci, seg, Cs, Hs, Ws, c0, c1, out, OH, OW)
     return out
 
 
@@ -64,9 +63,8 @@ def mask_volume(feats_cl, segmap, c0=SEG_CHANNELS[0], c1=SEG_CHANNELS[1], ksize=
     e = lambda c: torch.empty(N, D, H, W, c, device=feats.device, dtype=torch.float32)
     masked_cl = e(C) if masked_cl is None else masked_cl
     motion_cl = e(C + 2) if motion_cl is None else motion_cl
-    _lib.check(_lib.load().r3d_torso_mask_volume(_lib.ptr(feats), N, D, H, W, C, _lib.ptr(seg), seg.shape[1], seg.shape[2], seg.shape[3], c0, c1,
-                                                 int(ksize), int(bool(mul_mask)), _lib.ptr(masked_cl), _lib.ptr(motion_cl), _lib.stream_ptr()),
-               "torso_mask_volume")
+    _lib.call("r3d_torso_mask_volume", feats, N, D, H, W, C, seg, seg.shape[1], seg.shape[2], seg.shape[3], c0, c1, int(ksize), int(bool(mul_mask)),
+              masked_cl, motion_cl)
     return masked_cl, motion_cl
 
 
@@ -98,7 +96,7 @@ class TorsoForwardState:
         self.work, self.identity_j = {}, {}
 
     def buffers(self, dev, N, in_dim, H, W, D, h, w, C):
-        key = (dev, _lib.stream_ptr(), N)
+        key = (dev, torch.cuda.current_stream().cuda_stream, N)
         b = self.work.get(key)
         if b is None or b["shape"] != (in_dim, H, W, D, h, w, C):
             e = lambda *s: torch.empty(*s, device=dev, dtype=torch.float32)

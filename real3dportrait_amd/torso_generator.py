@@ -76,11 +76,11 @@ class Generator(_TorsoModule):
         if grid.shape[0] != N or grid.shape[4] != 3:
             raise ValueError("deformation: expected [%d, Do, Ho, Wo, 3], got %s" % (N, tuple(grid.shape)))
         Do, Ho, Wo = grid.shape[1:4]
-        lib, P, st = _lib.load(), _lib.ptr, _lib.stream_ptr()
+        st = torch.cuda.current_stream().cuda_stream
 
         def to_cl(_):
             cl = torch.empty(N, D, H, W, C, device=fs.device, dtype=torch.float32)
-            _lib.check(lib.r3d_torso_volume_to_cl(P(fs), N, C, D, H, W, P(cl), st), "torso_volume_to_cl")
+            _lib.call("r3d_torso_volume_to_cl", fs, N, C, D, H, W, cl, st)
             return cl
 
         cl = _VOLUME_CL.setdefault(st, _Cached()).get(key, to_cl)
@@ -92,8 +92,7 @@ class Generator(_TorsoModule):
         """network2.py:297-301: grid_sample(fs, deformation, align_corners=True, padding_mode='border').view(N, -1, H, W)."""
         fs, grid, cl, (N, C, D, H, W, Do, Ho, Wo) = Generator._warp_inputs(fs, deformation)
         out = torch.empty(N, C, Do, Ho, Wo, device=fs.device, dtype=torch.float32)
-        _lib.check(_lib.load().r3d_torso_warp(_lib.ptr(cl), N, C, D, H, W, _lib.ptr(grid), Do, Ho, Wo, _lib.ptr(out), 0, _lib.stream_ptr()),
-                   "torso_warp")
+        _lib.call("r3d_torso_warp", cl, N, C, D, H, W, grid, Do, Ho, Wo, out, 0)
         return out.view(N, -1, H, W)
 
     def _decode(self, x, in_nchw, N, H, W, return_hid):
@@ -121,8 +120,7 @@ class Generator(_TorsoModule):
             raise ValueError("Generator: expected fs [N, %d, %d, H, W] and deformation [N, %d, H, W, 3], got %s and %s"
                              % (self.input_channels, self.depth, self.depth, tuple(fs.shape), tuple(grid.shape)))
         warped = self._buffers_for(fs.device, N, H, W)["warp"]
-        _lib.check(_lib.load().r3d_torso_warp(_lib.ptr(cl), N, C, D, H, W, _lib.ptr(grid), Do, Ho, Wo, _lib.ptr(warped), 1, _lib.stream_ptr()),
-                   "torso_warp")
+        _lib.call("r3d_torso_warp", cl, N, C, D, H, W, grid, Do, Ho, Wo, warped, 1)
         return self._decode(warped, False, N, H, W, return_hid)
 
     @torch.no_grad()
@@ -135,8 +133,7 @@ class Generator(_TorsoModule):
             raise ValueError("Generator: expected fs_cl [N, %d, H, W, %d] and deformation [N, %d, H, W, 3], got %s and %s"
                              % (self.depth, self.input_channels, self.depth, tuple(cl.shape), tuple(grid.shape)))
         warped = self._buffers_for(cl.device, N, H, W)["warp"]
-        _lib.check(_lib.load().r3d_torso_warp(_lib.ptr(cl), N, C, D, H, W, _lib.ptr(grid), D, H, W, _lib.ptr(warped), 1, _lib.stream_ptr()),
-                   "torso_warp")
+        _lib.call("r3d_torso_warp", cl, N, C, D, H, W, grid, D, H, W, warped, 1)
         return self._decode(warped, False, N, H, W, return_hid)
 
     @torch.no_grad()

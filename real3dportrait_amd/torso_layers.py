@@ -161,7 +161,7 @@ class _TorsoModule(nn.Module):
         return self._derived
 
     def _buffers_for(self, dev, *shape):
-        key = (dev, _lib.stream_ptr()) + shape
+        key = (dev, torch.cuda.current_stream().cuda_stream) + shape
         w = self._work.get(key)
         if w is None:
             w = self._work[key] = self._new_buffers(dev, *shape)
@@ -178,40 +178,30 @@ class _TorsoModule(nn.Module):
 # ---- one wrapper per conv entry point.  f32 goes through r3d_torso_conv / r3d_torso_conv3d, another tier through their _prec forms.
 
 def _conv(x, B, Hs, Ws, cin, L, y=None, y_nchw=None, in_nchw=False, res=None, precision=F32):
-    P = _lib.ptr
-    args = (P(x), B, Hs, Ws, cin, int(in_nchw), L["up"], P(L["ps"]), P(L["pt"]), 0.0, P(L["w"]), P(L["b"]), L["w"].shape[0], L["k"], L["act"],
-            L["slope"], P(res), P(y), P(y_nchw))
+    args = (x, B, Hs, Ws, cin, int(in_nchw), L["up"], L["ps"], L["pt"], 0.0, L["w"], L["b"], L["w"].shape[0], L["k"], L["act"], L["slope"], res, y, y_nchw)
     if precision == F32:
-        _lib.check(_lib.load().r3d_torso_conv(*args, _lib.stream_ptr()), "torso_conv")
+        _lib.call("r3d_torso_conv", *args)
     else:
-        _lib.check(_lib.load().r3d_torso_conv_prec(*args, PRECISIONS[precision], _lib.stream_ptr()), "torso_conv_prec")
+        _lib.call("r3d_torso_conv_prec", *args, PRECISIONS[precision])
 
 
 def _conv3d(x, B, D, Hs, Ws, cin, L, k, y, ycs=None, yco=0, up=0, act=NONE, pool=0, full_depth=0, y_ncdhw=None, precision=F32):
-    P = _lib.ptr
     cout = L["w"].shape[0]
-    args = (P(x), B, D, Hs, Ws, cin, up, P(L["w"]), P(L["b"]), cout, k, full_depth, act, 0.0, pool, P(y), cout if ycs is None else ycs, yco,
-            P(y_ncdhw))
+    args = (x, B, D, Hs, Ws, cin, up, L["w"], L["b"], cout, k, full_depth, act, 0.0, pool, y, cout if ycs is None else ycs, yco, y_ncdhw)
     if precision == F32:
-        _lib.check(_lib.load().r3d_torso_conv3d(*args, _lib.stream_ptr()), "torso_conv3d")
+        _lib.call("r3d_torso_conv3d", *args)
     else:
-        _lib.check(_lib.load().r3d_torso_conv3d_prec(*args, PRECISIONS[precision], _lib.stream_ptr()), "torso_conv3d_prec")
+        _lib.call("r3d_torso_conv3d_prec", *args, PRECISIONS[precision])
 
 
 def _conv_pool(x, B, Hs, Ws, cin, L, y, precision):
-    P = _lib.ptr
-    _lib.check(_lib.load().r3d_torso_conv_pool(P(x), B, Hs, Ws, cin, 0, P(L["w"]), P(L["b"]), L["w"].shape[0], 3, LEAKY, 0.0, 1, P(y),
-                                               PRECISIONS[precision], _lib.stream_ptr()), "torso_conv_pool")
+    _lib.call("r3d_torso_conv_pool", x, B, Hs, Ws, cin, 0, L["w"], L["b"], L["w"].shape[0], 3, LEAKY, 0.0, 1, y, PRECISIONS[precision])
 
 
 def _conv_split(x, B, Hs, Ws, cin, L, depth, y, precision):
-    P = _lib.ptr
-    _lib.check(_lib.load().r3d_torso_conv_split(P(x), B, Hs, Ws, cin, 0, P(L["w"]), P(L["b"]), L["w"].shape[0], 1, NONE, 0.0, depth, P(y),
-                                                PRECISIONS[precision], _lib.stream_ptr()), "torso_conv_split")
+    _lib.call("r3d_torso_conv_split", x, B, Hs, Ws, cin, 0, L["w"], L["b"], L["w"].shape[0], 1, NONE, 0.0, depth, y, PRECISIONS[precision])
 
 
 def _conv3d_res(x, B, D, Hs, Ws, cin, L, res, y, y_ncdhw, precision):
-    P = _lib.ptr
-    _lib.check(_lib.load().r3d_torso_conv3d_res(P(x), B, D, Hs, Ws, cin, P(L["ps"]), P(L["pt"]), 0.0, P(L["w"]), P(L["b"]), L["w"].shape[0], 3,
-                                                L["act"], 0.0, P(res), P(y), P(y_ncdhw), PRECISIONS[precision], _lib.stream_ptr()),
-               "torso_conv3d_res")
+    _lib.call("r3d_torso_conv3d_res", x, B, D, Hs, Ws, cin, L["ps"], L["pt"], 0.0, L["w"], L["b"], L["w"].shape[0], 3, L["act"], 0.0, res, y, y_ncdhw,
+              PRECISIONS[precision])

@@ -143,16 +143,16 @@ class MotionFieldEstimator(_TorsoModule):
             raise ValueError("MotionFieldEstimator: expected kp_s, kp_d [N, %d, 3], got %s and %s" % (K, tuple(kp_s.shape), tuple(kp_d.shape)))
         dev = fs.device
         F, w = self._prepare(), self._buffers_for(dev, N)
-        lib, P, st = _lib.load(), _lib.ptr, _lib.stream_ptr()
+        st = torch.cuda.current_stream().cuda_stream
         cp, pr = _pad4(5 * (K + 1)), self.precision
         fcs = cp + 2 * HID
         # the hourglass input, also the first channel group of the fuser's input
         fs_cl = fs
         if not channel_last:
             fs_cl = w["fs"]
-            _lib.check(lib.r3d_torso_volume_to_cl(P(fs), N, C, D, S, S, P(fs_cl), st), "torso_volume_to_cl")
-        _lib.check(lib.r3d_torso_motion_input(P(fs_cl), N, C, D, S, S, P(F["compress"]["w"]), P(F["compress"]["b"]), P(kp_s), P(kp_d), P(J),
-                                              K, P(w["inp"]), cp, P(w["fuse"]), fcs, st), "torso_motion_input")
+            _lib.call("r3d_torso_volume_to_cl", fs, N, C, D, S, S, fs_cl, st)
+        _lib.call("r3d_torso_motion_input", fs_cl, N, C, D, S, S, F["compress"]["w"], F["compress"]["b"], kp_s, kp_d, J, K, w["inp"], cp, w["fuse"],
+                  fcs, st)
         # the hourglass; its last conv writes the second group
         x, cin, size = w["inp"], cp, S
         for i, L in enumerate(F["down"]):
@@ -165,7 +165,7 @@ class MotionFieldEstimator(_TorsoModule):
             x, cin, size = (None if last else w["up"][i]), L["w"].shape[0], size * 2
         # the head branch: 256^2 -> 128^2, tgt_head_encoder, -> 64^2, repeated over depth into the third group
         head_in = torch.cat([img, wts], dim=1)
-        _lib.check(lib.r3d_resize_bilinear(P(head_in), N * 4, HEAD, HEAD, P(w["head"]), 128, 128, 0, st), "resize_bilinear")
+        _lib.call("r3d_resize_bilinear", head_in, N * 4, HEAD, HEAD, w["head"], 128, 128, 0, st)
         E = F["enc"]
         _conv(w["head"], N, 128, 128, 4, E[0], y=w["e0"], in_nchw=True, precision=pr)
         for i in range(3):
@@ -174,13 +174,13 @@ class MotionFieldEstimator(_TorsoModule):
                 _conv(w["e1"], N, 128, 128, HID, E[2 + 2 * i], y=w["e0"], res=w["e0"], precision=pr)
             else:
                 _conv(w["e1"], N, 128, 128, HID, E[2 + 2 * i], y_nchw=w["feats"], res=w["e0"], precision=pr)
-        _lib.check(lib.r3d_resize_bilinear(P(w["feats"]), N * HID, 128, 128, P(w["feats64"]), S, S, 0, st), "resize_bilinear")
-        _lib.check(lib.r3d_torso_motion_broadcast(P(w["feats64"]), N, HID, S, S, D, P(w["fuse"]), fcs, cp + HID, st), "torso_motion_broadcast")
+        _lib.call("r3d_resize_bilinear", w["feats"], N * HID, 128, 128, w["feats64"], S, S, 0, st)
+        _lib.call("r3d_torso_motion_broadcast", w["feats64"], N, HID, S, S, D, w["fuse"], fcs, cp + HID, st)
         # fuser, mask, deformation, occlusions
         _conv3d(w["fuse"], N, D, S, S, fcs, F["fuser"], 7, w["x"], precision=pr)
         _conv3d(w["x"], N, D, S, S, HID, F["mask"], 7, w["mask"], precision=pr)
         deformation = torch.empty(N, D, S, S, 3, device=dev, dtype=torch.float32)
-        _lib.check(lib.r3d_torso_motion_deform(P(w["mask"]), N, D, S, S, K, P(kp_s), P(kp_d), P(J), P(deformation), st), "torso_motion_deform")
+        _lib.call("r3d_torso_motion_deform", w["mask"], N, D, S, S, K, kp_s, kp_d, J, deformation, st)
         occ = torch.empty(N, 2, S, S, device=dev, dtype=torch.float32)
         _conv3d(w["x"], N, D, S, S, HID, F["occ"], 7, None, act=SIGMOID, full_depth=1, y_ncdhw=occ, precision=pr)
         return deformation, occ[:, 0:1].contiguous(), occ[:, 1:2].contiguous()

@@ -31,13 +31,11 @@ class RaySampler(nn.Module):
         super().__init__()
 
     def forward(self, cam2world_matrix, intrinsics, resolution):
-        lib = _lib.load()
         c2w, K = _f32c(cam2world_matrix), _f32c(intrinsics)
         N, R = c2w.shape[0], int(resolution)
         origins = torch.empty(N, R * R, 3, device=c2w.device, dtype=torch.float32)
         dirs = torch.empty_like(origins)
-        _lib.check(lib.r3d_raygen(_lib.ptr(c2w), _lib.ptr(K), N, R, _lib.ptr(origins), _lib.ptr(dirs),
-                                  _lib.stream_ptr()), "raygen")
+        _lib.call("r3d_raygen", c2w, K, N, R, origins, dirs)
         return origins, dirs
 
 
@@ -129,7 +127,6 @@ class ImportanceRenderer(nn.Module):
         """NCHW [N,3,C,H,W] (+ optional per-frame residual, secc_img2plane.py:76-77) -> channel-last.
         add_flip = SECC_PLANE_FLIPS when `add` is the raw to_plane_cnn output ([N,96,H,W], before the torch.flip calls of
         SegFormerSECC2PlaneBackbone.forward): the flips are applied while the residual is read."""
-        lib = _lib.load()
         planes = _f32c(planes)
         N, P, CD, H, W = planes.shape
         D = self.triplane_depth
@@ -140,27 +137,26 @@ class ImportanceRenderer(nn.Module):
         # one allocation: the channel-last planes, then the per-block |max| partials of the layout pass (the bound the renderer's fp16
         # range fold needs, r3d_hip.h "plane_absmax") -- the tensor handed back is the view of the first part
         numel = N * 3 * D * H * W * C
-        npart = int(lib.r3d_planes_absmax_partials(N, C, H, W, D))
+        npart = _lib.call("r3d_planes_absmax_partials", N, C, H, W, D)
         buf = torch.empty(numel + npart, device=planes.device, dtype=torch.float32)
         out = buf[:numel].view((N, 3, H, W, C) if D == 1 else (N, 3, D, H, W, C))
         part = buf[numel:]
         addc = _f32c(add).reshape(planes.shape) if add is not None else None
         nwritten = ctypes.c_int(0)
-        _lib.check(lib.r3d_planes_to_nhwc(_lib.ptr(planes), _lib.ptr(addc), _lib.ptr(out), N, C, H, W, D,
-                                          int(add_flip), part.data_ptr(), ctypes.byref(nwritten), _lib.stream_ptr()), "planes_to_nhwc")
+        _lib.call("r3d_planes_to_nhwc", planes, addc, out, N, C, H, W, D, int(add_flip), part, ctypes.byref(nwritten))
         out._r3d_nhwc = True
         out._r3d_absmax = (part, int(nwritten.value), out._version)
         return out
 
     @staticmethod
     def _absmax_of(planes_nhwc):
-        """(partials pointer, count) for r3d_render_forward / r3d_run_model, or (None, 0) = "measure the bound inside the call".  The
+        """(partials tensor, count) for r3d_render_forward / r3d_run_model, or (None, 0) = "measure the bound inside the call".  The
         partials of prepare_planes are only trusted while the tensor is the one that pass wrote: an in-place update afterwards bumps
         its version, and a stale bound would let the kernel's unguarded fp16 split (split8_bounded) overflow silently."""
         tag = getattr(planes_nhwc, "_r3d_absmax", None)
         if tag is None or tag[2] != planes_nhwc._version:
             return None, 0
-        return tag[0].data_ptr(), tag[1]
+        return tag[0], tag[1]
 
     def _planes_nhwc(self, planes):
         """Channel-last copy of `planes`, cached for static planes.  The cache entry holds the SOURCE tensor itself and is valid
@@ -205,7 +201,6 @@ class ImportanceRenderer(nn.Module):
                             _split_for=_split_for)
 
     def forward(self, planes, decoder, ray_origins, ray_directions, rendering_options, _camera=None, _split_for=None):
-        lib = _lib.load()
         self._check_options(rendering_options)
         planes_nhwc = self._planes_nhwc(planes)
         N, H, W = planes_nhwc.shape[0], planes_nhwc.shape[-3], planes_nhwc.shape[-2]
@@ -246,7 +241,7 @@ class ImportanceRenderer(nn.Module):
         depth = torch.empty(N, M, 1, device=dev, dtype=torch.float32) if self.need_depth else None
         wsum = torch.empty(N, M, 1, device=dev, dtype=torch.float32)
         valid = torch.empty(N, M, 1, device=dev, dtype=torch.bool)
-        need = self._ensure_workspace(lib.r3d_render_workspace_bytes(N, M, Nc, Nf), dev)
+        need = self._ensure_workspace(_lib.call("r3d_render_workspace_bytes", N, M, Nc, Nf), dev)
         part, npart = self._absmax_of(planes_nhwc)        # None (caller's own layout, or updated in place since): measured inside the call
         x_split, sp_scale, sp_stride = None, None, 0
         if _split_for is not None:
@@ -254,21 +249,15 @@ class ImportanceRenderer(nn.Module):
             R = int(round(M ** 0.5))
             assert R * R == M, "the SPLIT copy is an image: M must be a square"
             x_split = sr_activation.tag_split(sr_activation.empty("split", N, 32, R, R, dev), "split", consumer)
-        _lib.check(lib.r3d_render_forward(
-            _lib.ptr(planes_nhwc), N, H, W, D, _lib.ptr(w1), _lib.ptr(b1), _lib.ptr(w2), _lib.ptr(b2),
-            _lib.ptr(o), _lib.ptr(d), M, Nc, Nf, float(rendering_options["box_warp"]),
-            int(bool(rendering_options.get("white_back", False))),
-            _lib.ptr(noise_c), _lib.ptr(u_f), int(self.seed) & 0xFFFFFFFFFFFFFFFF,
-            _lib.ptr(rgb_cm), int(self.rgb_channel_major), _lib.ptr(depth), _lib.ptr(wsum), _lib.ptr(valid),
-            part, npart, _lib.ptr(c2w), _lib.ptr(K),
-            _lib.ptr(x_split), None if sp_scale is None else sp_scale.data_ptr(), int(sp_stride),
-            _lib.ptr(self._workspace), need, _lib.stream_ptr()), "render_forward")
+        _lib.call("r3d_render_forward", planes_nhwc, N, H, W, D, w1, b1, w2, b2, o, d, M, Nc, Nf, float(rendering_options["box_warp"]),
+                  int(bool(rendering_options.get("white_back", False))), noise_c, u_f, int(self.seed) & 0xFFFFFFFFFFFFFFFF,
+                  rgb_cm, int(self.rgb_channel_major), depth, wsum, valid, part, npart, c2w, K, x_split, sp_scale, int(sp_stride),
+                  self._workspace, need)
         if x_split is not None:
             rgb._r3d_split = x_split
         return rgb, depth, wsum, valid
 
     def run_model(self, planes, decoder, sample_coordinates, sample_directions, options):
-        lib = _lib.load()
         if self.triplane_feature_type not in ("triplane", "trigrid", "trigrid_v2"):
             raise NotImplementedError("triplane_feature_type=%r" % self.triplane_feature_type)
         if options.get("density_noise", 0) > 0:
@@ -282,10 +271,8 @@ class ImportanceRenderer(nn.Module):
         w1, b1, w2, b2 = decoder_params(decoder)
         rgb = torch.empty(N, npts, 32, device=coords.device, dtype=torch.float32)
         sigma = torch.empty(N, npts, 1, device=coords.device, dtype=torch.float32)
-        need = self._ensure_workspace(lib.r3d_run_model_workspace_bytes(), coords.device)
+        need = self._ensure_workspace(_lib.call("r3d_run_model_workspace_bytes"), coords.device)
         part, npart = self._absmax_of(planes_nhwc)
-        _lib.check(lib.r3d_run_model(_lib.ptr(planes_nhwc), N, H, W, D, _lib.ptr(w1), _lib.ptr(b1), _lib.ptr(w2),
-                                     _lib.ptr(b2), _lib.ptr(coords), npts, float(options["box_warp"]),
-                                     _lib.ptr(rgb), _lib.ptr(sigma), part, npart,
-                                     _lib.ptr(self._workspace), need, _lib.stream_ptr()), "run_model")
+        _lib.call("r3d_run_model", planes_nhwc, N, H, W, D, w1, b1, w2, b2, coords, npts, float(options["box_warp"]), rgb, sigma, part, npart,
+                  self._workspace, need)
         return {"rgb": rgb, "sigma": sigma}

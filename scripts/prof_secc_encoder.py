@@ -31,27 +31,11 @@ def timed(fn, iters, warm=5):
 
 
 def count_launches(m, x):
-    """Kernel launches of one forward_features, counted by wrapping the r3d_secc_* entry points (embed1 and a conv with a LayerNorm
-    epilogue are two launches each)."""
-    lib = _lib.load()
-    names = [n for n in _lib.SIGNATURES if n.startswith("r3d_secc_")]
-    orig = {n: getattr(lib, n) for n in names}
-    count = [0]
-
-    def wrap(n, f):
-        def g(*a):
-            count[0] += 2 if n == "r3d_secc_embed1" or (n == "r3d_secc_conv" and a[11] is not None) else 1
-            return f(*a)
-        return g
-
-    for n in names:
-        setattr(lib, n, wrap(n, orig[n]))
-    try:
+    """Kernel launches of one forward_features, counted at the r3d_secc_* entry points (embed1 and a conv with a LayerNorm epilogue are
+    two launches each)."""
+    with _lib.counting() as calls:
         m.forward_features(x)
-    finally:
-        for n in names:
-            setattr(lib, n, orig[n])
-    return count[0]
+    return sum(2 if n == "r3d_secc_embed1" or (n == "r3d_secc_conv" and a[11] is not None) else 1 for n, a in calls if n.startswith("r3d_secc_"))
 
 
 def main():

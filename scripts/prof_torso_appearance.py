@@ -15,6 +15,7 @@ print one JSON line:
         the per-launch table of that trace (median over the forwards), with each layer's GFLOP and TFLOP/s
 """
 import argparse
+import collections
 import csv
 import json
 import os
@@ -97,25 +98,9 @@ def main():
         return statistics.median(ev[i].elapsed_time(ev[i + 1]) for i in range(calls))
 
     def count_launches(fn):
-        lib = _lib.load()
-        names = [n for n in _lib.SIGNATURES if n.startswith("r3d_torso_")]
-        orig = {n: getattr(lib, n) for n in names}
-        count = {n: 0 for n in names}
-
-        def wrap(n, f):
-            def g(*args):
-                count[n] += 1
-                return f(*args)
-            return g
-
-        for n in names:
-            setattr(lib, n, wrap(n, orig[n]))
-        try:
+        with _lib.counting() as calls:
             fn()
-        finally:
-            for n in names:
-                setattr(lib, n, orig[n])
-        return {n: c for n, c in count.items() if c}
+        return dict(collections.Counter(n for n, _ in calls if n.startswith("r3d_torso_")))
 
     dev = "cuda:0"
     sd = synth.synth_torso_appearance(181, 5)

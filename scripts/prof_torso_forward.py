@@ -12,6 +12,7 @@
     python scripts/prof_torso_forward.py [--calls 100] [--blocks 5] [--out DIR]     (writes DIR/prof_torso_forward.json)
 """
 import argparse
+import collections
 import json
 import os
 import statistics
@@ -44,25 +45,9 @@ def main():
         return statistics.median(ev[i].elapsed_time(ev[i + 1]) for i in range(calls))
 
     def count_launches(fn):
-        lib = _lib.load()
-        names = [n for n in _lib.SIGNATURES if n.startswith("r3d_torso_") or n == "r3d_resize_bilinear"]
-        orig = {n: getattr(lib, n) for n in names}
-        count = {n: 0 for n in names}
-
-        def wrap(n, f):
-            def g(*args):
-                count[n] += 1
-                return f(*args)
-            return g
-
-        for n in names:
-            setattr(lib, n, wrap(n, orig[n]))
-        try:
+        with _lib.counting() as calls:
             fn()
-        finally:
-            for n in names:
-                setattr(lib, n, orig[n])
-        return {n: c for n, c in count.items() if c}
+        return dict(collections.Counter(n for n, _ in calls if n.startswith("r3d_torso_") or n == "r3d_resize_bilinear"))
 
     dev = "cuda:0"
     switches = dict(torso_appearance=True, torso_motion=True, torso_generator=True)

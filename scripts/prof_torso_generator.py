@@ -17,6 +17,7 @@ output) and print one JSON line:
         (writes DIR/prof_torso_generator_precision.json); --precision bf16x3 with --forwards: that tier's forwards for a trace
 """
 import argparse
+import collections
 import json
 import os
 import statistics
@@ -47,25 +48,9 @@ def block_median(fn, calls):
 
 
 def count_launches(fn):
-    lib = _lib.load()
-    names = [n for n in _lib.SIGNATURES if n.startswith("r3d_torso_")]
-    orig = {n: getattr(lib, n) for n in names}
-    count = {n: 0 for n in names}
-
-    def wrap(n, f):
-        def g(*a):
-            count[n] += 1
-            return f(*a)
-        return g
-
-    for n in names:
-        setattr(lib, n, wrap(n, orig[n]))
-    try:
+    with _lib.counting() as calls:
         fn()
-    finally:
-        for n in names:
-            setattr(lib, n, orig[n])
-    return count
+    return dict(collections.Counter(n for n, _ in calls if n.startswith("r3d_torso_")))
 
 
 def compare_tiers(fns, calls, blocks, block_median):
@@ -130,7 +115,7 @@ def main():
                     fn()
             out = {"metric": "torso_generator_b1_64_precision_tiers", "B": 1, "grid": [64, 64], "calls_per_block": a.calls, "blocks": a.blocks}
             out.update(compare_tiers(fns, a.calls, a.blocks, block_median))
-            out["launches_by_entry_point"] = {t: {n: c for n, c in count_launches(fn).items() if c} for t, fn in fns.items()}
+            out["launches_by_entry_point"] = {t: count_launches(fn) for t, fn in fns.items()}
             out["bf16x3_vs_f32_max_rel_diff_rgb_hid_occ2"] = [float((x - y).abs().max() / y.abs().max()) for x, y in zip(fns["bf16x3"](), hip())]
             print(json.dumps(out))
             if a.out:

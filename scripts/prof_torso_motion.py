@@ -19,6 +19,7 @@ volume, a 256^2 head image) and print one JSON line:
         (writes DIR/prof_torso_motion_precision.json); --precision bf16x3 with --forwards: that tier's forwards for a trace
 """
 import argparse
+import collections
 import csv
 import json
 import os
@@ -124,25 +125,9 @@ def main():
         return statistics.median(ev[i].elapsed_time(ev[i + 1]) for i in range(calls))
 
     def count_launches(fn):
-        lib = _lib.load()
-        names = [n for n in _lib.SIGNATURES if n.startswith("r3d_torso_") or n == "r3d_resize_bilinear"]
-        orig = {n: getattr(lib, n) for n in names}
-        count = {n: 0 for n in names}
-
-        def wrap(n, f):
-            def g(*args):
-                count[n] += 1
-                return f(*args)
-            return g
-
-        for n in names:
-            setattr(lib, n, wrap(n, orig[n]))
-        try:
+        with _lib.counting() as calls:
             fn()
-        finally:
-            for n in names:
-                setattr(lib, n, orig[n])
-        return {n: c for n, c in count.items() if c}
+        return dict(collections.Counter(n for n, _ in calls if n.startswith("r3d_torso_") or n == "r3d_resize_bilinear"))
 
     dev = "cuda:0"
     sd = synth.synth_torso_motion(171, 4)

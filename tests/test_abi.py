@@ -24,6 +24,85 @@ def test_every_declared_symbol_is_exported_and_bound():
     assert set(_lib.SIGNATURES) == set(syms)
 
 
+def header_declarations():
+    """{name: (return type, [parameter type, ...])} of every function include/r3d_hip.h declares: comments stripped, `const` dropped, no
+    blanks around a star ("const float* const* ext_bounds" -> "float**", "unsigned long long* cycles" -> "unsigned long long*")."""
+    src = open(os.path.join(ROOT, "include", "r3d_hip.h")).read()
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    src = re.sub(r"//[^\n]*", "", src)
+    norm = lambda t: re.sub(r"\s*\*\s*", "*", " ".join(re.sub(r"\bconst\b", " ", t).split()))
+    decls = {}
+    for ret, name, params in re.findall(r"^\s*([A-Za-z_][\w \*]*?)\s*\b(r3d_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", src, flags=re.M):
+        assert name not in decls, name
+        types = []
+        for p in (params.split(",") if params.strip() not in ("", "void") else []):
+            m = re.match(r"^(.*?)(\w+)$", " ".join(p.split()))          # everything up to the parameter's name
+            assert m and m.group(1).strip(), (name, p)
+            types.append(norm(m.group(1)))
+        decls[name] = (norm(ret), types)
+    return decls
+
+
+C_SCALARS = {"int": ctypes.c_int, "float": ctypes.c_float, "double": ctypes.c_double, "size_t": ctypes.c_size_t, "uint32_t": ctypes.c_uint32,
+             "uint64_t": ctypes.c_uint64, "unsigned long long": ctypes.c_ulonglong}
+C_RETURNS = dict(C_SCALARS, **{"char*": ctypes.c_char_p})
+# what a bare c_void_p in the table (a host pointer the package never looks into) may stand for: an opaque handle or the 128-byte id (void*),
+# the array of chain ops, an array of device addresses; a host pointer to a scalar or a handle is a ctypes.POINTER of exactly that type
+UNTYPED_HOST = {"void*", "r3d_chain_op*", "float**"}
+
+
+def entry_matches(entry, ctype, _lib):
+    """Does one table entry stand for the header's parameter type `ctype`, exactly?"""
+    if ctype == "r3d_stream_t":
+        return isinstance(entry, _lib.Stream)
+    if isinstance(entry, _lib.DevPtr):
+        return ctype == entry.elem + "*" and entry.elem in _lib.DevPtr.DTYPES
+    if isinstance(entry, _lib.Stream):
+        return False
+    if ctype in C_SCALARS:
+        return entry is C_SCALARS[ctype]
+    if entry is ctypes.c_void_p:
+        return ctype in UNTYPED_HOST
+    if ctype == "void**":
+        return entry is ctypes.POINTER(ctypes.c_void_p)
+    return ctype.endswith("*") and ctype[:-1] in C_SCALARS and entry is ctypes.POINTER(C_SCALARS[ctype[:-1]])
+
+
+def test_table_mirrors_every_header_declaration():
+    """Every declaration of include/r3d_hip.h is bound with the same parameter count, the exact ctypes type of every scalar, the header's
+    element type of every pointer (device pointers by their marker, host pointers by their ctypes.POINTER) and the same return type;
+    and load() derives each function's argtypes from that line."""
+    from real3dportrait_amd import _lib
+    lib = _lib.load()
+    decls = header_declarations()
+    assert len(decls) == 74 and set(decls) == set(_lib.SIGNATURES) == set(declared_symbols())
+    for name, (ret, types) in decls.items():
+        res, entries = _lib.SIGNATURES[name]
+        assert res is C_RETURNS[ret], (name, ret, res)
+        assert len(entries) == len(types), (name, len(entries), len(types))
+        for i, (e, t) in enumerate(zip(entries, types)):
+            assert entry_matches(e, t, _lib), "%s: parameter %d is %s in the header, %r in the table" % (name, i, t, e)
+        assert all(isinstance(e, _lib.Stream) is (i == len(entries) - 1) for i, e in enumerate(entries) if isinstance(e, _lib.Stream)), name
+        fn = getattr(lib, name)
+        assert fn.restype is res and list(fn.argtypes) == [getattr(e, "ctype", e) for e in entries], name
+    assert _lib.F.ctype is ctypes.c_void_p and _lib.S.ctype is ctypes.c_void_p
+
+
+def test_debug_twins_extend_their_product_function():
+    """An OPTIONAL_SIGNATURES twin of a product function takes the product's parameters, then the documented extras, then the stream."""
+    from real3dportrait_amd import _lib
+    extras = {"r3d_debug_raster_forward": ("r3d_raster_forward", [ctypes.c_int, ctypes.c_int]),          # large-face threshold, stage mask
+              "r3d_debug_secc_blink": ("r3d_secc_blink", [ctypes.c_int])}                                 # stage mask
+    assert set(_lib.OPTIONAL_SIGNATURES) == set(extras) | {"r3d_debug_merge_fallbacks"}
+    header = header_declarations()
+    for twin, (product, extra) in extras.items():
+        assert twin not in header
+        (res, got), (pres, want) = _lib.OPTIONAL_SIGNATURES[twin], _lib.SIGNATURES[product]
+        assert res is pres and isinstance(want[-1], _lib.Stream)
+        assert got[:len(want) - 1] == want[:-1] and got[len(want) - 1:-1] == extra and got[-1] is want[-1], twin
+    assert _lib.OPTIONAL_SIGNATURES["r3d_debug_merge_fallbacks"] == (ctypes.c_int, [ctypes.POINTER(ctypes.c_ulonglong), ctypes.c_int])
+
+
 def test_version_and_sizes():
     from real3dportrait_amd import _lib
     lib = _lib.load()

@@ -5,14 +5,12 @@ The symbols, the argument check of the C entry points (which runs before any HIP
 against the reference's own outputs (tests/golden/face_model_*.npz), the synthetic face model, the kernels' scratch use and the blink
 schedule's use of the random generator."""
 import ctypes
-import os
 import random
-import re
 
 import numpy as np
 import pytest
 
-from conftest import ROOT, load_golden
+from conftest import load_golden
 import blink_ref as BR
 import face_model_ref64 as F64
 import raster_ref64 as R64
@@ -44,12 +42,8 @@ def test_symbols_are_declared_exported_and_bound():
     import real3dportrait_amd
     lib = _lib.load()
     assert lib.r3d_version() == 80 == _lib.ABI_VERSION
-    header = open(os.path.join(ROOT, "include", "r3d_hip.h")).read()
-    for name in ("r3d_face_vertex", "r3d_face_landmarks"):
+    for name in ("r3d_face_vertex", "r3d_face_landmarks"):          # (header against table: tests/test_abi.py)
         assert name in _lib.SIGNATURES and hasattr(lib, name)
-        decl = re.search(r"\bint %s\(([^;]*)\);" % name, header)
-        assert decl is not None, name
-        assert len(decl.group(1).split(",")) == len(_lib.SIGNATURES[name][1]), name
     assert len(_lib.SIGNATURES["r3d_face_vertex"][1]) == 15 and len(_lib.SIGNATURES["r3d_face_landmarks"][1]) == 18
     from real3dportrait_amd import driving_motion, face_model
     for name in ("compute_face_vertex", "reconstruct_lm2d", "patch_face_model", "patch_face3d_helper"):

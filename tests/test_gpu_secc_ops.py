@@ -325,3 +325,46 @@ def test_head(H1, W1):
     y64 = check("head %dx%d" % (H1, W1), out, ref, 32)
     clipped = float((y64 == 0).double().mean())
     assert 0.05 < clipped < 0.5, clipped          # ReLU clips some outputs, not most
+
+
+# ---- the call path (_lib.call) against the raw idiom of `call` above ------------------------------------------------------
+def _layernorm_case():
+    """M = 5 rows of C = 32: the last block of four rows is ragged."""
+    g = torch.Generator().manual_seed(811)
+    return dev(randn(g, 5, 32)), dev(uniform(g, 0.5, 1.5, 32)), dev(randn(g, 32, scale=0.1))
+
+
+def test_call_path_and_raw_idiom_are_bit_identical():
+    x, lg, lb = _layernorm_case()
+    raw, via = torch.full_like(x, float("nan")), torch.full_like(x, float("nan"))
+    call("layernorm", x, 5, 32, lg, lb, 1e-5, raw)
+    _lib.call("r3d_secc_layernorm", x, 5, 32, lg, lb, 1e-5, via)
+    torch.cuda.synchronize()
+    assert bool(torch.isfinite(raw).all()) and torch.equal(raw, via)          # the same kernel with the same arguments: no tolerance
+
+
+def test_call_path_passes_the_current_stream_or_the_one_given():
+    x, lg, lb = _layernorm_case()
+    y, side, other = torch.empty_like(x), torch.cuda.Stream(DEV), torch.cuda.Stream(DEV)
+    side.wait_stream(torch.cuda.current_stream(DEV))
+    other.wait_stream(torch.cuda.current_stream(DEV))
+    with _lib.counting() as calls:
+        with torch.cuda.stream(side):
+            _lib.call("r3d_secc_layernorm", x, 5, 32, lg, lb, 1e-5, y)
+            side.synchronize()
+            _lib.call("r3d_secc_layernorm", x, 5, 32, lg, lb, 1e-5, y, other.cuda_stream)          # explicit: used as given
+            other.synchronize()
+    assert [n for n, _ in calls] == ["r3d_secc_layernorm"] * 2
+    assert calls[0][1] == (x.data_ptr(), 5, 32, lg.data_ptr(), lb.data_ptr(), 1e-5, y.data_ptr(), side.cuda_stream)
+    assert calls[1][1][-1] == other.cuda_stream != side.cuda_stream
+
+
+def test_call_path_refuses_device_tensors_before_any_launch():
+    x, lg, lb = _layernorm_case()
+    y = torch.empty_like(x)
+    with _lib.counting() as calls:
+        with pytest.raises(ValueError, match="r3d_secc_layernorm: argument 0 .* not contiguous"):
+            _lib.call("r3d_secc_layernorm", dev(torch.zeros(5, 64))[:, ::2], 5, 32, lg, lb, 1e-5, y)
+        with pytest.raises(TypeError, match=r"r3d_secc_layernorm: argument 6 is a float\*, got a torch.int32"):
+            _lib.call("r3d_secc_layernorm", x, 5, 32, lg, lb, 1e-5, torch.zeros(5, 32, dtype=torch.int32, device=DEV))
+    assert calls == []

@@ -2,6 +2,8 @@
 on fresh inputs, the fp64 restatement (tests/torso_appearance_ref64.py); determinism across batch, repeats and streams; the bf16x3 tier;
 the number of kernel launches per forward; the patch_model swap of all three torso modules on a stand-in torso model whose forward
 restates the reference's (facev2v_warp/model2.py:226-263)."""
+import collections
+
 import numpy as np
 import pytest
 import torch
@@ -97,25 +99,9 @@ def test_launches_per_forward():
     for precision, first in (("f32", "r3d_torso_conv"), ("bf16x3", "r3d_torso_conv_prec")):
         sd, m, x = fresh(241, 243, 1, 5, 32, 32, precision)
         out = m(x)                                                      # the fold and the buffers
-        lib, counts = _lib.load(), {}
-
-        class Counting:
-            def __getattr__(self, name):
-                fn = getattr(lib, name)
-                if not name.startswith("r3d_") or name in ("r3d_last_error", "r3d_version"):
-                    return fn
-
-                def counted(*a):
-                    counts[name] = counts.get(name, 0) + 1
-                    return fn(*a)
-                return counted
-
-        real = _lib._lib
-        _lib._lib = Counting()
-        try:
+        with _lib.counting() as calls:
             again = m(x)
-        finally:
-            _lib._lib = real
+        counts = dict(collections.Counter(name for name, _ in calls))
         torch.cuda.synchronize()
         print("launches:", counts)
         assert sum(counts.values()) == LAUNCHES, counts

@@ -3,6 +3,8 @@ against their public forwards, bit for bit; patch_model(torso_forward=True) on t
 tests/test_gpu_torso_appearance.py against the fp64 chain that test builds, next to the parent path (the stand-in's torch glue over the
 same three HIP modules); `ret`, the losses, the launch count, determinism across batch, repeats and streams, and that nothing is cached
 from one call to the next."""
+import collections
+
 import numpy as np
 import pytest
 import torch
@@ -187,25 +189,9 @@ def test_launches_per_forward():
     tm = patched(True)
     frame = synth_frame(FRAME)
     rgb, _ = tm.forward(*frame)                                             # the folds and the buffers
-    lib, counts = _lib.load(), {}
-
-    class Counting:
-        def __getattr__(self, name):
-            fn = getattr(lib, name)
-            if not name.startswith("r3d_") or name in ("r3d_last_error", "r3d_version"):
-                return fn
-
-            def counted(*a):
-                counts[name] = counts.get(name, 0) + 1
-                return fn(*a)
-            return counted
-
-    real = _lib._lib
-    _lib._lib = Counting()
-    try:
+    with _lib.counting() as calls:
         again, _ = tm.forward(*frame)
-    finally:
-        _lib._lib = real
+    counts = dict(collections.Counter(name for name, _ in calls))
     torch.cuda.synchronize()
     print("launches:", counts)
     assert "r3d_torso_volume_to_cl" not in counts
@@ -213,12 +199,9 @@ def test_launches_per_forward():
     assert sum(counts.values()) == LAUNCHES, counts
     assert torch.equal(rgb, again)
     # the parent path on the same frame, for comparison: two transposes and no glue kernel
-    counts.clear()
-    _lib._lib = Counting()
-    try:
+    with _lib.counting() as calls:
         patched(False).forward(*frame)
-    finally:
-        _lib._lib = real
+    counts = dict(collections.Counter(name for name, _ in calls))
     torch.cuda.synchronize()
     print("parent path launches:", counts)
     assert counts["r3d_torso_volume_to_cl"] == 2 and "r3d_torso_mask_volume" not in counts and sum(counts.values()) == LAUNCHES

@@ -1,6 +1,8 @@
 """GPU: the HIP motion-field estimator (real3dportrait_amd/torso_motion.py) against the reference's goldens and, on fresh
 inputs, the fp64 restatement (tests/torso_motion_ref64.py); determinism across batch, repeats and streams; the patch_model swap on a torso
 model whose modules are plain-torch stand-ins with the reference's layout; the number of kernel launches per forward."""
+import collections
+
 import pytest
 import torch
 import torch.nn.functional as F
@@ -102,25 +104,9 @@ def test_launches_per_forward():
     m = hip_estimator(synth.synth_torso_motion(191, 4), 4).to(DEV)
     args = to_dev(synth.synth_torso_motion_inputs(193, 1, 4))
     m(*args)                                                           # the fold and the buffers
-    lib, counts = _lib.load(), {}
-
-    class Counting:
-        def __getattr__(self, name):
-            fn = getattr(lib, name)
-            if not name.startswith("r3d_") or name in ("r3d_last_error", "r3d_version"):
-                return fn
-
-            def counted(*a):
-                counts[name] = counts.get(name, 0) + 1
-                return fn(*a)
-            return counted
-
-    real = _lib._lib
-    _lib._lib = Counting()
-    try:
+    with _lib.counting() as calls:
         out = m(*args)
-    finally:
-        _lib._lib = real
+    counts = dict(collections.Counter(name for name, _ in calls))
     torch.cuda.synchronize()
     print("launches:", counts)
     assert sum(counts.values()) == LAUNCHES, counts

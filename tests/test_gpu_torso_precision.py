@@ -2,6 +2,8 @@
 tier's tests at their tolerance; fresh inputs against the fp64 restatements, held both to that tolerance and to the exact tier's own error
 on the same inputs; bit-identity across batch, repeats and streams; the launch counts of the exact tier under the _prec names; the patched
 stand-in chain estimator -> generator -> predictor."""
+import collections
+
 import pytest
 import torch
 
@@ -117,27 +119,10 @@ def test_generator_batch_repeat_and_side_stream_are_bit_identical():
 
 # ---- launch counts -----------------------------------------------------------------------------------------------------------------------
 def _count(fn):
-    lib, counts = _lib.load(), {}
-
-    class Counting:
-        def __getattr__(self, name):
-            f = getattr(lib, name)
-            if not name.startswith("r3d_") or name in ("r3d_last_error", "r3d_version"):
-                return f
-
-            def counted(*a):
-                counts[name] = counts.get(name, 0) + 1
-                return f(*a)
-            return counted
-
-    real = _lib._lib
-    _lib._lib = Counting()
-    try:
+    with _lib.counting() as calls:
         fn()
-    finally:
-        _lib._lib = real
     torch.cuda.synchronize()
-    return counts
+    return dict(collections.Counter(name for name, _ in calls))
 
 
 def _renamed(counts):

@@ -127,8 +127,8 @@ def test_patch_model_converts_fusion_stacks_of_a_warp_sr():
 
 def test_operators_refuse_cpu_tensors_and_bad_options():
     from real3dportrait_amd import ImportanceRenderer, RaySampler
-    with pytest.raises(AssertionError):
-        RaySampler()(torch.eye(4)[None], torch.eye(3)[None], 8)          # device tensors only, no CPU fallback
+    with pytest.raises(ValueError, match="r3d_raygen: argument 0 .* not on a GPU"):
+        RaySampler()(torch.eye(4)[None], torch.eye(3)[None], 8)          # device tensors only, no CPU fallback (a raise, not an assert: python -O keeps it)
     ren = ImportanceRenderer(hp={"triplane_feature_type": "3dgrid"})
     with pytest.raises(NotImplementedError):
         ren._check_options({"ray_start": "auto", "ray_end": "auto"})

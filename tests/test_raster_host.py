@@ -6,7 +6,6 @@ The symbols, the argument check of the C entry point (which runs before any HIP 
 kernels' scratch use."""
 import ctypes
 import os
-import re
 
 import numpy as np
 import pytest
@@ -36,11 +35,8 @@ def test_symbols_are_declared_exported_and_bound():
     lib = _lib.load()
     assert lib.r3d_version() == 80 == _lib.ABI_VERSION
     header = open(os.path.join(ROOT, "include", "r3d_hip.h")).read()
-    for name, ret in (("r3d_raster_workspace_bytes", "size_t"), ("r3d_raster_forward", "int")):
+    for name in ("r3d_raster_workspace_bytes", "r3d_raster_forward"):          # (header against table: tests/test_abi.py)
         assert name in _lib.SIGNATURES and hasattr(lib, name)
-        decl = re.search(r"\b%s %s\(([^;]*)\);" % (ret, name), header)
-        assert decl is not None, name
-        assert len(decl.group(1).split(",")) == len(_lib.SIGNATURES[name][1]), name
     assert "r3d_debug_raster_forward" in _lib.OPTIONAL_SIGNATURES and "r3d_debug_raster_forward" not in header
     assert len(_lib.OPTIONAL_SIGNATURES["r3d_debug_raster_forward"][1]) == len(_lib.SIGNATURES["r3d_raster_forward"][1]) + 2
     from real3dportrait_amd import mesh_renderer

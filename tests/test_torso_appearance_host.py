@@ -347,17 +347,6 @@ def test_load_reports_a_library_without_the_new_symbols_as_stale(monkeypatch):
     assert _lib._lib is None
 
 
-def test_header_signatures_and_library_agree():
-    import os
-    import re
-    from real3dportrait_amd import _lib
-    header = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "r3d_hip.h")).read()
-    for name in ("r3d_torso_conv_pool", "r3d_torso_conv_split", "r3d_torso_conv3d_res"):
-        decl = re.search(r"\bint %s\(([^;]*)\);" % name, header)
-        assert decl is not None, name
-        assert len(decl.group(1).split(",")) == len(_lib.SIGNATURES[name][1]), name
-
-
 def test_appearance_kernels_do_not_use_scratch():
     from test_render_kernel_resources import _kernel_metadata
     from real3dportrait_amd import _lib

@@ -5,8 +5,6 @@ The fp64 restatement of the glue (tests/torso_glue_ref64.py) against the referen
 validation of the two C entry points (which runs before any HIP call), the patch_model switch and its refusals, the losses against the
 reference's formulas, and the kernels' scratch use."""
 import ctypes
-import os
-import re
 
 import numpy as np
 import pytest
@@ -14,7 +12,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from conftest import ROOT, load_golden
+from conftest import load_golden
 import torso_glue_ref64 as G64
 from real3dportrait_amd import synth
 
@@ -135,12 +133,8 @@ def test_c_entry_points_reject_bad_arguments_without_a_gpu():
 def test_header_signatures_and_library_agree():
     from real3dportrait_amd import _lib
     lib = _lib.load()
-    header = open(os.path.join(ROOT, "include", "r3d_hip.h")).read()
-    for name in ("r3d_torso_seg_input", "r3d_torso_mask_volume"):
+    for name in ("r3d_torso_seg_input", "r3d_torso_mask_volume"):          # (header against table: tests/test_abi.py)
         assert name in _lib.SIGNATURES and hasattr(lib, name)
-        decl = re.search(r"\bint %s\(([^;]*)\);" % name, header)
-        assert decl is not None, name
-        assert len(decl.group(1).split(",")) == len(_lib.SIGNATURES[name][1]), name
 
 
 def test_glue_kernels_do_not_use_scratch():
