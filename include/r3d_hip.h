@@ -705,6 +705,10 @@ int r3d_face_landmarks(const float* key_mean, const float* key_id_base, const fl
                        const float* id, const float* exp, const float* euler, const float* trans, int T, float camera_distance,
                        int to_camera, float focal, float center, float image_size, float* lm2d, r3d_stream_t stream);
 
+/* --- per-clip conditions: the camera trajectory and the smoothed key points, inference (added under ABI 0.8.0) ----------------------------
+ * Declared in the companion header next to this one, which this header includes: a program that includes r3d_hip.h sees them. */
+#include "r3d_hip_clip.h"
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,6 +14,8 @@ Operators keep the reference's names and signatures (see each module's docstring
     blink_eye_for_secc, blink_frames, apply_periodic_blink, blink_schedule, patch_blink (edit_secc.py: the driving maps' blink edit)
     compute_face_vertex, reconstruct_lm2d, patch_face_model, patch_face3d_helper (face_model.py: the morphable model's vertices and landmarks)
     get_driving_motion, patch_driving_motion             (driving_motion.py: face model -> rasteriser -> blink -> landmarks on the device)
+    clip_camera, camera_pose_intrinsic, smooth_camera_sequence, smooth_features_xd, clip_keypoints, patch_infer_utils
+                                                         (clip_conditions.py: the clip's camera trajectory and smoothed key points)
     render_clip_sharded                                  (frames.py: frame sharding + RCCL gather)
 All compute goes through libr3d_hip.so (include/r3d_hip.h); there is no eager/CPU fallback.
 """
@@ -58,6 +60,9 @@ def __getattr__(name):      # lazy: importing the package (e.g. for synth) must 
     if name in ("get_driving_motion", "patch_driving_motion"):
         import importlib
         return getattr(importlib.import_module(".driving_motion", __name__), name)
+    if name in ("camera_pose_intrinsic", "smooth_camera_sequence", "clip_camera", "smooth_features_xd", "clip_keypoints", "patch_infer_utils"):
+        import importlib
+        return getattr(importlib.import_module(".clip_conditions", __name__), name)
     if name in ("render_clip_sharded", "shard_frames"):
         from . import frames as m
         return getattr(m, name)

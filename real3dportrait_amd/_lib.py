@@ -1,4 +1,4 @@
-"""ctypes binding of libr3d_hip.so (the C ABI declared in include/r3d_hip.h).
+"""ctypes binding of libr3d_hip.so (the C ABI declared in include/r3d_hip.h and the companion header it includes).
 
 The product path has NO fallback: if the HIP library is missing or fails to load, importing an
 operator raises.  Build it with `python -c "import __graft_entry__ as g; g.build()"` or
@@ -129,6 +129,14 @@ SIGNATURES = {
     "r3d_face_landmarks": (c_int, [F, F, F, c_int, c_int, c_int, F, F, F, F, c_int, c_float, c_int, c_float, c_float, c_float, F, S]),
 }
 
+# the same for the companion header include/r3d_hip_clip.h, which r3d_hip.h includes (tests/test_clip_conditions_host.py compares every
+# declaration); bound by load() exactly as SIGNATURES is: a library that lacks one of them does not load
+CLIP_SIGNATURES = {
+    "r3d_clip_camera": (c_int, [F, F, c_int, c_int, ctypes.c_double, F, S]),
+    "r3d_camera_smooth": (c_int, [F, c_int, c_int, c_int, F, S]),
+    "r3d_smooth_features": (c_int, [F, c_int, c_int, c_int, c_int, F, S]),
+}
+
 # test hooks outside the C ABI of include/r3d_hip.h: bound when the library exports them, absent otherwise (nothing in the product calls
 # them, and a library built from older sources -- the other side of a scripts/gpu_lib_ab.sh comparison, say -- must keep loading)
 OPTIONAL_SIGNATURES = {
@@ -192,7 +200,7 @@ def load():
         lib = ctypes.CDLL(LIB_PATH)
     except OSError as e:
         raise RuntimeError("real3dportrait_amd: cannot load %s: %s" % (LIB_PATH, e))
-    for name, (res, params) in SIGNATURES.items():
+    for name, (res, params) in list(SIGNATURES.items()) + list(CLIP_SIGNATURES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError:       # functions are added without a new ABI number: a stale in-tree build lacks them
