@@ -19,26 +19,23 @@ import random
 import torch
 
 from . import _lib
+from ._state import StreamBuffers
 
 MIN_SIZE, MAX_SIZE = 16, 4096          # r3d_secc_blink's limits on h and w
-_WORKSPACE = {}                        # (device, stream, F, H, W) -> uint8 workspace: two streams in flight never share one
 
 _STATUS_TEXT = {1: "no eye pixel in one of the two prior regions (the reference fails in min() of an empty array)",
                 2: "no face pixel left around the eyes (the reference fails fitting a kd-tree on nothing)",
                 3: "frame index or close_eye_percent out of range"}
 
 
-def _workspace(dev, F, H, W):
-    key = (dev, torch.cuda.current_stream().cuda_stream, F, H, W)
-    ws = _WORKSPACE.get(key)
-    if ws is None:
-        nbytes = _lib.call("r3d_secc_blink_workspace_bytes", F, H, W)
-        if nbytes == 0:
-            raise ValueError("blink: F = %d frames of %d x %d are outside what r3d_secc_blink accepts" % (F, H, W))
-        if len(_WORKSPACE) >= 8:          # a clip uses one or two shapes; do not collect every shape a long-lived process ever saw
-            _WORKSPACE.clear()
-        ws = _WORKSPACE[key] = torch.empty(nbytes, device=dev, dtype=torch.uint8)
-    return ws
+def _new_workspace(dev, F, H, W):
+    nbytes = _lib.call("r3d_secc_blink_workspace_bytes", F, H, W)
+    if nbytes == 0:
+        raise ValueError("blink: F = %d frames of %d x %d are outside what r3d_secc_blink accepts" % (F, H, W))
+    return torch.empty(nbytes, device=dev, dtype=torch.uint8)
+
+
+_WORKSPACE = StreamBuffers(_new_workspace, cap=8)          # a clip uses one or two shapes
 
 
 def _check_maps(x, what, dims):
@@ -81,7 +78,7 @@ def blink_frames(drv_secc, frame_idx, percents, out=None):
         target = out.detach()
         target.copy_(drv_secc)
     with torch.cuda.device(dev):
-        ws = _workspace(dev, F, H, W)
+        ws = _WORKSPACE.get(dev, F, H, W)
         d_idx = torch.tensor(idx, dtype=torch.int32).to(dev, non_blocking=True)
         d_pct = torch.tensor(pct, dtype=torch.float64).to(dev, non_blocking=True)
         status = torch.empty(F, dtype=torch.int32, device=dev)

@@ -20,9 +20,9 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from ._state import StreamBuffers
 
 _TRI = {}              # id(tri) -> (weak reference to tri, its version, N checked against, the int32 copy the kernels read or None)
-_WORKSPACE = {}        # (device, stream, B, S, M) -> uint8 workspace: two streams in flight never share one
 
 
 def _checked_tri(tri, N):
@@ -45,17 +45,14 @@ def _checked_tri(tri, N):
     return t32
 
 
-def _workspace(dev, B, S, M):
-    key = (dev, torch.cuda.current_stream().cuda_stream, B, S, M)
-    ws = _WORKSPACE.get(key)
-    if ws is None:
-        nbytes = _lib.call("r3d_raster_workspace_bytes", B, S, M)
-        if nbytes == 0:
-            raise ValueError("rasterize: B = %d meshes of M = %d faces at S = %d are outside what r3d_raster_forward accepts" % (B, M, S))
-        if len(_WORKSPACE) >= 8:          # a clip uses one or two shapes; do not collect every shape a long-lived process ever saw
-            _WORKSPACE.clear()
-        ws = _WORKSPACE[key] = torch.empty(nbytes, device=dev, dtype=torch.uint8)
-    return ws
+def _new_workspace(dev, B, S, M):
+    nbytes = _lib.call("r3d_raster_workspace_bytes", B, S, M)
+    if nbytes == 0:
+        raise ValueError("rasterize: B = %d meshes of M = %d faces at S = %d are outside what r3d_raster_forward accepts" % (B, M, S))
+    return torch.empty(nbytes, device=dev, dtype=torch.uint8)
+
+
+_WORKSPACE = StreamBuffers(_new_workspace, cap=8)          # a clip uses one or two shapes
 
 
 @torch.no_grad()
@@ -94,7 +91,7 @@ def rasterize(vertex, tri, S, fov, znear, feat=None, negate_x=True, first_face_i
         feat = feat.detach().float().contiguous()
         C = feat.shape[2]
     t32 = _checked_tri(tri, N)
-    ws = _workspace(v.device, B, S, M)
+    ws = _WORKSPACE.get(v.device, B, S, M)
     e = lambda c: torch.empty(B, c, S, S, device=v.device, dtype=torch.float32)
     p2f = torch.empty(B, S, S, device=v.device, dtype=torch.int64) if want_pix_to_face else None
     mask, depth, image = e(1), e(1), (e(C) if feat is not None else None)
@@ -120,7 +117,7 @@ def _rasterize_into(vertex, tri, S, fov, znear, feat, image, mask, depth, out_sc
         if tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_contiguous() or t.device != vertex.device:
             raise ValueError("_rasterize_into: %s must be a contiguous float32 %s tensor on %s" % (what, shape, vertex.device))
     t32 = _checked_tri(tri, N)
-    ws = _workspace(vertex.device, B, S, M)
+    ws = _WORKSPACE.get(vertex.device, B, S, M)
     _lib.call("r3d_raster_forward", vertex, feat, t32, int(tri.dim() == 3), B, N, M, C, S, float(fov), float(znear), 1, 1, float(out_scale),
               float(out_shift), None, mask, depth, image, ws, ws.numel())
 

@@ -13,6 +13,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from ._state import _FoldedModule
 from .superresolution import Conv2d, ConvStack
 from .synth import SECC_DIMS, SECC_HEADS, SECC_SR
 
@@ -100,7 +101,7 @@ class _SegFormerHead(nn.Module):
         self.linear_fuse = _ConvModule()
 
 
-class SegFormerSECC2PlaneBackbone(nn.Module):
+class SegFormerSECC2PlaneBackbone(_FoldedModule):
     def __init__(self, mode="b0", out_channels=96, pncc_cond_mode="cano_src_tgt"):
         super().__init__()
         if mode != "b0":
@@ -113,56 +114,40 @@ class SegFormerSECC2PlaneBackbone(nn.Module):
         self.to_plane_cnn = ConvStack(Conv2d(256, 256, 3, 1, 1), nn.LeakyReLU(0.01), Conv2d(256, 256, 3, 1, 1), nn.LeakyReLU(0.01),
                                       Conv2d(256, 256, 3, 1, 1), nn.LeakyReLU(0.01), nn.UpsamplingBilinear2d(scale_factor=2.0),
                                       Conv2d(256, out_channels, 3, 1, 1))
-        self._derived_key = None
-        self._derived = None
-        self._work = {}          # (device, stream, B, H, W) -> activation buffers: two streams in flight never share one
 
-    # ---- parameters in the kernels' layouts (once per parameter version) ----------------------------------------------------------
-    def _params_key(self):
-        return tuple((p.data_ptr(), p._version) for p in self.parameters()) + tuple((b.data_ptr(), b._version) for b in self.buffers())
-
-    def _prepare(self):
-        key = self._params_key()
-        if key == self._derived_key:
-            return self._derived
+    # ---- parameters in the kernels' layouts (_prepare: once per parameter version) -------------------------------------------------
+    def _fold(self):
         mv, fh = self.mix_vit, self.fuse_head
         d = {"conv": {}}
-        with torch.no_grad():
-            for s in range(1, 5):
-                pe = getattr(mv, "patch_embed%d" % s)
-                d["conv"]["pe%d" % s] = pe.proj.weight.detach().permute(0, 2, 3, 1).contiguous().float()
-                for j, blk in enumerate(getattr(mv, "block%d" % s)):
-                    if hasattr(blk.attn, "sr"):
-                        d["conv"]["sr%d.%d" % (s, j)] = blk.attn.sr.weight.detach().permute(0, 2, 3, 1).contiguous().float()
-            # the head fold, in fp64: W'_i = W_fuse[:, block(i)] W_ci, const = sum_i W_fuse[:, block(i)] b_ci, BN -> scale, shift
-            wf = fh.linear_fuse.conv.weight.detach().double()[:, :, 0, 0]
-            const = torch.zeros(256, dtype=torch.float64, device=wf.device)
-            for blk, s in enumerate((4, 3, 2, 1)):
-                part = wf[:, 256 * blk:256 * (blk + 1)]
-                lin = getattr(fh, "linear_c%d" % s).proj
-                d["wfold%d" % s] = (part @ lin.weight.detach().double()).float().contiguous()
-                const = const + part @ lin.bias.detach().double()
-            bn = fh.linear_fuse.bn
-            scale = bn.weight.detach().double() / torch.sqrt(bn.running_var.detach().double() + bn.eps)
-            d["hconst"] = const.float().contiguous()
-            d["bn_scale"] = scale.float().contiguous()
-            d["bn_shift"] = (bn.bias.detach().double() - bn.running_mean.detach().double() * scale).float().contiguous()
-        self._derived_key, self._derived = key, d
+        for s in range(1, 5):
+            pe = getattr(mv, "patch_embed%d" % s)
+            d["conv"]["pe%d" % s] = pe.proj.weight.detach().permute(0, 2, 3, 1).contiguous().float()
+            for j, blk in enumerate(getattr(mv, "block%d" % s)):
+                if hasattr(blk.attn, "sr"):
+                    d["conv"]["sr%d.%d" % (s, j)] = blk.attn.sr.weight.detach().permute(0, 2, 3, 1).contiguous().float()
+        # the head fold, in fp64: W'_i = W_fuse[:, block(i)] W_ci, const = sum_i W_fuse[:, block(i)] b_ci, BN -> scale, shift
+        wf = fh.linear_fuse.conv.weight.detach().double()[:, :, 0, 0]
+        const = torch.zeros(256, dtype=torch.float64, device=wf.device)
+        for blk, s in enumerate((4, 3, 2, 1)):
+            part = wf[:, 256 * blk:256 * (blk + 1)]
+            lin = getattr(fh, "linear_c%d" % s).proj
+            d["wfold%d" % s] = (part @ lin.weight.detach().double()).float().contiguous()
+            const = const + part @ lin.bias.detach().double()
+        bn = fh.linear_fuse.bn
+        scale = bn.weight.detach().double() / torch.sqrt(bn.running_var.detach().double() + bn.eps)
+        d["hconst"] = const.float().contiguous()
+        d["bn_scale"] = scale.float().contiguous()
+        d["bn_shift"] = (bn.bias.detach().double() - bn.running_mean.detach().double() * scale).float().contiguous()
         return d
 
-    def _buffers_for(self, B, H, W, dev):
-        key = (dev, torch.cuda.current_stream().cuda_stream, B, H, W)
-        w = self._work.get(key)
-        if w is None:
-            n1 = B * (H // 4) * (W // 4)
-            L = B * (H // 32) * (W // 32) * 64       # spatial-reduction output rows x C, the largest stage (C sr^2 = 2048 ... 256)
-            e = lambda n: torch.empty(n, device=dev, dtype=torch.float32)
-            w = {"x": e(n1 * 32), "t": e(n1 * 32), "q": e(n1 * 32), "o": e(n1 * 32), "h1": e(n1 * 128), "h2": e(n1 * 128),
-                 "sr": e(L * 4), "kv": e(L * 8),
-                 "c": [e(n1 * 32), e(n1 // 4 * 64), e(n1 // 16 * 160), e(n1 // 64 * 256)],
-                 "f": [None, e(n1 // 4 * 256), e(n1 // 16 * 256), e(n1 // 64 * 256)]}
-            self._work[key] = w
-        return w
+    def _new_buffers(self, dev, B, H, W):
+        n1 = B * (H // 4) * (W // 4)
+        L = B * (H // 32) * (W // 32) * 64       # spatial-reduction output rows x C, the largest stage (C sr^2 = 2048 ... 256)
+        e = lambda n: torch.empty(n, device=dev, dtype=torch.float32)
+        return {"x": e(n1 * 32), "t": e(n1 * 32), "q": e(n1 * 32), "o": e(n1 * 32), "h1": e(n1 * 128), "h2": e(n1 * 128),
+                "sr": e(L * 4), "kv": e(L * 8),
+                "c": [e(n1 * 32), e(n1 // 4 * 64), e(n1 // 16 * 160), e(n1 // 64 * 256)],
+                "f": [None, e(n1 // 4 * 256), e(n1 // 16 * 256), e(n1 // 64 * 256)]}
 
     # ---- the encoder ---------------------------------------------------------------------------------------------------------------
     def _check_input(self, x):
@@ -181,7 +166,7 @@ class SegFormerSECC2PlaneBackbone(nn.Module):
         x = x.detach().float().contiguous()
         st = torch.cuda.current_stream().cuda_stream
         d = self._prepare()
-        w = self._buffers_for(B, H, W, x.device)
+        w = self._buffers_for(x.device, B, H, W)
         mv = self.mix_vit
         X, T, Q, O, H1, H2, SR, KV = w["x"], w["t"], w["q"], w["o"], w["h1"], w["h2"], w["sr"], w["kv"]
         h, wd = H // 4, W // 4

@@ -19,8 +19,8 @@ import torch
 
 from . import _lib
 from .sr_activation import _tag, as_input, bound_of, empty, fmt_of, logical_shape, tag_split
+from ._state import Derived
 from .superresolution import _BoundMeter, _f32c, blend_cat, chain_fold, const_bound, resize_bilinear
-from .torso_layers import _Cached
 
 
 import os
@@ -65,7 +65,7 @@ class WarpSRState:
         self.slots = None
         self.split_fold_pending = False     # split_input_spec() folded block0 for a SPLIT input that forward() has not consumed yet
         self.meter_x, self.meter_hid = _BoundMeter(), _BoundMeter()
-        self.c_torso256, self.c_bg256, self.c_xbg, self.c_ws3 = _Cached(), _Cached(), _Cached(), _Cached()
+        self.c_torso256, self.c_bg256, self.c_xbg, self.c_ws3 = Derived(), Derived(), Derived(), Derived()
 
     def slot(self, k, N, dev):
         if self.slots is None or self.slots.shape[1] != N or self.slots.device != dev:
@@ -83,7 +83,7 @@ def warp_split_input_spec(self, ws, N, dev):
     b0 = self.block0
     if b0.precision not in ("f16x3", "f16mx") or self.input_resolution != 128:
         return None
-    ws3 = S.c_ws3.get(ws, lambda w: w[:, -1:, :].expand(N, 3, -1).contiguous())
+    ws3 = S.c_ws3.get([ws], lambda: ws[:, -1:, :].expand(N, 3, -1).contiguous())
     b0.prepare(ws3, dev, ws_key=ws)
     chain_fold([b0.chain_op(-1)], N, [const_bound(1.01, N, dev)], zero=[S.slot(0, N, dev)])
     S.split_fold_pending = True
@@ -156,14 +156,14 @@ def _forward_v2(self, S, rgb, x, ws, ref_torso_rgb, ref_bg_rgb, weights_img, seg
     aa = self.sr_antialias
     weights_img = weights_img.detach()
     N, dev = rgb.shape[0], rgb.device
-    ws3 = S.c_ws3.get(ws, lambda w: w[:, -1:, :].expand(N, 3, -1).contiguous())                      # :69
+    ws3 = S.c_ws3.get([ws], lambda: ws[:, -1:, :].expand(N, 3, -1).contiguous())                   # :69
     if fmt_of(x) != "split" and x.shape[-1] != self.input_resolution:                                   # :71-75, cold
         sz = (self.input_resolution, self.input_resolution)
         x, rgb = resize_bilinear(x, sz, aa), resize_bilinear(rgb, sz, aa)
     rgb_256 = resize_bilinear(rgb, (256, 256), aa)                                                      # :77
     weights_256 = resize_bilinear(weights_img, (256, 256), aa)                                          # :78
-    ref_torso_rgb_256 = S.c_torso256.get(ref_torso_rgb, lambda t: resize_bilinear(t, (256, 256), aa))  # :80 (clip constant)
-    ref_bg_rgb_256 = S.c_bg256.get(ref_bg_rgb, lambda t: resize_bilinear(t, (256, 256), aa))           # :82 (clip constant)
+    ref_torso_rgb_256 = S.c_torso256.get([ref_torso_rgb], lambda: resize_bilinear(ref_torso_rgb, (256, 256), aa))  # :80 (clip constant)
+    ref_bg_rgb_256 = S.c_bg256.get([ref_bg_rgb], lambda: resize_bilinear(ref_bg_rgb, (256, 256), aa))  # :82 (clip constant)
 
     b0, b1, hb = self.block0, self.block1, self.head_torso_block
     fuse_ht, fuse_fg = self.fuse_head_torso_convs, self.fuse_fg_bg_convs
@@ -199,7 +199,7 @@ def _forward_v2(self, S, rgb, x, ws, ref_torso_rgb, ref_bg_rgb, weights_img, seg
         and Ca % 16 == 0 and fmt_of(hid) == "nchw"
     if not fuse_cat:
         x_torso = self.torso_encoder(hid, out_format="cb8")                                            # :88 (1x1 conv, measured input)
-    x_bg = S.c_xbg.get(ref_bg_rgb, lambda _: _measured(self.bg_encoder(ref_bg_rgb_256, out_format="cb8"), S))   # :90 (clip constant)
+    x_bg = S.c_xbg.get([ref_bg_rgb], lambda: _measured(self.bg_encoder(ref_bg_rgb_256, out_format="cb8"), S))   # :90 (clip constant)
 
     # ---- head / torso fusion (:99-105) -----------------------------------------------------------------------------------------------
     alpha = weights_256                                   # `head_torso_alpha[head_torso_alpha > weights_256] = ...` (:101-102) is a no-op

@@ -28,6 +28,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from ._state import Derived, _DeviceBuffers
 from .sr_activation import (FMT, MAX_DEPTH, SPLIT_FORMATS, _keep_tags, _tag, as_input, bound_of, empty, fmt_of, logical_shape, out_target,  # noqa: F401
                             tag_bound, tag_split)          # (_tag, _keep_tags, bound_of, MAX_DEPTH: imported from here by tests and scripts)
 from .volumetric_rendering import _FC, _f32c
@@ -130,17 +131,6 @@ def chain_fold(ops, N, ext, zero=()):
               ctypes.cast(zptrs, ctypes.c_void_p), len(zero))
 
 
-class _DeviceBuffers:
-    """`_buf(name, nbytes, dev)`: the uint8 device buffer kept in attribute `name`, grown (or moved) when it does not hold nbytes on dev."""
-
-    def _buf(self, name, nbytes, dev):
-        t = getattr(self, name)
-        if t is None or t.numel() < nbytes or t.device != dev:
-            t = torch.empty(nbytes, device=dev, dtype=torch.uint8)
-            setattr(self, name, t)
-        return t
-
-
 class SynthesisLayer(nn.Module):
     """Parameter container with the reference's names/shapes (networks_stylegan2.py:286-320)."""
 
@@ -215,10 +205,9 @@ class SynthesisBlock(_DeviceBuffers, nn.Module):
         # Override per module (`.precision`, set_sr_precision()) or for the process with R3D_SR_PRECISION.
         self.precision = os.environ.get("R3D_SR_PRECISION", DEFAULT_SR_PRECISION)
         self._prepacked = None
-        self._prepack_key = None
+        self._prepack_state = Derived()         # is _prepacked that of the two conv weights?
         self._styles = None
-        self._styles_key = None
-        self._styles_ws = None         # keeps the ws tensor of the cached styles alive (its address cannot be recycled)
+        self._styles_state = Derived()          # is _styles that of ws and the parameters?
         self._workspace = None
         self._meter = _BoundMeter()
         self._depth_in = 0             # layers between the last measurement and this block's input (set by whoever folds it)
@@ -239,10 +228,10 @@ class SynthesisBlock(_DeviceBuffers, nn.Module):
         return -1.0 if self.conv_clamp is None else float(self.conv_clamp)
 
     def prepare(self, ws, dev=None, ws_key=None):
-        """Static weight re-layout (cached on parameter versions) + the per-sample style / demodulation vectors for
-        `ws` [N,3,w_dim] (cached on the identity + version of `ws_key`, default `ws` itself, and the parameter versions:
-        a clip renders every frame with the same ws).  Returns (prepacked, styles) device buffers.  The FOLDED vectors the
-        f16x3 kernels read are written by `fold()` / chain_fold, every forward."""
+        """Static weight re-layout (cached on the two conv weights) + the per-sample style / demodulation vectors for `ws` [N,3,w_dim]
+        (cached on `ws_key`, default `ws` itself, and the parameters: a clip renders every frame with the same ws), both by the rule of
+        _state.Derived.  Returns (prepacked, styles) device buffers.  The FOLDED vectors the f16x3 kernels read are written by `fold()` /
+        chain_fold, every forward."""
         Cin, Cout = self.in_channels, self.out_channels
         c0, c1, tr = self.conv0, self.conv1, self.torgb
         params = (c0.weight, c0.bias, c0.affine.weight, c0.affine.bias, c1.weight, c1.bias, c1.affine.weight, c1.affine.bias,
@@ -250,20 +239,20 @@ class SynthesisBlock(_DeviceBuffers, nn.Module):
         keep = [_f32c(t) for t in params]
         dev = keep[0].device if dev is None else dev
         prec = self._prec()
-        key = (keep[0].data_ptr(), c0.weight._version, keep[4].data_ptr(), c1.weight._version, str(dev), prec)
-        if self._prepack_key != key:
+        N = ws.shape[0]
+
+        def prepack():
             pre = self._buf("_prepacked", _lib.call("r3d_sr_block_prepacked_bytes", Cin, Cout), dev)
             _lib.call("r3d_sr_block_prepack", Cin, Cout, keep[0], keep[4], pre, prec)
-            self._prepack_key = key
-        src = ws if ws_key is None else ws_key
-        N = ws.shape[0]
-        skey = (id(src), src._version, tuple(src.shape), N, str(dev)) + tuple((t.data_ptr(), p._version) for t, p in zip(keep, params))
-        if self._styles_key != skey or self._styles_ws is not src:
-            ws = _f32c(ws)
-            assert ws.shape[1] == self.num_conv + self.num_torgb and ws.shape[2] == self.w_dim, ws.shape
-            styles = self._buf("_styles", _lib.call("r3d_sr_block_styles_bytes", N, Cin, Cout), dev)
-            _lib.call("r3d_sr_block_styles", ws, N, self.w_dim, Cin, Cout, *keep, styles)
-            self._styles_key, self._styles_ws = skey, src
+
+        def styles():
+            w = _f32c(ws)
+            assert w.shape[1] == self.num_conv + self.num_torgb and w.shape[2] == self.w_dim, w.shape
+            buf = self._buf("_styles", _lib.call("r3d_sr_block_styles_bytes", N, Cin, Cout), dev)
+            _lib.call("r3d_sr_block_styles", w, N, self.w_dim, Cin, Cout, *keep, buf)
+
+        self._prepack_state.get([c0.weight, c1.weight], prepack, (dev, prec))
+        self._styles_state.get([ws if ws_key is None else ws_key, *params], styles, (N, dev))
         return self._prepacked, self._styles
 
     def styles_stride(self):
@@ -360,7 +349,7 @@ class Conv2d(_DeviceBuffers, nn.Module):
         self.weight = nn.Parameter(ref.weight.detach().clone())
         self.bias = nn.Parameter(ref.bias.detach().clone()) if bias else None
         self._prepacked = None
-        self._prepack_key = None
+        self._prepack_state = Derived()         # is _prepacked that of the weight?
         self._workspace = None
         self._scales = None
         self._bias32 = None
@@ -375,14 +364,14 @@ class Conv2d(_DeviceBuffers, nn.Module):
         return self.precision == "f16mx" and self.kernel_size[0] == 3 and self.in_channels % 16 == 0
 
     def prepare(self, N, dev):
-        """Static weight re-layout (cached on the parameter version) and this call's scales buffer."""
+        """Static weight re-layout (cached on the weight, _state.Derived) and this call's scales buffer."""
         Cin, Cout, k = self.in_channels, self.out_channels, self.kernel_size[0]
-        w = _f32c(self.weight)
-        key = (w.data_ptr(), self.weight._version, str(dev))
-        if self._prepack_key != key:
+
+        def prepack():
             pre = self._buf("_prepacked", _lib.call("r3d_conv_prepacked_bytes", Cin, Cout, k), dev)
-            _lib.call("r3d_conv_prepack", w, Cin, Cout, k, pre)
-            self._prepack_key = key
+            _lib.call("r3d_conv_prepack", _f32c(self.weight), Cin, Cout, k, pre)
+
+        self._prepack_state.get([self.weight], prepack, dev)
         self._bias32 = _f32c(self.bias) if self.bias is not None else None
         self._buf("_scales", _lib.call("r3d_conv_scales_bytes", N, Cin, Cout), dev)
 
@@ -501,9 +490,6 @@ def resize_bilinear(x, size, antialias=True):
     return y
 
 
-_BLEND_METERS = {}
-
-
 def blend_cat(a, b, mask, consumer, ws=None, _folded_head=None, _b_channels=None, _dst=None):
     """(b = None with _b_channels = Cb and _dst = the concatenated tensor: only the `a` part is written; Conv2d.forward_cat fills channels [Ca, Ca + Cb).)
     cat([a * mask, b * (1 - mask)], dim=1) (sr_with_ref.py:104,114,126,136) written directly as the SPLIT input of
@@ -526,7 +512,9 @@ def blend_cat(a, b, mask, consumer, ws=None, _folded_head=None, _b_channels=None
     if _folded_head is not None:
         head = _folded_head
     else:
-        meters = _BLEND_METERS.setdefault(id(consumer), (_BoundMeter(), _BoundMeter()))
+        if not hasattr(consumer, "_blend_meters"):
+            object.__setattr__(consumer, "_blend_meters", (_BoundMeter(), _BoundMeter()))
+        meters = consumer._blend_meters
         L = consumer.num_layers()
         (ba, da), (bb, db) = bound_of(a, meters[0], L), bound_of(b, meters[1], L)
         head = consumer.fold_for_input(N, a.device, [ba, bb], ws=ws, depth=max(da, db))
@@ -671,24 +659,16 @@ class SuperresolutionHybrid8XDC(nn.Module):
                                      use_fp16=False, conv_clamp=None, **block_kwargs)
         self.block1.return_x = False           # forward() only returns rgb (:359)
         self._meter = _BoundMeter()
-        self._ws3 = None                       # (ws, version, ws[:, -1:].repeat(1, 3, 1)): a clip renders every frame with one ws
+        self._ws3 = Derived()                  # ws[:, -1:].repeat(1, 3, 1): a clip renders every frame with one ws
         self._mx_slot = None                   # f16mx: max|block0 output| measured in its conv1 epilogue
-        self._fold_sig, self._fold_bx = None, None
-
-    def _ws_last3(self, ws):
-        c = self._ws3
-        if c is not None and c[0] is ws and c[1] == ws._version:
-            return c[2]
-        ws3 = ws[:, -1:, :].repeat(1, 3, 1)          # :349
-        self._ws3 = (ws, ws._version, ws3)
-        return ws3
+        self._fold = Derived()                 # is the main fold in place?  Source: the bound tensor; extra: _sig
 
     FEATURE_BOUND = 1.01      # |renderer feature image| <= 1.002 by construction (sigmoid * 1.002 - 0.001 composited with weights summing to <= 1)
 
     def _prepare_and_fold(self, ws, N, dev, bx, dx):
         """Style vectors of both blocks (cached per ws) + the range fold for an input bounded by bx (skipped while nothing it depends on
         changed).  Returns (ws3, prep0, prep1, x_absmax slot or None)."""
-        ws3 = self._ws_last3(ws)
+        ws3 = self._ws3.get([ws], lambda: ws[:, -1:, :].repeat(1, 3, 1))          # :349
         b0, b1 = self.block0, self.block1
         b1.precision = b0.precision
         prep0 = b0.prepare(ws3, dev, ws_key=ws)
@@ -707,15 +687,15 @@ class SuperresolutionHybrid8XDC(nn.Module):
             # const_bound) and the per-clip style cache unchanged, the folded vectors of the previous frame are still in place:
             # skip the launch (13 us per frame).  f16mx: the per-frame tail fold (forward) re-arms the max|x0| slot and only rewrites
             # block1's conv1 operand vectors, which it rewrites again next frame before they are read: the main fold can be skipped too.
-            if not getattr(bx, "_r3d_const", False) or self._fold_sig != self._sig(bx, dx):
+            if not getattr(bx, "_r3d_const", False) or not self._fold.valid([bx], self._sig(dx)):
                 chain_fold([b0.chain_op(-1), b1.chain_op(0)], N, [bx], zero=[x_absmax] if mx else ())
-                self._fold_sig = self._sig(bx, dx)
-                self._fold_bx = bx           # keeps id(bx) from being recycled
+                self._fold.put([bx], None, self._sig(dx))
         return ws3, prep0, prep1, x_absmax
 
-    def _sig(self, bx, dx):
+    def _sig(self, dx):
+        """What the main fold depends on besides the bound tensor: both blocks' style vectors, and that nobody folded a block since."""
         b0, b1 = self.block0, self.block1
-        return (id(bx), dx, b0._styles_key, b1._styles_key, b0._fold_epoch, b1._fold_epoch, b0.precision)
+        return (dx, b0._styles_state.generation, b1._styles_state.generation, b0._fold_epoch, b1._fold_epoch, b0.precision)
 
     def split_input_spec(self, ws, N, dev):
         """For a producer that writes this network's input directly in the SPLIT format (the ray kernel, r3d_render_forward `split_out`):
@@ -757,9 +737,9 @@ class SuperresolutionHybrid8XDC(nn.Module):
         if mx:
             # tail fold: block1's conv1 operand from the MEASURED max|x0|; clears the slot for the next frame (the kernel reads its
             # bounds before it zeroes) -- our own fold, so the main fold's signature stays valid
-            fresh = self._fold_sig == self._sig(bx, dx)
+            fresh = self._fold.valid([bx], self._sig(dx))
             chain_fold([b1.chain_op(-1, tail=True)], x.shape[0], [x_absmax], zero=[x_absmax])
             if fresh:
-                self._fold_sig = self._sig(bx, dx)
+                self._fold.put([bx], None, self._sig(dx))
         x, rgb = b1(x, rgb, ws3, _prepared=prep1, _folded=True, _u8_out=_u8_out, _need_img=_need_img, **block_kwargs)
         return rgb

@@ -23,6 +23,7 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib
+from ._state import StreamBuffers
 from .torso_appearance import LAUNCHES as EXTRACTOR_LAUNCHES
 from .torso_layers import _check_f32
 from .torso_motion import jacobian
@@ -89,20 +90,16 @@ def losses(occlusion, occlusion_2, target_torso_mask=None, unmask_factor=None):
 
 
 class TorsoForwardState:
-    """What `forward` keeps on the torso model between calls: work buffers per (device, stream, N) -- two streams in flight never share
-    one -- and the Jacobian of the identity rotations per (device, N).  No result of a call is among them."""
+    """What `forward` keeps on the torso model between calls: work buffers per (device, stream, shape) and the Jacobian of the identity
+    rotations per (device, N).  No result of a call is among them."""
 
     def __init__(self):
-        self.work, self.identity_j = {}, {}
+        self.work, self.identity_j = StreamBuffers(self._new_buffers), {}
 
-    def buffers(self, dev, N, in_dim, H, W, D, h, w, C):
-        key = (dev, torch.cuda.current_stream().cuda_stream, N)
-        b = self.work.get(key)
-        if b is None or b["shape"] != (in_dim, H, W, D, h, w, C):
-            e = lambda *s: torch.empty(*s, device=dev, dtype=torch.float32)
-            b = self.work[key] = {"shape": (in_dim, H, W, D, h, w, C), "x": e(N, in_dim, H, W), "masked_cl": e(N, D, h, w, C),
-                                  "motion_cl": e(N, D, h, w, C + 2)}
-        return b
+    @staticmethod
+    def _new_buffers(dev, N, in_dim, H, W, D, h, w, C):
+        e = lambda *s: torch.empty(*s, device=dev, dtype=torch.float32)
+        return {"x": e(N, in_dim, H, W), "masked_cl": e(N, D, h, w, C), "motion_cl": e(N, D, h, w, C + 2)}
 
     def jacobian(self, dev, N):
         J = self.identity_j.get((dev, N))
@@ -139,7 +136,7 @@ def forward(self, torso_src_img, segmap, kp_s, kp_d, tgt_head_img, tgt_head_weig
                          "extractor of in_dim 3 or 5, got %s, %s and in_dim %d" % (tuple(img.shape), tuple(seg.shape), ext.in_dim))
     state = self._r3d_torso_forward
     D, h, w, C = ext.D, H // 4, W // 4, ext.C
-    b = state.buffers(img.device, N, ext.in_dim, H, W, D, h, w, C)
+    b = state.work.get(img.device, N, ext.in_dim, H, W, D, h, w, C)
     x = seg_input(img, seg, out=b["x"]) if ext.in_dim == 5 else img          # torso_inp_mode rgb_alpha: read off the extractor's width
     feats_cl = ext.forward_cl(x)
     masked_cl, motion_cl = mask_volume(feats_cl, seg, ksize=hp.get("torso_mask_dilate_ksize", 7), mul_mask=hp.get("mul_torso_mask", True),

@@ -15,7 +15,8 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from .torso_layers import (LEAKY, SIGMOID, _Cached, _check_f32, _conv, _ConvBlock, _ResBlock, _TorsoModule, conv_layer, conv_weight64, fold_cna,
+from ._state import Derived, StreamBuffers
+from .torso_layers import (LEAKY, SIGMOID, _check_f32, _conv, _ConvBlock, _ResBlock, _TorsoModule, conv_layer, conv_weight64, fold_cna,
                            fold_res_pair, sn_weight64)
 from .torso_precision import F32
 
@@ -40,7 +41,7 @@ def fold_generator(gen, dtype=torch.float32):
     return L
 
 
-_VOLUME_CL = {}          # stream -> _Cached: the channel-last copy of the appearance volume (constant over a clip)
+_VOLUME_CL = StreamBuffers(lambda dev: Derived())          # per stream: the channel-last copy of the appearance volume (constant over a clip)
 
 
 class Generator(_TorsoModule):
@@ -78,12 +79,12 @@ class Generator(_TorsoModule):
         Do, Ho, Wo = grid.shape[1:4]
         st = torch.cuda.current_stream().cuda_stream
 
-        def to_cl(_):
+        def to_cl():
             cl = torch.empty(N, D, H, W, C, device=fs.device, dtype=torch.float32)
             _lib.call("r3d_torso_volume_to_cl", fs, N, C, D, H, W, cl, st)
             return cl
 
-        cl = _VOLUME_CL.setdefault(st, _Cached()).get(key, to_cl)
+        cl = _VOLUME_CL.get(fs.device).get([key], to_cl)
         return fs, grid, cl, (N, C, D, H, W, Do, Ho, Wo)
 
     @staticmethod

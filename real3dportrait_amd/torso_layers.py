@@ -1,39 +1,23 @@
 """What the four HIP torso modules (torso_generator.py, torso_motion.py, torso_appearance.py, torso_forward.py) share: the reference's
-building blocks with its state_dict keys, the fp64 folds of spectral norm and BatchNorm into kernel weights, the module base that caches
-the folded weights per parameter version and the work buffers per (device, stream, shape), and one launch wrapper per conv entry point
+building blocks with its state_dict keys, the fp64 folds of spectral norm and BatchNorm into kernel weights, the module base (folded
+weights and work buffers kept by the rules of _state.py), and one launch wrapper per conv entry point
 of include/r3d_hip.h (r3d_torso_conv, r3d_torso_conv3d, r3d_torso_conv_pool, r3d_torso_conv_split, r3d_torso_conv3d_res).
 """
 import torch
 import torch.nn as nn
 
 from . import _lib
+from ._state import _FoldedModule
 from .torso_precision import F32, PRECISIONS, check_precision
 
 NONE, LEAKY, SIGMOID = 0, 1, 2          # the conv entry points' `act`
 BN_EPS = 1e-5
 
 
-class _Cached:
-    """value = fn(tensor), recomputed only when `tensor` is another object or was modified in place (the entry holds the tensor)."""
-
-    def __init__(self):
-        self._src, self._ver, self._val = None, None, None
-
-    def get(self, t, fn):
-        if self._src is not t or self._ver != t._version:
-            self._val = fn(t)
-            self._src, self._ver = t, t._version
-        return self._val
-
-
 def _check_f32(t, what, dims):
     if not torch.is_tensor(t) or t.dim() != dims:
         raise ValueError("%s: expected a %d-D tensor" % (what, dims))
     return t.detach().float().contiguous()
-
-
-def _params_key(m):
-    return tuple((p.data_ptr(), p._version) for p in m.parameters()) + tuple((b.data_ptr(), b._version) for b in m.buffers())
 
 
 def _pad4(c):
@@ -141,31 +125,14 @@ def conv_layer(w, b, k, dtype=torch.float32, ps=None, pt=None, up=0, act=NONE, s
     return {"w": _kernel_weight(w, dtype), "b": f(b), "ps": f(ps), "pt": f(pt), "k": k, "up": up, "act": act, "slope": slope, "res": res}
 
 
-class _TorsoModule(nn.Module):
-    """The host side every HIP torso module has: the derived (folded) weights, recomputed when a parameter or buffer is another tensor or
-    was modified in place; work buffers per (device, stream, *shape), so that two streams in flight never share one; from_reference.
-    A subclass supplies _fold() -> the derived weights, _new_buffers(dev, *shape) -> the buffers, and _reference_args(ref) -> the constructor
-    arguments of a HIP copy of the reference module `ref`."""
+class _TorsoModule(_FoldedModule):
+    """The host side every HIP torso module has: the derived (folded) weights and the work buffers per (device, stream, *shape), both by
+    the rules of _state.py; from_reference.  A subclass supplies _fold() -> the derived weights, _new_buffers(dev, *shape) -> the buffers,
+    and _reference_args(ref) -> the constructor arguments of a HIP copy of the reference module `ref`."""
 
     def __init__(self, precision):
         super().__init__()
         self.precision = check_precision(precision, "%s: precision" % type(self).__name__)
-        self._derived_key, self._derived = None, None
-        self._work = {}
-
-    def _prepare(self):
-        key = _params_key(self)
-        if key != self._derived_key:
-            with torch.no_grad():
-                self._derived_key, self._derived = key, self._fold()
-        return self._derived
-
-    def _buffers_for(self, dev, *shape):
-        key = (dev, torch.cuda.current_stream().cuda_stream) + shape
-        w = self._work.get(key)
-        if w is None:
-            w = self._work[key] = self._new_buffers(dev, *shape)
-        return w
 
     @classmethod
     def from_reference(cls, ref, precision=F32):

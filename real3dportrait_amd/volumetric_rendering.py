@@ -18,6 +18,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib, sr_activation
+from ._state import Derived, _DeviceBuffers
 
 
 def _f32c(t):
@@ -90,7 +91,7 @@ def decoder_params(decoder):
     return w1, b1, w2, b2
 
 
-class ImportanceRenderer(nn.Module):
+class ImportanceRenderer(_DeviceBuffers, nn.Module):
     """renderer.py:107-297 restated as one fused HIP kernel per frame (see csrc/r3d_render.hip).
 
     rendering_options keys read (same as the reference): ray_start, ray_end (must both be 'auto': the
@@ -115,7 +116,7 @@ class ImportanceRenderer(nn.Module):
         self.noise_mode = "torch"
         self.noise_override = None
         self.seed = 0
-        self._plane_cache = None       # (source tensor, version, nhwc tensor)
+        self._plane_cache = Derived()  # the channel-last copy of static planes
         self.rgb_channel_major = True  # memory layout of the colours (the returned tensor is [N,M,32] either way)
         self.need_depth = True         # False: forward returns depth = None and skips the depth-clamp launch (ClipRenderer: frames only)
         self._workspace = None
@@ -159,24 +160,11 @@ class ImportanceRenderer(nn.Module):
         return tag[0], tag[1]
 
     def _planes_nhwc(self, planes):
-        """Channel-last copy of `planes`, cached for static planes.  The cache entry holds the SOURCE tensor itself and is valid
-        only for that very object at the same version: a freed tensor's address (and a fresh tensor's version 0) can be handed
-        to the next frame's planes by the caching allocator, so an address/version key alone would render stale planes."""
+        """Channel-last copy of `planes`, cached for static planes (valid for that very tensor at the same version, _state.Derived: an
+        address / version key would render the previous frame's planes from a recycled block)."""
         if getattr(planes, "_r3d_nhwc", False):
             return planes
-        c = self._plane_cache
-        if c is not None and c[0] is planes and c[1] == planes._version:
-            return c[2]
-        out = self.prepare_planes(planes)
-        self._plane_cache = (planes, planes._version, out)
-        return out
-
-    def _ensure_workspace(self, need, dev):
-        """Make self._workspace hold at least `need` bytes on `dev` (it only ever grows on one device); returns int(need)."""
-        need = int(need)
-        if self._workspace is None or self._workspace.numel() < need or self._workspace.device != dev:
-            self._workspace = torch.empty(need, device=dev, dtype=torch.uint8)
-        return need
+        return self._plane_cache.get([planes], lambda: self.prepare_planes(planes))
 
     def _check_options(self, opts):
         if self.triplane_feature_type not in ("triplane", "trigrid", "trigrid_v2"):
@@ -241,7 +229,7 @@ class ImportanceRenderer(nn.Module):
         depth = torch.empty(N, M, 1, device=dev, dtype=torch.float32) if self.need_depth else None
         wsum = torch.empty(N, M, 1, device=dev, dtype=torch.float32)
         valid = torch.empty(N, M, 1, device=dev, dtype=torch.bool)
-        need = self._ensure_workspace(_lib.call("r3d_render_workspace_bytes", N, M, Nc, Nf), dev)
+        need = _lib.call("r3d_render_workspace_bytes", N, M, Nc, Nf)
         part, npart = self._absmax_of(planes_nhwc)        # None (caller's own layout, or updated in place since): measured inside the call
         x_split, sp_scale, sp_stride = None, None, 0
         if _split_for is not None:
@@ -252,7 +240,7 @@ class ImportanceRenderer(nn.Module):
         _lib.call("r3d_render_forward", planes_nhwc, N, H, W, D, w1, b1, w2, b2, o, d, M, Nc, Nf, float(rendering_options["box_warp"]),
                   int(bool(rendering_options.get("white_back", False))), noise_c, u_f, int(self.seed) & 0xFFFFFFFFFFFFFFFF,
                   rgb_cm, int(self.rgb_channel_major), depth, wsum, valid, part, npart, c2w, K, x_split, sp_scale, int(sp_stride),
-                  self._workspace, need)
+                  self._buf("_workspace", need, dev), need)
         if x_split is not None:
             rgb._r3d_split = x_split
         return rgb, depth, wsum, valid
@@ -271,8 +259,8 @@ class ImportanceRenderer(nn.Module):
         w1, b1, w2, b2 = decoder_params(decoder)
         rgb = torch.empty(N, npts, 32, device=coords.device, dtype=torch.float32)
         sigma = torch.empty(N, npts, 1, device=coords.device, dtype=torch.float32)
-        need = self._ensure_workspace(_lib.call("r3d_run_model_workspace_bytes"), coords.device)
+        need = _lib.call("r3d_run_model_workspace_bytes")
         part, npart = self._absmax_of(planes_nhwc)
         _lib.call("r3d_run_model", planes_nhwc, N, H, W, D, w1, b1, w2, b2, coords, npts, float(options["box_warp"]), rgb, sigma, part, npart,
-                  self._workspace, need)
+                  self._buf("_workspace", need, coords.device), need)
         return {"rgb": rgb, "sigma": sigma}

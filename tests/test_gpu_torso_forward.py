@@ -108,11 +108,11 @@ def test_generator_forward_cl_is_the_forward_of_the_transposed_input(N):
     inp = synth.synth_torso_inputs(266, N, 24, 20)
     fs, grid = (torch.from_numpy(inp[k]).to(DEV) for k in ("torso_appearance_feats", "deformation"))
     rgb, hid = m(fs, grid, None, return_hid=True)
-    cached = {k: v._src for k, v in torso_generator._VOLUME_CL.items()}
+    cached = {k: v._srcs for k, v in torso_generator._VOLUME_CL._entries.items()}
     rgb_cl, hid_cl = m.forward_cl(to_cl(fs), grid, None, return_hid=True)
     assert torch.equal(rgb, rgb_cl) and torch.equal(hid, hid_cl)
     assert torch.equal(m.forward_cl(to_cl(fs), grid), rgb)
-    assert {k: v._src for k, v in torso_generator._VOLUME_CL.items()} == cached          # _VOLUME_CL is not touched
+    assert {k: v._srcs for k, v in torso_generator._VOLUME_CL._entries.items()} == cached          # _VOLUME_CL is not touched
     with pytest.raises(ValueError, match="expected fs_cl"):
         m.forward_cl(fs, grid)
 

@@ -101,6 +101,28 @@ def test_state_dict_keys_match_the_reference_layout():
         m.load_state_dict({k: torch.from_numpy(v) for k, v in synth.synth_secc_backbone(3, mode).items()}, strict=True)
 
 
+def test_parameter_edits_and_replacements_are_seen_by_the_next_prepare():
+    from real3dportrait_amd import SegFormerSECC2PlaneBackbone
+    from test_state_host import replaced_at_same_address
+    m = SegFormerSECC2PlaneBackbone().eval()
+    a = m._prepare()
+    assert m._prepare() is a
+    with torch.no_grad():
+        m.mix_vit.patch_embed2.proj.weight.add_(0.01)
+    b = m._prepare()
+    assert b is not a and not torch.equal(b["conv"]["pe2"], a["conv"]["pe2"]) and torch.equal(b["wfold1"], a["wfold1"])
+    with torch.no_grad():
+        m.fuse_head.linear_fuse.bn.running_var.mul_(2.0)
+    c = m._prepare()
+    assert c is not b and not torch.equal(c["bn_scale"], b["bn_scale"]) and torch.equal(c["conv"]["pe2"], b["conv"]["pe2"])
+    # a parameter replaced by another tensor at the same address and version (what the caching allocator makes of a freed one)
+    d, e = replaced_at_same_address(m.fuse_head.linear_c1.proj, "weight", m._prepare)
+    # (3 w rounds to fp32 and so does the folded row, a dot product of 32 terms in fp64: <= 34 x 2^-24 of max|3 wfold1| = 2e-6)
+    assert e is not d and float((e["wfold1"] - d["wfold1"] * 3.0).abs().max()) <= 1e-5 * float(d["wfold1"].abs().max())
+    assert not torch.equal(e["wfold1"], d["wfold1"]) and torch.equal(e["wfold2"], d["wfold2"])
+    assert m._prepare() is e
+
+
 def test_unsupported_configurations_raise():
     from real3dportrait_amd.segformer import SegFormerSECC2PlaneBackbone
     with pytest.raises(NotImplementedError):

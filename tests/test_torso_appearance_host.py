@@ -218,6 +218,11 @@ def test_in_place_parameter_edits_are_seen_by_the_next_prepare():
         m.mid_conv.bias.add_(1.0)
     d = m._prepare()
     assert d is not c and float(d["mid"]["b"][5] - c["mid"]["b"][5]) == pytest.approx(1.0, abs=1e-6)
+    # a parameter replaced by another tensor at the same address and version (what the caching allocator makes of a freed one)
+    from test_state_host import replaced_at_same_address
+    e, f = replaced_at_same_address(m.down[1].layers[0].layers[0], "weight", m._prepare)
+    assert f is not e and not torch.equal(f["down"][1]["w"], e["down"][1]["w"]) and torch.equal(f["down"][0]["w"], e["down"][0]["w"])
+    assert m._prepare() is f
 
 
 def test_patch_model_swaps_the_extractor_only_with_the_flag():

@@ -166,6 +166,11 @@ def test_in_place_parameter_edits_are_seen_by_the_next_prepare():
     with torch.no_grad():
         getattr(pred, "2").weight.add_(0.5)
     assert pred._prepare() is not p0
+    # a parameter replaced by another tensor at the same address and version (what the caching allocator makes of a freed one)
+    from test_state_host import replaced_at_same_address
+    d, e = replaced_at_same_address(gen.mid_conv, "weight", gen._prepare)
+    assert e is not d and torch.equal(e[1]["w"], d[1]["w"] * 3.0) and torch.equal(e[2]["w"], d[2]["w"])
+    assert gen._prepare() is e
 
 
 def test_c_entry_points_reject_bad_arguments_without_a_gpu():

@@ -273,6 +273,11 @@ def test_in_place_parameter_edits_are_seen_by_the_next_prepare():
         m.occlusion_conv2.bias.add_(1.0)
     d = m._prepare()
     assert d is not c and float(d["occ"]["b"][1] - c["occ"]["b"][1]) == pytest.approx(1.0, abs=1e-6) and torch.equal(d["occ"]["b"][0], c["occ"]["b"][0])
+    # a parameter replaced by another tensor at the same address and version (what the caching allocator makes of a freed one)
+    from test_state_host import replaced_at_same_address
+    e, f = replaced_at_same_address(m.down[1].layers[0].layers[0], "weight", m._prepare)
+    assert f is not e and not torch.equal(f["down"][1]["w"], e["down"][1]["w"]) and torch.equal(f["down"][0]["w"], e["down"][0]["w"])
+    assert m._prepare() is f
 
 
 def test_patch_model_swaps_the_estimator_only_with_the_flag():
