@@ -16,6 +16,8 @@ Operators keep the reference's names and signatures (see each module's docstring
     get_driving_motion, patch_driving_motion             (driving_motion.py: face model -> rasteriser -> blink -> landmarks on the device)
     clip_camera, camera_pose_intrinsic, smooth_camera_sequence, smooth_features_xd, clip_keypoints, patch_infer_utils
                                                          (clip_conditions.py: the clip's camera trajectory and smoothed key points)
+    depth_range, compose_debug_frames, clip_frames, secc2video_frames, write_video, patch_secc2video
+                                                         (video_frames.py: the clip's output frames, out_mode 'final' and 'concat_debug')
     render_clip_sharded                                  (frames.py: frame sharding + RCCL gather)
 All compute goes through libr3d_hip.so (include/r3d_hip.h); there is no eager/CPU fallback.
 """
@@ -63,6 +65,9 @@ def __getattr__(name):      # lazy: importing the package (e.g. for synth) must 
     if name in ("camera_pose_intrinsic", "smooth_camera_sequence", "clip_camera", "smooth_features_xd", "clip_keypoints", "patch_infer_utils"):
         import importlib
         return getattr(importlib.import_module(".clip_conditions", __name__), name)
+    if name in ("depth_range", "compose_debug_frames", "clip_frames", "secc2video_frames", "write_video", "patch_secc2video"):
+        import importlib
+        return getattr(importlib.import_module(".video_frames", __name__), name)
     if name in ("render_clip_sharded", "shard_frames"):
         from . import frames as m
         return getattr(m, name)

@@ -1,4 +1,4 @@
-"""ctypes binding of libr3d_hip.so (the C ABI declared in include/r3d_hip.h and the companion header it includes).
+"""ctypes binding of libr3d_hip.so (the C ABI declared in include/r3d_hip.h and the companion headers it includes).
 
 The product path has NO fallback: if the HIP library is missing or fails to load, importing an
 operator raises.  Build it with `python -c "import __graft_entry__ as g; g.build()"` or
@@ -137,6 +137,13 @@ CLIP_SIGNATURES = {
     "r3d_smooth_features": (c_int, [F, c_int, c_int, c_int, c_int, F, S]),
 }
 
+# the same for the companion header include/r3d_hip_video.h (tests/test_video_frames_host.py compares every declaration)
+VIDEO_SIGNATURES = {
+    "r3d_video_depth_range": (c_int, [F, c_size_t, c_int, I32, S]),
+    "r3d_video_compose_debug": (c_int, [F, F, c_int, c_int, F, c_int, c_int, F, c_int, c_int, F, c_int, c_int, c_int, c_int, I32, U8, S]),
+}
+VIDEO_STATE_WORDS, VIDEO_PANELS_ALL, VIDEO_PANEL_DEPTH = 8, 31, 8          # R3D_VIDEO_* of that header
+
 # test hooks outside the C ABI of include/r3d_hip.h: bound when the library exports them, absent otherwise (nothing in the product calls
 # them, and a library built from older sources -- the other side of a scripts/gpu_lib_ab.sh comparison, say -- must keep loading)
 OPTIONAL_SIGNATURES = {
@@ -200,7 +207,7 @@ def load():
         lib = ctypes.CDLL(LIB_PATH)
     except OSError as e:
         raise RuntimeError("real3dportrait_amd: cannot load %s: %s" % (LIB_PATH, e))
-    for name, (res, params) in list(SIGNATURES.items()) + list(CLIP_SIGNATURES.items()):
+    for name, (res, params) in list(SIGNATURES.items()) + list(CLIP_SIGNATURES.items()) + list(VIDEO_SIGNATURES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError:       # functions are added without a new ABI number: a stale in-tree build lacks them
