@@ -713,6 +713,10 @@ int r3d_face_landmarks(const float* key_mean, const float* key_id_base, const fl
  * Declared in the companion header next to this one, which this header includes: a program that includes r3d_hip.h sees them. */
 #include "r3d_hip_video.h"
 
+/* --- the source image's head, torso and background: the frame loop's conditions, inference (added under ABI 0.8.0) ---------------------------
+ * Declared in the companion header next to this one, which this header includes: a program that includes r3d_hip.h sees them. */
+#include "r3d_hip_source.h"
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,6 +18,9 @@ Operators keep the reference's names and signatures (see each module's docstring
                                                          (clip_conditions.py: the clip's camera trajectory and smoothed key points)
     depth_range, compose_debug_frames, clip_frames, secc2video_frames, write_video, patch_secc2video
                                                          (video_frames.py: the clip's output frames, out_mode 'final' and 'concat_debug')
+    nearest_seed, head_image, inpaint_torso_job, extract_background, source_to_planes, patch_segment_imgs
+                                                         (source_conditions.py: the source image's head, torso and background conditions;
+                                                         the name source_conditions is the module, its function source_conditions.source_conditions)
     render_clip_sharded                                  (frames.py: frame sharding + RCCL gather)
 All compute goes through libr3d_hip.so (include/r3d_hip.h); there is no eager/CPU fallback.
 """
@@ -68,6 +71,9 @@ def __getattr__(name):      # lazy: importing the package (e.g. for synth) must 
     if name in ("depth_range", "compose_debug_frames", "clip_frames", "secc2video_frames", "write_video", "patch_secc2video"):
         import importlib
         return getattr(importlib.import_module(".video_frames", __name__), name)
+    if name in ("nearest_seed", "head_image", "inpaint_torso_job", "extract_background", "source_to_planes", "patch_segment_imgs"):
+        import importlib
+        return getattr(importlib.import_module(".source_conditions", __name__), name)
     if name in ("render_clip_sharded", "shard_frames"):
         from . import frames as m
         return getattr(m, name)

@@ -144,6 +144,18 @@ VIDEO_SIGNATURES = {
 }
 VIDEO_STATE_WORDS, VIDEO_PANELS_ALL, VIDEO_PANEL_DEPTH = 8, 31, 8          # R3D_VIDEO_* of that header
 
+# the same for the companion header include/r3d_hip_source.h (tests/test_source_conditions_host.py compares every declaration); the darkening
+# table and the blur weights of r3d_source_torso are HOST arrays
+SOURCE_SIGNATURES = {
+    "r3d_source_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "r3d_source_nearest": (c_int, [U8, c_int, c_int, c_int, I32, I32, I32, V, c_size_t, S]),
+    "r3d_source_background": (c_int, [U8, U8, c_int, c_int, c_int, U8, I32, V, c_size_t, S]),
+    "r3d_source_torso": (c_int, [U8, U8, c_int, c_int, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(c_int), U8, U8, U8, U8, V, c_size_t, S]),
+    "r3d_source_select": (c_int, [U8, U8, c_int, c_int, c_int, U8, U8, S]),
+    "r3d_source_to_planes": (c_int, [U8, U8, c_int, c_int, c_int, F, S]),
+}
+SOURCE_MAX_SIDE, SOURCE_STATUS_WORDS, SOURCE_DARKEN, SOURCE_HEAD_CLASSES = 2048, 2, 53, 42          # R3D_SOURCE_* of that header
+
 # test hooks outside the C ABI of include/r3d_hip.h: bound when the library exports them, absent otherwise (nothing in the product calls
 # them, and a library built from older sources -- the other side of a scripts/gpu_lib_ab.sh comparison, say -- must keep loading)
 OPTIONAL_SIGNATURES = {
@@ -207,7 +219,8 @@ def load():
         lib = ctypes.CDLL(LIB_PATH)
     except OSError as e:
         raise RuntimeError("real3dportrait_amd: cannot load %s: %s" % (LIB_PATH, e))
-    for name, (res, params) in list(SIGNATURES.items()) + list(CLIP_SIGNATURES.items()) + list(VIDEO_SIGNATURES.items()):
+    for name, (res, params) in list(SIGNATURES.items()) + list(CLIP_SIGNATURES.items()) + list(VIDEO_SIGNATURES.items()) \
+            + list(SOURCE_SIGNATURES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError:       # functions are added without a new ABI number: a stale in-tree build lacks them

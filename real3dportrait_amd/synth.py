@@ -636,6 +636,44 @@ def synth_secc_eyes(H, W, seed, crossing=False, zero_channel=0, right_hole=True)
 SECC_EYES = ((0.37, 0.385), (0.63, 0.398))          # (u, v) of synth_secc_eyes' two holes, half-axes 0.065 x 0.028 of the image
 
 
+def synth_portrait_segmap(H, W, seed, shift=0.0, low_neck=True):
+    """A one-hot portrait segmap uint8 [6, H, W] for real3dportrait_amd/source_conditions.py, the segmenter's classes: 0 background,
+    1 hair, 2 body skin (the neck), 3 face skin, 4 clothes, 5 others (a glasses strip).  u, v are the pixel centres in [0, 1], the person
+    is centred on u = 0.5 + shift.  Clothes lie below a wavy shoulder line v_s(u) that falls away from the neck; the neck is the strip
+    |u - c| < 0.085 between the face and the shoulder line; the hair is an ellipse behind the face with two strands (0.17 < |u - c| <
+    0.23) that hang down to the shoulder line, so in their columns clothes lie directly under hair; the face is an ellipse over both; the
+    glasses a horizontal strip across it.  low_neck: in the columns 0.04 < u < 0.10 a patch of face skin ends 5 rows above the bottom of
+    the image and the bottom row is body skin, so the dilated neck of these columns has 4 pixels (the bottom border cuts it) with face
+    skin directly above: the only way a column of inpaint_torso_job has a pixel count below 5."""
+    v, u = np.meshgrid((np.arange(H) + 0.5) / H, (np.arange(W) + 0.5) / W, indexing="ij")
+    c = 0.5 + shift
+    du = np.abs(u - c)
+    v_s = 0.74 + 0.025 * np.sin(2 * np.pi * 2.5 * u + 0.7 * seed) + 0.5 * np.maximum(du - 0.12, 0.0)
+    label = np.zeros((H, W), np.int64)
+    label[(v > v_s) & (du < 0.46)] = 4
+    label[(du < 0.085) & (v > 0.45) & (v <= v_s)] = 2
+    label[((u - c) / 0.25) ** 2 + ((v - 0.33) / 0.25) ** 2 < 1.0] = 1
+    label[(du > 0.17) & (du < 0.23) & (v > 0.33) & (v <= v_s)] = 1
+    label[((u - c) / 0.17) ** 2 + ((v - 0.40) / 0.20) ** 2 < 1.0] = 3
+    label[(np.abs(v - 0.37) < 0.018) & (du < 0.14)] = 5
+    if low_neck:
+        cols = (u[0] > 0.04) & (u[0] < 0.10)
+        label[H - 12:H - 4, cols] = 3
+        label[H - 1, cols] = 2
+    return (label[None] == np.arange(6)[:, None, None]).astype(np.uint8)
+
+
+def synth_portrait_image(H, W, seed, shift=0.0):
+    """The image uint8 [H, W, 3] that goes with synth_portrait_segmap: smooth colours that move with the person plus per-pixel noise, so
+    that no two neighbouring pixels are likely to agree in all three channels."""
+    v, u = np.meshgrid((np.arange(H) + 0.5) / H, (np.arange(W) + 0.5) / W, indexing="ij")
+    u = u - shift
+    noise = hash_unitvar(seed, (3, H, W), stream=60).astype(np.float64)
+    x = np.stack([0.5 + 0.3 * np.sin(5.1 * u + 0.3 * seed) * np.cos(3.3 * v), 0.5 + 0.3 * np.cos(6.7 * u * v + 0.2 * seed),
+                  0.5 + 0.25 * np.sin(7.0 * (u - v)) + 0.1 * v]) + 0.08 * noise
+    return np.ascontiguousarray(np.clip(x * 255.0, 0.0, 255.0).astype(np.uint8).transpose(1, 2, 0))
+
+
 def synth_face_model(G, seed, Ki=80, Ke=64):
     """A morphable face model for real3dportrait_amd/face_model.py and driving_motion.py, with the attributes the reference's
     ParametricFaceModel, SECC_Renderer and Face3DHelper carry (BFM data exists on no machine this project is built on):
