@@ -40,7 +40,8 @@ class Stream:
 F, F64, I32, I64, U8, U16, V = (DevPtr(e) for e in ("float", "double", "int32_t", "int64_t", "uint8_t", "uint16_t", "void"))
 S = Stream()
 
-# name -> (restype, [one entry per parameter]); mirrors include/r3d_hip.h one to one (tests/test_abi.py compares every declaration).
+# name -> (restype, [one entry per parameter]); mirrors include/r3d_hip.h and the three companion headers it includes one to one
+# (tests/test_abi.py compares every declaration of the four).  A library that lacks one of them does not load.
 # An entry is a ctypes type (scalars; host pointers as ctypes.POINTER(...) or, untyped, H), a device pointer named by the header's element
 # type (F float*, F64 double*, I32 int32_t*, I64 int64_t*, U8 uint8_t*, U16 uint16_t*, V void*), or S, the trailing r3d_stream_t.
 SIGNATURES = {
@@ -127,26 +128,14 @@ SIGNATURES = {
     "r3d_secc_blink": (c_int, [F, c_int, c_int, c_int, I32, F64, c_int, F, I32, V, c_size_t, S]),
     "r3d_face_vertex": (c_int, [F, F, F, c_int, c_int, c_int, F, F, F, F, c_int, c_float, c_int, F, S]),
     "r3d_face_landmarks": (c_int, [F, F, F, c_int, c_int, c_int, F, F, F, F, c_int, c_float, c_int, c_float, c_float, c_float, F, S]),
-}
-
-# the same for the companion header include/r3d_hip_clip.h, which r3d_hip.h includes (tests/test_clip_conditions_host.py compares every
-# declaration); bound by load() exactly as SIGNATURES is: a library that lacks one of them does not load
-CLIP_SIGNATURES = {
+    # include/r3d_hip_clip.h
     "r3d_clip_camera": (c_int, [F, F, c_int, c_int, ctypes.c_double, F, S]),
     "r3d_camera_smooth": (c_int, [F, c_int, c_int, c_int, F, S]),
     "r3d_smooth_features": (c_int, [F, c_int, c_int, c_int, c_int, F, S]),
-}
-
-# the same for the companion header include/r3d_hip_video.h (tests/test_video_frames_host.py compares every declaration)
-VIDEO_SIGNATURES = {
+    # include/r3d_hip_video.h
     "r3d_video_depth_range": (c_int, [F, c_size_t, c_int, I32, S]),
     "r3d_video_compose_debug": (c_int, [F, F, c_int, c_int, F, c_int, c_int, F, c_int, c_int, F, c_int, c_int, c_int, c_int, I32, U8, S]),
-}
-VIDEO_STATE_WORDS, VIDEO_PANELS_ALL, VIDEO_PANEL_DEPTH = 8, 31, 8          # R3D_VIDEO_* of that header
-
-# the same for the companion header include/r3d_hip_source.h (tests/test_source_conditions_host.py compares every declaration); the darkening
-# table and the blur weights of r3d_source_torso are HOST arrays
-SOURCE_SIGNATURES = {
+    # include/r3d_hip_source.h; the darkening table and the blur weights of r3d_source_torso are HOST arrays
     "r3d_source_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "r3d_source_nearest": (c_int, [U8, c_int, c_int, c_int, I32, I32, I32, V, c_size_t, S]),
     "r3d_source_background": (c_int, [U8, U8, c_int, c_int, c_int, U8, I32, V, c_size_t, S]),
@@ -154,7 +143,8 @@ SOURCE_SIGNATURES = {
     "r3d_source_select": (c_int, [U8, U8, c_int, c_int, c_int, U8, U8, S]),
     "r3d_source_to_planes": (c_int, [U8, U8, c_int, c_int, c_int, F, S]),
 }
-SOURCE_MAX_SIDE, SOURCE_STATUS_WORDS, SOURCE_DARKEN, SOURCE_HEAD_CLASSES = 2048, 2, 53, 42          # R3D_SOURCE_* of that header
+VIDEO_STATE_WORDS, VIDEO_PANELS_ALL, VIDEO_PANEL_DEPTH = 8, 31, 8          # R3D_VIDEO_* of include/r3d_hip_video.h
+SOURCE_MAX_SIDE, SOURCE_STATUS_WORDS, SOURCE_DARKEN, SOURCE_HEAD_CLASSES = 2048, 2, 53, 42          # R3D_SOURCE_* of include/r3d_hip_source.h
 
 # test hooks outside the C ABI of include/r3d_hip.h: bound when the library exports them, absent otherwise (nothing in the product calls
 # them, and a library built from older sources -- the other side of a scripts/gpu_lib_ab.sh comparison, say -- must keep loading)
@@ -219,8 +209,7 @@ def load():
         lib = ctypes.CDLL(LIB_PATH)
     except OSError as e:
         raise RuntimeError("real3dportrait_amd: cannot load %s: %s" % (LIB_PATH, e))
-    for name, (res, params) in list(SIGNATURES.items()) + list(CLIP_SIGNATURES.items()) + list(VIDEO_SIGNATURES.items()) \
-            + list(SOURCE_SIGNATURES.items()):
+    for name, (res, params) in SIGNATURES.items():
         try:
             fn = getattr(lib, name)
         except AttributeError:       # functions are added without a new ABI number: a stale in-tree build lacks them

@@ -251,7 +251,7 @@ extern "C" int r3d_clip_camera(const float* euler, const float* trans, int T, in
     const char* what = "clip_camera";
     if (!euler || !trans || !camera) { set_error("%s: NULL pointer", what); return R3D_ERR_INVALID_ARG; }
     if (!clip::window_ok(what, T, kernel_size)) return R3D_ERR_INVALID_ARG;
-    if ((double)T * clip::ROW >= 2147483648.0) { set_error("%s: 25 T = %.0f elements, the limit is 2^31", what, (double)T * clip::ROW); return R3D_ERR_INVALID_ARG; }
+    if (!below_2_31(what, "25 T", (double)T * clip::ROW, "elements")) return R3D_ERR_INVALID_ARG;
     if (!(radius >= 0.0) || radius - radius != 0.0) { set_error("%s: radius = %g must be finite and not negative (0: no rescaling)", what, radius); return R3D_ERR_INVALID_ARG; }
     const size_t nout = (size_t)T * clip::ROW, nin = (size_t)T * 3;
     if (overlap(camera, nout, euler, nin) || overlap(camera, nout, trans, nin)) { set_error("%s: the output overlaps an input", what); return R3D_ERR_INVALID_ARG; }
@@ -268,7 +268,7 @@ extern "C" int r3d_camera_smooth(const float* camera_in, int row_stride, int T, 
     if (!camera_in || !camera_out) { set_error("%s: NULL pointer", what); return R3D_ERR_INVALID_ARG; }
     if (row_stride != 16 && row_stride != clip::ROW) { set_error("%s: row_stride = %d, a camera row has 16 or 25 values", what, row_stride); return R3D_ERR_INVALID_ARG; }
     if (!clip::window_ok(what, T, kernel_size)) return R3D_ERR_INVALID_ARG;
-    if ((double)T * row_stride >= 2147483648.0) { set_error("%s: T row_stride = %.0f elements, the limit is 2^31", what, (double)T * row_stride); return R3D_ERR_INVALID_ARG; }
+    if (!below_2_31(what, "T row_stride", (double)T * row_stride, "elements")) return R3D_ERR_INVALID_ARG;
     const size_t n = (size_t)T * row_stride;
     if (overlap(camera_out, n, camera_in, n)) { set_error("%s: the output overlaps the input (a frame reads its neighbours)", what); return R3D_ERR_INVALID_ARG; }
     ProfScope ps(R3D_PROF_MISC, (hipStream_t)stream);
@@ -289,7 +289,7 @@ extern "C" int r3d_smooth_features(const float* x, int T, int C, int kernel_size
     const int g = zero_columns_every;
     if (g < 0 || (g > 0 && C % g != 0)) { set_error("%s: zero_columns_every = %d must be 0 or a divisor of C = %d", what, g, C); return R3D_ERR_INVALID_ARG; }
     const long long Cout = g > 0 ? (long long)C + C / g : (long long)C;
-    if ((double)T * (double)Cout >= 2147483648.0) { set_error("%s: T C = %.0f elements with the zero columns, the limit is 2^31", what, (double)T * (double)Cout); return R3D_ERR_INVALID_ARG; }
+    if (!below_2_31(what, "T C", (double)T * (double)Cout, "elements with the zero columns")) return R3D_ERR_INVALID_ARG;
     const size_t nin = (size_t)T * C, nout = (size_t)T * (size_t)Cout;
     if (overlap(y, nout, x, nin)) { set_error("%s: the output overlaps the input (a frame reads its neighbours)", what); return R3D_ERR_INVALID_ARG; }
     ProfScope ps(R3D_PROF_MISC, (hipStream_t)stream);

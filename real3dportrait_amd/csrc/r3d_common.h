@@ -4,16 +4,11 @@
 #include <stdint.h>
 
 #include "../../include/r3d_hip.h"
+#include "r3d_args.h"
 
 namespace r3d {
 
-void set_error(const char* fmt, ...);
 int check_launch(const char* what);
-
-// Host side, for the argument checks: [a, a + na) and [b, b + nb) (counts of floats) share an element
-inline bool overlap(const float* a, size_t na, const float* b, size_t nb) { return a < b + nb && b < a + na; }
-// p can take 16-byte loads; nullptr (an optional operand that is absent) passes
-inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 // Optional per-launch-site timing with HIP events recorded ON THE LAUNCH STREAM (r3d_profile_* in r3d_hip.h).
 void prof_begin(int id, hipStream_t st);

@@ -178,17 +178,16 @@ static int launch(const char* what, bool lm, const float* mean, const float* id_
     if (N < 1 || T < 1) { set_error("%s: bad argument (%s = %d, T = %d must be positive)", what, lm ? "L" : "N", N, T); return R3D_ERR_INVALID_ARG; }
     if (Ki < 1 || Ke < 0 || (long long)Ki + Ke > 512) { set_error("%s: Ki = %d, Ke = %d: need Ki >= 1, Ke >= 0, Ki + Ke <= 512", what, Ki, Ke); return R3D_ERR_INVALID_ARG; }
     if (Ke > 0 && !exp_base) { set_error("%s: exp_base is NULL with Ke = %d", what, Ke); return R3D_ERR_INVALID_ARG; }
-    if (3.0 * (double)N * (double)T >= 2147483648.0) { set_error("%s: 3 N T = %.0f elements, the limit is 2^31", what, 3.0 * (double)N * (double)T); return R3D_ERR_INVALID_ARG; }
+    if (!below_2_31(what, lm ? "3 L T" : "3 N T", 3.0 * (double)N * (double)T, "elements")) return R3D_ERR_INVALID_ARG;
     if (!finite(camera_distance)) { set_error("%s: camera_distance is not finite", what); return R3D_ERR_INVALID_ARG; }
     if (lm) {
         if (!finite(focal) || !finite(center) || !finite(image_size)) { set_error("%s: focal, center or image_size is not finite", what); return R3D_ERR_INVALID_ARG; }
         if (!(focal > 0.0f) || !(image_size > 0.0f)) { set_error("%s: focal = %g and image_size = %g must be positive", what, (double)focal, (double)image_size); return R3D_ERR_INVALID_ARG; }
     }
     const size_t rows = (size_t)3 * N, nout = (size_t)(lm ? 2 : 3) * N * T;
-    if (overlap(out, nout, mean, rows) || overlap(out, nout, id_base, rows * Ki) || (exp_base && Ke > 0 && overlap(out, nout, exp_base, rows * Ke)) ||
-        overlap(out, nout, id, (size_t)T * Ki) || (exp && Ke > 0 && overlap(out, nout, exp, (size_t)T * Ke)) ||
-        (euler && overlap(out, nout, euler, (size_t)T * 3)) || (trans && overlap(out, nout, trans, (size_t)T * 3)))
-        { set_error("%s: the output overlaps an input", what); return R3D_ERR_INVALID_ARG; }
+    const Span spans[] = {writes(out, nout), reads(mean, rows), reads(id_base, rows * Ki), reads(exp_base, rows * Ke), reads(id, (size_t)T * Ki),
+                          reads(exp, (size_t)T * Ke), reads(euler, (size_t)T * 3), reads(trans, (size_t)T * 3)};          // (absent, or Ke = 0: no part)
+    if (clash(spans)) { set_error("%s: the output overlaps an input", what); return R3D_ERR_INVALID_ARG; }
 
     Args a;
     a.mean = mean; a.id_base = id_base; a.exp_base = Ke > 0 ? exp_base : nullptr; a.euler = euler; a.trans = trans;
@@ -204,8 +203,8 @@ static int launch(const char* what, bool lm, const float* mean, const float* id_
     const long long per = ((long long)T + want - 1) / want;
     a.chunk = (int)std::min((long long)T, (per + GROUP - 1) / GROUP * GROUP);
     const unsigned yblocks = (unsigned)(((long long)T + a.chunk - 1) / a.chunk);
-    a.id_wide = ((uintptr_t)id_base & 15) == 0 && (Ki & 3) == 0;
-    a.exp_wide = Ke > 0 && ((uintptr_t)exp_base & 15) == 0 && (Ke & 3) == 0;
+    a.id_wide = aligned16(id_base) && (Ki & 3) == 0;
+    a.exp_wide = Ke > 0 && aligned16(exp_base) && (Ke & 3) == 0;
     a.camera_distance = camera_distance; a.focal = focal; a.center = center; a.image_size = image_size; a.to_camera = to_camera ? 1 : 0;
     const size_t lds = ((size_t)K * a.V * 3 + GROUP * THREADS + GROUP * POSE) * sizeof(float);
 

@@ -205,10 +205,16 @@ __global__ void __launch_bounds__(256) resolve(Args a)
 
 inline size_t keys_per_image(int S) { return (size_t)((S + 3) / 4) * ((S + 1) / 2) * 8; }
 
-// the sizes every entry point accepts: B, M >= 1, 1 <= S <= 16384 (a pixel centre's numerator is exact in fp32), B M and B S S below 2^31
-inline bool sizes_ok(int B, int S, int M)
+// the sizes every entry point accepts: B, N, M >= 1, 1 <= S <= 16384 (a pixel centre's numerator is exact in fp32), C in 1 .. 4, B M and B S S
+// below 2^31.  With a name the first miss is that entry point's message; without one (r3d_raster_workspace_bytes, which knows neither N
+// nor C and passes 1 for both) nothing is said.
+static bool sizes_ok(const char* what, int B, int N, int M, int C, int S)
 {
-    return B >= 1 && M >= 1 && S >= 1 && S <= 16384 && (double)B * M < 2147483648.0 && (double)B * S * S < 2147483648.0;
+    auto no = [&](const char* fmt, auto... v) { if (what) set_error(fmt, what, v...); return false; };
+    if (S < 1 || S > 16384) return no("%s: image size S = %d is not in 1 .. 16384", S);
+    if (B < 1 || N < 1 || M < 1) return no("%s: bad argument (B = %d, N = %d, M = %d must be positive)", B, N, M);
+    if (C < 1 || C > 4) return no("%s: C = %d attribute channels, supported are 1 .. 4", C);
+    return below_2_31(what, "B M", (double)B * M, "faces (the packed 31-bit face index)") && below_2_31(what, "B S S", (double)B * S * S, "pixels");
 }
 
 inline size_t workspace_bytes(int B, int S, int M)
@@ -225,19 +231,11 @@ static int forward(const float* vertex, const float* feat, const int32_t* tri, i
 {
     if (!vertex || !tri || !mask || !depth) { set_error("raster_forward: NULL pointer (vertex, tri, mask and depth are required)"); return R3D_ERR_INVALID_ARG; }
     if ((feat == nullptr) != (image == nullptr)) { set_error("raster_forward: feat and image are given together or not at all"); return R3D_ERR_INVALID_ARG; }
-    if (S < 1 || S > 16384) { set_error("raster_forward: image size S = %d is not in 1 .. 16384", S); return R3D_ERR_INVALID_ARG; }
-    if (B < 1 || N < 1 || M < 1) { set_error("raster_forward: bad argument (B = %d, N = %d, M = %d must be positive)", B, N, M); return R3D_ERR_INVALID_ARG; }
-    if (feat && (C < 1 || C > 4)) { set_error("raster_forward: C = %d attribute channels, supported are 1 .. 4", C); return R3D_ERR_INVALID_ARG; }
-    if ((double)B * M >= 2147483648.0) { set_error("raster_forward: B M = %.0f faces do not fit the packed 31-bit face index", (double)B * M); return R3D_ERR_INVALID_ARG; }
-    if ((double)B * S * S >= 2147483648.0 || (double)B * N * 4.0 >= 2147483648.0)
-        { set_error("raster_forward: B S S pixels or B N vertices beyond 2^31 elements"); return R3D_ERR_INVALID_ARG; }
+    if (!sizes_ok("raster_forward", B, N, M, feat ? C : 1, S) || !below_2_31("raster_forward", "4 B N", 4.0 * B * N, "elements")) return R3D_ERR_INVALID_ARG;
     if (!(fov_deg > 0.0f && fov_deg < 180.0f)) { set_error("raster_forward: fov_deg = %g is not a finite angle in (0, 180)", (double)fov_deg); return R3D_ERR_INVALID_ARG; }
     if (!(znear == znear) || !(out_scale == out_scale) || !(out_shift == out_shift)) { set_error("raster_forward: znear or the output affine is NaN"); return R3D_ERR_INVALID_ARG; }
     if (large_box < 0 || stages < 0 || stages > STAGE_ALL) { set_error("raster_forward: bad test-hook argument"); return R3D_ERR_INVALID_ARG; }
-    if (!workspace) { set_error("raster_forward: NULL workspace"); return R3D_ERR_WORKSPACE; }
-    const size_t need = workspace_bytes(B, S, M);
-    if (workspace_bytes_given < need) { set_error("raster_forward: workspace of %zu bytes, %zu needed", workspace_bytes_given, need); return R3D_ERR_WORKSPACE; }
-    if (((uintptr_t)workspace & 7) != 0) { set_error("raster_forward: workspace is not 8-byte aligned"); return R3D_ERR_WORKSPACE; }
+    if (!workspace_ok("raster_forward", workspace, workspace_bytes_given, workspace_bytes(B, S, M), 8, "r3d_raster_workspace_bytes")) return R3D_ERR_WORKSPACE;
 
     Args a;
     a.vertex = vertex; a.feat = feat; a.tri = tri;
@@ -269,7 +267,7 @@ using namespace r3d;
 
 extern "C" size_t r3d_raster_workspace_bytes(int B, int S, int M)
 {
-    return raster::sizes_ok(B, S, M) ? raster::workspace_bytes(B, S, M) : 0;
+    return raster::sizes_ok(nullptr, B, 1, M, 1, S) ? raster::workspace_bytes(B, S, M) : 0;
 }
 
 extern "C" int r3d_raster_forward(const float* vertex, const float* feat, const int32_t* tri, int tri_batched, int B, int N, int M, int C, int S,

@@ -282,9 +282,14 @@ __global__ void __launch_bounds__(FILL_PIXELS * FILL_WAVES) fill(Args a)
     }
 }
 
-inline bool sizes_ok(int F, int H, int W)
+// the sizes every entry point accepts; with a name the first miss is that entry point's message, without one
+// (r3d_secc_blink_workspace_bytes, which knows no T and passes F) nothing is said
+static bool sizes_ok(const char* what, int T, int F, int H, int W)
 {
-    return F >= 1 && F <= MAX_FRAMES && H >= MIN_SIZE && H <= MAX_SIZE && W >= MIN_SIZE && W <= MAX_SIZE;
+    auto no = [&](const char* fmt, auto... v) { if (what) set_error(fmt, what, v...); return false; };
+    if (H < MIN_SIZE || H > MAX_SIZE || W < MIN_SIZE || W > MAX_SIZE) return no("%s: map size H = %d, W = %d is not in %d .. %d", H, W, MIN_SIZE, MAX_SIZE);
+    if (T < 1 || F < 1 || F > T || F > MAX_FRAMES) return no("%s: F = %d selected frames of T = %d (1 <= F <= T, F <= %d)", F, T, MAX_FRAMES);
+    return true;
 }
 
 inline size_t round256(size_t n) { return (n + 255) & ~(size_t)255; }
@@ -312,15 +317,10 @@ static int run(const float* secc, int T, int H, int W, const int32_t* frame_idx,
 {
     if (!secc || !out || !frame_idx || !percent || !status)
         { set_error("secc_blink: NULL pointer (secc, frame_idx, percent, out and status are required)"); return R3D_ERR_INVALID_ARG; }
-    if (H < MIN_SIZE || H > MAX_SIZE || W < MIN_SIZE || W > MAX_SIZE)
-        { set_error("secc_blink: map size H = %d, W = %d is not in %d .. %d", H, W, MIN_SIZE, MAX_SIZE); return R3D_ERR_INVALID_ARG; }
-    if (T < 1 || F < 1 || F > T || F > MAX_FRAMES)
-        { set_error("secc_blink: F = %d selected frames of T = %d (1 <= F <= T, F <= %d)", F, T, MAX_FRAMES); return R3D_ERR_INVALID_ARG; }
+    if (!sizes_ok("secc_blink", T, F, H, W)) return R3D_ERR_INVALID_ARG;
     if (stages < 0 || stages > STAGE_ALL) { set_error("secc_blink: bad test-hook argument"); return R3D_ERR_INVALID_ARG; }
-    if (!workspace) { set_error("secc_blink: NULL workspace"); return R3D_ERR_WORKSPACE; }
     const Layout l = layout(F, H, W);
-    if (workspace_bytes < l.total) { set_error("secc_blink: workspace of %zu bytes, %zu needed", workspace_bytes, l.total); return R3D_ERR_WORKSPACE; }
-    if (((uintptr_t)workspace & 7) != 0) { set_error("secc_blink: workspace is not 8-byte aligned"); return R3D_ERR_WORKSPACE; }
+    if (!workspace_ok("secc_blink", workspace, workspace_bytes, l.total, 8, "r3d_secc_blink_workspace_bytes")) return R3D_ERR_WORKSPACE;
 
     Args a;
     a.secc = secc; a.out = out; a.frame_idx = frame_idx; a.percent = percent; a.status = status;
@@ -348,7 +348,7 @@ using namespace r3d;
 
 extern "C" size_t r3d_secc_blink_workspace_bytes(int F, int H, int W)
 {
-    return blink::sizes_ok(F, H, W) ? blink::layout(F, H, W).total : 0;
+    return blink::sizes_ok(nullptr, F, F, H, W) ? blink::layout(F, H, W).total : 0;
 }
 
 extern "C" int r3d_secc_blink(const float* secc, int T, int H, int W, const int32_t* frame_idx, const double* percent, int F, float* out,

@@ -370,9 +370,9 @@ extern "C" int r3d_secc_linear(const float* x, int M, int K, const float* ln_g, 
                                const float* bias, int N, int gelu, const float* residual, float* y, r3d_stream_t stream)
 {
     if (!x || !w || !y || (!ln_g) != (!ln_b)) { set_error("secc_linear: NULL pointer"); return R3D_ERR_INVALID_ARG; }
-    if (M <= 0 || K <= 0 || N <= 0 || K > 4096 || N > 4096 || (residual && residual != y && (residual < y + (size_t)M * N && y < residual + (size_t)M * N)))
+    if (M <= 0 || K <= 0 || N <= 0 || K > 4096 || N > 4096 || (residual && residual != y && overlap(residual, (size_t)M * N, y, (size_t)M * N)))
         { set_error("secc_linear: bad argument"); return R3D_ERR_INVALID_ARG; }
-    if (x < y + (size_t)M * N && y < x + (size_t)M * K) { set_error("secc_linear: x and y overlap"); return R3D_ERR_INVALID_ARG; }
+    if (overlap(x, (size_t)M * K, y, (size_t)M * N)) { set_error("secc_linear: x and y overlap"); return R3D_ERR_INVALID_ARG; }
     GemmArgs g = {};
     g.a = x; g.M = M; g.K = K; g.lda = K; g.ln_g = ln_g; g.ln_b = ln_b; g.ln_eps = ln_eps;
     g.w = w; g.N = N; g.bias = bias; g.gelu = gelu ? 1 : 0; g.res = residual; g.y = y; g.ldy = N;
@@ -416,10 +416,9 @@ extern "C" int r3d_secc_head(const float* c1, int B, int H1, int W1, const float
     if (!c1 || !w1f || !f2 || !f3 || !f4 || !hconst || !bn_scale || !bn_shift || !out) { set_error("secc_head: NULL pointer"); return R3D_ERR_INVALID_ARG; }
     if (B <= 0 || H1 <= 0 || W1 <= 0 || H1 % 8 || W1 % 8) { set_error("secc_head: H1, W1 (= H/4, W/4) must be positive multiples of 8"); return R3D_ERR_INVALID_ARG; }
     const size_t hw = (size_t)H1 * W1, nout = (size_t)B * 256 * hw;
-    if (overlap(out, nout, c1, (size_t)B * hw * 32) || overlap(out, nout, f2, (size_t)B * hw / 4 * 256) ||
-        overlap(out, nout, f3, (size_t)B * hw / 16 * 256) || overlap(out, nout, f4, (size_t)B * hw / 64 * 256) ||
-        overlap(out, nout, w1f, 256 * 32) || overlap(out, nout, hconst, 256) || overlap(out, nout, bn_scale, 256) ||
-        overlap(out, nout, bn_shift, 256)) { set_error("secc_head: out overlaps an input"); return R3D_ERR_INVALID_ARG; }
+    const Span spans[] = {writes(out, nout), reads(c1, (size_t)B * hw * 32), reads(f2, (size_t)B * hw / 4 * 256), reads(f3, (size_t)B * hw / 16 * 256),
+                          reads(f4, (size_t)B * hw / 64 * 256), reads(w1f, 256 * 32), reads(hconst, 256), reads(bn_scale, 256), reads(bn_shift, 256)};
+    if (clash(spans)) { set_error("secc_head: out overlaps an input"); return R3D_ERR_INVALID_ARG; }
     GemmArgs g = {};
     g.a = c1; g.M = B * H1 * W1; g.K = 32; g.lda = 32; g.w = w1f; g.N = 256;
     g.f2 = f2; g.f3 = f3; g.f4 = f4; g.hconst = hconst; g.bn_s = bn_scale; g.bn_t = bn_shift; g.H1 = H1; g.W1 = W1; g.y = out;

@@ -390,35 +390,21 @@ __global__ void __launch_bounds__(THREADS) to_planes(const uint8_t* __restrict__
 }
 
 // ---- the host side: every check runs before any HIP call --------------------------------------------------------------------------------
-struct Span { const void* p; double n; bool output; };
-
-static bool spans_clash(const Span* s, int count)
-{
-    for (int i = 0; i < count; ++i)
-        for (int j = i + 1; j < count; ++j) {
-            if (!s[i].p || !s[j].p || !(s[i].output || s[j].output)) continue;
-            const double a = (double)(uintptr_t)s[i].p, b = (double)(uintptr_t)s[j].p;          // (sizes below 2^33: exact)
-            if (a < b + s[j].n && b < a + s[i].n) return true;
-        }
-    return false;
-}
-
+// the sizes every entry point accepts (min_side: 3 where the blur reflects 2 pixels); with a name the first miss is that entry point's
+// message, without one (r3d_source_workspace_bytes) nothing is said
 static bool sizes_ok(const char* what, int B, int H, int W, int min_side)
 {
-    if (B < 1 || H < 1 || W < 1) { set_error("%s: B = %d, H = %d, W = %d: every size must be positive", what, B, H, W); return false; }
-    if (H < min_side || W < min_side) { set_error("%s: H = %d, W = %d: a side below %d (the blur reflects 2 pixels)", what, H, W, min_side); return false; }
-    if (B > MAX_FRAMES) { set_error("%s: B = %d frames, above %d (a grid dimension)", what, B, MAX_FRAMES); return false; }
-    if (H > MAX_SIDE || W > MAX_SIDE) { set_error("%s: H = %d, W = %d: a side above %d (the key holds 11 bits of a row and of a column)", what, H, W, MAX_SIDE); return false; }
-    const double bytes = 4.0 * B * (double)H * (double)W;
-    if (bytes >= 2147483648.0) { set_error("%s: 4 B H W = %.0f bytes, the limit per call is 2^31", what, bytes); return false; }
-    return true;
+    auto no = [&](const char* fmt, auto... v) { if (what) set_error(fmt, what, v...); return false; };
+    if (B < 1 || H < 1 || W < 1) return no("%s: B = %d, H = %d, W = %d: every size must be positive", B, H, W);
+    if (H < min_side || W < min_side) return no("%s: H = %d, W = %d: a side below %d (the blur reflects 2 pixels)", H, W, min_side);
+    if (B > MAX_FRAMES) return no("%s: B = %d frames, above %d (a grid dimension)", B, MAX_FRAMES);
+    if (H > MAX_SIDE || W > MAX_SIDE) return no("%s: H = %d, W = %d: a side above %d (the key holds 11 bits of a row and of a column)", H, W, MAX_SIDE);
+    return below_2_31(what, "4 B H W", 4.0 * B * (double)H * (double)W, "bytes");
 }
 
 static bool workspace_ok(const char* what, const void* ws, size_t ws_bytes, const Layout& L)
 {
-    if ((uintptr_t)ws & 15) { set_error("%s: the workspace is not 16-byte aligned", what); return false; }
-    if (ws_bytes < L.total) { set_error("%s: the workspace holds %zu bytes, %zu are needed (r3d_source_workspace_bytes)", what, ws_bytes, L.total); return false; }
-    return true;
+    return r3d::workspace_ok(what, ws, ws_bytes, L.total, 16, "r3d_source_workspace_bytes", true);          // (alignment first, then the size)
 }
 
 static unsigned blocks_for(size_t lanes) { return (unsigned)((lanes + THREADS - 1) / THREADS); }
@@ -438,8 +424,7 @@ using namespace r3d;
 
 extern "C" size_t r3d_source_workspace_bytes(int B, int H, int W)
 {
-    if (B < 1 || H < 1 || W < 1 || B > source::MAX_FRAMES || H > source::MAX_SIDE || W > source::MAX_SIDE || 4.0 * B * (double)H * (double)W >= 2147483648.0) return 0;
-    return source::Layout(B, H, W).total;
+    return source::sizes_ok(nullptr, B, H, W, 1) ? source::Layout(B, H, W).total : 0;
 }
 
 extern "C" int r3d_source_nearest(const uint8_t* mask, int B, int H, int W, int32_t* d2, int32_t* index, int32_t* status, void* workspace,
@@ -448,13 +433,12 @@ extern "C" int r3d_source_nearest(const uint8_t* mask, int B, int H, int W, int3
     const char* what = "source_nearest";
     if (!mask || !status || !workspace || (!d2 && !index)) { set_error("%s: NULL pointer", what); return R3D_ERR_INVALID_ARG; }
     if (!source::sizes_ok(what, B, H, W, 1)) return R3D_ERR_INVALID_ARG;
-    if (((uintptr_t)d2 | (uintptr_t)index | (uintptr_t)status) & 3) { set_error("%s: d2, index or the status is not 4-byte aligned", what); return R3D_ERR_INVALID_ARG; }
+    if (!aligned(d2, 4) || !aligned(index, 4) || !aligned(status, 4)) { set_error("%s: d2, index or the status is not 4-byte aligned", what); return R3D_ERR_INVALID_ARG; }
     const source::Layout L(B, H, W);
     if (!source::workspace_ok(what, workspace, workspace_bytes, L)) return R3D_ERR_INVALID_ARG;
-    const double n = (double)B * H * W;
-    const source::Span spans[5] = {{mask, n, false}, {d2, 4 * n, true}, {index, 4 * n, true}, {status, 4.0 * R3D_SOURCE_STATUS_WORDS, true},
-                                   {workspace, (double)L.total, true}};
-    if (source::spans_clash(spans, 5)) { set_error("%s: an output, the status or the workspace overlaps another array", what); return R3D_ERR_INVALID_ARG; }
+    const size_t n = (size_t)B * H * W;
+    const Span spans[] = {reads(mask, n), writes(d2, n), writes(index, n), writes(status, R3D_SOURCE_STATUS_WORDS), {workspace, L.total, true}};
+    if (clash(spans)) { set_error("%s: an output, the status or the workspace overlaps another array", what); return R3D_ERR_INVALID_ARG; }
     ProfScope ps(R3D_PROF_LAYOUT, (hipStream_t)stream);
     hipStream_t st = (hipStream_t)stream;
     uint8_t* ws = static_cast<uint8_t*>(workspace);
@@ -469,13 +453,12 @@ extern "C" int r3d_source_background(const uint8_t* img, const uint8_t* bg, int 
     const char* what = "source_background";
     if (!img || !bg || !out || !status || !workspace) { set_error("%s: NULL pointer", what); return R3D_ERR_INVALID_ARG; }
     if (!source::sizes_ok(what, B, H, W, 1)) return R3D_ERR_INVALID_ARG;
-    if (((uintptr_t)out | (uintptr_t)status) & 3) { set_error("%s: out or the status is not 4-byte aligned", what); return R3D_ERR_INVALID_ARG; }
+    if (!aligned(out, 4) || !aligned(status, 4)) { set_error("%s: out or the status is not 4-byte aligned", what); return R3D_ERR_INVALID_ARG; }
     const source::Layout L(B, H, W);
     if (!source::workspace_ok(what, workspace, workspace_bytes, L)) return R3D_ERR_INVALID_ARG;
-    const double n = (double)H * W;
-    const source::Span spans[5] = {{img, 3 * n * B, false}, {bg, n * B, false}, {out, 3 * n, true}, {status, 4.0 * R3D_SOURCE_STATUS_WORDS, true},
-                                   {workspace, (double)L.total, true}};
-    if (source::spans_clash(spans, 5)) { set_error("%s: an output, the status or the workspace overlaps another array", what); return R3D_ERR_INVALID_ARG; }
+    const size_t n = (size_t)H * W;
+    const Span spans[] = {reads(img, 3 * n * B), reads(bg, n * B), writes(out, 3 * n), writes(status, R3D_SOURCE_STATUS_WORDS), {workspace, L.total, true}};
+    if (clash(spans)) { set_error("%s: an output, the status or the workspace overlaps another array", what); return R3D_ERR_INVALID_ARG; }
     ProfScope ps(R3D_PROF_LAYOUT, (hipStream_t)stream);
     hipStream_t st = (hipStream_t)stream;
     uint8_t* ws = static_cast<uint8_t*>(workspace);
@@ -507,15 +490,15 @@ extern "C" int r3d_source_torso(const uint8_t* img, const uint8_t* segmap, int H
     for (int k = 0; k < source::NECK_L; ++k)
         if (!(darken[k] >= 0.0 && darken[k] <= 1.0)) { set_error("%s: darken[%d] = %g outside 0 .. 1", what, k, darken[k]); return R3D_ERR_INVALID_ARG; }
     if (sum > 256) { set_error("%s: the blur weights sum to %d, above 256 (the horizontal sum has 16 bits)", what, sum); return R3D_ERR_INVALID_ARG; }
-    if (((uintptr_t)torso_img | (uintptr_t)torso_mask | (uintptr_t)with_bg_img | (uintptr_t)with_bg_mask) & 3) {
+    if (!aligned(torso_img, 4) || !aligned(torso_mask, 4) || !aligned(with_bg_img, 4) || !aligned(with_bg_mask, 4)) {
         set_error("%s: an output is not 4-byte aligned", what); return R3D_ERR_INVALID_ARG;
     }
     const source::Layout L(1, H, W);
     if (!source::workspace_ok(what, workspace, workspace_bytes, L)) return R3D_ERR_INVALID_ARG;
-    const double n = (double)H * W;
-    const source::Span spans[7] = {{img, 3 * n, false}, {segmap, 6 * n, false}, {torso_img, 3 * n, true}, {torso_mask, n, true}, {with_bg_img, 3 * n, true},
-                                   {with_bg_mask, n, true}, {workspace, (double)L.total, true}};
-    if (source::spans_clash(spans, 7)) { set_error("%s: an output or the workspace overlaps another array", what); return R3D_ERR_INVALID_ARG; }
+    const size_t n = (size_t)H * W;
+    const Span spans[] = {reads(img, 3 * n), reads(segmap, 6 * n), writes(torso_img, 3 * n), writes(torso_mask, n), writes(with_bg_img, 3 * n),
+                          writes(with_bg_mask, n), {workspace, L.total, true}};
+    if (clash(spans)) { set_error("%s: an output or the workspace overlaps another array", what); return R3D_ERR_INVALID_ARG; }
     ProfScope ps(R3D_PROF_LAYOUT, (hipStream_t)stream);
     hipStream_t st = (hipStream_t)stream;
     uint8_t* ws = static_cast<uint8_t*>(workspace);
@@ -538,10 +521,10 @@ extern "C" int r3d_source_select(const uint8_t* img, const uint8_t* segmap, int 
     if (!img || !segmap || !out) { set_error("%s: NULL pointer", what); return R3D_ERR_INVALID_ARG; }
     if (!source::sizes_ok(what, 1, H, W, 1)) return R3D_ERR_INVALID_ARG;
     if (classes < 1 || classes > 63) { set_error("%s: classes = %d outside 1 .. 63", what, classes); return R3D_ERR_INVALID_ARG; }
-    if (((uintptr_t)out | (uintptr_t)mask) & 3) { set_error("%s: an output is not 4-byte aligned", what); return R3D_ERR_INVALID_ARG; }
-    const double n = (double)H * W;
-    const source::Span spans[4] = {{img, 3 * n, false}, {segmap, 6 * n, false}, {out, 3 * n, true}, {mask, n, true}};
-    if (source::spans_clash(spans, 4)) { set_error("%s: an output overlaps another array", what); return R3D_ERR_INVALID_ARG; }
+    if (!aligned(out, 4) || !aligned(mask, 4)) { set_error("%s: an output is not 4-byte aligned", what); return R3D_ERR_INVALID_ARG; }
+    const size_t n = (size_t)H * W;
+    const Span spans[] = {reads(img, 3 * n), reads(segmap, 6 * n), writes(out, 3 * n), writes(mask, n)};
+    if (clash(spans)) { set_error("%s: an output overlaps another array", what); return R3D_ERR_INVALID_ARG; }
     ProfScope ps(R3D_PROF_LAYOUT, (hipStream_t)stream);
     const int N = H * W;
     hipLaunchKernelGGL(source::select, dim3(source::blocks_for(((size_t)N + 3) / 4)), dim3(source::THREADS), 0, (hipStream_t)stream, img, segmap, classes, N, out,
@@ -555,10 +538,10 @@ extern "C" int r3d_source_to_planes(const uint8_t* img, const uint8_t* segmap, i
     if (!img || !out) { set_error("%s: NULL pointer", what); return R3D_ERR_INVALID_ARG; }
     if (!source::sizes_ok(what, 1, H, W, 1)) return R3D_ERR_INVALID_ARG;
     if (segmap && (classes < 1 || classes > 63)) { set_error("%s: classes = %d outside 1 .. 63", what, classes); return R3D_ERR_INVALID_ARG; }
-    if ((uintptr_t)out & 3) { set_error("%s: out is not 4-byte aligned", what); return R3D_ERR_INVALID_ARG; }
-    const double n = (double)H * W;
-    const source::Span spans[3] = {{img, 3 * n, false}, {segmap, 6 * n, false}, {out, 12 * n, true}};
-    if (source::spans_clash(spans, 3)) { set_error("%s: the output overlaps an input", what); return R3D_ERR_INVALID_ARG; }
+    if (!aligned(out, 4)) { set_error("%s: out is not 4-byte aligned", what); return R3D_ERR_INVALID_ARG; }
+    const size_t n = (size_t)H * W;
+    const Span spans[] = {reads(img, 3 * n), reads(segmap, 6 * n), writes(out, 3 * n)};
+    if (clash(spans)) { set_error("%s: the output overlaps an input", what); return R3D_ERR_INVALID_ARG; }
     ProfScope ps(R3D_PROF_LAYOUT, (hipStream_t)stream);
     const int N = H * W;
     hipLaunchKernelGGL(source::to_planes, dim3(source::blocks_for(((size_t)N + 3) / 4)), dim3(source::THREADS), 0, (hipStream_t)stream, img, segmap, classes, N,

@@ -177,13 +177,11 @@ extern "C" int r3d_torso_split_bf16x3(const float* x, size_t n, uint16_t* h, uin
 {
     if (!x || !h || !m || !l) { set_error("torso_split_bf16x3: NULL pointer"); return R3D_ERR_INVALID_ARG; }
     if (n == 0 || n > 2147483647u) { set_error("torso_split_bf16x3: n is not in 1 .. 2^31 - 1"); return R3D_ERR_INVALID_ARG; }
-    const char *xb = (const char*)x, *xe = xb + 4 * n;
-    uint16_t* const out[3] = {h, m, l};
-    for (int i = 0; i < 3; ++i) {
-        const char *ob = (const char*)out[i], *oe = ob + 2 * n;
-        if (ob < xe && xb < oe) { set_error("torso_split_bf16x3: an output overlaps x"); return R3D_ERR_INVALID_ARG; }
-        for (int j = 0; j < i; ++j)
-            if (out[i] < out[j] + n && out[j] < out[i] + n) { set_error("torso_split_bf16x3: two outputs overlap"); return R3D_ERR_INVALID_ARG; }
+    const Span spans[4] = {reads(x, n), writes(h, n), writes(m, n), writes(l, n)};
+    for (int i = 1; i < 4; ++i) {          // every output against x, then against the outputs before it
+        const Span with_x[2] = {spans[0], spans[i]};
+        if (clash(with_x)) { set_error("torso_split_bf16x3: an output overlaps x"); return R3D_ERR_INVALID_ARG; }
+        if (clash(spans + 1, i)) { set_error("torso_split_bf16x3: two outputs overlap"); return R3D_ERR_INVALID_ARG; }
     }
     hipLaunchKernelGGL(torso_bf3::torso_split, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, n, h, m, l);
     return check_launch("torso_split_bf16x3");

@@ -199,16 +199,14 @@ extern "C" int r3d_torso_mask_volume(const float* feats_cl, int N, int D, int H,
     const size_t vox = (size_t)N * D * H * W, nf = vox * C, nm = vox * (C + 2), nseg = (size_t)N * Cs * Hs * Ws;
     if (masked_cl != feats_cl && overlap(masked_cl, nf, feats_cl, nf))
         { set_error("torso_mask_volume: masked_cl overlaps feats_cl without being feats_cl"); return R3D_ERR_INVALID_ARG; }
-    if (overlap(masked_cl, nf, segmap, nseg) || overlap(motion_cl, nm, segmap, nseg) || overlap(motion_cl, nm, feats_cl, nf) ||
-        overlap(motion_cl, nm, masked_cl, nf))
-        { set_error("torso_mask_volume: an output overlaps the segmap, feats_cl or the other output"); return R3D_ERR_INVALID_ARG; }
+    const Span spans[] = {reads(segmap, nseg), writes(masked_cl, nf), writes(motion_cl, nm)};          // (feats_cl: masked_cl may be it)
+    if (clash(spans) || overlap(motion_cl, nm, feats_cl, nf)) { set_error("torso_mask_volume: an output overlaps the segmap, feats_cl or the other output"); return R3D_ERR_INVALID_ARG; }
     const int tiles_x = (W + TW - 1) / TW, tiles = tiles_x * ((H + TH - 1) / TH);
     // a block resizes and dilates its tile once per run of depth slices: runs of D / 8, so that the product shape (64 x 64 x 16) still
     // gives every compute unit two blocks
     const int dchunk = (D + 7) / 8, zc = (D + dchunk - 1) / dchunk;
     MaskArgs a = {feats_cl, N, D, H, W, C, segmap, Cs, Hs, Ws, c0, c1, pad, mul_mask ? 1 : 0, dchunk, tiles_x, masked_cl, motion_cl};
-    auto aligned = [](const void* p, uintptr_t m) { return ((uintptr_t)p & m) == 0; };
-    const bool vec = C % 4 == 0 && aligned(feats_cl, 15) && aligned(masked_cl, 15) && aligned(motion_cl, 7);
+    const bool vec = C % 4 == 0 && aligned(feats_cl, 16) && aligned(masked_cl, 16) && aligned(motion_cl, 8);
     const dim3 grid((unsigned)tiles, (unsigned)zc, (unsigned)N);
     if (vec) hipLaunchKernelGGL(mask_volume<true>, grid, dim3(256), lds, (hipStream_t)stream, a);
     else hipLaunchKernelGGL(mask_volume<false>, grid, dim3(256), lds, (hipStream_t)stream, a);

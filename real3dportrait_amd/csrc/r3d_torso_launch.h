@@ -81,17 +81,15 @@ inline int check_conv(const char* what, const ConvCall& c)
         { set_error("%s: more than 2^31 - 1 output positions", what); return R3D_ERR_INVALID_ARG; }
     const size_t nin = (size_t)c.B * c.D * c.Hs * c.Ws * c.Cin, nw = (size_t)c.Cout * c.kd() * c.ksize * c.ksize * c.Cin;
     const size_t rows = (size_t)c.B * Do * (H >> c.pool) * (W >> c.pool), ny = rows * (size_t)(c.y ? c.ycs : 0), nyn = rows * c.Cout;
-    for (int o = 0; o < 2; ++o) {
+    for (int o = 0; o < 2; ++o) {          // (an output, a bias or a prologue that is absent takes no part)
         const float* p = o ? c.yn : c.y;
         const size_t np = o ? nyn : ny;
-        if (!p) continue;
-        if (overlap(p, np, c.x, nin) || overlap(p, np, c.w, nw) || (c.bias && overlap(p, np, c.bias, c.Cout)) ||
-            (c.ps && (overlap(p, np, c.ps, c.Cin) || overlap(p, np, c.pt, c.Cin))))
-            { set_error("%s: an output overlaps x, w, bias or the prologue", what); return R3D_ERR_INVALID_ARG; }
-        if (c.res && c.res != c.y && overlap(p, np, c.res, nyn))
+        const Span spans[] = {writes(p, np), reads(c.x, nin), reads(c.w, nw), reads(c.bias, c.Cout), reads(c.ps, c.Cin), reads(c.pt, c.Cin)};
+        if (clash(spans)) { set_error("%s: an output overlaps x, w, bias or the prologue", what); return R3D_ERR_INVALID_ARG; }
+        if (c.res != c.y && overlap(p, np, c.res, nyn))
             { set_error("%s: an output overlaps the residual without y being the residual", what); return R3D_ERR_INVALID_ARG; }
     }
-    if (c.y && c.yn && overlap(c.y, ny, c.yn, nyn))
+    if (overlap(c.y, ny, c.yn, nyn))
         { set_error("%s: y and %s overlap", what, c.volume ? "y_ncdhw" : "y_nchw"); return R3D_ERR_INVALID_ARG; }
     return R3D_OK;
 }

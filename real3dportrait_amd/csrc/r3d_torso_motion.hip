@@ -225,15 +225,12 @@ extern "C" int r3d_torso_motion_input(const float* fs_cl, int N, int C, int D, i
         { set_error("torso_motion_input: bad argument (1 <= C <= 4096, 5 (K + 1) <= inp_channels <= fuse_cstride, fewer than 2^31 elements)");
           return R3D_ERR_INVALID_ARG; }
     const size_t vox = (size_t)N * D * H * W, nfs = vox * C, ninp = vox * inp_channels, nfuse = fuse ? vox * fuse_cstride : 0;
-    for (int o = 0; o < 2; ++o) {
-        const float* p = o ? fuse : inp;
-        const size_t np = o ? nfuse : ninp;
-        if (!p) continue;
-        if (overlap(p, np, fs_cl, nfs) || overlap(p, np, compress_w, (size_t)4 * C) || overlap(p, np, compress_b, 4) ||
-            overlap(p, np, kp_s, (size_t)N * K * 3) || overlap(p, np, kp_d, (size_t)N * K * 3) || overlap(p, np, J, (size_t)N * 9))
-            { set_error("torso_motion_input: an output overlaps an input"); return R3D_ERR_INVALID_ARG; }
-    }
-    if (fuse && overlap(inp, ninp, fuse, nfuse)) { set_error("torso_motion_input: inp and fuse overlap"); return R3D_ERR_INVALID_ARG; }
+    Span spans[] = {writes(inp, ninp), reads(fs_cl, nfs), reads(compress_w, (size_t)4 * C), reads(compress_b, 4), reads(kp_s, (size_t)N * K * 3),
+                    reads(kp_d, (size_t)N * K * 3), reads(J, (size_t)N * 9)};
+    const bool inp_clashes = clash(spans);
+    spans[0] = writes(fuse, nfuse);          // the other output against the same inputs (absent: no part)
+    if (inp_clashes || clash(spans)) { set_error("torso_motion_input: an output overlaps an input"); return R3D_ERR_INVALID_ARG; }
+    if (overlap(inp, ninp, fuse, nfuse)) { set_error("torso_motion_input: inp and fuse overlap"); return R3D_ERR_INVALID_ARG; }
     MotionArgs a = {};
     a.fs = fs_cl; a.N = N; a.C = C; a.D = D; a.H = H; a.W = W; a.cw = compress_w; a.cb = compress_b; a.kp_s = kp_s; a.kp_d = kp_d; a.J = J;
     a.K = K; a.inp = inp; a.cpad = inp_channels; a.fuse = fuse; a.fcs = fuse_cstride;
@@ -248,9 +245,9 @@ extern "C" int r3d_torso_motion_deform(const float* mask, int N, int D, int H, i
     if (!mask || !out) { set_error("torso_motion_deform: NULL pointer"); return R3D_ERR_INVALID_ARG; }
     if (int rc = motion_common("torso_motion_deform", kp_s, kp_d, J, N, D, H, W, K)) return rc;
     const size_t vox = (size_t)N * D * H * W;
-    if (overlap(out, vox * 3, mask, vox * (K + 1)) || overlap(out, vox * 3, kp_s, (size_t)N * K * 3) ||
-        overlap(out, vox * 3, kp_d, (size_t)N * K * 3) || overlap(out, vox * 3, J, (size_t)N * 9))
-        { set_error("torso_motion_deform: out overlaps an input"); return R3D_ERR_INVALID_ARG; }
+    const Span spans[] = {writes(out, vox * 3), reads(mask, vox * (K + 1)), reads(kp_s, (size_t)N * K * 3), reads(kp_d, (size_t)N * K * 3),
+                          reads(J, (size_t)N * 9)};
+    if (clash(spans)) { set_error("torso_motion_deform: out overlaps an input"); return R3D_ERR_INVALID_ARG; }
     MotionArgs a = {};
     a.N = N; a.D = D; a.H = H; a.W = W; a.kp_s = kp_s; a.kp_d = kp_d; a.J = J; a.K = K; a.mask = mask; a.out = out;
     hipLaunchKernelGGL(motion_deform, dim3((unsigned)((vox + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);

@@ -207,12 +207,6 @@ __global__ void __launch_bounds__(THREADS) compose_kernel(const ComposeArgs a)
     }
 }
 
-static bool bytes_overlap(const void* a, double na, const void* b, double nb)
-{
-    const double pa = (double)(uintptr_t)a, pb = (double)(uintptr_t)b;          // (sizes below 2^31: exact)
-    return pa < pb + nb && pb < pa + na;
-}
-
 }  // namespace video
 }  // namespace r3d
 
@@ -223,9 +217,10 @@ extern "C" int r3d_video_depth_range(const float* depth, size_t count, int reset
     const char* what = "video_depth_range";
     if (!depth || !state) { set_error("%s: NULL pointer", what); return R3D_ERR_INVALID_ARG; }
     if (count < 1) { set_error("%s: count = 0 must be positive", what); return R3D_ERR_INVALID_ARG; }
-    if ((double)count * 4.0 >= 2147483648.0) { set_error("%s: 4 count = %.0f bytes, the limit per call is 2^31", what, (double)count * 4.0); return R3D_ERR_INVALID_ARG; }
-    if ((uintptr_t)state & 3) { set_error("%s: the state is not 4-byte aligned", what); return R3D_ERR_INVALID_ARG; }
-    if (video::bytes_overlap(state, 4.0 * R3D_VIDEO_STATE_WORDS, depth, (double)count * 4.0)) { set_error("%s: the state overlaps the input", what); return R3D_ERR_INVALID_ARG; }
+    if (!below_2_31(what, "4 count", (double)count * 4.0, "bytes")) return R3D_ERR_INVALID_ARG;
+    if (!aligned(state, 4)) { set_error("%s: the state is not 4-byte aligned", what); return R3D_ERR_INVALID_ARG; }
+    const Span spans[] = {writes(state, R3D_VIDEO_STATE_WORDS), reads(depth, count)};
+    if (clash(spans)) { set_error("%s: the state overlaps the input", what); return R3D_ERR_INVALID_ARG; }
     ProfScope ps(R3D_PROF_LAYOUT, (hipStream_t)stream);
     const size_t per_block = (size_t)video::THREADS * video::RANGE_PER_THREAD;
     size_t blocks = (count + per_block - 1) / per_block;
@@ -266,18 +261,17 @@ extern "C" int r3d_video_compose_debug(const float* ref, const float* secc, int 
     const double bytes[5] = {3.0 * frame, 12.0 * n * hs * (double)ws, 12.0 * n * hr * (double)wr, 4.0 * n * hd * (double)wd, 3.0 * n * frame};
     const double out_bytes = 15.0 * n * (double)H * (double)W;
     const void* srcs[5] = {ref, secc, raw, depth, image};
-    if (out_bytes >= 2147483648.0) { set_error("%s: 15 n H W = %.0f bytes of output, the limit per call is 2^31", what, out_bytes); return R3D_ERR_INVALID_ARG; }
+    const char* const panel[5] = {"panel 0, 12 H W", "panel 1, 12 n hs ws", "panel 2, 12 n hr wr", "panel 3, 4 n hd wd", "panel 4, 12 n H W"};
+    if (!below_2_31(what, "15 n H W", out_bytes, "bytes of output")) return R3D_ERR_INVALID_ARG;
     for (int p = 0; p < 5; ++p)
-        if (on[p] && bytes[p] >= 2147483648.0) { set_error("%s: panel %d reads %.0f bytes, the limit per call is 2^31", what, p, bytes[p]); return R3D_ERR_INVALID_ARG; }
-    if ((uintptr_t)out & 3) { set_error("%s: out is not 4-byte aligned", what); return R3D_ERR_INVALID_ARG; }
-    if (on[3] && ((uintptr_t)state & 3)) { set_error("%s: the state is not 4-byte aligned", what); return R3D_ERR_INVALID_ARG; }
+        if (on[p] && !below_2_31(what, panel[p], bytes[p], "bytes")) return R3D_ERR_INVALID_ARG;
+    if (!aligned(out, 4)) { set_error("%s: out is not 4-byte aligned", what); return R3D_ERR_INVALID_ARG; }
+    if (on[3] && !aligned(state, 4)) { set_error("%s: the state is not 4-byte aligned", what); return R3D_ERR_INVALID_ARG; }
+    Span spans[7] = {writes(out, (size_t)out_bytes), reads(state, on[3] ? R3D_VIDEO_STATE_WORDS : 0)};          // (a panel that is off: no bytes)
+    for (int p = 0; p < 5; ++p) spans[2 + p] = Span{srcs[p], on[p] ? (size_t)bytes[p] : 0, false};
+    if (clash(spans)) { set_error("%s: the output overlaps an input", what); return R3D_ERR_INVALID_ARG; }
     bool vec = W % 16 == 0 && aligned16(out);
-    for (int p = 0; p < 5; ++p) {
-        if (!on[p]) continue;
-        if (video::bytes_overlap(out, out_bytes, srcs[p], bytes[p])) { set_error("%s: the output overlaps an input", what); return R3D_ERR_INVALID_ARG; }
-        vec = vec && aligned16(srcs[p]);
-    }
-    if (on[3] && video::bytes_overlap(out, out_bytes, state, 4.0 * R3D_VIDEO_STATE_WORDS)) { set_error("%s: the output overlaps an input", what); return R3D_ERR_INVALID_ARG; }
+    for (int p = 0; p < 5; ++p) vec = vec && (!on[p] || aligned16(srcs[p]));
     video::ComposeArgs a;
     a.ref = ref; a.secc = secc; a.raw = raw; a.depth = depth; a.image = image; a.state = reinterpret_cast<const int*>(state); a.out = out;
     a.hs = hs; a.ws = ws; a.hr = hr; a.wr = wr; a.hd = hd; a.wd = wd; a.n = n; a.H = H; a.W = W; a.panels = panels;

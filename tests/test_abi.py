@@ -7,10 +7,17 @@ import re
 from conftest import ROOT
 
 
+HEADERS = {"r3d_hip.h": 74, "r3d_hip_clip.h": 3, "r3d_hip_video.h": 2, "r3d_hip_source.h": 6}          # the header and the three it includes: declarations
+
+
+def header_source(header):
+    """include/<header> without its comments."""
+    src = open(os.path.join(ROOT, "include", header)).read()
+    return re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", src, flags=re.S))
+
+
 def declared_symbols():
-    src = open(os.path.join(ROOT, "include", "r3d_hip.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return sorted(set(re.findall(r"\b(r3d_[a-z0-9_]+)\s*\(", src)))
+    return sorted(set(s for h in HEADERS for s in re.findall(r"\b(r3d_[a-z0-9_]+)\s*\(", header_source(h))))
 
 
 def test_every_declared_symbol_is_exported_and_bound():
@@ -24,15 +31,13 @@ def test_every_declared_symbol_is_exported_and_bound():
     assert set(_lib.SIGNATURES) == set(syms)
 
 
-def header_declarations():
-    """{name: (return type, [parameter type, ...])} of every function include/r3d_hip.h declares: comments stripped, `const` dropped, no
-    blanks around a star ("const float* const* ext_bounds" -> "float**", "unsigned long long* cycles" -> "unsigned long long*")."""
-    src = open(os.path.join(ROOT, "include", "r3d_hip.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    src = re.sub(r"//[^\n]*", "", src)
+def header_declarations(header="r3d_hip.h"):
+    """{name: (return type, [parameter type, ...])} of every function include/<header> declares itself (not the headers it includes):
+    comments stripped, `const` dropped, no blanks around a star ("const float* const* ext_bounds" -> "float**",
+    "unsigned long long* cycles" -> "unsigned long long*")."""
     norm = lambda t: re.sub(r"\s*\*\s*", "*", " ".join(re.sub(r"\bconst\b", " ", t).split()))
     decls = {}
-    for ret, name, params in re.findall(r"^\s*([A-Za-z_][\w \*]*?)\s*\b(r3d_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", src, flags=re.M):
+    for ret, name, params in re.findall(r"^\s*([A-Za-z_][\w \*]*?)\s*\b(r3d_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", header_source(header), flags=re.M):
         assert name not in decls, name
         types = []
         for p in (params.split(",") if params.strip() not in ("", "void") else []):
@@ -69,13 +74,21 @@ def entry_matches(entry, ctype, _lib):
 
 
 def test_table_mirrors_every_header_declaration():
-    """Every declaration of include/r3d_hip.h is bound with the same parameter count, the exact ctypes type of every scalar, the header's
-    element type of every pointer (device pointers by their marker, host pointers by their ctypes.POINTER) and the same return type;
-    and load() derives each function's argtypes from that line."""
+    """Every declaration of include/r3d_hip.h and of the three companion headers it includes (each exactly once) is bound in the one table
+    with the same parameter count, the exact ctypes type of every scalar, the header's element type of every pointer (device pointers by
+    their marker, host pointers by their ctypes.POINTER) and the same return type; the stream is the last parameter and no other (and
+    every status-returning entry point of a companion header has one); and load() derives each function's argtypes from that line."""
     from real3dportrait_amd import _lib
     lib = _lib.load()
-    decls = header_declarations()
-    assert len(decls) == 74 and set(decls) == set(_lib.SIGNATURES) == set(declared_symbols())
+    per_header = {h: header_declarations(h) for h in HEADERS}
+    assert {h: len(d) for h, d in per_header.items()} == HEADERS
+    main = open(os.path.join(ROOT, "include", "r3d_hip.h")).read()
+    decls = {}
+    for h, d in per_header.items():
+        assert h == "r3d_hip.h" or main.count('#include "%s"' % h) == 1, h
+        assert not set(d) & (set(decls) | set(_lib.OPTIONAL_SIGNATURES)), h
+        decls.update(d)
+    assert set(decls) == set(_lib.SIGNATURES) == set(declared_symbols())
     for name, (ret, types) in decls.items():
         res, entries = _lib.SIGNATURES[name]
         assert res is C_RETURNS[ret], (name, ret, res)
@@ -83,6 +96,8 @@ def test_table_mirrors_every_header_declaration():
         for i, (e, t) in enumerate(zip(entries, types)):
             assert entry_matches(e, t, _lib), "%s: parameter %d is %s in the header, %r in the table" % (name, i, t, e)
         assert all(isinstance(e, _lib.Stream) is (i == len(entries) - 1) for i, e in enumerate(entries) if isinstance(e, _lib.Stream)), name
+        if name not in per_header["r3d_hip.h"] and res is ctypes.c_int:
+            assert isinstance(entries[-1], _lib.Stream), name
         fn = getattr(lib, name)
         assert fn.restype is res and list(fn.argtypes) == [getattr(e, "ctype", e) for e in entries], name
     assert _lib.F.ctype is ctypes.c_void_p and _lib.S.ctype is ctypes.c_void_p

@@ -12,14 +12,13 @@ bounded by n max|x|, the factor 1 / n, its own rounding and the product's."""
 import ctypes
 import glob
 import os
-import re
 import types
 
 import numpy as np
 import pytest
 import torch
 
-from conftest import GOLDEN, ROOT, load_golden
+from conftest import GOLDEN, load_golden
 import clip_conditions_ref64 as C64
 
 CAMERA_CASES = ("a_t1_zero", "b_t2", "c_t3_static", "d_t9_k7", "d_t9_k3", "d_t9_k1", "e_t41", "f_t70_smooth", "g_t12_k1_axes")
@@ -43,41 +42,17 @@ def test_every_fixture_is_listed_and_small():
     assert all(os.path.getsize(os.path.join(GOLDEN, n + ".npz")) <= 524288 for n in names)
 
 
-def companion_declarations():
-    """{name: (return type, [parameter type, ...])} of include/r3d_hip_clip.h, normalised as tests/test_abi.py normalises r3d_hip.h."""
-    src = open(os.path.join(ROOT, "include", "r3d_hip_clip.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    norm = lambda t: re.sub(r"\s*\*\s*", "*", " ".join(re.sub(r"\bconst\b", " ", t).split()))
-    decls = {}
-    for ret, name, params in re.findall(r"^\s*([A-Za-z_][\w \*]*?)\s*\b(r3d_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", src, flags=re.M):
-        assert name not in decls, name
-        decls[name] = (norm(ret), [norm(re.match(r"^(.*?)(\w+)$", " ".join(q.split())).group(1)) for q in params.split(",")])
-    return decls
-
-
 def test_symbols_are_declared_exported_and_bound():
-    """The three entry points live in the companion header include/r3d_hip_clip.h, which r3d_hip.h includes, and in _lib.CLIP_SIGNATURES:
-    every declaration is bound with the same parameter count, the exact type of every scalar, the header's element type of every
-    pointer and the stream last, the library exports it and load() has set its argtypes from that line (what tests/test_abi.py checks
-    of r3d_hip.h and SIGNATURES)."""
+    """The three entry points live in the companion header include/r3d_hip_clip.h (tests/test_abi.py compares every declaration with the
+    binding table and with what load() bound); here what is this unit's own: the parameter counts, the radius as a double, the ABI number
+    and the package's names."""
     from real3dportrait_amd import _lib
-    from test_abi import C_RETURNS, entry_matches
+    from test_abi import header_declarations
     import real3dportrait_amd
     lib = _lib.load()
     assert lib.r3d_version() == 80 == _lib.ABI_VERSION
-    main = open(os.path.join(ROOT, "include", "r3d_hip.h")).read()
-    assert main.count('#include "r3d_hip_clip.h"') == 1
-    decls = companion_declarations()
-    assert set(decls) == set(_lib.CLIP_SIGNATURES) == {"r3d_clip_camera", "r3d_camera_smooth", "r3d_smooth_features"}
-    assert not set(decls) & (set(_lib.SIGNATURES) | set(_lib.OPTIONAL_SIGNATURES))
-    for name, (ret, types) in decls.items():
-        res, entries = _lib.CLIP_SIGNATURES[name]
-        assert res is C_RETURNS[ret] and len(entries) == len(types), name
-        for i, (e, t) in enumerate(zip(entries, types)):
-            assert entry_matches(e, t, _lib), "%s: parameter %d is %s in the header, %r in the table" % (name, i, t, e)
-        assert [isinstance(e, _lib.Stream) for e in entries] == [False] * (len(entries) - 1) + [True], name
-        fn = getattr(lib, name)
-        assert fn.restype is res and list(fn.argtypes) == [getattr(e, "ctype", e) for e in entries], name
+    decls = header_declarations("r3d_hip_clip.h")
+    assert set(decls) == {"r3d_clip_camera", "r3d_camera_smooth", "r3d_smooth_features"} <= set(_lib.SIGNATURES)
     assert [len(decls[n][1]) for n in ("r3d_clip_camera", "r3d_camera_smooth", "r3d_smooth_features")] == [7, 6, 7]
     assert decls["r3d_clip_camera"][1][4] == "double"                                  # the radius
     from real3dportrait_amd import clip_conditions

@@ -16,7 +16,7 @@ import numpy as np
 import pytest
 import torch
 
-from conftest import GOLDEN, ROOT, load_golden
+from conftest import GOLDEN, load_golden
 import source_conditions_ref as R
 
 CASES = ("1_96", "2_128x96", "3_96x160", "4_96x70", "5_128_b3")
@@ -100,39 +100,19 @@ def test_the_blur_model_is_within_its_derived_bound_of_the_fp64_gaussian():
     assert err <= bound
 
 
-def source_declarations():
-    """{name: (return type, [parameter type, ...])} of include/r3d_hip_source.h, normalised as tests/test_abi.py normalises r3d_hip.h."""
-    src = open(os.path.join(ROOT, "include", "r3d_hip_source.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    norm = lambda t: re.sub(r"\s*\*\s*", "*", " ".join(re.sub(r"\bconst\b", " ", t).split()))
-    decls = {}
-    for ret, name, params in re.findall(r"^\s*([A-Za-z_][\w \*]*?)\s*\b(r3d_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", src, flags=re.M):
-        assert name not in decls, name
-        decls[name] = (norm(ret), [norm(re.match(r"^(.*?)(\w+)$", " ".join(q.split())).group(1)) for q in params.split(",")])
-    return decls, src
-
-
 def test_symbols_are_declared_exported_and_bound():
+    """The six entry points live in the companion header include/r3d_hip_source.h (tests/test_abi.py compares every declaration with the
+    binding table and with what load() bound); here what is this unit's own: the parameter counts, the header's macros against the
+    package's constants, the ABI number and the package's names."""
     from real3dportrait_amd import _lib
-    from test_abi import C_RETURNS, entry_matches
+    from test_abi import header_declarations, header_source
     import real3dportrait_amd
     lib = _lib.load()
     assert lib.r3d_version() == 80 == _lib.ABI_VERSION
-    main = open(os.path.join(ROOT, "include", "r3d_hip.h")).read()
-    assert main.count('#include "r3d_hip_source.h"') == 1
-    decls, src = source_declarations()
-    assert set(decls) == set(_lib.SOURCE_SIGNATURES) == set(ENTRY_POINTS)
-    assert not set(decls) & (set(_lib.SIGNATURES) | set(_lib.CLIP_SIGNATURES) | set(_lib.VIDEO_SIGNATURES) | set(_lib.OPTIONAL_SIGNATURES))
-    for name, (ret, types_) in decls.items():
-        res, entries = _lib.SOURCE_SIGNATURES[name]
-        assert res is C_RETURNS[ret] and len(entries) == len(types_) == ENTRY_POINTS[name], name
-        for i, (e, t) in enumerate(zip(entries, types_)):
-            assert entry_matches(e, t, _lib), "%s: parameter %d is %s in the header, %r in the table" % (name, i, t, e)
-        if name != "r3d_source_workspace_bytes":
-            assert [isinstance(e, _lib.Stream) for e in entries] == [False] * (len(entries) - 1) + [True], name
-        fn = getattr(lib, name)
-        assert fn.restype is res and list(fn.argtypes) == [getattr(e, "ctype", e) for e in entries], name
-    macros = dict(re.findall(r"^#define (R3D_SOURCE_\w+) (\d+)$", src, flags=re.M))
+    decls = header_declarations("r3d_hip_source.h")
+    assert set(decls) == set(ENTRY_POINTS) <= set(_lib.SIGNATURES)
+    assert {name: len(types_) for name, (ret, types_) in decls.items()} == ENTRY_POINTS
+    macros = dict(re.findall(r"^#define (R3D_SOURCE_\w+) (\d+)$", header_source("r3d_hip_source.h"), flags=re.M))
     assert macros == {"R3D_SOURCE_MAX_SIDE": str(_lib.SOURCE_MAX_SIDE), "R3D_SOURCE_STATUS_WORDS": str(_lib.SOURCE_STATUS_WORDS),
                       "R3D_SOURCE_DARKEN": str(_lib.SOURCE_DARKEN), "R3D_SOURCE_HEAD_CLASSES": str(_lib.SOURCE_HEAD_CLASSES)}
     assert _lib.SOURCE_HEAD_CLASSES == (1 << 1) | (1 << 3) | (1 << 5)
