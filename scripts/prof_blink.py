@@ -15,15 +15,13 @@ one JSON line:
 
     python scripts/prof_blink.py [--calls 20] [--blocks 5] [--size 512] [--out DIR]     (writes DIR/prof_blink.json)
 """
-import argparse
-import json
 import os
 import statistics
-import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import _prof
+
+_prof.paths()
 
 STAGES = (("clear", 1), ("quantise_bounds", 3), ("erode", 7), ("columns", 15), ("fill", 31))          # cumulative stage masks
 HOST_FIGURE = "41 to 51 ms per frame at p > 0 and 6 ms at p = 0 for the reference function with sklearn 1.7.2, measured on a CPU-only machine"
@@ -70,11 +68,8 @@ def kdtree_blink(img, p):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--calls", type=int, default=20)
-    ap.add_argument("--blocks", type=int, default=5)
+    ap = _prof.parser(__doc__, calls=20)
     ap.add_argument("--size", type=int, default=512)
-    ap.add_argument("--out", default=None)
     a = ap.parse_args()
     import numpy as np
     import torch
@@ -96,26 +91,6 @@ def main():
     ws = torch.empty(lib.r3d_secc_blink_workspace_bytes(F, S, S), device=dev, dtype=torch.uint8)
     P = _lib.ptr
 
-    def block_median(fn, calls):
-        ev = [torch.cuda.Event(enable_timing=True) for _ in range(calls + 1)]
-        ev[0].record()
-        for i in range(calls):
-            fn()
-            ev[i + 1].record()
-        ev[-1].synchronize()
-        return statistics.median(ev[i].elapsed_time(ev[i + 1]) for i in range(calls))
-
-    def measure(fns):
-        for _ in range(3):
-            for fn in fns.values():
-                fn()
-        torch.cuda.synchronize()
-        meds = {t: [] for t in fns}
-        for _ in range(a.blocks):
-            for t, fn in fns.items():
-                meds[t].append(block_median(fn, a.calls))
-        return {t: {"ms": round(statistics.median(v), 4), "spread_ms": round(max(v) - min(v), 4)} for t, v in meds.items()}
-
     def call():
         _lib.check(lib.r3d_secc_blink(P(clip), T, S, S, P(d_idx), P(d_pct), F, P(out_buf), P(status), P(ws), ws.numel(), _lib.stream_ptr()),
                    "secc_blink")
@@ -127,7 +102,8 @@ def main():
     fns = {"call": call}
     for name, bits in STAGES:
         fns["up_to_" + name] = lambda bits=bits: stage(bits)
-    res = measure(fns)
+    samples = _prof.alternate(_prof.routes(fns, _prof.block_median, a.calls), a.blocks, warmup=3)
+    res = {t: _prof.ms_spread(v) for t, v in samples.items()}
     before = 0.0
     for name, _ in STAGES:
         upto = res.pop("up_to_" + name)
@@ -141,22 +117,13 @@ def main():
     gpu = out_buf[:F].cpu().numpy()
 
     one = clip[6].clone()
-    for _ in range(3):
-        blink_eye_for_secc(one, 0.64)
-    walls = []
-    for _ in range(a.calls):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        blink_eye_for_secc(one, 0.64)
-        walls.append((time.perf_counter() - t0) * 1e3)
+    one_frame = lambda: blink_eye_for_secc(one, 0.64)          # ends in its status read, a synchronisation
+    _prof.by_host_clock(one_frame, 3)
+    walls = [_prof.by_host_clock(one_frame, 1) for _ in range(a.calls)]
 
     def batched_in_place():
         work = clip[:F + 1].clone()
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        blink_frames(work, frames, percents)
-        torch.cuda.synchronize()
-        return (time.perf_counter() - t0) * 1e3
+        return _prof.by_host_clock(lambda: blink_frames(work, frames, percents), 1)
     batched_in_place()
     batched = [batched_in_place() for _ in range(a.calls)]
 
@@ -191,11 +158,7 @@ def main():
                                    "pixels_differing_from_the_hip_result": differ}
     else:
         out["host_kdtree_path"] = {"sklearn": "does not import on this machine", "quoted": HOST_FIGURE}
-    print(json.dumps(out))
-    if a.out:
-        os.makedirs(a.out, exist_ok=True)
-        with open(os.path.join(a.out, "prof_blink.json"), "w") as f:
-            f.write(json.dumps(out, indent=1) + "\n")
+    _prof.emit(out, a.out, "prof_blink")
 
 
 if __name__ == "__main__":

@@ -9,25 +9,15 @@
 
     python scripts/prof_clip_conditions.py [--calls 50] [--blocks 5] [--host-calls 2] [--out DIR]
 """
-import argparse
-import json
-import os
-import statistics
-import sys
-import time
+import _prof
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+_prof.paths(tests=True)
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--calls", type=int, default=50)
-    ap.add_argument("--blocks", type=int, default=5)
+    ap = _prof.parser(__doc__, calls=50)
     ap.add_argument("--host-calls", type=int, default=2)
     ap.add_argument("--frames", type=int, nargs="+", default=[250, 2500])
-    ap.add_argument("--out", default=None)
     a = ap.parse_args()
     import numpy as np
     import torch
@@ -55,40 +45,25 @@ def main():
         cam = C64.clip_camera(euler.cpu().numpy(), trans.cpu().numpy(), 7)
         return torch.tensor(cam).to(dev).float()
 
-    def timed(fn, calls):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(calls):
-            fn()
-        torch.cuda.synchronize()
-        return (time.perf_counter() - t0) / calls * 1e3
+    def timed(fn, calls):          # warm-up: code objects, the allocator's blocks
+        return _prof.route(fn, _prof.by_host_clock, calls, warmup=min(calls, 3))
 
     result = {"unit": "ms per call", "calls": a.calls, "blocks": a.blocks, "host_calls": a.host_calls, "device": torch.cuda.get_device_name(0)}
     for T in a.frames:
         e_np, t_np = C64.trajectory(T)
         euler, trans = D(e_np), D(t_np)
         drv, src = D(C64.uniform(1, (T, 68, 2), 1.0)), D(C64.uniform(2, (1, 68, 2), 1.0))
-        routes = {"hip_clip_camera": (lambda: clip_camera(euler, trans), a.calls),
-                  "hip_clip_keypoints": (lambda: clip_keypoints(src, drv), a.calls),
-                  "torch_device_keypoints": (lambda: torch_keypoints(src, drv), a.calls),
-                  "host_numpy_camera_stand_in": (lambda: host_camera(euler, trans), a.host_calls)}
+        routes = {"hip_clip_camera": timed(lambda: clip_camera(euler, trans), a.calls),
+                  "hip_clip_keypoints": timed(lambda: clip_keypoints(src, drv), a.calls),
+                  "torch_device_keypoints": timed(lambda: torch_keypoints(src, drv), a.calls),
+                  "host_numpy_camera_stand_in": timed(lambda: host_camera(euler, trans), a.host_calls)}
         got, ref = clip_keypoints(src, drv)[1], torch_keypoints(src, drv)[1]
         kp_diff = float((got - ref).abs().max())
         cam_diff = float((clip_camera(euler, trans) - host_camera(euler, trans)).abs().max())
-        for fn, calls in routes.values():          # warm-up: code objects, the allocator's blocks
-            timed(fn, min(calls, 3))
-        samples = {k: [] for k in routes}
-        for _ in range(a.blocks):                  # alternating blocks
-            for k, (fn, calls) in routes.items():
-                samples[k].append(timed(fn, calls))
-        result["T%d" % T] = dict({k: {"median": statistics.median(v), "min": min(v), "max": max(v)} for k, v in samples.items()},
+        samples = _prof.alternate(routes, a.blocks, warmup=0)          # every route brings its own
+        result["T%d" % T] = dict({k: _prof.median_min_max(v) for k, v in samples.items()},
                                  max_abs_diff_keypoints_hip_vs_torch=kp_diff, max_abs_diff_camera_hip_vs_host=cam_diff)
-    line = json.dumps(result)
-    print(line)
-    if a.out:
-        os.makedirs(a.out, exist_ok=True)
-        with open(os.path.join(a.out, "prof_clip_conditions.json"), "w") as f:
-            f.write(json.dumps(result, indent=1) + "\n")
+    _prof.emit(result, a.out, "prof_clip_conditions")
 
 
 if __name__ == "__main__":

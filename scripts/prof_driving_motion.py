@@ -12,28 +12,21 @@
 
     python scripts/prof_driving_motion.py [--calls 20] [--blocks 5] [--clip-calls 3] [--frames 250] [--size 512] [--grid 188] [--out DIR]
 """
-import argparse
-import json
-import os
 import random
 import statistics
-import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import _prof
+
+_prof.paths()
 HBM_TBPS = 8.0
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--calls", type=int, default=20)
-    ap.add_argument("--blocks", type=int, default=5)
+    ap = _prof.parser(__doc__, calls=20)
     ap.add_argument("--clip-calls", type=int, default=3)
     ap.add_argument("--frames", type=int, default=250)
     ap.add_argument("--size", type=int, default=512)
     ap.add_argument("--grid", type=int, default=188)
-    ap.add_argument("--out", default=None)
     a = ap.parse_args()
     import numpy as np
     import torch
@@ -86,40 +79,17 @@ def main():
     vertex = torch.empty(CH, N, 3, device=dev)
     zeros = torch.zeros(T, 3, device=dev)
 
-    def block_median(fn, calls):
-        ev = [torch.cuda.Event(enable_timing=True) for _ in range(calls + 1)]
-        ev[0].record()
-        for i in range(calls):
-            fn()
-            ev[i + 1].record()
-        ev[-1].synchronize()
-        return statistics.median(ev[i].elapsed_time(ev[i + 1]) for i in range(calls))
-
     def wall(fn, calls):
-        out = []
-        for _ in range(calls):
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            fn()
-            torch.cuda.synchronize()
-            out.append((time.perf_counter() - t0) * 1e3)
-        return statistics.median(out)
+        """The median of `calls` calls, each alone between two synchronises on the host clock."""
+        return statistics.median(_prof.by_host_clock(fn, 1) for _ in range(calls))
 
     def measure(fns, timer, calls):
-        for _ in range(2):
-            for fn in fns.values():
-                fn()
-        torch.cuda.synchronize()
-        meds = {t: [] for t in fns}
-        for _ in range(a.blocks):
-            for t, fn in fns.items():
-                meds[t].append(timer(fn, calls))
-        return {t: {"ms": round(statistics.median(v), 4), "spread_ms": round(max(v) - min(v), 4), "block_medians_ms": [round(x, 4) for x in v]}
-                for t, v in meds.items()}
+        samples = _prof.alternate(_prof.routes(fns, timer, calls), a.blocks, warmup=2)
+        return {t: _prof.ms_spread(v, keep_blocks=True) for t, v in samples.items()}
 
     hip_chunk = lambda: FM.face_vertex(arrays, idc[:CH], expc[:CH], None, None, out=vertex)
     torch_chunk = lambda: secc.face_model.compute_face_vertex(idc[:CH], expc[:CH], zeros[:CH], zeros[:CH])
-    kernel = measure({"r3d_face_vertex": hip_chunk, "torch_ops": torch_chunk}, block_median, a.calls)
+    kernel = measure({"r3d_face_vertex": hip_chunk, "torch_ops": torch_chunk}, _prof.block_median, a.calls)
     err = float((hip_chunk() - torch_chunk()).abs().max())
     base_bytes, out_bytes = 3 * N * (Ki + Ke) * 4, CH * N * 3 * 4
     kernel["bytes"] = {"bases_read_once": base_bytes, "vertices_written": out_bytes,
@@ -170,11 +140,7 @@ def main():
     out = {"metric": "driving_motion_%d_frames_s%d" % (T, S), "S": S, "frames": T, "chunk": CH, "N": N, "Ki": Ki, "Ke": Ke, "faces": int(m["tri"].shape[0]),
            "calls_per_block": a.calls, "clip_calls_per_block": a.clip_calls, "blocks": a.blocks, "shader_clock": "not measured",
            "face_vertex_chunk_of_50_device_events": kernel, "whole_function_wall_with_sync": whole}
-    print(json.dumps(out))
-    if a.out:
-        os.makedirs(a.out, exist_ok=True)
-        with open(os.path.join(a.out, "prof_driving_motion.json"), "w") as f:
-            f.write(json.dumps(out, indent=1) + "\n")
+    _prof.emit(out, a.out, "prof_driving_motion")
 
 
 if __name__ == "__main__":

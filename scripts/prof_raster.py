@@ -14,15 +14,13 @@ and print one JSON line:
 
     python scripts/prof_raster.py [--calls 20] [--blocks 5] [--frames 50] [--out DIR]     (writes DIR/prof_raster.json)
 """
-import argparse
 import json
 import math
-import os
-import statistics
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import _prof
+
+_prof.paths()
 
 WINDOW = 16
 STAGES = (("clear", 1), ("scatter", 3), ("large_faces", 7), ("resolve", 15))          # cumulative stage masks: every timed call starts from its own clear
@@ -83,12 +81,9 @@ def torch_rasterize(v, tri, feat, S, fov_deg, znear, window=WINDOW):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--calls", type=int, default=20)
-    ap.add_argument("--blocks", type=int, default=5)
+    ap = _prof.parser(__doc__, calls=20)
     ap.add_argument("--frames", type=int, default=50)
     ap.add_argument("--size", type=int, default=512)
-    ap.add_argument("--out", default=None)
     a = ap.parse_args()
     import torch
 
@@ -97,25 +92,9 @@ def main():
     dev, S, B = "cuda:0", a.size, a.frames
     lib = _lib.load()
 
-    def block_median(fn, calls):
-        ev = [torch.cuda.Event(enable_timing=True) for _ in range(calls + 1)]
-        ev[0].record()
-        for i in range(calls):
-            fn()
-            ev[i + 1].record()
-        ev[-1].synchronize()
-        return statistics.median(ev[i].elapsed_time(ev[i + 1]) for i in range(calls))
-
     def measure(fns):
-        for _ in range(3):
-            for fn in fns.values():
-                fn()
-        torch.cuda.synchronize()
-        meds = {t: [] for t in fns}
-        for _ in range(a.blocks):
-            for t, fn in fns.items():
-                meds[t].append(block_median(fn, a.calls))
-        return {t: {"ms": round(statistics.median(v), 4), "spread_ms": round(max(v) - min(v), 4)} for t, v in meds.items()}
+        samples = _prof.alternate(_prof.routes(fns, _prof.block_median, a.calls), a.blocks, warmup=3)
+        return {t: _prof.ms_spread(v) for t, v in samples.items()}
 
     out = {"metric": "raster_chunk_s%d_b%d" % (S, B), "S": S, "frames": B, "calls_per_block": a.calls, "blocks": a.blocks,
            "fov_deg": synth.BFM_FOV_DEG, "shader_clock": "not measured", "cases": {}}
@@ -164,11 +143,7 @@ def main():
                                               "image": float((timage - image[0])[:, same].abs().max())},
             "bytes_per_frame": bytes_frame, "bytes_per_frame_total": total, "ms_per_frame_at_4TBps": round(total / 4e12 * 1e3, 5)}
         print("G %d: %s" % (G, json.dumps(out["cases"]["G%d" % G])), file=sys.stderr, flush=True)
-    print(json.dumps(out))
-    if a.out:
-        os.makedirs(a.out, exist_ok=True)
-        with open(os.path.join(a.out, "prof_raster.json"), "w") as f:
-            f.write(json.dumps(out, indent=1) + "\n")
+    _prof.emit(out, a.out, "prof_raster")
 
 
 if __name__ == "__main__":

@@ -16,16 +16,13 @@ B = 1, what prepare_batch_from_inp does once per clip (inference/real3d_infer.py
 
     python scripts/prof_source_conditions.py [--calls 20] [--blocks 5] [--size 512] [--out DIR]     (writes DIR/prof_source_conditions.json)
 """
-import argparse
 import ctypes
-import json
 import os
-import statistics
-import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import _prof
+
+_prof.paths()
 
 HOST_FIGURE = "1.2 s for the two kd-tree stages at 512 x 512 with sklearn 1.7.2, one run on a CPU-only machine: a stand-in from another host"
 BLUR = (48, 53, 54, 53, 48)
@@ -90,11 +87,8 @@ def host_torso(img, seg):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--calls", type=int, default=20)
-    ap.add_argument("--blocks", type=int, default=5)
+    ap = _prof.parser(__doc__, calls=20)
     ap.add_argument("--size", type=int, default=512)
-    ap.add_argument("--out", default=None)
     a = ap.parse_args()
     import numpy as np
     import torch
@@ -121,20 +115,8 @@ def main():
         "torso": lambda: _lib.call("r3d_source_torso", img, seg, N, N, darken, weights, outs[1], masks[0], outs[2], masks[1], ws, ws.numel()),
         "to_planes": lambda: _lib.call("r3d_source_to_planes", img, seg, S.HEAD_CLASSES, N, N, planes),
     }
-    for _ in range(3):
-        for fn in fns.values():
-            fn()
-    torch.cuda.synchronize()
-    per_call = {t: [] for t in fns}
-    for _ in range(a.blocks):
-        for t, fn in fns.items():
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            for _ in range(a.calls):
-                fn()
-            torch.cuda.synchronize()
-            per_call[t].append((time.perf_counter() - t0) * 1e3 / a.calls)
-    hip = {t: {"ms": round(statistics.median(v), 4), "spread_ms": round(max(v) - min(v), 4)} for t, v in per_call.items()}
+    per_call = _prof.alternate(_prof.routes(fns, _prof.by_host_clock, a.calls), a.blocks, warmup=3)
+    hip = {t: _prof.ms_spread(v) for t, v in per_call.items()}
     evaluations = N * N * N
     floor_ms = evaluations / 64 * 5 * 2 / 1024 / 2.4e9 * 1e3
     out = {"metric": "source_conditions_s%d" % N, "S": N, "B": 1, "calls_per_block": a.calls, "blocks": a.blocks, "shader_clock": "not measured",
@@ -176,11 +158,7 @@ def main():
                              "head_values_differing_from_the_hip_result": int((to_dev(head) != got["ref_head_img"]).sum())}
     else:
         out["host_route"] = {"sklearn_or_scipy": "does not import on this machine", "quoted": HOST_FIGURE}
-    print(json.dumps(out))
-    if a.out:
-        os.makedirs(a.out, exist_ok=True)
-        with open(os.path.join(a.out, "prof_source_conditions.json"), "w") as f:
-            f.write(json.dumps(out, indent=1) + "\n")
+    _prof.emit(out, a.out, "prof_source_conditions")
 
 
 if __name__ == "__main__":

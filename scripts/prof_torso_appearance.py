@@ -14,17 +14,13 @@ print one JSON line:
     python scripts/prof_torso_appearance.py --summarise DIR/.../appearance_kernel_trace.csv --forwards 20
         the per-launch table of that trace (median over the forwards), with each layer's GFLOP and TFLOP/s
 """
-import argparse
 import collections
 import csv
-import json
-import os
 import statistics
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+import _prof
+
+_prof.paths(tests=True)
 
 PEAK_TFLOPS = 157.3
 
@@ -71,12 +67,9 @@ def summarise(path, forwards):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--calls", type=int, default=100)
-    ap.add_argument("--blocks", type=int, default=5)
+    ap = _prof.parser(__doc__, calls=100)
     ap.add_argument("--forwards", type=int, default=0)
     ap.add_argument("--summarise", default=None)
-    ap.add_argument("--out", default=None)
     ap.add_argument("--precision", default="f32", choices=("f32", "bf16x3"))
     a = ap.parse_args()
     if a.summarise is not None:
@@ -87,15 +80,6 @@ def main():
     import torso_appearance_ref64 as R
     from real3dportrait_amd import _lib, synth
     from real3dportrait_amd.torso_appearance import AppearanceFeatureExtractor
-
-    def block_median(fn, calls):
-        ev = [torch.cuda.Event(enable_timing=True) for _ in range(calls + 1)]
-        ev[0].record()
-        for i in range(calls):
-            fn()
-            ev[i + 1].record()
-        ev[-1].synchronize()
-        return statistics.median(ev[i].elapsed_time(ev[i + 1]) for i in range(calls))
 
     def count_launches(fn):
         with _lib.counting() as calls:
@@ -121,14 +105,7 @@ def main():
             torch.cuda.synchronize()
             return
         fns["eager"] = lambda: R.extractor(sdd, x, dtype=torch.float32)
-        for _ in range(10):
-            for fn in fns.values():
-                fn()
-        torch.cuda.synchronize()
-        meds = {t: [] for t in fns}
-        for _ in range(a.blocks):
-            for t, fn in fns.items():
-                meds[t].append(block_median(fn, a.calls))
+        meds = _prof.alternate(_prof.routes(fns, _prof.block_median, a.calls), a.blocks, warmup=10)
         launches = {t: count_launches(fns[t]) for t in mods}
         ref = R.extractor(sdd, x)
         rel = lambda y: float((y.double() - ref).abs().max() / ref.abs().max())
@@ -151,11 +128,7 @@ def main():
     out["launches_per_forward"] = {t: sum(c.values()) for t, c in launches.items()}
     out["launches_by_entry_point"] = launches
     out["max_rel_diff"] = agreement
-    print(json.dumps(out))
-    if a.out:
-        os.makedirs(a.out, exist_ok=True)
-        with open(os.path.join(a.out, "prof_torso_appearance.json"), "w") as f:
-            f.write(json.dumps(out, indent=1) + "\n")
+    _prof.emit(out, a.out, "prof_torso_appearance")
 
 
 if __name__ == "__main__":

@@ -11,38 +11,21 @@
 
     python scripts/prof_torso_forward.py [--calls 100] [--blocks 5] [--out DIR]     (writes DIR/prof_torso_forward.json)
 """
-import argparse
 import collections
-import json
-import os
 import statistics
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+import _prof
+
+_prof.paths(tests=True)
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--calls", type=int, default=100)
-    ap.add_argument("--blocks", type=int, default=5)
-    ap.add_argument("--out", default=None)
-    a = ap.parse_args()
+    a = _prof.parser(__doc__, calls=100).parse_args()
     import torch
 
     from test_gpu_torso_appearance import stand_in_torso_model, synth_frame
     from test_torso_generator_host import model_shell
     from real3dportrait_amd import _lib, patch_model, torso_mask_volume, torso_seg_input
-
-    def block_median(fn, calls):
-        ev = [torch.cuda.Event(enable_timing=True) for _ in range(calls + 1)]
-        ev[0].record()
-        for i in range(calls):
-            fn()
-            ev[i + 1].record()
-        ev[-1].synchronize()
-        return statistics.median(ev[i].elapsed_time(ev[i + 1]) for i in range(calls))
 
     def count_launches(fn):
         with _lib.counting() as calls:
@@ -63,14 +46,7 @@ def main():
     fns["mask_volume_kernel"] = lambda: torso_mask_volume(feats_cl, seg, masked_cl=masked, motion_cl=motion)
     fns["seg_input_kernel"] = lambda: torso_seg_input(frame[0], seg, out=x5)
     with torch.no_grad():
-        for _ in range(10):
-            for fn in fns.values():
-                fn()
-        torch.cuda.synchronize()
-        meds = {t: [] for t in fns}
-        for _ in range(a.blocks):
-            for t, fn in fns.items():
-                meds[t].append(block_median(fn, a.calls))
+        meds = _prof.alternate(_prof.routes(fns, _prof.block_median, a.calls), a.blocks, warmup=10)
         launches = {t: count_launches(fns[t]) for t in tms}
         (rgb, ret), (rgb_p, ret_p) = fns["hip_forward"](), fns["parent_path"]()
         rel = lambda y, r: float((y.double() - r.double()).abs().max() / r.double().abs().max())
@@ -91,11 +67,7 @@ def main():
     out["launches_per_forward"] = {t: sum(c.values()) for t, c in launches.items()}
     out["launches_by_entry_point"] = launches
     out["max_rel_diff_hip_vs_parent"] = agreement
-    print(json.dumps(out))
-    if a.out:
-        os.makedirs(a.out, exist_ok=True)
-        with open(os.path.join(a.out, "prof_torso_forward.json"), "w") as f:
-            f.write(json.dumps(out, indent=1) + "\n")
+    _prof.emit(out, a.out, "prof_torso_forward")
 
 
 if __name__ == "__main__":

@@ -16,53 +16,22 @@ output) and print one JSON line:
         the two precision tiers of the convolutions in alternating blocks in one run, no eager side
         (writes DIR/prof_torso_generator_precision.json); --precision bf16x3 with --forwards: that tier's forwards for a trace
 """
-import argparse
 import collections
-import json
-import os
 import statistics
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
-import torch.nn.functional as F  # noqa: E402
+import _prof
 
-import torso_ref64 as R  # noqa: E402
-from real3dportrait_amd import _lib, synth  # noqa: E402
-from real3dportrait_amd.torso_generator import Generator, Occlusion2Predictor  # noqa: E402
+_prof.paths(tests=True)
 
 GFLOP, PEAK_TFLOPS = 92.5, 157.3
 
 
-def block_median(fn, calls):
-    ev = [torch.cuda.Event(enable_timing=True) for _ in range(calls + 1)]
-    ev[0].record()
-    for i in range(calls):
-        fn()
-        ev[i + 1].record()
-    ev[-1].synchronize()
-    return statistics.median(ev[i].elapsed_time(ev[i + 1]) for i in range(calls))
-
-
-def count_launches(fn):
-    with _lib.counting() as calls:
-        fn()
-    return dict(collections.Counter(n for n, _ in calls if n.startswith("r3d_torso_")))
-
-
-def compare_tiers(fns, calls, blocks, block_median):
-    """fns: {tier: callable}.  The tiers timed in alternating blocks in one run: per tier the median of the block medians, the block
-    medians and their spread (max - min), in ms; faster_by_more_than_the_spreads: f32 - bf16x3 exceeds the sum of the two spreads."""
-    meds = {t: [] for t in fns}
-    for _ in range(blocks):
-        for t, fn in fns.items():
-            meds[t].append(block_median(fn, calls))
-    out = {}
-    for t, v in meds.items():
-        out[t] = {"ms": round(statistics.median(v), 4), "block_medians_ms": [round(x, 4) for x in v], "spread_ms": round(max(v) - min(v), 4)}
+def compare_tiers(fns, calls, blocks):
+    """fns: {tier: callable}.  The tiers timed in alternating blocks in one run after 10 calls of warm-up: per tier the median of the block
+    medians, the block medians and their spread (max - min), in ms; faster_by_more_than_the_spreads: f32 - bf16x3 exceeds the sum of the
+    two spreads."""
+    samples = _prof.alternate(_prof.routes(fns, _prof.block_median, calls), blocks, warmup=10)
+    out = {t: _prof.ms_spread(v, keep_blocks=True) for t, v in samples.items()}
     gain = out["f32"]["ms"] - out["bf16x3"]["ms"]
     out["f32_minus_bf16x3_ms"] = round(gain, 4)
     out["f32_over_bf16x3"] = round(out["f32"]["ms"] / out["bf16x3"]["ms"], 3)
@@ -71,13 +40,23 @@ def compare_tiers(fns, calls, blocks, block_median):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--calls", type=int, default=200)
-    ap.add_argument("--blocks", type=int, default=5)
+    ap = _prof.parser(__doc__, calls=200)
     ap.add_argument("--forwards", type=int, default=0)
-    ap.add_argument("--out", default=None)
     ap.add_argument("--precision", default="f32", choices=("f32", "bf16x3", "both"))
     a = ap.parse_args()
+    import numpy as np
+    import torch
+    import torch.nn.functional as F
+
+    import torso_ref64 as R
+    from real3dportrait_amd import _lib, synth
+    from real3dportrait_amd.torso_generator import Generator, Occlusion2Predictor
+
+    def count_launches(fn):
+        with _lib.counting() as calls:
+            fn()
+        return dict(collections.Counter(n for n, _ in calls if n.startswith("r3d_torso_")))
+
     dev = "cuda:0"
     T = lambda sd: {k: torch.from_numpy(np.ascontiguousarray(v)) for k, v in sd.items()}
     sd, psd = synth.synth_torso_generator(71), synth.synth_torso_predictor(72)
@@ -110,26 +89,12 @@ def main():
         if a.precision == "both":
             gb, pb = modules("bf16x3")
             fns = {"f32": hip, "bf16x3": lambda: hip(gb, pb)}
-            for _ in range(10):
-                for fn in fns.values():
-                    fn()
             out = {"metric": "torso_generator_b1_64_precision_tiers", "B": 1, "grid": [64, 64], "calls_per_block": a.calls, "blocks": a.blocks}
-            out.update(compare_tiers(fns, a.calls, a.blocks, block_median))
+            out.update(compare_tiers(fns, a.calls, a.blocks))
             out["launches_by_entry_point"] = {t: count_launches(fn) for t, fn in fns.items()}
             out["bf16x3_vs_f32_max_rel_diff_rgb_hid_occ2"] = [float((x - y).abs().max() / y.abs().max()) for x, y in zip(fns["bf16x3"](), hip())]
-            print(json.dumps(out))
-            if a.out:
-                os.makedirs(a.out, exist_ok=True)
-                with open(os.path.join(a.out, "prof_torso_generator_precision.json"), "w") as f:
-                    f.write(json.dumps(out, indent=1) + "\n")
-            return
-        for _ in range(10):
-            hip()
-            eager()
-        hb, eb = [], []
-        for _ in range(a.blocks):
-            hb.append(block_median(hip, a.calls))
-            eb.append(block_median(eager, a.calls))
+            return _prof.emit(out, a.out, "prof_torso_generator_precision")
+        hb, eb = _prof.alternate(_prof.routes({"hip": hip, "eager": eager}, _prof.block_median, a.calls), a.blocks, warmup=10).values()
         launches = count_launches(hip)
         diffs = [float((x - y).abs().max() / y.abs().max()) for x, y in zip(hip(), eager())]
     h, e = statistics.median(hb), statistics.median(eb)
@@ -140,11 +105,7 @@ def main():
            "launches_per_forward": sum(launches.values()), "launches_by_entry_point": launches,
            "fp32_matrix_floor_ms": round(GFLOP / PEAK_TFLOPS, 4), "share_of_floor": round(GFLOP / PEAK_TFLOPS / h, 3),
            "hip_vs_eager_max_rel_diff_rgb_hid_occ2": diffs}
-    print(json.dumps(out))
-    if a.out:
-        os.makedirs(a.out, exist_ok=True)
-        with open(os.path.join(a.out, "prof_torso_generator.json"), "w") as f:
-            f.write(json.dumps(out, indent=1) + "\n")
+    _prof.emit(out, a.out, "prof_torso_generator")
 
 
 if __name__ == "__main__":

@@ -18,18 +18,13 @@ volume, a 256^2 head image) and print one JSON line:
         the two precision tiers of the convolutions in alternating blocks in one run, no eager side
         (writes DIR/prof_torso_motion_precision.json); --precision bf16x3 with --forwards: that tier's forwards for a trace
 """
-import argparse
 import collections
 import csv
-import json
-import os
 import statistics
-import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+import _prof
+
+_prof.paths(tests=True)
 
 GFLOP, PEAK_TFLOPS = 208.6, 157.3
 INPUT_ORDER = ("fs", "kp_s", "kp_d", "Rs", "Rd", "tgt_head_img", "tgt_head_weights")
@@ -80,16 +75,12 @@ def summarise(path, forwards):
           % (total, span, GFLOP, PEAK_TFLOPS, GFLOP / PEAK_TFLOPS * 1e3))
 
 
-def compare_tiers(fns, calls, blocks, block_median):
-    """fns: {tier: callable}.  The tiers timed in alternating blocks in one run: per tier the median of the block medians, the block
-    medians and their spread (max - min), in ms; faster_by_more_than_the_spreads: f32 - bf16x3 exceeds the sum of the two spreads."""
-    meds = {t: [] for t in fns}
-    for _ in range(blocks):
-        for t, fn in fns.items():
-            meds[t].append(block_median(fn, calls))
-    out = {}
-    for t, v in meds.items():
-        out[t] = {"ms": round(statistics.median(v), 4), "block_medians_ms": [round(x, 4) for x in v], "spread_ms": round(max(v) - min(v), 4)}
+def compare_tiers(fns, calls, blocks):
+    """fns: {tier: callable}.  The tiers timed in alternating blocks in one run after 10 calls of warm-up: per tier the median of the block
+    medians, the block medians and their spread (max - min), in ms; faster_by_more_than_the_spreads: f32 - bf16x3 exceeds the sum of the
+    two spreads."""
+    samples = _prof.alternate(_prof.routes(fns, _prof.block_median, calls), blocks, warmup=10)
+    out = {t: _prof.ms_spread(v, keep_blocks=True) for t, v in samples.items()}
     gain = out["f32"]["ms"] - out["bf16x3"]["ms"]
     out["f32_minus_bf16x3_ms"] = round(gain, 4)
     out["f32_over_bf16x3"] = round(out["f32"]["ms"] / out["bf16x3"]["ms"], 3)
@@ -98,12 +89,9 @@ def compare_tiers(fns, calls, blocks, block_median):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--calls", type=int, default=200)
-    ap.add_argument("--blocks", type=int, default=5)
+    ap = _prof.parser(__doc__, calls=200)
     ap.add_argument("--forwards", type=int, default=0)
     ap.add_argument("--summarise", default=None)
-    ap.add_argument("--out", default=None)
     ap.add_argument("--precision", default="f32", choices=("f32", "bf16x3", "both"))
     a = ap.parse_args()
     if a.summarise:
@@ -114,15 +102,6 @@ def main():
     import torso_motion_ref64 as R
     from real3dportrait_amd import _lib, synth
     from real3dportrait_amd.torso_motion import MotionFieldEstimator
-
-    def block_median(fn, calls):
-        ev = [torch.cuda.Event(enable_timing=True) for _ in range(calls + 1)]
-        ev[0].record()
-        for i in range(calls):
-            fn()
-            ev[i + 1].record()
-        ev[-1].synchronize()
-        return statistics.median(ev[i].elapsed_time(ev[i + 1]) for i in range(calls))
 
     def count_launches(fn):
         with _lib.counting() as calls:
@@ -152,34 +131,18 @@ def main():
         if a.precision == "both":
             mb = module("bf16x3")
             fns = {"f32": hip, "bf16x3": lambda: mb(*args)}
-            for _ in range(10):
-                for fn in fns.values():
-                    fn()
             out = {"metric": "torso_motion_b1_k4_precision_tiers", "B": 1, "K": 4, "calls_per_block": a.calls, "blocks": a.blocks}
-            out.update(compare_tiers(fns, a.calls, a.blocks, block_median))
+            out.update(compare_tiers(fns, a.calls, a.blocks))
             out["launches_by_entry_point"] = {t: count_launches(fn) for t, fn in fns.items()}
             out["bf16x3_vs_f32_max_rel_diff_deformation_occ_occ2"] = [float((x - y).abs().max() / y.abs().max()) for x, y in zip(fns["bf16x3"](), hip())]
-            print(json.dumps(out))
-            if a.out:
-                os.makedirs(a.out, exist_ok=True)
-                with open(os.path.join(a.out, "prof_torso_motion_precision.json"), "w") as f:
-                    f.write(json.dumps(out, indent=1) + "\n")
-            return
+            return _prof.emit(out, a.out, "prof_torso_motion_precision")
         for _ in range(3):
             hip()
             eager()
-        torch.cuda.synchronize()
-        t0 = time.time()
-        eager()
-        torch.cuda.synchronize()
-        warm_ms = (time.time() - t0) * 1e3
+        warm_ms = _prof.by_host_clock(eager, 1)
         ecalls = a.calls if warm_ms <= 50.0 else max(5, min(a.calls, int(10000.0 / warm_ms)))
-        for _ in range(7):
-            hip()
-        hb, eb = [], []
-        for _ in range(a.blocks):
-            hb.append(block_median(hip, a.calls))
-            eb.append(block_median(eager, ecalls))
+        sides = {"hip": _prof.route(hip, _prof.block_median, a.calls, warmup=7), "eager": _prof.route(eager, _prof.block_median, ecalls)}
+        hb, eb = _prof.alternate(sides, a.blocks, warmup=0).values()          # both sides had 3 calls above
         launches = count_launches(hip)
         diffs = [float((x - y).abs().max() / y.abs().max()) for x, y in zip(hip(), eager())]
     h, e = statistics.median(hb), statistics.median(eb)
@@ -190,11 +153,7 @@ def main():
            "launches_per_forward": sum(launches.values()), "launches_by_entry_point": launches,
            "fp32_matrix_floor_ms": round(GFLOP / PEAK_TFLOPS, 4), "share_of_floor": round(GFLOP / PEAK_TFLOPS / h, 3),
            "hip_vs_eager_max_rel_diff_deformation_occ_occ2": diffs}
-    print(json.dumps(out))
-    if a.out:
-        os.makedirs(a.out, exist_ok=True)
-        with open(os.path.join(a.out, "prof_torso_motion.json"), "w") as f:
-            f.write(json.dumps(out, indent=1) + "\n")
+    _prof.emit(out, a.out, "prof_torso_motion")
 
 
 if __name__ == "__main__":

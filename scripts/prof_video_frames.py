@@ -12,27 +12,17 @@ SECC maps 512 x 512), out_mode 'concat_debug', and print one JSON line:
 
     python scripts/prof_video_frames.py [--frames 250] [--host-frames 50] [--calls 10] [--blocks 5] [--out DIR]
 """
-import argparse
-import json
-import os
-import statistics
-import sys
-import time
+import _prof
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+_prof.paths(tests=True)
 FLOAT4_COPY_BYTES_PER_S = 6.29e12          # the measured rate of a float4 copy on the MI355X
 
 
 def main():
-    ap = argparse.ArgumentParser()
+    ap = _prof.parser(__doc__, calls=10)
     ap.add_argument("--frames", type=int, default=250)
     ap.add_argument("--host-frames", type=int, default=50)
-    ap.add_argument("--calls", type=int, default=10)
-    ap.add_argument("--blocks", type=int, default=5)
     ap.add_argument("--size", type=int, default=512)
-    ap.add_argument("--out", default=None)
     a = ap.parse_args()
     import numpy as np
     import torch
@@ -76,24 +66,6 @@ def main():
         hip_kernels()
         host_out.copy_(out)
 
-    def by_events(fn, calls):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda.synchronize()
-        e0.record()
-        for _ in range(calls):
-            fn()
-        e1.record()
-        torch.cuda.synchronize()
-        return e0.elapsed_time(e1) / calls
-
-    def by_host_clock(fn, calls):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(calls):
-            fn()
-        torch.cuda.synchronize()
-        return (time.perf_counter() - t0) / calls * 1e3
-
     # the three routes give the same bytes
     hip_kernels()
     on_device = torch_device(T)
@@ -102,40 +74,29 @@ def main():
     del on_device
     same_host = bool(np.array_equal(V.compose_debug_frames(ref, secc[:a.host_frames], raw[:a.host_frames], depth[:a.host_frames],
                                                            img[:a.host_frames]).cpu().numpy(), host_reference(a.host_frames)))
-    routes = {"hip_range": (hip_range, by_events, a.calls), "hip_compose": (hip_compose, by_events, a.calls),
-              "hip_kernels": (hip_kernels, by_events, a.calls), "hip_kernels_and_copy": (hip_kernels_and_copy, by_host_clock, a.calls),
-              "torch_device": (lambda: torch_device(T), by_host_clock, max(1, a.calls // 5)),
-              "host_reference": (lambda: host_reference(a.host_frames), by_host_clock, 1)}
+    route, by_events, by_host_clock = _prof.route, _prof.by_events, _prof.by_host_clock
+    routes = {"hip_range": route(hip_range, by_events, a.calls), "hip_compose": route(hip_compose, by_events, a.calls),
+              "hip_kernels": route(hip_kernels, by_events, a.calls), "hip_kernels_and_copy": route(hip_kernels_and_copy, by_host_clock, a.calls),
+              "torch_device": route(lambda: torch_device(T), by_host_clock, max(1, a.calls // 5)),
+              "host_reference": route(lambda: host_reference(a.host_frames), by_host_clock, 1, warmup=0, blocks=2)}      # seconds per call
     # the composer one panel at a time: which panel's arithmetic or gather costs what (each writes a fifth of the output)
     srcs = (ref, secc, raw, depth, img)
     for p in range(5):
         args = [x if i == p else None for i, x in enumerate(srcs)]
-        routes["hip_compose_panel_%d" % p] = (lambda args=args, p=p: V._compose(*args, T, S, S, 1 << p, state if p == 3 else None, out), by_events, a.calls)
-    for k, (fn, timer, calls) in routes.items():          # warm-up: code objects, the allocator's blocks, the pinned buffer
-        if k != "host_reference":
-            timer(fn, 2)
-    samples = {k: [] for k in routes}
-    for b in range(a.blocks):                               # alternating blocks
-        for k, (fn, timer, calls) in routes.items():
-            if k != "host_reference" or b < 2:
-                samples[k].append(timer(fn, calls))
+        routes["hip_compose_panel_%d" % p] = route(lambda args=args, p=p: V._compose(*args, T, S, S, 1 << p, state if p == 3 else None, out), by_events, a.calls)
+    samples = _prof.alternate(routes, a.blocks, warmup=2)          # warm-up: code objects, the allocator's blocks, the pinned buffer
     read = 4 * (ref.numel() + secc.numel() + raw.numel() + depth.numel() + img.numel())
     result = {"unit": "ms per call", "frames": T, "size": S, "calls": a.calls, "blocks": a.blocks, "host_frames": a.host_frames,
               "device": torch.cuda.get_device_name(0), "bytes_equal_hip_vs_torch_device": same_device,
               "bytes_differing_hip_vs_torch_device_per_panel": differing, "bytes_equal_hip_vs_host_reference_first_frames": same_host,
               "compose_bytes_read": read, "compose_bytes_written": out.numel(), "range_bytes_read": 4 * depth.numel()}
-    result.update({k: {"median": statistics.median(v), "min": min(v), "max": max(v)} for k, v in samples.items()})
+    result.update({k: _prof.median_min_max(v) for k, v in samples.items()})
     rate = (read + out.numel()) / (result["hip_compose"]["median"] * 1e-3)
     result["compose_bytes_per_s"] = rate
     result["compose_fraction_of_float4_copy"] = rate / FLOAT4_COPY_BYTES_PER_S
     result["range_bytes_per_s"] = 4 * depth.numel() / (result["hip_range"]["median"] * 1e-3)
     result["host_reference_ms_per_frame"] = result["host_reference"]["median"] / a.host_frames
-    line = json.dumps(result)
-    print(line)
-    if a.out:
-        os.makedirs(a.out, exist_ok=True)
-        with open(os.path.join(a.out, "prof_video_frames.json"), "w") as f:
-            f.write(json.dumps(result, indent=1) + "\n")
+    _prof.emit(result, a.out, "prof_video_frames")
 
 
 if __name__ == "__main__":
