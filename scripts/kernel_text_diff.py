@@ -4,6 +4,9 @@
     hipcc <Makefile FLAGS> <DEVFLAGS> --cuda-device-only -S unit.hip -o A.s      (at two commits)
     python scripts/kernel_text_diff.py A.s B.s
 
+For two whole trees, `scripts/ab.py text PARENT_TREE CHANGE_TREE` makes the listings of every unit with each tree's own Makefile flags and
+calls main() per unit.
+
 A symbol is everything from its `name:` line to `.Lfunc_end` (a data symbol: to its `.size`); comments, debug / section directives and the
 names of local labels are dropped, so two listings are "identical" when their instructions and operands are.
 Exit status 1 when a function was added or differs (data symbols, `.type name,@object`, may: the per-unit

@@ -462,7 +462,7 @@ def test_product_has_no_oracle_dependency():
 
 # The kernel sources carry no experiment switches (DESIGN "Retired experiment switches"): a build option or an environment variable read inside the library
 # is a deliberate addition to one of these two lists, with its test, not a silent #ifndef.
-CSRC_CONDITIONAL_MACROS = {"R3D_STAMPS"}          # the instrumented build (scripts/gpu_*_stamps.py)
+CSRC_CONDITIONAL_MACROS = {"R3D_STAMPS"}          # the instrumented build (scripts/gpu_stamps.py)
 CSRC_GETENV_NAMES = {"R3D_CONV_WINO"}             # include/r3d_hip.h; tests/test_gpu_wino.py
 
 
