@@ -21,6 +21,7 @@ Operators keep the reference's names and signatures (see each module's docstring
     nearest_seed, head_image, inpaint_torso_job, extract_background, source_to_planes, patch_segment_imgs
                                                          (source_conditions.py: the source image's head, torso and background conditions;
                                                          the name source_conditions is the module, its function source_conditions.source_conditions)
+    PitchContourVAEModel, VAEModel, patch_audio2secc     (audio2motion.py: the audio-to-motion VAE behind forward_audio2secc)
     render_clip_sharded                                  (frames.py: frame sharding + RCCL gather)
 All compute goes through libr3d_hip.so (include/r3d_hip.h); there is no eager/CPU fallback.
 """
@@ -74,6 +75,9 @@ def __getattr__(name):      # lazy: importing the package (e.g. for synth) must 
     if name in ("nearest_seed", "head_image", "inpaint_torso_job", "extract_background", "source_to_planes", "patch_segment_imgs"):
         import importlib
         return getattr(importlib.import_module(".source_conditions", __name__), name)
+    if name in ("PitchContourVAEModel", "VAEModel", "patch_audio2secc"):
+        import importlib
+        return getattr(importlib.import_module(".audio2motion", __name__), name)
     if name in ("render_clip_sharded", "shard_frames"):
         from . import frames as m
         return getattr(m, name)

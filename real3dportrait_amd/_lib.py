@@ -143,6 +143,15 @@ SIGNATURES = {
     "r3d_source_select": (c_int, [U8, U8, c_int, c_int, c_int, U8, U8, S]),
     "r3d_source_to_planes": (c_int, [U8, U8, c_int, c_int, c_int, F, S]),
 }
+# include/r3d_hip_audio.h, the companion header r3d_hip.h does not include: the audio-to-motion VAE (audio2motion.py).  Bound by load() as
+# SIGNATURES is -- a library that lacks one of them does not load -- and mirrored one to one by tests/test_audio2motion_host.py.
+AUDIO_SIGNATURES = {
+    "r3d_a2m_conv1d": (c_int, [F, c_int, c_int, c_int, c_int, c_int, c_int, F, F, c_int, c_int, c_int, c_int, c_int, F, F, I64, c_int, c_int, F, F, F, F, F, F,
+                               c_int, c_int, c_int, S]),
+    "r3d_a2m_wn_layer": (c_int, [F, F, c_int, c_int, c_int, c_int, c_int, F, F, F, F, F, c_int, c_int, F, F, S]),
+    "r3d_a2m_pitch_embed": (c_int, [F, c_int, c_int, F, c_int, c_int, I32, F, S]),
+}
+A2M_WN_ROWS = 16          # R3D_A2M_WN_ROWS of include/r3d_hip_audio.h: the time rows one block of r3d_a2m_wn_layer owns
 VIDEO_STATE_WORDS, VIDEO_PANELS_ALL, VIDEO_PANEL_DEPTH = 8, 31, 8          # R3D_VIDEO_* of include/r3d_hip_video.h
 SOURCE_MAX_SIDE, SOURCE_STATUS_WORDS, SOURCE_DARKEN, SOURCE_HEAD_CLASSES = 2048, 2, 53, 42          # R3D_SOURCE_* of include/r3d_hip_source.h
 
@@ -209,7 +218,7 @@ def load():
         lib = ctypes.CDLL(LIB_PATH)
     except OSError as e:
         raise RuntimeError("real3dportrait_amd: cannot load %s: %s" % (LIB_PATH, e))
-    for name, (res, params) in SIGNATURES.items():
+    for name, (res, params) in list(SIGNATURES.items()) + list(AUDIO_SIGNATURES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError:       # functions are added without a new ABI number: a stale in-tree build lacks them

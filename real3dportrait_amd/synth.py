@@ -731,3 +731,84 @@ def synth_face_model(G, seed, Ki=80, Ke=64):
             "feat": (0.02 + 0.98 * hash_uniform(seed, 3 * n, stream=76).reshape(n, 3)).astype(np.float32), "keypoints": key,
             "key_mean_shape": mean32[key], "key_id_base": id_base.reshape(n, 3, Ki)[key].reshape(3 * 68, Ki),
             "key_exp_base": exp_base.reshape(n, 3, Ke)[key].reshape(3 * 68, Ke), "camera_distance": 10.0}
+
+
+AUDIO2MOTION_HPARAMS = {"use_mouth_amp_embed": True, "use_eye_amp_embed": False}          # egs/os_avatar/audio2motion_vae.yaml
+
+
+def audio2motion_shapes(pitch=True, audio_in_dim=1024):
+    """{state_dict key: shape} of PitchContourVAEModel(AUDIO2MOTION_HPARAMS) / VAEModel (modules/audio2motion/vae.py:272-454), in
+    state_dict order, read off this package's classes (tests compare the names with the recorded reference's)."""
+    from . import audio2motion as a
+    m = a.PitchContourVAEModel(AUDIO2MOTION_HPARAMS, audio_in_dim=audio_in_dim) if pitch else a.VAEModel(audio_in_dim=audio_in_dim)
+    return {k: tuple(v.shape) for k, v in m.state_dict().items()}
+
+
+def synth_audio2motion(seed, pitch=True, audio_in_dim=1024):
+    """A state_dict (numpy) for the audio-to-motion VAE at which a passing comparison means something: every convolution keeps its input's
+    scale (sigma = gain / sqrt(fan in)), so the gates stay unsaturated; weight_g is ||v|| times 1.25 .. 1.5, never the ||v|| a missing
+    gain would give; the flows' post layers, which the reference initialises to zero, are not zero; the BatchNorm statistics are not
+    (0, 1) and its affine part is not (1, 0).  Every number from hash_*: the same arguments give the same model everywhere."""
+    shapes = audio2motion_shapes(pitch, audio_in_dim)
+    sd = {}
+    for n, (key, shape) in enumerate(shapes.items()):
+        st = 1000 + 2 * n
+        leaf = key.rsplit(".", 1)[-1]
+        if leaf == "num_batches_tracked":
+            sd[key] = np.array(1, np.int64)
+        elif leaf == "running_var":
+            sd[key] = (0.5 + hash_uniform(seed, shape[0], st)).astype(np.float32)
+        elif leaf == "running_mean":
+            sd[key] = (0.3 * hash_unitvar(seed, shape, st)).astype(np.float32)
+        elif leaf == "weight_g":
+            sd[key] = (1.25 + 0.25 * hash_uniform(seed, shape[0], st)).reshape(shape).astype(np.float32)          # x ||v|| below
+        elif len(shape) == 1 and leaf == "weight":                       # BatchNorm1d's
+            sd[key] = (1.0 + 0.3 * hash_unitvar(seed, shape, st)).astype(np.float32)
+        elif len(shape) == 1 and leaf in ("mouth_amp_embed", "eye_amp_embed"):
+            sd[key] = hash_unitvar(seed, shape, st)
+        elif len(shape) == 1:                                            # biases
+            sd[key] = (0.1 * hash_unitvar(seed, shape, st)).astype(np.float32)
+        elif "embed" in key:                                             # blink_embed, pitch_embed
+            sd[key] = hash_unitvar(seed, shape, st)
+        else:
+            # Conv1d [cout, cin, k], Linear [cout, cin]: fan in cin k; ConvTranspose1d(16, 256, 4, 4) [cin, cout, k]: one tap reaches an output row
+            fan = shape[0] if "decoder.pre_net" in key else int(np.prod(shape[1:]))
+            gain = 0.7 if leaf == "weight_v" else (2.0 if key.endswith("post.weight") else 1.0)
+            sd[key] = (hash_unitvar(seed, shape, st) * np.float32(gain / math.sqrt(fan))).astype(np.float32)
+    for key in shapes:
+        if key.endswith("weight_g"):
+            v = sd[key[:-1] + "v"].astype(np.float64)
+            sd[key] = (sd[key] * np.sqrt((v * v).sum(axis=(1, 2), keepdims=True))).astype(np.float32)
+    return sd
+
+
+def synth_audio2motion_inputs(seed, B, T):
+    """One batch for the audio-to-motion VAE: audio [B, 2 T, 1024] of unit variance, f0 [B, 2 T] in Hz, blink [B, 2 T, 1] int64, mouth_amp
+    [B, 1], y_mask [B, T]; sample b differs from sample 0 in all of them.  f0: a slow contour between 80 and 400 Hz; the frames 4 n + 2
+    (at least three, and every one of a short clip's tail) are unvoiced, f0 = 0; a voiced frame whose f0_to_coarse value + 0.5 (in fp64)
+    lies within 2e-3 of an integer is moved up in steps of 0.37 Hz until it does not, so that no fp32 log can move an index.  blink: ones
+    on the frames [T / 2, T / 2 + 3) of sample 0, every fifth frame of the others.  y_mask: ones, and zeros on the last max(1, T / 4)
+    rows of every sample but the first."""
+    audio = hash_unitvar(seed, (B, 2 * T, 1024), stream=1)
+    ph = hash_uniform(seed, 3 * B, stream=2).reshape(B, 3).astype(np.float64)
+    t = np.arange(2 * T, dtype=np.float64)[None]
+    f0 = 240.0 + 160.0 * np.sin(2 * math.pi * (ph[:, :1] + t * (0.013 + 0.01 * ph[:, 1:2]))) * np.cos(0.05 * t + ph[:, 2:3])
+    f0 += 3.0 * hash_unitvar(seed, (B, 2 * T), stream=3)
+    f0 = np.clip(f0, 80.0, 400.0).astype(np.float32)
+    lo, hi = 1127 * math.log(1 + 50.0 / 700), 1127 * math.log(1 + 1100.0 / 700)
+    for _ in range(64):
+        m = (1127 * np.log(1 + f0.astype(np.float64) / 700) - lo) * 254 / (hi - lo) + 1 + 0.5
+        near = np.abs(m - np.rint(m)) < 2e-3
+        if not near.any():
+            break
+        f0 = np.where(near, f0 + np.float32(0.37), f0).astype(np.float32)
+    f0[:, 2::4] = 0.0
+    if T < 6:
+        f0[:, 2:] = 0.0
+    blink = np.zeros((B, 2 * T, 1), np.int64)
+    blink[0, T // 2:T // 2 + 3] = 1
+    blink[1:, ::5] = 1
+    mask = np.ones((B, T), np.float32)
+    mask[1:, T - max(1, T // 4):] = 0.0
+    amp = (0.25 + 0.5 * hash_uniform(seed, B, stream=4)).reshape(B, 1).astype(np.float32)
+    return {"audio": audio, "f0": f0, "blink": blink, "mouth_amp": amp, "y_mask": mask}
