@@ -151,6 +151,16 @@ AUDIO_SIGNATURES = {
     "r3d_a2m_wn_layer": (c_int, [F, F, c_int, c_int, c_int, c_int, c_int, F, F, F, F, F, c_int, c_int, F, F, S]),
     "r3d_a2m_pitch_embed": (c_int, [F, c_int, c_int, F, c_int, c_int, I32, F, S]),
 }
+# include/r3d_hip_fit.h, likewise a companion r3d_hip.h does not include: the landmark-driven 3DMM fit (fit_3dmm.py), mirrored one to one by
+# tests/test_fit_3dmm_host.py.  `lambdas` is a HOST array of six floats.
+_FIT_COMMON = [F, F, F, c_int, c_int, c_int, F, F, c_int, c_int, c_float, c_float, c_float, ctypes.POINTER(c_float)]
+FIT_SIGNATURES = {
+    "r3d_fit_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "r3d_fit_state_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "r3d_fit_landmark_grad": (c_int, _FIT_COMMON + [F, F, F, F, F, F, F, F, F, V, c_size_t, S]),
+    "r3d_fit_landmark_run": (c_int, _FIT_COMMON + [c_float, c_float, c_int, c_int, c_int, c_int, F, V, c_size_t, S]),
+}
+FIT_LOSS_WORDS, FIT_LAUNCHES = 8, 2          # R3D_FIT_* of include/r3d_hip_fit.h
 A2M_WN_ROWS = 16          # R3D_A2M_WN_ROWS of include/r3d_hip_audio.h: the time rows one block of r3d_a2m_wn_layer owns
 VIDEO_STATE_WORDS, VIDEO_PANELS_ALL, VIDEO_PANEL_DEPTH = 8, 31, 8          # R3D_VIDEO_* of include/r3d_hip_video.h
 SOURCE_MAX_SIDE, SOURCE_STATUS_WORDS, SOURCE_DARKEN, SOURCE_HEAD_CLASSES = 2048, 2, 53, 42          # R3D_SOURCE_* of include/r3d_hip_source.h
@@ -218,7 +228,7 @@ def load():
         lib = ctypes.CDLL(LIB_PATH)
     except OSError as e:
         raise RuntimeError("real3dportrait_amd: cannot load %s: %s" % (LIB_PATH, e))
-    for name, (res, params) in list(SIGNATURES.items()) + list(AUDIO_SIGNATURES.items()):
+    for name, (res, params) in list(SIGNATURES.items()) + list(AUDIO_SIGNATURES.items()) + list(FIT_SIGNATURES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError:       # functions are added without a new ABI number: a stale in-tree build lacks them

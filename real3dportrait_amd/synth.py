@@ -733,6 +733,24 @@ def synth_face_model(G, seed, Ki=80, Ke=64):
             "key_exp_base": exp_base.reshape(n, 3, Ke)[key].reshape(3 * 68, Ke), "camera_distance": 10.0}
 
 
+MP468_UNMATCHED = (93, 127, 132, 234, 323, 356, 361, 454)          # unmatch_mask of fit_3dmm_landmark.py: mediapipe points without a mesh vertex
+
+
+def synth_face_keys(model, L, seed):
+    """L key rows of a synth_face_model for the landmark fit (real3dportrait_amd/fit_3dmm.py), as ParametricFaceModel cuts them with
+    keypoint_mode='mediapipe' (bfm.py:60-63, 80-82): one vertex per point, drawn by the project's hash from the point's stretch of the mesh (distinct vertices, as landmarks are), and the MP468_UNMATCHED indices below L
+    mapped to vertex 0 as the reference maps its negative entries.  Returns keypoints [L] int64, key_mean_shape [L, 3], key_id_base
+    [3 L, Ki] and key_exp_base [3 L, Ke]; `model` itself is not changed."""
+    n = model["mean_shape"].size // 3
+    Ki, Ke = model["id_base"].shape[1], model["exp_base"].shape[1]
+    lo = (np.arange(L + 1, dtype=np.int64) * n) // L          # point i draws from vertices lo[i] .. lo[i + 1]: distinct while L <= n, and spread
+    key = np.minimum(lo[:-1] + (hash_uniform(seed, L, stream=77).astype(np.float64) * np.maximum(lo[1:] - lo[:-1], 1)).astype(np.int64), n - 1)
+    key[[i for i in MP468_UNMATCHED if i < L]] = 0
+    return {"keypoints": key, "key_mean_shape": model["mean_shape"].reshape(n, 3)[key],
+            "key_id_base": model["id_base"].reshape(n, 3, Ki)[key].reshape(3 * L, Ki),
+            "key_exp_base": model["exp_base"].reshape(n, 3, Ke)[key].reshape(3 * L, Ke)}
+
+
 AUDIO2MOTION_HPARAMS = {"use_mouth_amp_embed": True, "use_eye_amp_embed": False}          # egs/os_avatar/audio2motion_vae.yaml
 
 
