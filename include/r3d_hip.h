@@ -717,6 +717,14 @@ int r3d_face_landmarks(const float* key_mean, const float* key_id_base, const fl
  * Declared in the companion header next to this one, which this header includes: a program that includes r3d_hip.h sees them. */
 #include "r3d_hip_source.h"
 
+/* --- audio to motion: the VAE between the audio features and the expression coefficients, inference (added under ABI 0.8.0) ------------------
+ * Declared in the companion header next to this one, which this header includes: a program that includes r3d_hip.h sees them. */
+#include "r3d_hip_audio.h"
+
+/* --- fit the morphable model to 2-D landmarks: the Adam loops, data generation (added under ABI 0.8.0) ---------------------------------------
+ * Declared in the companion header next to this one, which this header includes: a program that includes r3d_hip.h sees them. */
+#include "r3d_hip_fit.h"
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,7 +1,6 @@
 /*
- * r3d_hip_audio.h -- companion header of r3d_hip.h (C ABI of libr3d_hip.so): the audio-to-motion VAE.  It includes r3d_hip.h; r3d_hip.h
- * does not include it (r3d_version() stays as it is: functions only).  The Python binding table of this header is
- * real3dportrait_amd/_lib.py AUDIO_SIGNATURES.
+ * r3d_hip_audio.h -- companion header of r3d_hip.h (C ABI of libr3d_hip.so): the audio-to-motion VAE.  r3d_hip.h includes it; it can also
+ * be included on its own.  The Python binding table of this header is real3dportrait_amd/_lib.py SIGNATURES.
  */
 #ifndef R3D_HIP_AUDIO_H
 #define R3D_HIP_AUDIO_H

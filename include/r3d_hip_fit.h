@@ -1,7 +1,6 @@
 /*
- * r3d_hip_fit.h -- companion header of r3d_hip.h (C ABI of libr3d_hip.so): the landmark-driven 3DMM fit.  It includes r3d_hip.h; r3d_hip.h
- * does not include it (r3d_version() stays as it is: functions only).  The Python binding table of this header is
- * real3dportrait_amd/_lib.py FIT_SIGNATURES.
+ * r3d_hip_fit.h -- companion header of r3d_hip.h (C ABI of libr3d_hip.so): the landmark-driven 3DMM fit.  r3d_hip.h includes it; it can
+ * also be included on its own.  The Python binding table of this header is real3dportrait_amd/_lib.py SIGNATURES.
  */
 #ifndef R3D_HIP_FIT_H
 #define R3D_HIP_FIT_H

@@ -1,6 +1,6 @@
 /*
  * r3d_hip_video.h -- companion header of r3d_hip.h (C ABI of libr3d_hip.so): the clip's output video frames.  r3d_hip.h includes it; it can
- * also be included on its own.  The Python binding table of this header is real3dportrait_amd/_lib.py VIDEO_SIGNATURES.
+ * also be included on its own.  The Python binding table of this header is real3dportrait_amd/_lib.py SIGNATURES.
  */
 #ifndef R3D_HIP_VIDEO_H
 #define R3D_HIP_VIDEO_H

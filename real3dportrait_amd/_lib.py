@@ -1,4 +1,4 @@
-"""ctypes binding of libr3d_hip.so (the C ABI declared in include/r3d_hip.h and the companion headers it includes).
+"""ctypes binding of libr3d_hip.so (the C ABI declared in include/r3d_hip.h and the five companion headers it includes).
 
 The product path has NO fallback: if the HIP library is missing or fails to load, importing an
 operator raises.  Build it with `python -c "import __graft_entry__ as g; g.build()"` or
@@ -39,9 +39,11 @@ class Stream:
 
 F, F64, I32, I64, U8, U16, V = (DevPtr(e) for e in ("float", "double", "int32_t", "int64_t", "uint8_t", "uint16_t", "void"))
 S = Stream()
+# what the two r3d_fit_landmark_* entry points begin with; `lambdas` is a HOST array of six floats
+_FIT_COMMON = [F, F, F, c_int, c_int, c_int, F, F, c_int, c_int, c_float, c_float, c_float, ctypes.POINTER(c_float)]
 
-# name -> (restype, [one entry per parameter]); mirrors include/r3d_hip.h and the three companion headers it includes one to one
-# (tests/test_abi.py compares every declaration of the four).  A library that lacks one of them does not load.
+# name -> (restype, [one entry per parameter]); mirrors include/r3d_hip.h and the five companion headers it includes one to one
+# (tests/test_abi.py compares every declaration of the six).  A library that lacks one of them does not load.
 # An entry is a ctypes type (scalars; host pointers as ctypes.POINTER(...) or, untyped, H), a device pointer named by the header's element
 # type (F float*, F64 double*, I32 int32_t*, I64 int64_t*, U8 uint8_t*, U16 uint16_t*, V void*), or S, the trailing r3d_stream_t.
 SIGNATURES = {
@@ -142,28 +144,24 @@ SIGNATURES = {
     "r3d_source_torso": (c_int, [U8, U8, c_int, c_int, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(c_int), U8, U8, U8, U8, V, c_size_t, S]),
     "r3d_source_select": (c_int, [U8, U8, c_int, c_int, c_int, U8, U8, S]),
     "r3d_source_to_planes": (c_int, [U8, U8, c_int, c_int, c_int, F, S]),
-}
-# include/r3d_hip_audio.h, the companion header r3d_hip.h does not include: the audio-to-motion VAE (audio2motion.py).  Bound by load() as
-# SIGNATURES is -- a library that lacks one of them does not load -- and mirrored one to one by tests/test_audio2motion_host.py.
-AUDIO_SIGNATURES = {
+    # include/r3d_hip_audio.h
     "r3d_a2m_conv1d": (c_int, [F, c_int, c_int, c_int, c_int, c_int, c_int, F, F, c_int, c_int, c_int, c_int, c_int, F, F, I64, c_int, c_int, F, F, F, F, F, F,
                                c_int, c_int, c_int, S]),
     "r3d_a2m_wn_layer": (c_int, [F, F, c_int, c_int, c_int, c_int, c_int, F, F, F, F, F, c_int, c_int, F, F, S]),
     "r3d_a2m_pitch_embed": (c_int, [F, c_int, c_int, F, c_int, c_int, I32, F, S]),
-}
-# include/r3d_hip_fit.h, likewise a companion r3d_hip.h does not include: the landmark-driven 3DMM fit (fit_3dmm.py), mirrored one to one by
-# tests/test_fit_3dmm_host.py.  `lambdas` is a HOST array of six floats.
-_FIT_COMMON = [F, F, F, c_int, c_int, c_int, F, F, c_int, c_int, c_float, c_float, c_float, ctypes.POINTER(c_float)]
-FIT_SIGNATURES = {
+    # include/r3d_hip_fit.h
     "r3d_fit_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "r3d_fit_state_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "r3d_fit_landmark_grad": (c_int, _FIT_COMMON + [F, F, F, F, F, F, F, F, F, V, c_size_t, S]),
     "r3d_fit_landmark_run": (c_int, _FIT_COMMON + [c_float, c_float, c_int, c_int, c_int, c_int, F, V, c_size_t, S]),
 }
-FIT_LOSS_WORDS, FIT_LAUNCHES = 8, 2          # R3D_FIT_* of include/r3d_hip_fit.h
-A2M_WN_ROWS = 16          # R3D_A2M_WN_ROWS of include/r3d_hip_audio.h: the time rows one block of r3d_a2m_wn_layer owns
-VIDEO_STATE_WORDS, VIDEO_PANELS_ALL, VIDEO_PANEL_DEPTH = 8, 31, 8          # R3D_VIDEO_* of include/r3d_hip_video.h
-SOURCE_MAX_SIDE, SOURCE_STATUS_WORDS, SOURCE_DARKEN, SOURCE_HEAD_CLASSES = 2048, 2, 53, 42          # R3D_SOURCE_* of include/r3d_hip_source.h
+
+# The headers' constants the package uses: _lib.X mirrors R3D_X of the header named (tests/test_abi.py compares every one).
+CHAIN_SR_BLOCK, CHAIN_CONV, CHAIN_SR_BLOCK_TAIL, CHAIN_SRC_NONE, CHAIN_MAX_OPS, CHAIN_MAX_EXT, CHAIN_MAX_ZERO = 0, 1, 2, -1000, 12, 4, 4      # r3d_hip.h
+VIDEO_STATE_WORDS, VIDEO_PANELS_ALL, VIDEO_PANEL_DEPTH = 8, 31, 8                                           # r3d_hip_video.h
+SOURCE_MAX_SIDE, SOURCE_STATUS_WORDS, SOURCE_DARKEN, SOURCE_HEAD_CLASSES = 2048, 2, 53, 42                  # r3d_hip_source.h
+A2M_WN_ROWS = 16                                          # r3d_hip_audio.h: the time rows one block of r3d_a2m_wn_layer owns
+FIT_LOSS_WORDS, FIT_LAUNCHES = 8, 2                       # r3d_hip_fit.h
 
 # test hooks outside the C ABI of include/r3d_hip.h: bound when the library exports them, absent otherwise (nothing in the product calls
 # them, and a library built from older sources -- the other side of a scripts/ab.py comparison, say -- must keep loading)
@@ -183,8 +181,6 @@ class ChainOp(ctypes.Structure):
                 ("gain", c_float), ("clamp", c_float), ("src_a", c_int), ("src_b", c_int),
                 ("scales", c_void_p), ("prepacked", c_void_p), ("bias", c_void_p)]
 
-
-CHAIN_SR_BLOCK, CHAIN_CONV, CHAIN_SR_BLOCK_TAIL, CHAIN_SRC_NONE, CHAIN_MAX_OPS, CHAIN_MAX_EXT, CHAIN_MAX_ZERO = 0, 1, 2, -1000, 12, 4, 4
 
 ABI_VERSION = 80          # r3d_version() of the library this table mirrors (include/r3d_hip.h)
 _lib = None
@@ -228,7 +224,7 @@ def load():
         lib = ctypes.CDLL(LIB_PATH)
     except OSError as e:
         raise RuntimeError("real3dportrait_amd: cannot load %s: %s" % (LIB_PATH, e))
-    for name, (res, params) in list(SIGNATURES.items()) + list(AUDIO_SIGNATURES.items()) + list(FIT_SIGNATURES.items()):
+    for name, (res, params) in SIGNATURES.items():
         try:
             fn = getattr(lib, name)
         except AttributeError:       # functions are added without a new ABI number: a stale in-tree build lacks them

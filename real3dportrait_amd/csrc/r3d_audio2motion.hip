@@ -5,7 +5,6 @@
 #include <math.h>
 
 #include "r3d_common.h"
-#include "../../include/r3d_hip_audio.h"
 
 namespace r3d {
 namespace a2m {

@@ -14,7 +14,6 @@
 //              gradient itself.  Its last block reduces the loss record.
 // Iterations are separated by launch boundaries alone; nothing waits for another block.
 #include "r3d_common.h"
-#include "../../include/r3d_hip_fit.h"
 
 #include <algorithm>
 #include <cmath>

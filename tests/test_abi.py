@@ -3,17 +3,23 @@ validation (which runs before any HIP call) reports errors through return codes 
 import ctypes
 import os
 import re
+import subprocess
 
+import pytest
+
+from abi import C_RETURNS, HEADERS, entry_matches, header_constants, header_declarations, header_source
 from conftest import ROOT
 
-
-HEADERS = {"r3d_hip.h": 74, "r3d_hip_clip.h": 3, "r3d_hip_video.h": 2, "r3d_hip_source.h": 6}          # the header and the three it includes: declarations
-
-
-def header_source(header):
-    """include/<header> without its comments."""
-    src = open(os.path.join(ROOT, "include", header)).read()
-    return re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", src, flags=re.S))
+COMPANIONS = [h for h in HEADERS if h != "r3d_hip.h"]
+# the constants of each header that real3dportrait_amd/_lib.py mirrors, by _lib's name: _lib.X is R3D_X.  Listed here, so that a constant
+# deleted from _lib (or from its header) fails test_constants_mirror_the_headers
+MIRRORED = {"r3d_hip.h": ["CHAIN_SR_BLOCK", "CHAIN_CONV", "CHAIN_SR_BLOCK_TAIL", "CHAIN_SRC_NONE", "CHAIN_MAX_OPS", "CHAIN_MAX_EXT", "CHAIN_MAX_ZERO"],
+            "r3d_hip_clip.h": [],
+            "r3d_hip_video.h": ["VIDEO_STATE_WORDS", "VIDEO_PANELS_ALL", "VIDEO_PANEL_DEPTH"],
+            "r3d_hip_source.h": ["SOURCE_MAX_SIDE", "SOURCE_STATUS_WORDS", "SOURCE_DARKEN", "SOURCE_HEAD_CLASSES"],
+            "r3d_hip_audio.h": ["A2M_WN_ROWS"],
+            "r3d_hip_fit.h": ["FIT_LOSS_WORDS", "FIT_LAUNCHES"]}
+LLVM = "/opt/rocm/lib/llvm/bin"          # csrc/Makefile's LLVM
 
 
 def declared_symbols():
@@ -31,64 +37,24 @@ def test_every_declared_symbol_is_exported_and_bound():
     assert set(_lib.SIGNATURES) == set(syms)
 
 
-def header_declarations(header="r3d_hip.h"):
-    """{name: (return type, [parameter type, ...])} of every function include/<header> declares itself (not the headers it includes):
-    comments stripped, `const` dropped, no blanks around a star ("const float* const* ext_bounds" -> "float**",
-    "unsigned long long* cycles" -> "unsigned long long*")."""
-    norm = lambda t: re.sub(r"\s*\*\s*", "*", " ".join(re.sub(r"\bconst\b", " ", t).split()))
-    decls = {}
-    for ret, name, params in re.findall(r"^\s*([A-Za-z_][\w \*]*?)\s*\b(r3d_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", header_source(header), flags=re.M):
-        assert name not in decls, name
-        types = []
-        for p in (params.split(",") if params.strip() not in ("", "void") else []):
-            m = re.match(r"^(.*?)(\w+)$", " ".join(p.split()))          # everything up to the parameter's name
-            assert m and m.group(1).strip(), (name, p)
-            types.append(norm(m.group(1)))
-        decls[name] = (norm(ret), types)
-    return decls
-
-
-C_SCALARS = {"int": ctypes.c_int, "float": ctypes.c_float, "double": ctypes.c_double, "size_t": ctypes.c_size_t, "uint32_t": ctypes.c_uint32,
-             "uint64_t": ctypes.c_uint64, "unsigned long long": ctypes.c_ulonglong}
-C_RETURNS = dict(C_SCALARS, **{"char*": ctypes.c_char_p})
-# what a bare c_void_p in the table (a host pointer the package never looks into) may stand for: an opaque handle or the 128-byte id (void*),
-# the array of chain ops, an array of device addresses; a host pointer to a scalar or a handle is a ctypes.POINTER of exactly that type
-UNTYPED_HOST = {"void*", "r3d_chain_op*", "float**"}
-
-
-def entry_matches(entry, ctype, _lib):
-    """Does one table entry stand for the header's parameter type `ctype`, exactly?"""
-    if ctype == "r3d_stream_t":
-        return isinstance(entry, _lib.Stream)
-    if isinstance(entry, _lib.DevPtr):
-        return ctype == entry.elem + "*" and entry.elem in _lib.DevPtr.DTYPES
-    if isinstance(entry, _lib.Stream):
-        return False
-    if ctype in C_SCALARS:
-        return entry is C_SCALARS[ctype]
-    if entry is ctypes.c_void_p:
-        return ctype in UNTYPED_HOST
-    if ctype == "void**":
-        return entry is ctypes.POINTER(ctypes.c_void_p)
-    return ctype.endswith("*") and ctype[:-1] in C_SCALARS and entry is ctypes.POINTER(C_SCALARS[ctype[:-1]])
-
-
 def test_table_mirrors_every_header_declaration():
-    """Every declaration of include/r3d_hip.h and of the three companion headers it includes (each exactly once) is bound in the one table
-    with the same parameter count, the exact ctypes type of every scalar, the header's element type of every pointer (device pointers by
-    their marker, host pointers by their ctypes.POINTER) and the same return type; the stream is the last parameter and no other (and
-    every status-returning entry point of a companion header has one); and load() derives each function's argtypes from that line."""
+    """Every declaration of include/r3d_hip.h and of the five companion headers it includes (each exactly once) -- 92 in all -- is bound
+    in the one table with the same parameter count, the exact ctypes type of every scalar, the header's element type of every pointer
+    (device pointers by their marker, host pointers by their ctypes.POINTER) and the same return type; the stream is the last parameter
+    and no other (and every status-returning entry point of a companion header has one); and load() derives each function's argtypes and
+    call()'s plan from that line."""
     from real3dportrait_amd import _lib
     lib = _lib.load()
     per_header = {h: header_declarations(h) for h in HEADERS}
-    assert {h: len(d) for h, d in per_header.items()} == HEADERS
+    assert {h: len(d) for h, d in per_header.items()} == HEADERS and len(HEADERS) == 6 and sum(HEADERS.values()) == 92
     main = open(os.path.join(ROOT, "include", "r3d_hip.h")).read()
+    assert len(COMPANIONS) == 5 and re.findall(r'#include "(\w+\.h)"', main) == COMPANIONS
     decls = {}
     for h, d in per_header.items():
         assert h == "r3d_hip.h" or main.count('#include "%s"' % h) == 1, h
         assert not set(d) & (set(decls) | set(_lib.OPTIONAL_SIGNATURES)), h
         decls.update(d)
-    assert set(decls) == set(_lib.SIGNATURES) == set(declared_symbols())
+    assert set(decls) == set(_lib.SIGNATURES) == set(declared_symbols()) and len(decls) == 92
     for name, (ret, types) in decls.items():
         res, entries = _lib.SIGNATURES[name]
         assert res is C_RETURNS[ret], (name, ret, res)
@@ -100,7 +66,57 @@ def test_table_mirrors_every_header_declaration():
             assert isinstance(entries[-1], _lib.Stream), name
         fn = getattr(lib, name)
         assert fn.restype is res and list(fn.argtypes) == [getattr(e, "ctype", e) for e in entries], name
+        assert name in _lib._plans, name
     assert _lib.F.ctype is ctypes.c_void_p and _lib.S.ctype is ctypes.c_void_p
+
+
+def test_abi_number_is_pinned_once():
+    """The ABI number: the library's, the package's and this literal agree, and csrc/r3d_api.hip holds the one definition (functions are
+    added without a new number: the per-unit host tests compare the first two and leave the literal to this test)."""
+    from real3dportrait_amd import _lib
+    lib = _lib.load()
+    assert lib.r3d_version() == _lib.ABI_VERSION == 80
+    csrc = os.path.join(ROOT, "real3dportrait_amd", "csrc")
+    defs = {f: re.findall(r"\bint\s+r3d_version\s*\(\s*(?:void)?\s*\)\s*\{([^}]*)\}", open(os.path.join(csrc, f)).read())
+            for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".h"))}
+    assert {f: [b.strip() for b in d] for f, d in defs.items() if d} == {"r3d_api.hip": ["return 80;"]}
+
+
+def test_constants_mirror_the_headers():
+    """_lib.X mirrors R3D_X: every constant of a header that _lib holds under that name has the header's value, every name of MIRRORED is
+    in both, and a companion header defines no constant that _lib does not mirror."""
+    from real3dportrait_amd import _lib
+    assert set(MIRRORED) == set(HEADERS) and [len(MIRRORED[h]) for h in HEADERS] == [7, 0, 3, 4, 1, 2]
+    for h in HEADERS:
+        consts = header_constants(h)
+        for name in MIRRORED[h]:
+            assert "R3D_" + name in consts, "%s does not define R3D_%s" % (h, name)
+            assert hasattr(_lib, name), "_lib.%s (R3D_%s of %s) is gone" % (name, name, h)
+        for rname, value in consts.items():
+            if hasattr(_lib, rname[4:]):
+                assert getattr(_lib, rname[4:]) == value and type(getattr(_lib, rname[4:])) is int, (h, rname, value)
+                assert rname[4:] in MIRRORED[h], "_lib.%s mirrors %s of %s: list it in MIRRORED" % (rname[4:], rname, h)
+        if h != "r3d_hip.h":
+            assert set(consts) == {"R3D_" + n for n in MIRRORED[h]}, h
+    main = header_constants("r3d_hip.h")
+    assert main["R3D_CHAIN_SRC_NONE"] == -1000 and main["R3D_ERR_WORKSPACE"] == -2 and main["R3D_PROF_COUNT"] == 7 and len(main) >= 25
+
+
+@pytest.mark.parametrize("lang", ["c99", "c++17"])
+def test_headers_stand_alone(lang, tmp_path):
+    """Each of the six headers compiles as the only line of a translation unit, as C99 and as C++17 (-Wall -Werror, host only), and so do
+    all six in the reverse of the order r3d_hip.h includes them in."""
+    clang = os.path.join(LLVM, "clang")
+    if not os.path.exists(clang):
+        pytest.skip("no %s: the headers are not compiled here" % clang)
+    flags = ["-x", "c", "-std=c99"] if lang == "c99" else ["-x", "c++", "-std=c++17"]
+    units = [[h] for h in HEADERS] + [list(HEADERS)[::-1]]
+    for i, unit in enumerate(units):
+        src = tmp_path / ("unit%d.%s" % (i, "c" if lang == "c99" else "cpp"))
+        src.write_text("".join('#include "%s"\n' % h for h in unit))
+        r = subprocess.run([clang] + flags + ["-Wall", "-Werror", "-fsyntax-only", "-I", os.path.join(ROOT, "include"), str(src)],
+                           capture_output=True, text=True)
+        assert r.returncode == 0, "%s as %s:\n%s" % (" + ".join(unit), lang, r.stderr)
 
 
 def test_debug_twins_extend_their_product_function():

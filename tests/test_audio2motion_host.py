@@ -1,8 +1,6 @@
 """CPU: the host side of the audio-to-motion VAE (real3dportrait_amd/audio2motion.py, include/r3d_hip_audio.h): the
 reference's state_dict keys, the parameter folds against torch's own weight_norm / BatchNorm1d in fp64, the latent draw, the binding
 table against the header, and what the three entry points refuse before any launch."""
-import os
-import re
 import warnings
 
 import numpy as np
@@ -11,11 +9,11 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+import abi
 import audio2motion_ref64 as ref64
-from conftest import ROOT, load_golden
+from conftest import load_golden
 from real3dportrait_amd import _lib, synth
 from real3dportrait_amd import audio2motion as a2m
-from test_abi import C_RETURNS, entry_matches, header_declarations
 
 HP = synth.AUDIO2MOTION_HPARAMS
 
@@ -164,24 +162,15 @@ def test_patch_leaves_other_models_alone():
 
 
 def test_header_mirrors_the_audio_table():
+    """The three entry points live in the companion header include/r3d_hip_audio.h (tests/test_abi.py compares every declaration with the
+    binding table and with what load() bound, and the header's macro with the package's constant); here what is this unit's own: the
+    names, the parameter counts, the ABI number and the rows of a block against the module that sizes its launches by them."""
     lib = _lib.load()
-    decls = header_declarations("r3d_hip_audio.h")
-    assert set(decls) == set(_lib.AUDIO_SIGNATURES) and len(decls) == 3
-    assert not set(_lib.AUDIO_SIGNATURES) & (set(_lib.SIGNATURES) | set(_lib.OPTIONAL_SIGNATURES))
-    assert "r3d_hip_audio.h" not in open(os.path.join(ROOT, "include", "r3d_hip.h")).read()
-    assert '#include "r3d_hip.h"' in open(os.path.join(ROOT, "include", "r3d_hip_audio.h")).read()
-    for name, (ret, types) in decls.items():
-        res, entries = _lib.AUDIO_SIGNATURES[name]
-        assert res is C_RETURNS[ret] and len(entries) == len(types), name
-        for i, (e, t) in enumerate(zip(entries, types)):
-            assert entry_matches(e, t, _lib), "%s: parameter %d is %s in the header, %r in the table" % (name, i, t, e)
-        assert isinstance(entries[-1], _lib.Stream) and not any(isinstance(e, _lib.Stream) for e in entries[:-1]), name
-        fn = getattr(lib, name)          # exported, and bound by load() from the table line
-        assert fn.restype is res and list(fn.argtypes) == [getattr(e, "ctype", e) for e in entries], name
-        assert name in _lib._plans
-    assert lib.r3d_version() == _lib.ABI_VERSION == 80
-    rows = re.search(r"#define R3D_A2M_WN_ROWS (\d+)", open(os.path.join(ROOT, "include", "r3d_hip_audio.h")).read())
-    assert _lib.A2M_WN_ROWS == a2m.WN_ROWS == int(rows.group(1)) == 16
+    assert lib.r3d_version() == _lib.ABI_VERSION
+    decls = abi.header_declarations("r3d_hip_audio.h")
+    assert {name: len(types) for name, (ret, types) in decls.items()} == {"r3d_a2m_conv1d": 29, "r3d_a2m_wn_layer": 17, "r3d_a2m_pitch_embed": 9}
+    assert set(decls) <= set(_lib.SIGNATURES)
+    assert a2m.WN_ROWS == _lib.A2M_WN_ROWS == 16
 
 
 def test_argument_errors_are_refused_before_any_launch():
@@ -193,12 +182,7 @@ def test_argument_errors_are_refused_before_any_launch():
                 rows=0, step=1, amp0=None, u0=None, amp1=None, u1=None, sub=None, y=Y, ys=8, yo=0, flip=0)
     wn = dict(x=X, g=G, B=1, T=8, H=64, Cg=128, k=3, w_in=W, b_in=BIAS, w_rs=TAB, b_rs=U, mask=None, first=1, last=0, xn=XN, out=OUT)
     pitch = dict(f0=X, B=1, T=8, table=TAB, rows=300, C=128, index=IDX, y=Y)
-
-    def refused(fn, base, quote, **over):
-        a = dict(base, **over)
-        rc = getattr(lib, "r3d_a2m_" + fn)(*a.values(), None)
-        msg = lib.r3d_last_error()
-        assert rc == -1 and b"a2m_" + fn.encode() + b":" in msg and quote in msg, (fn, over, rc, msg)
+    refused = abi.refusals(lib, "r3d_a2m_")
 
     for p in ("x", "w", "y"):
         refused("conv1d", conv, b"NULL pointer", **{p: None})

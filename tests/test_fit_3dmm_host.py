@@ -2,45 +2,33 @@
 table against the header, what the two entry points refuse before any launch, the restatement tests/fit_3dmm_ref.py against the goldens
 (the reference's own two functions), the landmark weights against the reference's index lists, and the dead fine stage."""
 import ctypes
-import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
+import abi
 import fit_3dmm_ref as R
-from conftest import ROOT, load_golden
+from conftest import load_golden
 from real3dportrait_amd import _lib, synth
 from real3dportrait_amd import fit_3dmm as f3
-from test_abi import C_RETURNS, entry_matches, header_declarations
 
 GOLDENS = ("fit_3dmm_image_t1", "fit_3dmm_video_global_t7", "fit_3dmm_video_global_t53", "fit_3dmm_video_fine_t7")
 
 
 def test_header_mirrors_the_fit_table():
+    """The four entry points live in the companion header include/r3d_hip_fit.h (tests/test_abi.py compares every declaration with the
+    binding table and with what load() bound, and the header's macros with the package's constants); here what is this unit's own: the
+    names, the parameter counts, the ABI number, the loss record against the module's names for it, and `lambdas`, the one host array."""
     lib = _lib.load()
-    decls = header_declarations("r3d_hip_fit.h")
-    assert set(decls) == set(_lib.FIT_SIGNATURES) and len(decls) == 4
-    assert not set(_lib.FIT_SIGNATURES) & (set(_lib.SIGNATURES) | set(_lib.AUDIO_SIGNATURES) | set(_lib.OPTIONAL_SIGNATURES))
-    assert "r3d_hip_fit.h" not in open(os.path.join(ROOT, "include", "r3d_hip.h")).read()
-    header = open(os.path.join(ROOT, "include", "r3d_hip_fit.h")).read()
-    assert '#include "r3d_hip.h"' in header
-    for name, (ret, types) in decls.items():
-        res, entries = _lib.FIT_SIGNATURES[name]
-        assert res is C_RETURNS[ret] and len(entries) == len(types), name
-        for i, (e, t) in enumerate(zip(entries, types)):
-            assert entry_matches(e, t, _lib), "%s: parameter %d is %s in the header, %r in the table" % (name, i, t, e)
-        if res is ctypes.c_int:
-            assert isinstance(entries[-1], _lib.Stream), name
-        assert not any(isinstance(e, _lib.Stream) for e in entries[:-1]), name
-        fn = getattr(lib, name)          # exported, and bound by load() from the table line
-        assert fn.restype is res and list(fn.argtypes) == [getattr(e, "ctype", e) for e in entries], name
-        assert name in _lib._plans
-    assert lib.r3d_version() == _lib.ABI_VERSION == 80
-    words = re.search(r"#define R3D_FIT_LOSS_WORDS (\d+)", header)
-    launches = re.search(r"#define R3D_FIT_LAUNCHES (\d+)", header)
-    assert _lib.FIT_LOSS_WORDS == int(words.group(1)) == len(f3.LOSS_NAMES) == 8 and _lib.FIT_LAUNCHES == int(launches.group(1)) == 2
+    assert lib.r3d_version() == _lib.ABI_VERSION
+    decls = abi.header_declarations("r3d_hip_fit.h")
+    assert {name: len(types) for name, (ret, types) in decls.items()} == {"r3d_fit_workspace_bytes": 4, "r3d_fit_state_bytes": 4,
+                                                                          "r3d_fit_landmark_grad": 26, "r3d_fit_landmark_run": 24}
+    assert set(decls) <= set(_lib.SIGNATURES)
+    assert len(f3.LOSS_NAMES) == _lib.FIT_LOSS_WORDS == 8 and _lib.FIT_LAUNCHES == 2
+    for name in ("r3d_fit_landmark_grad", "r3d_fit_landmark_run"):
+        assert decls[name][1][13] == "float*" and _lib.SIGNATURES[name][1][13] is ctypes.POINTER(ctypes.c_float), name          # lambdas
 
 
 def test_sizes():
@@ -68,13 +56,7 @@ def test_argument_errors_are_refused_before_any_launch():
     grad = dict(common, id=ID, exp=EXP, euler=EU, trans=TR, gid=GID, gexp=GEXP, geu=GEU, gtr=GTR, loss=LOSS, ws=WS, wsb=BIG)
     run = dict(common, lr0=0.1, lr1=0.1, s0=0, s1=200, n=200, groups=3, state=STATE, ws=WS, wsb=BIG)
 
-    def refused(fn, base, quote, rc=-1, **over):
-        assert set(over) <= set(base), over
-        a = dict(base, **over)
-        got = getattr(lib, "r3d_fit_landmark_" + fn)(*a.values(), None)
-        msg = lib.r3d_last_error()
-        assert got == rc and b"fit_landmark_" + fn.encode() + b":" in msg and quote in msg, (fn, over, got, msg)
-
+    refused = abi.refusals(lib, "r3d_fit_landmark_")
     for fn, base in (("grad", grad), ("run", run)):
         for p in ("mean", "idb", "lms", "w", "lam"):
             refused(fn, base, b"NULL pointer", **{p: None})

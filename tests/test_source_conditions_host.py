@@ -9,7 +9,6 @@ points, which run before any HIP call; the Python functions' type, shape and dty
 import ctypes
 import glob
 import os
-import re
 import types
 
 import numpy as np
@@ -102,19 +101,16 @@ def test_the_blur_model_is_within_its_derived_bound_of_the_fp64_gaussian():
 
 def test_symbols_are_declared_exported_and_bound():
     """The six entry points live in the companion header include/r3d_hip_source.h (tests/test_abi.py compares every declaration with the
-    binding table and with what load() bound); here what is this unit's own: the parameter counts, the header's macros against the
-    package's constants, the ABI number and the package's names."""
+    binding table and with what load() bound, and the header's macros with the package's constants); here what is this unit's own: the
+    parameter counts, the ABI number and the package's names."""
     from real3dportrait_amd import _lib
-    from test_abi import header_declarations, header_source
+    from abi import header_declarations
     import real3dportrait_amd
     lib = _lib.load()
-    assert lib.r3d_version() == 80 == _lib.ABI_VERSION
+    assert lib.r3d_version() == _lib.ABI_VERSION
     decls = header_declarations("r3d_hip_source.h")
     assert set(decls) == set(ENTRY_POINTS) <= set(_lib.SIGNATURES)
     assert {name: len(types_) for name, (ret, types_) in decls.items()} == ENTRY_POINTS
-    macros = dict(re.findall(r"^#define (R3D_SOURCE_\w+) (\d+)$", header_source("r3d_hip_source.h"), flags=re.M))
-    assert macros == {"R3D_SOURCE_MAX_SIDE": str(_lib.SOURCE_MAX_SIDE), "R3D_SOURCE_STATUS_WORDS": str(_lib.SOURCE_STATUS_WORDS),
-                      "R3D_SOURCE_DARKEN": str(_lib.SOURCE_DARKEN), "R3D_SOURCE_HEAD_CLASSES": str(_lib.SOURCE_HEAD_CLASSES)}
     assert _lib.SOURCE_HEAD_CLASSES == (1 << 1) | (1 << 3) | (1 << 5)
     from real3dportrait_amd import source_conditions
     for name in ("nearest_seed", "head_image", "inpaint_torso_job", "extract_background", "source_to_planes", "patch_segment_imgs"):

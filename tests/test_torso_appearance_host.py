@@ -265,7 +265,7 @@ def test_patch_model_leaves_foreign_modules_alone():
 def test_c_entry_points_reject_bad_arguments_without_a_gpu():
     from real3dportrait_amd import _lib
     lib = _lib.load()
-    assert lib.r3d_version() == 80 == _lib.ABI_VERSION
+    assert lib.r3d_version() == _lib.ABI_VERSION
     at = lambda i: ctypes.c_void_p((1 << 30) + 4 * i)       # never dereferenced: validation fails first
     far, far2, far3, far4 = (ctypes.c_void_p(1 << s) for s in (40, 41, 42, 43))
     err = lambda: lib.r3d_last_error()

@@ -314,7 +314,7 @@ def test_patch_model_leaves_a_v1_estimator_alone():
 def test_c_entry_points_reject_bad_arguments_without_a_gpu():
     from real3dportrait_amd import _lib
     lib = _lib.load()
-    assert lib.r3d_version() == 80 == _lib.ABI_VERSION
+    assert lib.r3d_version() == _lib.ABI_VERSION
     at = lambda i: ctypes.c_void_p((1 << 30) + 4 * i)       # never dereferenced: validation fails first
     far, far2, far3 = ctypes.c_void_p(1 << 40), ctypes.c_void_p(1 << 41), ctypes.c_void_p(1 << 42)
     err = lambda: lib.r3d_last_error()

@@ -9,7 +9,6 @@ refusal of the two entry points, which run before any HIP call; the Python funct
 import ctypes
 import glob
 import os
-import re
 import types
 
 import numpy as np
@@ -105,19 +104,16 @@ def test_depth_is_normalised_over_the_clip_and_a_nan_is_byte_zero():
 
 def test_symbols_are_declared_exported_and_bound():
     """The two entry points live in the companion header include/r3d_hip_video.h (tests/test_abi.py compares every declaration with the
-    binding table and with what load() bound); here what is this unit's own: the parameter counts, the header's macros against the
-    package's constants, the ABI number and the package's names."""
+    binding table and with what load() bound, and the header's macros with the package's constants); here what is this unit's own: the
+    parameter counts, the ABI number and the package's names."""
     from real3dportrait_amd import _lib
-    from test_abi import header_declarations, header_source
+    from abi import header_declarations
     import real3dportrait_amd
     lib = _lib.load()
-    assert lib.r3d_version() == 80 == _lib.ABI_VERSION
+    assert lib.r3d_version() == _lib.ABI_VERSION
     decls = header_declarations("r3d_hip_video.h")
     assert set(decls) == {"r3d_video_depth_range", "r3d_video_compose_debug"} <= set(_lib.SIGNATURES)
     assert [len(decls[n][1]) for n in ("r3d_video_depth_range", "r3d_video_compose_debug")] == [5, 18]
-    macros = dict(re.findall(r"^#define (R3D_VIDEO_\w+) (\d+)$", header_source("r3d_hip_video.h"), flags=re.M))
-    assert macros == {"R3D_VIDEO_STATE_WORDS": str(_lib.VIDEO_STATE_WORDS), "R3D_VIDEO_PANELS_ALL": str(_lib.VIDEO_PANELS_ALL),
-                      "R3D_VIDEO_PANEL_DEPTH": str(_lib.VIDEO_PANEL_DEPTH)}
     from real3dportrait_amd import video_frames
     for name in ("depth_range", "compose_debug_frames", "clip_frames", "secc2video_frames", "write_video", "patch_secc2video"):
         assert getattr(real3dportrait_amd, name) is getattr(video_frames, name), name
