@@ -6,6 +6,8 @@ Operators keep the reference's names and signatures (see each module's docstring
     SynthesisBlockNoUp, Conv2d, ConvStack                (superresolution.py: torso/background fusion convs)
     TriPlaneGenerator (.synthesis contract), patch_model (triplane.py)
     SegFormerSECC2PlaneBackbone                          (segformer.py: the per-frame SECC encoder, mode b0)
+    Img2PlaneModel                                       (img2plane.py: the canonical image-to-plane backbone without its DeepLabV3;
+                                                         patch_model(cano_backbone=True) installs it)
     TorsoGenerator, Occlusion2Predictor                  (torso_generator.py: the torso network's warp + decoder, its Generator)
     TorsoMotionFieldEstimator                            (torso_motion.py: the torso network's per-frame MotionFieldEstimator)
     TorsoAppearanceFeatureExtractor                      (torso_appearance.py: the torso network's AppearanceFeatureExtractor)
@@ -24,7 +26,7 @@ Operators keep the reference's names and signatures (see each module's docstring
     PitchContourVAEModel, VAEModel, patch_audio2secc     (audio2motion.py: the audio-to-motion VAE behind forward_audio2secc)
     landmark_weights, fit_landmarks, fit_3dmm_for_landmarks, patch_fit_3dmm (fit_3dmm.py: the landmark-driven 3DMM fit, 400 Adam steps)
     render_clip_sharded                                  (frames.py: frame sharding + RCCL gather)
-All compute goes through libr3d_hip.so (include/r3d_hip.h); there is no eager/CPU fallback.
+All compute goes through libr3d_hip.so (include/r3d_hip.h, include/r3d_hip_img2plane.h); there is no eager/CPU fallback.
 """
 __version__ = "0.1.0"
 
@@ -41,6 +43,9 @@ def __getattr__(name):      # lazy: importing the package (e.g. for synth) must 
         return getattr(m, name)
     if name == "SegFormerSECC2PlaneBackbone":
         from . import segformer as m
+        return getattr(m, name)
+    if name == "Img2PlaneModel":
+        from . import img2plane as m
         return getattr(m, name)
     if name in ("TorsoGenerator", "Occlusion2Predictor"):
         from . import torso_generator as m

@@ -1,4 +1,5 @@
-"""ctypes binding of libr3d_hip.so (the C ABI declared in include/r3d_hip.h and the five companion headers it includes).
+"""ctypes binding of libr3d_hip.so (the C ABI declared in include/r3d_hip.h and the five companion headers it includes, and in the
+extension headers of EXTENSION_SIGNATURES, which include r3d_hip.h).
 
 The product path has NO fallback: if the HIP library is missing or fails to load, importing an
 operator raises.  Build it with `python -c "import __graft_entry__ as g; g.build()"` or
@@ -156,6 +157,19 @@ SIGNATURES = {
     "r3d_fit_landmark_run": (c_int, _FIT_COMMON + [c_float, c_float, c_int, c_int, c_int, c_int, F, V, c_size_t, S]),
 }
 
+# Headers that r3d_hip.h does not include (each includes r3d_hip.h instead): header -> its table, lines as in SIGNATURES.  load() binds them
+# the same way, and a library that lacks one of these functions does not load either; call() finds a name in whichever table holds it.
+EXTENSION_SIGNATURES = {
+    "r3d_hip_img2plane.h": {
+        "r3d_i2p_attention": (c_int, [F, F, c_int, c_int, c_int, c_int, c_int, c_float, F, S]),
+        "r3d_i2p_upsample2x": (c_int, [F, c_int, c_int, c_int, c_int, F, S]),
+        "r3d_i2p_pixel_shuffle": (c_int, [F, c_int, c_int, c_int, c_int, F, c_int, c_int, S]),
+        "r3d_i2p_copy_channels": (c_int, [F, c_size_t, c_int, F, c_int, c_int, S]),
+        "r3d_i2p_nchw_to_cl": (c_int, [F, c_int, c_int, c_int, c_int, F, S]),
+        "r3d_i2p_planes_out": (c_int, [F, c_int, c_int, c_int, c_int, F, S]),
+    },
+}
+
 # The headers' constants the package uses: _lib.X mirrors R3D_X of the header named (tests/test_abi.py compares every one).
 CHAIN_SR_BLOCK, CHAIN_CONV, CHAIN_SR_BLOCK_TAIL, CHAIN_SRC_NONE, CHAIN_MAX_OPS, CHAIN_MAX_EXT, CHAIN_MAX_ZERO = 0, 1, 2, -1000, 12, 4, 4      # r3d_hip.h
 VIDEO_STATE_WORDS, VIDEO_PANELS_ALL, VIDEO_PANEL_DEPTH = 8, 31, 8                                           # r3d_hip_video.h
@@ -224,7 +238,10 @@ def load():
         lib = ctypes.CDLL(LIB_PATH)
     except OSError as e:
         raise RuntimeError("real3dportrait_amd: cannot load %s: %s" % (LIB_PATH, e))
-    for name, (res, params) in SIGNATURES.items():
+    required = dict(SIGNATURES)
+    for table in EXTENSION_SIGNATURES.values():
+        required.update(table)
+    for name, (res, params) in required.items():
         try:
             fn = getattr(lib, name)
         except AttributeError:       # functions are added without a new ABI number: a stale in-tree build lacks them

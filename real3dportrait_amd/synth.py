@@ -278,6 +278,72 @@ def synth_secc_backbone(seed, pncc_cond_mode="cano_src_tgt", out_channels=96, qk
     return sd
 
 
+IMG2PLANE_BLOCKS = {"small": (2, 1), "standard": (5, 1), "large": (10, 3)}      # (LowResolutionViT, TriplanePredictorViT) blocks, segformer/models.py
+
+
+def img2plane_shapes(scale="standard", in_channels=5, out_channels=96):
+    """[(state_dict key, shape)] of Img2PlaneModel (modules/img2plane/img2plane_model.py:12-35) without low_reso_encoder.*: in_channels is
+    what the two encoders read, the mode's channels + 2 (rgb 5, rgb_alpha 6, rgb_camera 8, rgb_alpha_camera 9); 8 and 9 carry
+    camera_to_channel."""
+    out = [("camera_to_channel.weight", (3, 25)), ("camera_to_channel.bias", (3,))] if in_channels in (8, 9) else []
+    conv = lambda p, co, ci, k: [(p + ".weight", (co, ci, k, k)), (p + ".bias", (co,))]
+    lin = lambda p, co, ci: [(p + ".weight", (co, ci)), (p + ".bias", (co,))]
+    norm = lambda p: [(p + ".weight", (1024,)), (p + ".bias", (1024,))]
+
+    def block(p, sr):
+        b = norm(p + "norm1") + lin(p + "attn.q", 1024, 1024) + lin(p + "attn.kv", 2048, 1024) + lin(p + "attn.proj", 1024, 1024)
+        if sr > 1:
+            b += conv(p + "attn.sr", 1024, 1024, sr) + norm(p + "attn.norm")
+        return (b + norm(p + "norm2") + lin(p + "mlp.fc1", 2048, 1024) + [(p + "mlp.dwconv.dwconv.weight", (2048, 1, 3, 3)), (p + "mlp.dwconv.dwconv.bias", (2048,))]
+                + lin(p + "mlp.fc2", 1024, 2048))
+
+    n_low, n_pred = IMG2PLANE_BLOCKS[scale]
+    p = "high_reso_encoder."
+    out += conv(p + "first", 64, in_channels, 7) + conv(p + "conv_layers.0", 96, 64, 3)
+    for i in (2, 4, 6):
+        out += conv(p + "conv_layers.%d" % i, 96, 96, 3)
+    out += conv(p + "final", 96, 96, 3)
+    p = "low_reso_vit."
+    out += conv(p + "patch_embed.proj", 1024, 256, 3) + norm(p + "patch_embed.norm")
+    for i in range(1, n_low + 1):
+        out += block(p + "block%d." % i, 1)
+    out += conv(p + "conv_after_upsample1", 128, 256, 3) + conv(p + "conv_after_upsample2", 128, 128, 3) + conv(p + "final_conv", 96, 128, 3)
+    p = "triplane_predictor_vit."
+    out += conv(p + "first_conv", 256, 192, 3) + conv(p + "second_conv", 128, 256, 3)
+    out += conv(p + "patch_embed.proj", 1024, 128, 3) + norm(p + "patch_embed.norm")
+    for i in range(1, n_pred + 1):
+        out += block(p + "block%d." % i, 2)
+    out += conv(p + "first_conv_after_cat", 256, 352, 3) + conv(p + "second_conv_after_cat", 128, 256, 3)
+    out += conv(p + "third_conv_after_cat", 128, 128, 3) + conv(p + "final_conv", out_channels, 128, 3)
+    return out
+
+
+def synth_img2plane(seed, scale="standard", in_channels=5, qk_gain=1.5, out_channels=96):
+    """A state_dict (numpy) of Img2PlaneModel without low_reso_encoder.*, from hash_unitvar streams as synth_secc_backbone makes its own:
+    weights ~ N(0, gain / fan_in) with gain 2 in front of a ReLU / LeakyReLU / GELU and 1 elsewhere, biases 0.1 n, LayerNorm weights
+    1 + 0.1 n.  The q weights and the key half of the kv weights carry `qk_gain`: with LayerNorm-ed inputs the logits' spread is about
+    qk_gain^2, a softmax that is neither uniform nor one-hot at 16 .. 4096 keys."""
+    relu_fed = ("conv_layers", "conv_after_upsample", "first_conv", "second_conv", "third_conv", "mlp.fc1", "mlp.dwconv")
+    sd = {}
+    for i, (key, shape) in enumerate(img2plane_shapes(scale, in_channels, out_channels)):
+        st = 5000 + i
+        last = key.rsplit(".", 1)[-1]
+        if last == "bias":
+            v = hash_unitvar(seed, shape, st) * np.float32(0.1)
+        elif len(shape) == 1:
+            v = np.float32(1.0) + hash_unitvar(seed, shape, st) * np.float32(0.1)
+        else:
+            fan_in = int(np.prod(shape[1:]))
+            gain = 2.0 if any(n in key for n in relu_fed) else 1.0
+            v = hash_unitvar(seed, shape, st) * np.float32(math.sqrt(gain / fan_in))
+            if key.endswith("attn.q.weight"):
+                v = v * np.float32(qk_gain)
+            elif key.endswith("attn.kv.weight"):
+                v[: shape[0] // 2] *= np.float32(qk_gain)
+        sd[key] = np.asarray(v, dtype=np.float32)
+    return sd
+
+
 TORSO_C, TORSO_D = 32, 16          # the appearance volume [N, 32, 16, H, W] (facev2v_warp/network2.py:248-256)
 
 

@@ -181,7 +181,7 @@ def _reference_hparams(model):
 
 
 def patch_model(model, fuse_warp_sr=True, precision=None, secc_encoder=False, torso_generator=False, torso_motion=False, torso_precision=None,
-                torso_appearance=False, torso_forward=False):
+                torso_appearance=False, torso_forward=False, cano_backbone=False):
     """Swap the hot-path operators of a constructed reference model for the HIP ones (in place).  INFERENCE ONLY: the HIP modules
     detach their inputs and build no autograd graph (the reference runs this path under torch.no_grad(), real3d_infer.py:435,479).
     precision: SR precision of the installed blocks (None = the library default 'f16mx': inside the 2e-4 of SURVEY 8(d) on every golden and heavy-tail sweep,
@@ -226,6 +226,12 @@ def patch_model(model, fuse_warp_sr=True, precision=None, secc_encoder=False, to
       estimator, the interpolate + cat in front of occlusion_2_predictor, and the losses.  Every call computes everything; nothing is
       cached across calls.  If one of the three swaps was refused for this model, forward is left as it is; infer_forward_stage1 / 2
       always are.  The reference's forward stays reachable as torso_model._r3d_reference_forward.
+    * cano_backbone=True (opt-in): model.cano_img2plane_backbone (OSAvatarSECC_Img2plane, secc_img2plane.py:29,50-62), or
+      model.img2plane_backbone on OSAvatar_Img2plane, when -- and only when -- it is the reference's Img2PlaneModel
+      (modules/img2plane/img2plane_model.py:12-82), -> the HIP Img2PlaneModel (img2plane.py of this package: HighResoEncoder,
+      LowResolutionViT and TriplanePredictorViT in exact fp32).  Its low_reso_encoder (DeepLabV3) is the reference's own object and stays
+      torch, as does the input assembly.  The replaced module stays reachable as model._r3d_reference_cano_backbone.  Anything else is
+      left as it is.
     Parameters are copied with strict key matching; the decoder module is left untouched (the renderer reads
     decoder.net[0|2].{weight,bias} directly)."""
     import types
@@ -303,6 +309,14 @@ def patch_model(model, fuse_warp_sr=True, precision=None, secc_encoder=False, to
             tm._r3d_torso_forward = tf.TorsoForwardState()
             tm._r3d_reference_forward = tm.forward
             tm.forward = types.MethodType(tf.forward, tm)
+    if cano_backbone:
+        from . import img2plane as i2p
+        for name in ("cano_img2plane_backbone", "img2plane_backbone"):
+            bb = getattr(model, name, None)
+            if i2p.is_reference_img2plane(bb):
+                object.__setattr__(model, "_r3d_reference_cano_backbone", bb)        # reachable, not registered as a second sub-module
+                setattr(model, name, i2p.Img2PlaneModel.from_reference(bb))
+                break
     for owner in (getattr(model, "secc_img2plane_backbone", None), getattr(model, "img2plane_backbone", None)):
         _patch_sequential(owner, "to_plane_cnn", dev)       # per-frame plane producer tail (segformer.py:691-700)
     from .superresolution import set_sr_precision
