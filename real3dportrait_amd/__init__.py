@@ -24,9 +24,10 @@ Operators keep the reference's names and signatures (see each module's docstring
                                                          (source_conditions.py: the source image's head, torso and background conditions;
                                                          the name source_conditions is the module, its function source_conditions.source_conditions)
     PitchContourVAEModel, VAEModel, patch_audio2secc     (audio2motion.py: the audio-to-motion VAE behind forward_audio2secc)
+    HubertFeatureModel, hubert_features, chunk_plan, get_hubert, patch_hubert (hubert.py: the HuBERT audio features behind get_hubert)
     landmark_weights, fit_landmarks, fit_3dmm_for_landmarks, patch_fit_3dmm (fit_3dmm.py: the landmark-driven 3DMM fit, 400 Adam steps)
     render_clip_sharded                                  (frames.py: frame sharding + RCCL gather)
-All compute goes through libr3d_hip.so (include/r3d_hip.h, include/r3d_hip_img2plane.h); there is no eager/CPU fallback.
+All compute goes through libr3d_hip.so (include/r3d_hip.h, include/r3d_hip_img2plane.h, include/r3d_hip_hubert.h); there is no eager/CPU fallback.
 """
 __version__ = "0.1.0"
 
@@ -84,6 +85,9 @@ def __getattr__(name):      # lazy: importing the package (e.g. for synth) must 
     if name in ("PitchContourVAEModel", "VAEModel", "patch_audio2secc"):
         import importlib
         return getattr(importlib.import_module(".audio2motion", __name__), name)
+    if name in ("HubertFeatureModel", "hubert_features", "chunk_plan", "get_hubert", "patch_hubert"):
+        import importlib
+        return getattr(importlib.import_module(".hubert", __name__), name)
     if name in ("landmark_weights", "fit_landmarks", "fit_3dmm_for_landmarks", "patch_fit_3dmm"):
         import importlib
         return getattr(importlib.import_module(".fit_3dmm", __name__), name)

@@ -1,5 +1,5 @@
 """ctypes binding of libr3d_hip.so (the C ABI declared in include/r3d_hip.h and the five companion headers it includes, and in the
-extension headers of EXTENSION_SIGNATURES, which include r3d_hip.h).
+extension headers of EXTENSION_SIGNATURES and the feature headers of FEATURE_SIGNATURES, which include r3d_hip.h).
 
 The product path has NO fallback: if the HIP library is missing or fails to load, importing an
 operator raises.  Build it with `python -c "import __graft_entry__ as g; g.build()"` or
@@ -170,6 +170,17 @@ EXTENSION_SIGNATURES = {
     },
 }
 
+# Feature headers, each a stage of the pipeline of its own that includes r3d_hip.h: header -> its table, bound and found exactly as the
+# extension tables are (required; same _bind).
+FEATURE_SIGNATURES = {
+    "r3d_hip_hubert.h": {
+        "r3d_hubert_wave_stats": (c_int, [F, c_size_t, F64, S]),
+        "r3d_hubert_conv0": (c_int, [F, F64, c_int, c_size_t, c_size_t, c_int, F, F, F, F, c_float, c_int, c_int, c_int, F, S]),
+        "r3d_hubert_conv_ln_gelu": (c_int, [F, F, F, F, F, c_float, c_int, c_int, c_int, c_int, c_int, c_int, F, S]),
+        "r3d_hubert_pos_conv": (c_int, [F, F, F, c_int, c_int, c_int, c_int, c_int, F, S]),
+    },
+}
+
 # The headers' constants the package uses: _lib.X mirrors R3D_X of the header named (tests/test_abi.py compares every one).
 CHAIN_SR_BLOCK, CHAIN_CONV, CHAIN_SR_BLOCK_TAIL, CHAIN_SRC_NONE, CHAIN_MAX_OPS, CHAIN_MAX_EXT, CHAIN_MAX_ZERO = 0, 1, 2, -1000, 12, 4, 4      # r3d_hip.h
 VIDEO_STATE_WORDS, VIDEO_PANELS_ALL, VIDEO_PANEL_DEPTH = 8, 31, 8                                           # r3d_hip_video.h
@@ -239,7 +250,7 @@ def load():
     except OSError as e:
         raise RuntimeError("real3dportrait_amd: cannot load %s: %s" % (LIB_PATH, e))
     required = dict(SIGNATURES)
-    for table in EXTENSION_SIGNATURES.values():
+    for table in list(EXTENSION_SIGNATURES.values()) + list(FEATURE_SIGNATURES.values()):
         required.update(table)
     for name, (res, params) in required.items():
         try:

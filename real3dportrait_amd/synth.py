@@ -896,3 +896,59 @@ def synth_audio2motion_inputs(seed, B, T):
     mask[1:, T - max(1, T // 4):] = 0.0
     amp = (0.25 + 0.5 * hash_uniform(seed, B, stream=4)).reshape(B, 1).astype(np.float32)
     return {"audio": audio, "f0": f0, "blink": blink, "mouth_amp": amp, "y_mask": mask}
+
+
+# HuBERT-large (facebook/hubert-large-ls960-ft), the structure real3dportrait_amd/hubert.py builds; a config overrides any of these
+HUBERT_LARGE = {"hidden_size": 1024, "num_hidden_layers": 24, "num_attention_heads": 16, "intermediate_size": 4096, "conv_dim": (512,) * 7,
+                "conv_kernel": (10, 3, 3, 3, 3, 2, 2), "conv_stride": (5, 2, 2, 2, 2, 2, 2), "num_conv_pos_embeddings": 128,
+                "num_conv_pos_embedding_groups": 16, "layer_norm_eps": 1e-5}
+
+
+def hubert_shapes(cfg=None, masked_spec_embed=True):
+    """[(state_dict key, shape)] of transformers.HubertModel with the large model's structure (layer-norm feature extractor, stable layer
+    norm, a weight-norm positional conv held as parametrizations.weight.original0 / original1) for the widths of cfg over HUBERT_LARGE."""
+    c = dict(HUBERT_LARGE, **(cfg or {}))
+    H, I = c["hidden_size"], c["intermediate_size"]
+    lin = lambda p, co, ci: [(p + ".weight", (co, ci)), (p + ".bias", (co,))]
+    norm = lambda p, n: [(p + ".weight", (n,)), (p + ".bias", (n,))]
+    out = [("masked_spec_embed", (H,))] if masked_spec_embed else []
+    cin = 1
+    for i, (co, k) in enumerate(zip(c["conv_dim"], c["conv_kernel"])):
+        p = "feature_extractor.conv_layers.%d." % i
+        out += [(p + "conv.weight", (co, cin, k)), (p + "conv.bias", (co,))] + norm(p + "layer_norm", co)
+        cin = co
+    out += norm("feature_projection.layer_norm", cin) + lin("feature_projection.projection", H, cin)
+    kp, gp = c["num_conv_pos_embeddings"], c["num_conv_pos_embedding_groups"]
+    p = "encoder.pos_conv_embed.conv."
+    out += [(p + "bias", (H,)), (p + "parametrizations.weight.original0", (1, 1, kp)), (p + "parametrizations.weight.original1", (H, H // gp, kp))]
+    out += norm("encoder.layer_norm", H)
+    for i in range(c["num_hidden_layers"]):
+        p = "encoder.layers.%d." % i
+        for n in ("k_proj", "v_proj", "q_proj", "out_proj"):
+            out += lin(p + "attention." + n, H, H)
+        out += norm(p + "layer_norm", H) + lin(p + "feed_forward.intermediate_dense", I, H) + lin(p + "feed_forward.output_dense", H, I)
+        out += norm(p + "final_layer_norm", H)
+    return out
+
+
+def synth_hubert(seed, cfg=None, qk_gain=2.0, masked_spec_embed=True):
+    """A state_dict (numpy) for hubert_shapes: weights ~ N(0, 1 / fan_in) (2 / fan_in in front of a GELU), the q and k projections times
+    qk_gain, biases 0.1 n, LayerNorm weights 1 + 0.1 n, the weight-norm gain g = |n| + 0.5, masked_spec_embed uniform."""
+    sd = {}
+    for i, (key, shape) in enumerate(hubert_shapes(cfg, masked_spec_embed)):
+        st = 7000 + i
+        if key == "masked_spec_embed":
+            v = hash_uniform(seed, shape[0], st)
+        elif key.endswith("original0"):
+            v = np.abs(hash_unitvar(seed, shape, st)) + np.float32(0.5)
+        elif key.endswith(".bias"):
+            v = hash_unitvar(seed, shape, st) * np.float32(0.1)
+        elif len(shape) == 1:
+            v = np.float32(1.0) + hash_unitvar(seed, shape, st) * np.float32(0.1)
+        else:
+            gelu_fed = "conv" in key or "intermediate_dense" in key
+            v = hash_unitvar(seed, shape, st) * np.float32(math.sqrt((2.0 if gelu_fed else 1.0) / int(np.prod(shape[1:]))))
+            if "q_proj" in key or "k_proj" in key:
+                v = v * np.float32(qk_gain)
+        sd[key] = np.asarray(v, dtype=np.float32)
+    return sd
