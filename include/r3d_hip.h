@@ -683,8 +683,9 @@ int r3d_secc_blink(const float* secc, int T, int H, int W, const int32_t* frame_
  *   mean [3 N]; id_base [3 N, Ki] and exp_base [3 N, Ke] row-major (row 3 n + c is component c of vertex n); id [T, Ki], exp [T, Ke],
  *   euler [T, 3] in radians, trans [T, 3]; vertex [T, N, 3], the layout r3d_raster_forward reads; lm2d [T, L, 2].
  * Per frame t and vertex n:
- *   p = mean[3 n ..] + id_base[3 n .., :] . id[t] + exp_base[3 n .., :] . exp[t], one chain of fused multiply-adds per row, in this
- *       order: the mean, then k = 0 .. Ki - 1 of the identity, then k = 0 .. Ke - 1 of the expression;
+ *   p = (id_base[3 n .., :] . id[t] + exp_base[3 n .., :] . exp[t]) + mean[3 n ..]: per row one chain of fused multiply-adds from +0.0f,
+ *       in this order: k = 0 .. Ki - 1 of the identity, then k = 0 .. Ke - 1 of the expression; then one addition of the mean (last, as
+ *       bfm.py:114 adds it: the chain rounds at the size of its own sum, not at the mean's);
  *   q = M p + trans[t] with M = Rz Ry Rx of compute_rotation (bfm.py:204-238; the reference writes p @ (Rz Ry Rx)^T);
  *   q.z = camera_distance - q.z when to_camera != 0.
  * The landmarks continue with the projection of perspective_projection(focal, center): x' = (focal q.x + center q.z) / q.z, likewise

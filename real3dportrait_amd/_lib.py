@@ -197,6 +197,10 @@ OPTIONAL_SIGNATURES = {
                                          I64, F, F, F, V, c_size_t, c_int, c_int, S]),
     # r3d_secc_blink with a stage mask (1 clear, 2 quantise_bounds, 4 erode, 8 columns, 16 fill) in front of the stream
     "r3d_debug_secc_blink": (c_int, [F, c_int, c_int, c_int, I32, F64, c_int, F, I32, V, c_size_t, c_int, S]),
+    # the launch plans of the clip stage's two frame-walking kernels, host arithmetic only (no HIP call): (L, Ki, Ke, T) -> V, slabs, chunk,
+    # ychunks, nsplit, Kc, lds_bytes, ws_floats of fit_grad; (N, Ki, Ke, T) -> V, xblocks, chunk, yblocks, lds_bytes of face_model
+    "r3d_debug_fit_plan": (c_int, [c_int, c_int, c_int, c_int, ctypes.POINTER(ctypes.c_int32)]),
+    "r3d_debug_face_plan": (c_int, [c_int, c_int, c_int, c_int, ctypes.POINTER(ctypes.c_int32)]),
 }
 
 

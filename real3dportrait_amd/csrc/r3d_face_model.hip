@@ -1,7 +1,9 @@
 // Morphable face model: ParametricFaceModel.compute_face_vertex (deep_3drecon/deep_3drecon_models/bfm.py:332-347) and
 // Face3DHelper.reconstruct_lm2d (data_util/face3d_helper.py:132-169), inference only, fp32.  Per frame t and row r of the
 // bases (row 3 n + c is component c of vertex n):
-//   p[r]   = fma chain over k, in this order: mean[r], then id_base[r, 0 .. Ki) x id[t], then exp_base[r, 0 .. Ke) x exp[t]
+//   p[r]   = fma chain over k from 0.0f, in this order: id_base[r, 0 .. Ki) x id[t], then exp_base[r, 0 .. Ke) x exp[t]; then + mean[r].
+//            (The mean is added last, as the reference does: a chain begun at the mean, of size 1, rounds every one of its K small
+//            terms at the mean's ulp, and its error grows with K -- 2.9e-6 at K = 512 against 6e-7 this way.)
 //   q[c]   = fma(M[c][2], p.z, fma(M[c][1], p.y, M[c][0] p.x)) + trans[t][c], M = Rz Ry Rx (the reference multiplies p by its transpose
 //            from the right); q.z = camera_distance - q.z when to_camera
 //   lm2d   = ((focal q.x + center q.z) / q.z, image_size - (focal q.y + center q.z) / q.z) / image_size          (landmarks only)
@@ -91,7 +93,7 @@ __device__ __forceinline__ void frames(const Args& a, const float* __restrict__ 
     if (tid < F) pose(a, t0 + tid, posebuf + tid * POSE);
     float acc[F];
 #pragma unroll
-    for (int f = 0; f < F; ++f) acc[f] = mean;
+    for (int f = 0; f < F; ++f) acc[f] = 0.0f;
     if (tid < rows) {
         const float* __restrict__ ci = id + (size_t)t0 * a.Ki;
         const float* col = tile + tid;
@@ -117,7 +119,7 @@ __device__ __forceinline__ void frames(const Args& a, const float* __restrict__ 
         }
     }
 #pragma unroll
-    for (int f = 0; f < F; ++f) pbuf[f * THREADS + tid] = acc[f];
+    for (int f = 0; f < F; ++f) pbuf[f * THREADS + tid] = acc[f] + mean;          // the mean last, as the reference: the chain rounds at its own size
     __syncthreads();
     if (tid < rows) {
         const int v = tid / 3, c = tid - 3 * v;
@@ -170,15 +172,49 @@ __global__ void __launch_bounds__(THREADS) face_model(Args a, const float* __res
 
 inline bool finite(float x) { return x == x && x - x == 0.0f; }
 
+// The sizes both entry points (and the plan hook) refuse, in two steps because the entry points check exp_base between them: the counts ...
+static int check_counts(const char* what, bool lm, int N, int Ki, int Ke, int T)
+{
+    if (N < 1 || T < 1) { set_error("%s: bad argument (%s = %d, T = %d must be positive)", what, lm ? "L" : "N", N, T); return R3D_ERR_INVALID_ARG; }
+    if (Ki < 1 || Ke < 0 || (long long)Ki + Ke > 512) { set_error("%s: Ki = %d, Ke = %d: need Ki >= 1, Ke >= 0, Ki + Ke <= 512", what, Ki, Ke); return R3D_ERR_INVALID_ARG; }
+    return R3D_OK;
+}
+
+// ... and the index product
+static int check_product(const char* what, bool lm, int N, int T)
+{
+    return below_2_31(what, lm ? "3 L T" : "3 N T", 3.0 * (double)N * (double)T, "elements") ? R3D_OK : R3D_ERR_INVALID_ARG;
+}
+
+// The launch plan of accepted sizes.  A block owns V vertices and walks `chunk` frames: grid (xblocks, yblocks), lds bytes of LDS.
+struct Plan { int V, xblocks, chunk, yblocks; size_t lds; };
+
+static Plan plan(int N, int Ki, int Ke, int T)
+{
+    Plan p;
+    const int K = Ki + Ke;
+    p.V = std::min(std::min(LDS_FLOATS / (3 * K), THREADS / 3), N);          // K <= 512: at least 9 vertices
+    const long long xblocks = ((long long)N + p.V - 1) / p.V;
+    // frames are split over blockIdx.y only while the vertex tiles alone leave the chip idle (landmarks: L = 68 is two tiles); every split
+    // reads the tile again, and a frame's result does not depend on its split
+    long long want = std::max(1LL, 512 / xblocks);
+    want = std::min(std::min(want, ((long long)T + GROUP - 1) / GROUP), 65535LL);
+    const long long per = ((long long)T + want - 1) / want;
+    p.chunk = (int)std::min((long long)T, (per + GROUP - 1) / GROUP * GROUP);
+    p.xblocks = (int)xblocks;
+    p.yblocks = (int)(((long long)T + p.chunk - 1) / p.chunk);
+    p.lds = ((size_t)K * p.V * 3 + GROUP * THREADS + GROUP * POSE) * sizeof(float);
+    return p;
+}
+
 static int launch(const char* what, bool lm, const float* mean, const float* id_base, const float* exp_base, int N, int Ki, int Ke,
                   const float* id, const float* exp, const float* euler, const float* trans, int T, float camera_distance, int to_camera,
                   float focal, float center, float image_size, float* out, hipStream_t st)
 {
     if (!mean || !id_base || !id || !out) { set_error("%s: NULL pointer (mean, id_base, id and the output are required)", what); return R3D_ERR_INVALID_ARG; }
-    if (N < 1 || T < 1) { set_error("%s: bad argument (%s = %d, T = %d must be positive)", what, lm ? "L" : "N", N, T); return R3D_ERR_INVALID_ARG; }
-    if (Ki < 1 || Ke < 0 || (long long)Ki + Ke > 512) { set_error("%s: Ki = %d, Ke = %d: need Ki >= 1, Ke >= 0, Ki + Ke <= 512", what, Ki, Ke); return R3D_ERR_INVALID_ARG; }
+    if (const int rc = check_counts(what, lm, N, Ki, Ke, T)) return rc;
     if (Ke > 0 && !exp_base) { set_error("%s: exp_base is NULL with Ke = %d", what, Ke); return R3D_ERR_INVALID_ARG; }
-    if (!below_2_31(what, lm ? "3 L T" : "3 N T", 3.0 * (double)N * (double)T, "elements")) return R3D_ERR_INVALID_ARG;
+    if (const int rc = check_product(what, lm, N, T)) return rc;
     if (!finite(camera_distance)) { set_error("%s: camera_distance is not finite", what); return R3D_ERR_INVALID_ARG; }
     if (lm) {
         if (!finite(focal) || !finite(center) || !finite(image_size)) { set_error("%s: focal, center or image_size is not finite", what); return R3D_ERR_INVALID_ARG; }
@@ -193,24 +229,15 @@ static int launch(const char* what, bool lm, const float* mean, const float* id_
     a.mean = mean; a.id_base = id_base; a.exp_base = Ke > 0 ? exp_base : nullptr; a.euler = euler; a.trans = trans;
     if (Ke == 0) exp = nullptr;
     a.N = N; a.Ki = Ki; a.Ke = Ke; a.T = T;
-    const int K = Ki + Ke;
-    a.V = std::min(std::min(LDS_FLOATS / (3 * K), THREADS / 3), N);          // K <= 512: at least 9 vertices
-    const long long xblocks = ((long long)N + a.V - 1) / a.V;
-    // frames are split over blockIdx.y only while the vertex tiles alone leave the chip idle (landmarks: L = 68 is two tiles); every split
-    // reads the tile again, and a frame's result does not depend on its split
-    long long want = std::max(1LL, 512 / xblocks);
-    want = std::min(std::min(want, ((long long)T + GROUP - 1) / GROUP), 65535LL);
-    const long long per = ((long long)T + want - 1) / want;
-    a.chunk = (int)std::min((long long)T, (per + GROUP - 1) / GROUP * GROUP);
-    const unsigned yblocks = (unsigned)(((long long)T + a.chunk - 1) / a.chunk);
+    const Plan p = plan(N, Ki, Ke, T);
+    a.V = p.V; a.chunk = p.chunk;
     a.id_wide = aligned16(id_base) && (Ki & 3) == 0;
     a.exp_wide = Ke > 0 && aligned16(exp_base) && (Ke & 3) == 0;
     a.camera_distance = camera_distance; a.focal = focal; a.center = center; a.image_size = image_size; a.to_camera = to_camera ? 1 : 0;
-    const size_t lds = ((size_t)K * a.V * 3 + GROUP * THREADS + GROUP * POSE) * sizeof(float);
 
     ProfScope ps(R3D_PROF_MISC, st);
-    if (lm) hipLaunchKernelGGL(face_model<true>, dim3((unsigned)xblocks, yblocks), dim3(THREADS), lds, st, a, id, exp, out);
-    else hipLaunchKernelGGL(face_model<false>, dim3((unsigned)xblocks, yblocks), dim3(THREADS), lds, st, a, id, exp, out);
+    if (lm) hipLaunchKernelGGL(face_model<true>, dim3((unsigned)p.xblocks, (unsigned)p.yblocks), dim3(THREADS), p.lds, st, a, id, exp, out);
+    else hipLaunchKernelGGL(face_model<false>, dim3((unsigned)p.xblocks, (unsigned)p.yblocks), dim3(THREADS), p.lds, st, a, id, exp, out);
     return check_launch(what);
 }
 
@@ -233,4 +260,17 @@ extern "C" int r3d_face_landmarks(const float* key_mean, const float* key_id_bas
 {
     return face::launch("face_landmarks", true, key_mean, key_id_base, key_exp_base, L, Ki, Ke, id, exp, euler, trans, T, camera_distance,
                         to_camera, focal, center, image_size, lm2d, (hipStream_t)stream);
+}
+
+// Test hook outside the C ABI of include/r3d_hip.h (OPTIONAL_SIGNATURES of real3dportrait_amd/_lib.py): the plan both entry points launch
+// with at these sizes, out = V, xblocks, chunk, yblocks, lds_bytes; sizes they refuse are refused here with the same status.  No HIP call.
+extern "C" int r3d_debug_face_plan(int N, int Ki, int Ke, int T, int32_t out[5])
+{
+    const char* what = "debug_face_plan";
+    if (!out) { set_error("%s: NULL pointer (out)", what); return R3D_ERR_INVALID_ARG; }
+    if (const int rc = face::check_counts(what, false, N, Ki, Ke, T)) return rc;
+    if (const int rc = face::check_product(what, false, N, T)) return rc;
+    const face::Plan p = face::plan(N, Ki, Ke, T);
+    out[0] = p.V; out[1] = p.xblocks; out[2] = p.chunk; out[3] = p.yblocks; out[4] = (int32_t)p.lds;
+    return R3D_OK;
 }

@@ -104,6 +104,16 @@ __device__ __forceinline__ void copy_run(const float* __restrict__ src, float* _
     for (size_t i = threadIdx.x; i < n; i += THREADS) dst[i] = src[i];
 }
 
+// phase B's split of k: row r of a block's rows3 = 3 V rows is summed by nsplit threads, Kc terms each (the last part the rest).
+// Written once for the kernel and for the plan the host reports.
+struct Split { int nsplit, Kc; };
+
+__host__ __device__ __forceinline__ Split split_k(int K, int rows3)
+{
+    const int nsplit = THREADS / rows3;          // rows3 <= 255: at least one part
+    return {nsplit, (K + nsplit - 1) / nsplit};
+}
+
 __global__ void __launch_bounds__(THREADS) fit_grad(GradArgs a)
 {
     extern __shared__ float4 lds4[];
@@ -134,7 +144,8 @@ __global__ void __launch_bounds__(THREADS) fit_grad(GradArgs a)
         s += (size_t)a.T * 3;
         copy_run(a.trans + (size_t)t0 * 3, s + (size_t)t0 * 3, n * 3);
     }
-    const int nsplit = THREADS / rows3, Kc = (K + nsplit - 1) / nsplit;          // rows3 <= 255: at least one part
+    const Split sp = split_k(K, rows3);
+    const int nsplit = sp.nsplit, Kc = sp.Kc;
     const int part = tid / rows3, r = tid - part * rows3;
     for (int t = t0; t < t1; ++t) {
         // (the last reader of posebuf and cbuf, phase C / B of the frame before, is two barriers back)
@@ -333,7 +344,7 @@ __global__ void __launch_bounds__(THREADS) fit_step(StepArgs a)
 
 inline bool finite(float x) { return x == x && x - x == 0.0f; }
 
-struct Plan { int V, slabs, chunk, ychunks; size_t ws_floats, params, lds; };
+struct Plan { int V, slabs, chunk, ychunks, nsplit, Kc; size_t ws_floats, params, lds; };
 
 static bool sizes_ok(int L, int Ki, int Ke, int T) { return L >= 1 && T >= 1 && Ki >= 1 && Ke >= 0 && (long long)Ki + Ke <= 512; }
 
@@ -347,11 +358,13 @@ static Plan plan(int L, int Ki, int Ke, int T)
     long long want = std::max(1LL, 512LL / p.slabs);
     want = std::min(std::min(want, (long long)T), 65535LL);
     p.chunk = (int)(((long long)T + want - 1) / want);
-    p.ychunks = (T + p.chunk - 1) / p.chunk;
+    p.ychunks = (int)(((long long)T + p.chunk - 1) / p.chunk);
     p.ws_floats = (size_t)p.slabs * T * (K + SHARES);
     p.ws_floats = (p.ws_floats + 3) & ~(size_t)3;
     p.params = ((size_t)T * (K + 6) + 3) & ~(size_t)3;          // the snapshot's room: a row of id per frame at the most
     const int rows3 = 3 * p.V;
+    const Split sp = split_k(K, rows3);
+    p.nsplit = sp.nsplit; p.Kc = sp.Kc;
     p.lds = ((size_t)K * (rows3 | 1) + K + 2 * THREADS + SHARES * p.V + PG * POSE + rows3 + p.V) * sizeof(float);
     return p;
 }
@@ -363,21 +376,35 @@ struct Common {
     const float* lambdas;
 };
 
+// The sizes both entry points (and the plan hook) refuse, in two steps because the entry points check their other arguments between
+// them: the counts ...
+static int check_counts(const char* what, int L, int Ki, int Ke, int T)
+{
+    if (L < 1 || T < 1) { set_error("%s: bad argument (L = %d, T = %d must be positive)", what, L, T); return R3D_ERR_INVALID_ARG; }
+    if (Ki < 1 || Ke < 0 || (long long)Ki + Ke > 512) { set_error("%s: Ki = %d, Ke = %d: need Ki >= 1, Ke >= 0, Ki + Ke <= 512", what, Ki, Ke); return R3D_ERR_INVALID_ARG; }
+    return R3D_OK;
+}
+
+// ... and the index products, of counts that passed
+static int check_products(const char* what, int L, int Ki, int Ke, int T)
+{
+    const Plan p = plan(L, Ki, Ke, T);
+    if (!below_2_31(what, "slabs T (Ki + Ke + 7)", (double)p.slabs * T * (Ki + Ke + SHARES), "elements")) return R3D_ERR_INVALID_ARG;
+    if (!below_2_31(what, "2 L T", 2.0 * L * T, "elements")) return R3D_ERR_INVALID_ARG;
+    return R3D_OK;
+}
+
 static int check_common(const char* what, const Common& c)
 {
     if (!c.mean || !c.id_base || !c.lms || !c.weights || !c.lambdas) { set_error("%s: NULL pointer (key_mean, key_id_base, lms, weights and lambdas are required)", what); return R3D_ERR_INVALID_ARG; }
-    if (c.L < 1 || c.T < 1) { set_error("%s: bad argument (L = %d, T = %d must be positive)", what, c.L, c.T); return R3D_ERR_INVALID_ARG; }
-    if (c.Ki < 1 || c.Ke < 0 || (long long)c.Ki + c.Ke > 512) { set_error("%s: Ki = %d, Ke = %d: need Ki >= 1, Ke >= 0, Ki + Ke <= 512", what, c.Ki, c.Ke); return R3D_ERR_INVALID_ARG; }
+    if (const int rc = check_counts(what, c.L, c.Ki, c.Ke, c.T)) return rc;
     if (c.Ke > 0 && !c.exp_base) { set_error("%s: key_exp_base is NULL with Ke = %d", what, c.Ke); return R3D_ERR_INVALID_ARG; }
     if (c.id_rows != 1 && c.id_rows != c.T) { set_error("%s: id_rows = %d is neither 1 nor T = %d", what, c.id_rows, c.T); return R3D_ERR_INVALID_ARG; }
     if (!finite(c.camera_distance) || !finite(c.focal) || !finite(c.center)) { set_error("%s: camera_distance, focal or center is not finite", what); return R3D_ERR_INVALID_ARG; }
     if (!(c.focal > 0.0f)) { set_error("%s: focal = %g must be positive", what, (double)c.focal); return R3D_ERR_INVALID_ARG; }
     for (int i = 0; i < 6; ++i)
         if (!finite(c.lambdas[i])) { set_error("%s: lambdas[%d] is not finite", what, i); return R3D_ERR_INVALID_ARG; }
-    const Plan p = plan(c.L, c.Ki, c.Ke, c.T);
-    if (!below_2_31(what, "slabs T (Ki + Ke + 7)", (double)p.slabs * c.T * (c.Ki + c.Ke + SHARES), "elements")) return R3D_ERR_INVALID_ARG;
-    if (!below_2_31(what, "2 L T", 2.0 * c.L * c.T, "elements")) return R3D_ERR_INVALID_ARG;
-    return R3D_OK;
+    return check_products(what, c.L, c.Ki, c.Ke, c.T);
 }
 
 // the two launches of one evaluation: `g` and `s` hold everything but the plan's numbers
@@ -484,5 +511,20 @@ extern "C" int r3d_fit_landmark_run(const float* key_mean, const float* key_id_b
         s.rsq_frame = (float)std::sqrt(1.0 - std::pow(0.999, (double)s.step_frame));
         if (const int rc = fit::enqueue(what, c, p, g, s, workspace, (hipStream_t)stream)) return rc;
     }
+    return R3D_OK;
+}
+
+// Test hook outside the C ABI of include/r3d_hip_fit.h (OPTIONAL_SIGNATURES of real3dportrait_amd/_lib.py): the plan both entry points
+// launch fit_grad with at these sizes, out = V, slabs, chunk, ychunks, nsplit, Kc, lds_bytes, ws_floats (the partials' part of the
+// workspace; the snapshot's room follows it); sizes they refuse are refused here with the same status.  No HIP call.
+extern "C" int r3d_debug_fit_plan(int L, int Ki, int Ke, int T, int32_t out[8])
+{
+    const char* what = "debug_fit_plan";
+    if (!out) { set_error("%s: NULL pointer (out)", what); return R3D_ERR_INVALID_ARG; }
+    if (const int rc = fit::check_counts(what, L, Ki, Ke, T)) return rc;
+    if (const int rc = fit::check_products(what, L, Ki, Ke, T)) return rc;
+    const fit::Plan p = fit::plan(L, Ki, Ke, T);
+    out[0] = p.V; out[1] = p.slabs; out[2] = p.chunk; out[3] = p.ychunks; out[4] = p.nsplit; out[5] = p.Kc;
+    out[6] = (int32_t)p.lds; out[7] = (int32_t)p.ws_floats;
     return R3D_OK;
 }

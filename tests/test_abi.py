@@ -124,7 +124,11 @@ def test_debug_twins_extend_their_product_function():
     from real3dportrait_amd import _lib
     extras = {"r3d_debug_raster_forward": ("r3d_raster_forward", [ctypes.c_int, ctypes.c_int]),          # large-face threshold, stage mask
               "r3d_debug_secc_blink": ("r3d_secc_blink", [ctypes.c_int])}                                 # stage mask
-    assert set(_lib.OPTIONAL_SIGNATURES) == set(extras) | {"r3d_debug_merge_fallbacks"}
+    plans = {"r3d_debug_fit_plan", "r3d_debug_face_plan"}                                                 # host arithmetic, no product twin
+    assert set(_lib.OPTIONAL_SIGNATURES) == set(extras) | {"r3d_debug_merge_fallbacks"} | plans
+    for name in plans:
+        assert name not in header_declarations()
+        assert _lib.OPTIONAL_SIGNATURES[name] == (ctypes.c_int, [ctypes.c_int] * 4 + [ctypes.POINTER(ctypes.c_int32)]), name
     header = header_declarations()
     for twin, (product, extra) in extras.items():
         assert twin not in header

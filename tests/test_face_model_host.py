@@ -232,3 +232,103 @@ def test_python_wrappers_refuse_malformed_input_before_the_library():
         compute_face_vertex(m, torch.zeros(2, 7), torch.zeros(2, 5), torch.zeros(2, 3), torch.zeros(2, 3))
     with pytest.raises(ValueError, match="on the GPU"):
         get_driving_motion(None, None, torch.zeros(2, 7), torch.zeros(2, 5), torch.zeros(2, 3), torch.zeros(2, 3))
+
+
+# ---- the launch plan (face::plan of csrc/r3d_face_model.hip through the host-only hook r3d_debug_face_plan) ----
+PLAN_NS = (1, 5, 37, 68, 468, 625, 35709)
+PLAN_KS = (1, 3, 50, 51, 100, 144, 511, 512)
+PLAN_TS = (1, 7, 8, 9, 16, 17, 51, 500, 2000, 70000)
+FACE_PLAN = ("V", "xblocks", "chunk", "yblocks", "lds_bytes")
+# the shapes tests/test_gpu_face_model.py runs for their plan: (N, Ki, Ke, T) -> (chunk, yblocks, frames of the last chunk)
+GPU_PLAN_CASES = {(625, 448, 64, 100): (16, 7, 4), (625, 448, 64, 93): (16, 6, 13), (2200, 80, 64, 77): (16, 5, 13), (625, 80, 64, 300): (16, 19, 12)}
+
+
+def face_plan(N, Ki, Ke, T):
+    """-> (status, {V, xblocks, chunk, yblocks, lds_bytes}) of r3d_debug_face_plan; no HIP call is made."""
+    from real3dportrait_amd import _lib
+    lib = _lib.load()
+    assert hasattr(lib, "r3d_debug_face_plan"), "%s does not export the plan hook: rebuild it" % _lib.LIB_PATH
+    out = (ctypes.c_int32 * 5)(*[-1] * 5)
+    rc = lib.r3d_debug_face_plan(N, Ki, Ke, T, out)
+    return rc, dict(zip(FACE_PLAN, out))
+
+
+def test_plan_invariants_over_the_sweep():
+    """Every (N, K, T) of the sweep: what the kernel relies on (V vertices fit a block's threads and LDS, the chunks tile T with none
+    empty, whole groups of 8 frames per chunk unless one block walks all of T, grid.y within HIP's limit), and the sizes the entry points
+    refuse (3 N T >= 2^31) are refused by the hook with the same status and reason."""
+    from real3dportrait_amd import _lib
+    lib = _lib.load()
+    P = lambda k: ctypes.c_void_p(k << 40)              # never dereferenced: the refusal comes first
+    refused = 0
+    for N in PLAN_NS:
+        for K in PLAN_KS:
+            Ke = K // 3
+            Ki = K - Ke
+            for T in PLAN_TS:
+                rc, p = face_plan(N, Ki, Ke, T)
+                if 3 * N * T >= 1 << 31:
+                    assert rc == -1 and b"debug_face_plan" in lib.r3d_last_error() and b"2^31" in lib.r3d_last_error(), (N, K, T)
+                    assert lib.r3d_face_vertex(P(1), P(2), P(3), N, Ki, Ke, P(4), P(5), P(6), P(7), T, 10.0, 1, P(8), None) == rc
+                    assert b"face_vertex" in lib.r3d_last_error() and b"2^31" in lib.r3d_last_error()
+                    refused += 1
+                    continue
+                assert rc == 0, (N, K, T, lib.r3d_last_error())
+                V, xb, chunk, yb, lds = (p[k] for k in FACE_PLAN)
+                assert 1 <= V <= min(N, 128 // 3) and 3 * V * K <= 15000, (N, K, T, p)
+                assert V * (xb - 1) < N <= V * xb, (N, K, T, p)
+                assert lds == (3 * V * K + 8 * 128 + 8 * 12) * 4 and lds <= 65536, (N, K, T, p)
+                assert 1 <= chunk and chunk * (yb - 1) < T <= chunk * yb, (N, K, T, p)
+                assert 1 <= yb <= 65535 and 1 <= xb <= 2 ** 31 - 1, (N, K, T, p)
+                assert chunk % 8 == 0 or chunk == T, (N, K, T, p)
+    assert refused == len(PLAN_KS)          # N = 35 709 at T = 70 000 alone
+    out = (ctypes.c_int32 * 5)()
+    for bad in ((0, 80, 64, 5), (37, 0, 64, 5), (37, 80, -1, 5), (37, 449, 64, 5), (37, 80, 64, 0)):
+        assert lib.r3d_debug_face_plan(*bad, out) == -1 and b"debug_face_plan" in lib.r3d_last_error(), bad
+    assert lib.r3d_debug_face_plan(37, 80, 64, 5, None) == -1 and b"NULL" in lib.r3d_last_error()
+
+
+def test_plan_values_are_pinned():
+    """The regimes by number.  The product's mesh (N = 35 709, K = 80 + 64, T = 250): 1051 vertex tiles fill the chip, so the frames are
+    not split and ONE block walks all 250, 31 groups of 8 then 2.  The suite's older shapes: at most one group of 8 per block.  The shapes
+    of test_gpu_face_model.py's long-walk cases: chunks of 16, two groups of 8 per block, and the tails named there.  A change to a plan
+    constant has to come through here."""
+    assert face_plan(35709, 80, 64, 250) == (0, dict(V=34, xblocks=1051, chunk=250, yblocks=1, lds_bytes=(144 * 102 + 1024 + 96) * 4))
+    assert face_plan(68, 80, 64, 250)[1] == dict(V=34, xblocks=2, chunk=8, yblocks=32, lds_bytes=63232)          # landmarks: frames split
+    for N in (1, 37, 625):
+        for Ki, Ke in ((80, 64), (7, 5), (80, 0)):
+            for T in (1, 3, 5, 50, 51):
+                p = face_plan(N, Ki, Ke, T)[1]
+                assert p["chunk"] == min(T, 8), (N, Ki, Ke, T, p)
+    for (N, Ki, Ke, T), (chunk, yblocks, last) in GPU_PLAN_CASES.items():
+        p = face_plan(N, Ki, Ke, T)[1]
+        assert (p["chunk"], p["yblocks"], T - chunk * (yblocks - 1)) == (chunk, yblocks, last), (N, Ki, Ke, T, p)
+    assert face_plan(625, 448, 64, 100)[1]["V"] == 9 and face_plan(2200, 80, 64, 77)[1]["xblocks"] == 65
+
+
+def test_the_mean_is_added_last_because_a_chain_begun_at_it_misses_the_bound():
+    """Why the kernel's rule is `chain from 0, then + mean`, without a GPU: face_model_ref64.kernel_fp32 restates the kernel's fp32
+    operations in either order, on the inputs of test_gpu_face_model.py's long-walk cases.  Begun at the mean (of size 1) every one of
+    the K small terms is rounded at the mean's ulp: 2.907e-06 for vertices at K = 512 and 7.996e-07 for 2200 landmarks, over the bounds
+    the GPU tests hold (4 x the reference's own fp32 error on its fixture), and what the kernel measured while it summed that way.  With
+    the mean last: 6.2e-07 and 2.5e-07, what NumPy's fp32 evaluation of the reference's own expression gives."""
+    vert_tol = 4.0 * float(load_golden("face_model_b_n625_t51")["ref_err_vs_fp64"])
+    lm_tol = 4.0 * float(load_golden("face_model_c_lm68_t51")["ref_err_vs_fp64"])
+    N, Ki, Ke, T = 625, 448, 64, 100
+    m = synth.synth_face_model(24, 0, Ki, Ke)
+    host = m["mean_shape"].reshape(-1), m["id_base"], m["exp_base"]
+    coef = F64.coefficients(300 + N + T, T, Ki, Ke)
+    ref = F64.face_vertex(*host, *coef)
+    err = {first: float(np.abs(F64.kernel_fp32(*host, *coef, mean_first=first) - ref).max()) for first in (True, False)}
+    own = float(np.abs(F64.face_vertex(*host, *coef, dtype=np.float32) - ref).max())
+    print("vertices N %d T %d K %d+%d: chain begun at the mean %.3e, mean last %.3e, the reference's expression in fp32 %.3e (bound %.3e)"
+          % (N, T, Ki, Ke, err[True], err[False], own, vert_tol))
+    assert err[False] <= vert_tol / 2 < vert_tol < err[True] and err[False] <= 1.1 * own
+    L, T = 2200, 77
+    m = synth.synth_face_model(46, 0)
+    host = m["mean_shape"].reshape(-1)[:3 * L], m["id_base"][:3 * L], m["exp_base"][:3 * L]
+    coef = F64.coefficients(200 + L + T, T)
+    ref = F64.landmarks(*host, *coef)
+    err = {first: float(np.abs(F64.kernel_fp32(*host, *coef, mean_first=first, landmarks=True) - ref).max()) for first in (True, False)}
+    print("landmarks L %d T %d: chain begun at the mean %.3e, mean last %.3e (bound %.3e)" % (L, T, err[True], err[False], lm_tol))
+    assert err[False] <= lm_tol / 2 < lm_tol < err[True]

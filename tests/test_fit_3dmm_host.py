@@ -198,3 +198,93 @@ def test_exported_from_the_package():
     import real3dportrait_amd as pkg
     for name in ("landmark_weights", "fit_landmarks", "fit_3dmm_for_landmarks", "patch_fit_3dmm"):
         assert getattr(pkg, name) is getattr(f3, name)
+
+
+# ---- the launch plan (fit::plan of csrc/r3d_fit_3dmm.hip through the host-only hook r3d_debug_fit_plan) ----
+PLAN_LS = (1, 5, 37, 68, 468, 625, 35709)
+PLAN_KS = (1, 3, 50, 51, 100, 144, 511, 512)
+PLAN_TS = (1, 7, 8, 9, 16, 17, 51, 500, 2000, 70000)
+FIT_PLAN = ("V", "slabs", "chunk", "ychunks", "nsplit", "Kc", "lds_bytes", "ws_floats")
+PG = 16          # frames whose poses fit_grad computes together
+# the shapes tests/test_gpu_fit_3dmm.py runs for their plan: (L, Ki, Ke, T) -> (chunk, ychunks, frames of the last chunk, nsplit)
+GPU_PLAN_CASES = {(468, 80, 64, 497): (17, 30, 4, 2), (468, 448, 64, 137): (18, 8, 11, 10)}
+# ... and for their K regime, at T = 3: (L, Ki, Ke) -> (V, nsplit, Kc)
+GPU_K_CASES = {(468, 50, 0): (85, 1, 50), (468, 51, 0): (83, 1, 51), (468, 100, 0): (42, 2, 50), (40, 448, 64): (8, 10, 52), (468, 1, 0): (85, 1, 1)}
+
+
+def fit_plan(L, Ki, Ke, T):
+    """-> (status, {V, slabs, chunk, ychunks, nsplit, Kc, lds_bytes, ws_floats}) of r3d_debug_fit_plan; no HIP call is made."""
+    lib = _lib.load()
+    assert hasattr(lib, "r3d_debug_fit_plan"), "%s does not export the plan hook: rebuild it" % _lib.LIB_PATH
+    out = (ctypes.c_int32 * 8)(*[-1] * 8)
+    rc = lib.r3d_debug_fit_plan(L, Ki, Ke, T, out)
+    return rc, dict(zip(FIT_PLAN, out))
+
+
+def test_plan_invariants_over_the_sweep():
+    """Every (L, K, T) of the sweep: what fit_grad relies on (a thread per row of the slab, nsplit parts of a row within the block's 256
+    threads and pbuf's 256 floats, the parts cover K, the LDS request within 64 KiB, the chunks tile T with none empty, grid.y within
+    HIP's limit), the workspace the caller is asked for is the partial rows plus the snapshot's room, and the sizes the entry points refuse
+    are refused by the hook with the same status and reason."""
+    lib = _lib.load()
+    lam = (ctypes.c_float * 6)(0.2, 0.6, 1.0, 1.0, 0.3, 0.3)
+    refused = 0
+    for L in PLAN_LS:
+        for K in PLAN_KS:
+            Ke = K // 3
+            Ki = K - Ke
+            for T in PLAN_TS:
+                rc, p = fit_plan(L, Ki, Ke, T)
+                V = max(1, min(12800 // (3 * K), 85, L))
+                slabs = -(-L // V)
+                if slabs * T * (K + 7) >= 1 << 31 or 2 * L * T >= 1 << 31:
+                    msg = lib.r3d_last_error()
+                    assert rc == -1 and b"debug_fit_plan" in msg and b"2^31" in msg, (L, K, T)
+                    ptrs = [i << 40 for i in range(1, 15)]
+                    got = lib.r3d_fit_landmark_grad(ptrs[0], ptrs[1], ptrs[2], L, Ki, Ke, ptrs[3], ptrs[4], T, 1, 10.0, 1015.0, 112.0, lam,
+                                                    *ptrs[5:14], ptrs[13] + (1 << 39), 1 << 38, None)
+                    assert got == rc and lib.r3d_last_error() == msg.replace(b"debug_fit_plan", b"fit_landmark_grad"), (L, K, T)
+                    refused += 1
+                    continue
+                assert rc == 0, (L, K, T, lib.r3d_last_error())
+                assert (p["V"], p["slabs"]) == (V, slabs) and 1 <= V and 3 * V <= 255, (L, K, T, p)
+                chunk, ychunks, nsplit, Kc = p["chunk"], p["ychunks"], p["nsplit"], p["Kc"]
+                assert 1 <= chunk and chunk * (ychunks - 1) < T <= chunk * ychunks and 1 <= ychunks <= 65535, (L, K, T, p)
+                assert nsplit >= 1 and nsplit * 3 * V <= 256 and Kc * nsplit >= K, (L, K, T, p)
+                rows3 = 3 * V
+                assert p["lds_bytes"] == (K * (rows3 | 1) + K + 2 * 256 + 7 * V + PG * 39 + rows3 + V) * 4 and p["lds_bytes"] <= 65536, (L, K, T, p)
+                assert p["ws_floats"] == (slabs * T * (K + 7) + 3) // 4 * 4, (L, K, T, p)
+                room = (T * (K + 6) + 3) // 4 * 4          # the snapshot: a row of id per frame at the most
+                assert p["ws_floats"] + room == lib.r3d_fit_workspace_bytes(L, Ki, Ke, T) // 4, (L, K, T, p)
+    assert refused > 0
+    out = (ctypes.c_int32 * 8)()
+    for bad in ((0, 80, 64, 5), (468, 0, 64, 5), (468, 80, -1, 5), (468, 449, 64, 5), (468, 80, 64, 0), (1 << 20, 80, 64, 1 << 12)):
+        assert lib.r3d_debug_fit_plan(*bad, out) == -1 and b"debug_fit_plan" in lib.r3d_last_error(), bad
+    assert lib.r3d_debug_fit_plan(468, 80, 64, 5, None) == -1 and b"NULL" in lib.r3d_last_error()
+
+
+def test_plan_values_are_pinned():
+    """The regimes by number.  A video of 500 / 2000 frames (L = 468, K = 80 + 64): chunks of 17 / 67 frames, longer than the PG = 16
+    poses a block computes at once, so every block refreshes its poses mid-chunk.  The suite's older shapes: chunks of 1 or 2.  The K
+    regimes: K = 512, the top end (8 points a slab, rows split 10 ways, 52 + ... + 44 columns); K = 50 -> 51, where V steps from 85 to
+    83 and the LDS request is within 300 bytes of the largest (K = 52).  The shapes of test_gpu_fit_3dmm.py's long-chunk and K cases.  A change to a plan constant has
+    to come through here."""
+    p500, p2000 = fit_plan(468, 80, 64, 500)[1], fit_plan(468, 80, 64, 2000)[1]
+    assert (p500["V"], p500["slabs"], p500["chunk"], p500["ychunks"], p500["nsplit"]) == (29, 17, 17, 30, 2)
+    assert (p2000["chunk"], p2000["ychunks"]) == (67, 30) and p500["chunk"] > PG
+    for L in (5, 37, 468):
+        for Ki, Ke in ((3, 0), (80, 64)):
+            for T in (1, 2, 3, 7, 51, 53):
+                p = fit_plan(L, Ki, Ke, T)[1]
+                assert p["chunk"] in (1, 2), (L, Ki, Ke, T, p)
+    assert [(fit_plan(L, 3, 0, 3)[1]["V"], fit_plan(L, 3, 0, 3)[1]["nsplit"]) for L in (468, 5)] == [(85, 1), (5, 17)]
+    top = fit_plan(468, 448, 64, 3)[1]
+    assert (top["V"], top["nsplit"], top["Kc"], 512 - 9 * top["Kc"], top["lds_bytes"]) == (8, 10, 52, 44, 58144)
+    assert [(fit_plan(468, K, 0, 3)[1]["V"], fit_plan(468, K, 0, 3)[1]["lds_bytes"]) for K in (50, 51)] == [(85, 59484), (83, 59196)]
+    assert max(fit_plan(468, K, 0, 3)[1]["lds_bytes"] for K in range(1, 513)) == 59736          # K = 52, V = 82; every K stays under 64 KiB
+    for (L, Ki, Ke, T), (chunk, ychunks, last, nsplit) in GPU_PLAN_CASES.items():
+        p = fit_plan(L, Ki, Ke, T)[1]
+        assert (p["chunk"], p["ychunks"], T - chunk * (ychunks - 1), p["nsplit"]) == (chunk, ychunks, last, nsplit), (L, Ki, Ke, T, p)
+    for (L, Ki, Ke), want in GPU_K_CASES.items():
+        p = fit_plan(L, Ki, Ke, 3)[1]
+        assert (p["V"], p["nsplit"], p["Kc"]) == want, (L, Ki, Ke, p)

@@ -7,7 +7,9 @@ the figure it asserts (pytest -s).
 
 Measured on one MI355X, of max|ref|: gradients 1.3e-6 at worst (the restatement's own fp32 autograd: 2.7e-6), iterations 1.5e-6, whole
 fits 1.3e-5 (id of the image case; absolute 5.9e-6 / 7.8e-6 / 7.7e-8 / 6.2e-7 for id / exp / euler / trans, recorded per case as
-gpu_err_vs_fp64 in the goldens beside ref_err_vs_fp64, the fp32 restatement's own distance from fp64), final landmark loss 2.8e-6."""
+gpu_err_vs_fp64 in the goldens beside ref_err_vs_fp64, the fp32 restatement's own distance from fp64), final landmark loss 2.8e-6.
+The cases over chunks longer than a pose group and over the K regimes assert the plan they claim through the library's own answer,
+r3d_debug_fit_plan (tests/test_fit_3dmm_host.py pins the numbers): gradients 2.7e-7, iterations 1.0e-5 (three steps at T = 497)."""
 import types
 
 import numpy as np
@@ -17,6 +19,7 @@ import torch
 import fit_3dmm_ref as R
 from conftest import load_golden
 from real3dportrait_amd import _lib, synth
+from test_fit_3dmm_host import GPU_K_CASES, GPU_PLAN_CASES, PG, fit_plan
 
 pytestmark = pytest.mark.gpu
 
@@ -70,15 +73,9 @@ def close(got, ref, what, tol=TOL):
     return err / top if top else 0.0
 
 
-@pytest.mark.parametrize("id_rows_is_T", [False, True])
-@pytest.mark.parametrize("T", [1, 2, 3, 51])
-@pytest.mark.parametrize("Ki,Ke", [(3, 0), (80, 64)])
-@pytest.mark.parametrize("L", [5, 37, 468])
-def test_gradients_against_fp64_autograd(L, Ki, Ke, T, id_rows_is_T):
-    """r3d_fit_landmark_grad at non-zero random parameters: the loss record and each of the four gradients of the total against fp64
-    autograd of the restatement.  L = 5 is one partial slab, 37 and 468 end in a slab that is not full; T = 1, 2, 3 are the Laplacian's
-    replicate edges; id_rows 1 sums the id gradient over the frames.  The reference's own fp32 autograd error is printed beside."""
-    id_rows = T if id_rows_is_T else 1
+def check_gradients(L, Ki, Ke, T, id_rows):
+    """r3d_fit_landmark_grad at the case's inputs(): the loss record (1e-4 relative) and each of the four gradients of the total (TOL of
+    max|ref|) against fp64 autograd of the restatement; the restatement's own fp32 autograd error is printed beside."""
     arrays, lms, w, params = inputs(L, Ki, Ke, T, id_rows)
     words, grads = R.gradients(arrays, lms, w, LAMBDAS, params)
     _, grads32 = R.gradients(arrays, lms, w, LAMBDAS, params, dtype=torch.float32)
@@ -94,6 +91,41 @@ def test_gradients_against_fp64_autograd(L, Ki, Ke, T, id_rows_is_T):
     for i, name in enumerate(fit3d().LOSS_NAMES):
         print("loss %s: got %.6e ref %.6e" % (name, got[i], words[i]))
         assert abs(got[i] - words[i]) <= 1e-4 * abs(words[i]) + 1e-12, (name, got[i], words[i])
+
+
+@pytest.mark.parametrize("id_rows_is_T", [False, True])
+@pytest.mark.parametrize("T", [1, 2, 3, 51])
+@pytest.mark.parametrize("Ki,Ke", [(3, 0), (80, 64)])
+@pytest.mark.parametrize("L", [5, 37, 468])
+def test_gradients_against_fp64_autograd(L, Ki, Ke, T, id_rows_is_T):
+    """L = 5 is one partial slab, 37 and 468 end in a slab that is not full; T = 1, 2, 3 are the Laplacian's replicate edges; id_rows 1
+    sums the id gradient over the frames."""
+    check_gradients(L, Ki, Ke, T, T if id_rows_is_T else 1)
+
+
+@pytest.mark.parametrize("L,Ki,Ke,T,id_rows", [(468, 80, 64, 497, 1), (468, 448, 64, 137, 1), (468, 448, 64, 137, 137)])
+def test_gradients_over_chunks_longer_than_a_pose_group(L, Ki, Ke, T, id_rows):
+    """The regime of any video over 480 frames, asserted through the library's own plan (r3d_debug_fit_plan): a block walks a chunk of 17
+    or 18 frames, more than the PG = 16 poses it computes at once, so frame 16 (and 17) of every chunk follows the mid-chunk refresh
+    `f == 0 && tid < min(PG, t1 - t)` with t > t0 -- one or two lanes of it; the last chunks have 4 and 11 frames."""
+    chunk, ychunks, last, nsplit = GPU_PLAN_CASES[(L, Ki, Ke, T)]
+    rc, p = fit_plan(L, Ki, Ke, T)
+    assert rc == 0 and (p["chunk"], p["ychunks"], p["nsplit"]) == (chunk, ychunks, nsplit) and T - chunk * (ychunks - 1) == last, p
+    assert PG < p["chunk"] < 2 * PG and last < PG
+    print("L %d K %d+%d T %d id_rows %d: V %d slabs %d chunk %d x %d (last %d frames) nsplit %d Kc %d, %d B of LDS"
+          % (L, Ki, Ke, T, id_rows, p["V"], p["slabs"], p["chunk"], p["ychunks"], last, p["nsplit"], p["Kc"], p["lds_bytes"]))
+    check_gradients(L, Ki, Ke, T, id_rows)
+
+
+@pytest.mark.parametrize("L,Ki,Ke", sorted(GPU_K_CASES))
+def test_gradients_over_the_k_regimes(L, Ki, Ke):
+    """T = 3.  K = 50 and 51: V steps from 85 to 83 points a slab, at nearly the largest LDS request; K = 100: rows split 2 ways; K = 512, the
+    accepted top end: V = 8, rows split 10 ways, 52 columns a part and 44 in the last; K = 1: stage() advances 256 rows a step."""
+    rc, p = fit_plan(L, Ki, Ke, 3)
+    assert rc == 0 and (p["V"], p["nsplit"], p["Kc"]) == GPU_K_CASES[(L, Ki, Ke)], p
+    print("L %d K %d+%d: V %d slabs %d nsplit %d Kc %d (last part %d), %d B of LDS"
+          % (L, Ki, Ke, p["V"], p["slabs"], p["nsplit"], p["Kc"], Ki + Ke - (p["nsplit"] - 1) * p["Kc"], p["lds_bytes"]))
+    check_gradients(L, Ki, Ke, 3, 1)
 
 
 def _state(arrays, T, id_rows, params, seed):
@@ -117,12 +149,21 @@ def _run_from(arrays_dev, lms, w, id_rows, params, m, v, steps0, groups, n_iter)
     return views
 
 
-@pytest.mark.parametrize("n_iter", [1, 3])
-@pytest.mark.parametrize("groups", [1, 2, 3])
-@pytest.mark.parametrize("L,Ki,Ke,T,id_rows", [(468, 80, 64, 7, 1), (37, 80, 64, 3, 3), (5, 3, 0, 2, 1)])
+# every group mask at the small shapes; chunks longer than a pose group (the snapshot's copy_run over 17 and 18 frames, id_rows 1 and T)
+# with both groups, and with one group inactive for the first of them
+ITERATION_CASES = [c + (g, n) for n in (1, 3) for g in (1, 2, 3) for c in ((468, 80, 64, 7, 1), (37, 80, 64, 3, 3), (5, 3, 0, 2, 1))] + \
+                  [c + (3, n) for n in (1, 3) for c in ((468, 80, 64, 497, 1), (468, 448, 64, 137, 137))] + \
+                  [(468, 80, 64, 497, 1, g, 1) for g in (1, 2)]
+
+
+@pytest.mark.parametrize("L,Ki,Ke,T,id_rows,groups,n_iter", ITERATION_CASES)
 def test_iterations_from_a_given_state(L, Ki, Ke, T, id_rows, groups, n_iter):
     """One and three iterations per group mask: parameters and both moments against the restatement in fp64; an inactive group keeps
     its parameters and moments bit for bit."""
+    if (L, Ki, Ke, T) in GPU_PLAN_CASES:
+        chunk, ychunks, last, _ = GPU_PLAN_CASES[(L, Ki, Ke, T)]
+        p = fit_plan(L, Ki, Ke, T)[1]
+        assert (p["chunk"], p["ychunks"]) == (chunk, ychunks) and p["chunk"] > PG and T - chunk * (ychunks - 1) == last, p
     arrays, lms, w, params = inputs(L, Ki, Ke, T, id_rows)
     m, v = _state(arrays, T, id_rows, params, 3)
     steps0 = (7, 200)

@@ -154,6 +154,22 @@ def test_large_face_path():
     equal(run(v, tri, feat, S, _large_box=0), got)
 
 
+def test_large_face_path_with_more_faces_than_waves():
+    """large_faces has a fixed grid of 2048 waves, a face per wave and step.  With the threshold at 0 every face of a face-like mesh is
+    listed, and the fp64 restatement alone shows more than 2048 distinct faces winning a pixel: waves have to take a second step
+    (`e += waves`), and what they draw there is seen.  The result must be the restatement's, and the same bits as with the default
+    threshold and with the threshold raised so that no face is listed."""
+    S, G = 128, 40
+    v, tri, feat = face_case(S, G)
+    got = run(v, tri, feat, S, _large_box=0)
+    r64 = check(got, v, tri, feat, S, "every face through large_faces, S %d G %d" % (S, G))
+    winners = np.unique(r64["pix_to_face"][r64["pix_to_face"] >= 0])
+    print("distinct winning faces in fp64: %d of %d faces (large_faces has 2048 waves)" % (len(winners), tri.shape[0]))
+    assert len(winners) > 2048
+    equal(run(v, tri, feat, S), got)
+    equal(run(v, tri, feat, S, _large_box=1 << 30), got)
+
+
 def test_winding_changes_nothing():
     """Every triangle reversed: the same pixels, depths and attributes (to the rounding of another order of the same sums)."""
     v, tri, feat = face_case(64, 24, seeds=(0, 1))

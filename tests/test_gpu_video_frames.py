@@ -148,6 +148,39 @@ def test_depth_range_of_many_blocks_and_ragged_counts():
     assert z[:2].tolist() == [np.float32(-0.0).view(np.int32), 0]                   # -0.0 below +0.0, whatever the order
 
 
+def test_depth_range_beyond_the_grids_cap():
+    """depth_range_kernel's grid grows with the count, a block per 4096 floats, up to a cap of 1024 blocks (a 257-frame clip of 128 x 128
+    depth images is past it).  Below the cap a lane takes 4 grid-stride steps of a float4, or 16 of a float in the scalar loop, and every
+    other test stays there; past it the grid no longer grows and a lane takes more steps than the 16 floats a block is sized for.  With
+    1024 x 4096 + 3 x 4096 + 5 floats only such further steps reach the maximum, in the first block's worth past the cap, and the
+    minimum, in the last five elements (the last whole float4 and the ragged tail).  Once 16-byte aligned, once from a view one float
+    in (the scalar loop), once with a NaN past the cap: min, max and the NaN word as NumPy's, the partial words and the ticket zero
+    afterwards."""
+    from real3dportrait_amd import video_frames as V
+    cap = 1024 * 4096
+    count = cap + 3 * 4096 + 5
+    x = np.random.default_rng(11).normal(0, 3, count).astype(np.float32)
+    x[count - 3], x[cap + 1000] = -100.0, 100.0
+    assert x.argmin() == count - 3 >= count - 5 and cap <= x.argmax() < cap + 4096
+    aligned = dev(x)
+    buf = torch.empty(count + 1, dtype=torch.float32, device=DEV)
+    shifted = buf[1:]
+    shifted.copy_(aligned)
+    assert aligned.data_ptr() % 16 == 0 and shifted.data_ptr() % 16 == 4
+    for what, d in (("16-byte aligned", aligned), ("one float in", shifted)):
+        st = V.depth_range(d).cpu().numpy()
+        print("depth range of %d floats, %s: min %r max %r, state words 2.. %s" % (count, what, *st[:2].view(np.float32).tolist(), st[2:].tolist()))
+        assert st[:2].view(np.float32).tolist() == [x.min(), x.max()] == [-100.0, 100.0] and st[2:].tolist() == [0, 1, 0, 0, 0, 0], what
+    x[4200000] = np.nan
+    assert np.isnan(x.min()) and np.isnan(x.max())
+    for what, d in (("16-byte aligned", dev(x)), ("one float in", shifted)):
+        if d is shifted:
+            shifted[4200000] = float("nan")
+        st = V.depth_range(d).cpu().numpy()
+        print("depth range with a NaN at 4 200 000, %s: words %s" % (what, [hex(w) for w in st.view(np.uint32).tolist()]))
+        assert np.isnan(st[:2].view(np.float32)).all() and st[2:].tolist() == [1, 1, 0, 0, 0, 0], what
+
+
 def test_another_stream_two_runs_inputs_and_guard_bytes():
     """A run on a non-default stream; two runs bit-identical; the inputs are unchanged afterwards; 64 guard bytes in front of and behind
     `out` are untouched -- and again with `out` only 4-byte aligned, which takes the 4-pixel lanes at a W the 16-pixel lanes would take."""
