@@ -408,37 +408,40 @@ int r3d_profile_clock(int id, double* ghz, unsigned long long* cycles);
  * 73-81 -> SegFormerSECC2PlaneBackbone.forward, modules/real3d/segformer.py:710-718): prenet, the MiT-b0 encoder and the SegFormerHead.
  * Exact fp32 (every product on the f32 MFMA).  Activations are token-major: [B, H, W, C] with token index h W + w.  All weights are the
  * reference's parameters as stored, except that conv weights [Cout, Cin, k, k] are passed as [Cout, k, k, Cin] (permuted once per
- * parameter version by the Python module) and the head's parameters are folded (r3d_secc_head). */
+ * parameter version by the Python module) and the head's parameters are folded (r3d_secc_head).
+ * Checked on the host before any launch (R3D_ERR_INVALID_ARG, the message naming the values): the sizes below, the overlap rule of each
+ * entry point, and the 2^31 limit of a call: the GEMM kernels index token rows in int up to the end of the last 64-row tile, so "rows
+ * below 2^31" means the row count rounded up to a multiple of 64. */
 
 /* prenet (Conv2dLayer(in_dim, 3, 1), networks_stylegan2.py:139-190: weight * 1/sqrt(in_dim), + bias, linear) folded into the taps of
  * patch_embed1 (OverlapPatchEmbed, segformer.py:201-241: Conv2d(3, 32, 7, stride 4, padding 3), then LayerNorm eps 1e-5).
  * x [B, in_dim, H, W] NCHW (in_dim 9: pncc_cond_mode cano_src_tgt, 6: cano_tgt), prenet_w [3, in_dim], prenet_b [3], w [32, 7, 7, 3],
  * bias / ln_g / ln_b [32]; y [B, H/4, W/4, 32].  H and W must be multiples of 32 with (H/32)(W/32) <= 1024 (the attention's key limit).
- * y must not overlap x. */
+ * y must not overlap x.  B (H/4)(W/4) rows below 2^31. */
 int r3d_secc_embed1(const float* x, int B, int in_dim, int H, int W, const float* prenet_w, const float* prenet_b,
                     const float* w, const float* bias, const float* ln_g, const float* ln_b, float* y, r3d_stream_t stream);
 /* Strided conv over [B, Hin, Win, Cin] -> [B, Ho, Wo, Cout], zero padding, w [Cout, ksize, ksize, Cin], bias [Cout], then (ln_g, ln_b
  * not NULL) LayerNorm over Cout with ln_eps.  patch_embed2..4 (segformer.py:201-241: k3 s2 p1, LayerNorm eps 1e-5) and the attention's
  * spatial reduction Attention.sr (:119-121, k = s = sr_ratio, no padding; its LayerNorm goes to the kv r3d_secc_linear instead).
- * 1 <= ksize <= 8, 0 <= pad < ksize, Hin + 2 pad >= ksize and Win + 2 pad >= ksize (as nn.Conv2d), Cin and Cout <= 1024; y must not
- * overlap x. */
+ * 1 <= ksize <= 8, 0 <= pad < ksize, Hin + 2 pad >= ksize and Win + 2 pad >= ksize (as nn.Conv2d), Cin and Cout <= 1024 (so
+ * ksize^2 Cin <= 2^16), B Ho Wo rows below 2^31; y must not overlap x. */
 int r3d_secc_conv(const float* x, int B, int Hin, int Win, int Cin, const float* w, const float* bias, int Cout, int ksize,
                   int stride, int pad, const float* ln_g, const float* ln_b, float ln_eps, float* y, r3d_stream_t stream);
 /* y[M, N] = act(LN?(x[M, K]) w[N, K]^T + bias) (+ residual): nn.Linear with an optional LayerNorm prologue (ln_g / ln_b both given, eps
  * ln_eps), exact-erf GELU (gelu != 0) and a residual [M, N] that may be y itself.  Attention.q / kv / proj (segformer.py:110-115,
  * 135-148), Block's norm1 / norm2 and residual adds (:195-196), Mlp.fc1 / fc2 (:68-71) and the head's folded low-resolution GEMMs.
- * bias may be NULL; x must not overlap y. */
+ * bias may be NULL; K and N <= 4096, M rows below 2^31; y must not overlap x, nor the residual unless it is the residual. */
 int r3d_secc_linear(const float* x, int M, int K, const float* ln_g, const float* ln_b, float ln_eps, const float* w,
                     const float* bias, int N, int gelu, const float* residual, float* y, r3d_stream_t stream);
 /* nn.LayerNorm over the C entries of M rows (MixVisionTransformer.norm1..4, segformer.py:344-375).  y may be x itself, but must not
  * overlap it otherwise. */
 int r3d_secc_layernorm(const float* x, int M, int C, const float* ln_g, const float* ln_b, float eps, float* y, r3d_stream_t stream);
 /* softmax(q k^T * scale) v per head (Attention.forward, segformer.py:150-154): q [B, N, C], kv [B, L, 2C] with k in channels [0, C) and v
- * in [C, 2C), head h owns channels [32 h, 32 h + 32) (C = 32 heads), out [B, N, C].  1 <= L <= 1024.  out must not overlap kv; it may
- * be q itself (each block reads its queries before it writes them) but must not overlap q otherwise. */
+ * in [C, 2C), head h owns channels [32 h, 32 h + 32) (C = 32 heads), out [B, N, C].  1 <= L <= 1024, N rows below 2^31.  out must not
+ * overlap kv; it may be q itself (each block reads its queries before it writes them) but must not overlap q otherwise. */
 int r3d_secc_attention(const float* q, const float* kv, int B, int N, int L, int C, int heads, float scale, float* out, r3d_stream_t stream);
 /* DWConv (segformer.py:394-404: depthwise 3x3, padding 1, bias) + nn.GELU (exact erf) on [B, H, W, C]; w [C, 1, 3, 3].  y must not
- * overlap x. */
+ * overlap x.  One thread an element, 256 a block: ceil(B H W C / 256) blocks below 2^31. */
 int r3d_secc_dwconv_gelu(const float* x, int B, int H, int W, int C, const float* w, const float* bias, float* y, r3d_stream_t stream);
 /* SegFormerHead.forward (segformer.py:512-537) after the fold: with W_fuse = linear_fuse.conv.weight [256, 1024] and block(i) its input
  * columns of _c_i in the order [_c4, _c3, _c2, _c1],  w1f = W_fuse[:, block(1)] . linear_c1.proj.weight [256, 32],  f2 / f3 / f4 the
@@ -446,7 +449,7 @@ int r3d_secc_dwconv_gelu(const float* x, int B, int H, int W, int C, const float
  * 256],  hconst = sum_i W_fuse[:, block(i)] . linear_ci.proj.bias [256],  bn_scale / bn_shift the eval BatchNorm (eps 1e-5) as
  * gamma / sqrt(var + eps) and beta - mean * bn_scale.  out = relu(bn_scale (c1 . w1f^T + sum_i bilinear(f_i) + hconst) + bn_shift)
  * [B, 256, H1, W1] NCHW, the bilinear resize with align_corners=False.  c1 [B, H1, W1, 32]; H1, W1 multiples of 8 (H, W of 32).
- * out must not overlap any input. */
+ * out must not overlap any input.  B H1 W1 rows below 2^31. */
 int r3d_secc_head(const float* c1, int B, int H1, int W1, const float* w1f, const float* f2, const float* f3, const float* f4,
                   const float* hconst, const float* bn_scale, const float* bn_shift, float* out, r3d_stream_t stream);
 

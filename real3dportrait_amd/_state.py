@@ -81,3 +81,18 @@ class _FoldedModule(nn.Module):
 
     def _buffers_for(self, dev, *shape):
         return self._work.get(dev, *shape)
+
+    def _check_device(self, t, what, own=None):
+        """The device rule, first part: t (named `what` in the message) is on a GPU, and on the device of the module's parameters (of `own`,
+        one of them; the first by default).  Raised before the library is entered."""
+        if not t.is_cuda:
+            raise ValueError("%s: the %s is not on a GPU: the library operates on device tensors only" % (type(self).__name__, what))
+        own = (next(self.parameters()) if own is None else own).device
+        if own != t.device:
+            raise ValueError("%s: the %s is on %s, the module's parameters on %s" % (type(self).__name__, what, t.device, own))
+
+    @staticmethod
+    def _device_of(t):
+        """The device rule, second part: `with self._device_of(t):` makes t's device the current one for the launches, so that
+        torch.cuda.current_stream() is that device's stream whatever the process's current device is."""
+        return torch.cuda.device(t.device)

@@ -72,6 +72,8 @@ __device__ __forceinline__ float softplus20(float x) {
     return x > 20.0f ? x : r;
 }
 __device__ __forceinline__ float sigmoidf(float x) { return __builtin_amdgcn_rcpf(1.0f + fexp(-x)); }
+// nn.GELU() (approximate='none'), the exact-fp32 families' activation: v Phi(v) on ocml's erff
+__device__ __forceinline__ float gelu_erf(float v) { return 0.5f * v * (1.0f + erff(v * 0.70710678118654752f)); }
 
 // ---- output side: clamp(-1,1) then ((x + 1) / 2 * 255).int() -> uint8 (inference/real3d_infer.py:472,518-522).  (x + 1) / 2 is exact,
 // so fl((x + 1) * 127.5) is the same single rounding as fl(((x + 1) / 2) * 255); truncation toward zero; NaN -> 0.

@@ -15,8 +15,6 @@
 namespace r3d {
 namespace hub {
 
-__device__ __forceinline__ float gelu_erf(float v) { return 0.5f * v * (1.0f + erff(v * 0.70710678118654752f)); }
-
 // ---- clip statistics ------------------------------------------------------------------------------------------------------------------
 constexpr int ST_THREADS = 1024;
 

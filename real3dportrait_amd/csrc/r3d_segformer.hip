@@ -38,8 +38,6 @@ struct GemmArgs {
     int H1, W1;
 };
 
-__device__ __forceinline__ float gelu_erf(float v) { return 0.5f * v * (1.0f + erff(v * 0.70710678118654752f)); }
-
 // one element of A (zero outside [M, K] and outside the zero-padded input)
 template <int AMODE>
 __device__ __forceinline__ float load_a(const GemmArgs& g, int m, int k, float sh, float mu, float rs)
@@ -307,9 +305,16 @@ __global__ void __launch_bounds__(256) seg_attention(const float* q, const float
     }
 }
 
+// The kernels index the rows of a call in int, up to the end of the last 64-row tile (m0 + lr of seg_gemm, q0 + li of seg_attention): M, or
+// the product `expr` it stands for, rounded up to whole tiles, stays below 2^31.  Shown before the product is formed in int.
+static bool rows_ok(const char* what, const char* expr, double rows)
+{
+    return below_2_31(what, expr, ceil(rows / BM) * BM, "rows with the last 64-row tile filled up");
+}
+
 static int launch_gemm(int amode, bool head, const GemmArgs& g, hipStream_t st, const char* what)
 {
-    dim3 grid((g.M + BM - 1) / BM, (g.N + BN - 1) / BN);
+    dim3 grid((g.M - 1) / BM + 1, (g.N - 1) / BN + 1);
     if (head) hipLaunchKernelGGL((seg_gemm<A_ROW, true>), grid, dim3(256), 0, st, g);
     else if (amode == A_ROW) hipLaunchKernelGGL((seg_gemm<A_ROW, false>), grid, dim3(256), 0, st, g);
     else if (amode == A_CONV) hipLaunchKernelGGL((seg_gemm<A_CONV, false>), grid, dim3(256), 0, st, g);
@@ -319,7 +324,7 @@ static int launch_gemm(int amode, bool head, const GemmArgs& g, hipStream_t st, 
 
 static int launch_layernorm(const float* x, int M, int C, const float* gam, const float* bet, float eps, float* y, hipStream_t st)
 {
-    hipLaunchKernelGGL(seg_layernorm, dim3((M + 3) / 4), dim3(256), 0, st, x, M, C, gam, bet, eps, y);
+    hipLaunchKernelGGL(seg_layernorm, dim3((M - 1) / 4 + 1), dim3(256), 0, st, x, M, C, gam, bet, eps, y);
     return check_launch("secc_layernorm");
 }
 
@@ -333,15 +338,18 @@ extern "C" int r3d_secc_embed1(const float* x, int B, int in_dim, int H, int W, 
                                const float* w, const float* bias, const float* ln_g, const float* ln_b, float* y, r3d_stream_t stream)
 {
     if (!x || !prenet_w || !prenet_b || !w || !bias || !ln_g || !ln_b || !y) { set_error("secc_embed1: NULL pointer"); return R3D_ERR_INVALID_ARG; }
-    if (B <= 0 || (in_dim != 6 && in_dim != 9)) { set_error("secc_embed1: bad argument (B > 0, in_dim 6 or 9)"); return R3D_ERR_INVALID_ARG; }
+    if (B <= 0 || (in_dim != 6 && in_dim != 9)) { set_error("secc_embed1: bad argument: B = %d, in_dim = %d (B > 0, in_dim 6 or 9)", B, in_dim); return R3D_ERR_INVALID_ARG; }
     if (H <= 0 || W <= 0 || H % 32 || W % 32) { set_error("secc_embed1: H and W must be positive multiples of 32"); return R3D_ERR_INVALID_ARG; }
     if ((size_t)(H / 32) * (W / 32) > 1024) { set_error("secc_embed1: L = (H/32)(W/32) > 1024 keys"); return R3D_ERR_INVALID_ARG; }
-    if (overlap(x, (size_t)B * in_dim * H * W, y, (size_t)B * (H / 4) * (W / 4) * 32)) { set_error("secc_embed1: x and y overlap"); return R3D_ERR_INVALID_ARG; }
+    if (!rows_ok("secc_embed1", "B (H/4)(W/4)", (double)B * (H / 4) * (W / 4))) return R3D_ERR_INVALID_ARG;
+    const int M = B * (H / 4) * (W / 4);
+    const Span spans[] = {writes(y, (size_t)M * 32), reads(x, (size_t)B * in_dim * H * W)};
+    if (clash(spans)) { set_error("secc_embed1: x and y overlap"); return R3D_ERR_INVALID_ARG; }
     hipStream_t st = (hipStream_t)stream;
     GemmArgs g = {};
     g.a = x; g.Hin = H; g.Win = W; g.Cin = 3; g.Ho = H / 4; g.Wo = W / 4; g.ks = 7; g.stride = 4; g.pad = 3;
     g.pw = prenet_w; g.pb = prenet_b; g.pgain = (float)(1.0 / sqrt((double)in_dim)); g.Craw = in_dim;
-    g.M = B * g.Ho * g.Wo; g.K = 7 * 7 * 3; g.w = w; g.N = 32; g.bias = bias; g.y = y; g.ldy = 32;
+    g.M = M; g.K = 7 * 7 * 3; g.w = w; g.N = 32; g.bias = bias; g.y = y; g.ldy = 32;
     int rc = launch_gemm(A_PRENET, false, g, st, "secc_embed1");
     if (rc) return rc;
     return launch_layernorm(y, g.M, 32, ln_g, ln_b, 1e-5f, y, st);
@@ -351,16 +359,23 @@ extern "C" int r3d_secc_conv(const float* x, int B, int Hin, int Win, int Cin, c
                              int stride, int pad, const float* ln_g, const float* ln_b, float ln_eps, float* y, r3d_stream_t stream)
 {
     if (!x || !w || !bias || !y || (!ln_g) != (!ln_b)) { set_error("secc_conv: NULL pointer"); return R3D_ERR_INVALID_ARG; }
-    if (B <= 0 || Hin <= 0 || Win <= 0 || Cin <= 0 || Cout <= 0 || ksize <= 0 || stride <= 0 || pad < 0 || pad >= ksize ||
-        Cout > 1024 || Cin > 1024 || ksize > 8) { set_error("secc_conv: bad argument"); return R3D_ERR_INVALID_ARG; }
+    if (B <= 0 || Hin <= 0 || Win <= 0 || stride <= 0)
+        { set_error("secc_conv: bad argument: B = %d, Hin = %d, Win = %d, stride = %d must be positive", B, Hin, Win, stride); return R3D_ERR_INVALID_ARG; }
+    if (Cin <= 0 || Cout <= 0 || Cin > 1024 || Cout > 1024)
+        { set_error("secc_conv: bad argument: Cin = %d, Cout = %d outside 1 .. 1024", Cin, Cout); return R3D_ERR_INVALID_ARG; }
+    if (ksize <= 0 || ksize > 8 || pad < 0 || pad >= ksize)
+        { set_error("secc_conv: bad argument: ksize = %d outside 1 .. 8, or pad = %d outside 0 .. ksize - 1", ksize, pad); return R3D_ERR_INVALID_ARG; }
     // the padded input holds at least one window (C division truncates: without this, -stride < Hin + 2 pad - ksize < 0 gave Ho = 1)
-    if (Hin + 2 * pad < ksize || Win + 2 * pad < ksize) { set_error("secc_conv: empty output (Hin or Win + 2 pad < ksize)"); return R3D_ERR_INVALID_ARG; }
-    const int Ho = (Hin + 2 * pad - ksize) / stride + 1, Wo = (Win + 2 * pad - ksize) / stride + 1;
-    if (overlap(x, (size_t)B * Hin * Win * Cin, y, (size_t)B * Ho * Wo * Cout)) { set_error("secc_conv: x and y overlap"); return R3D_ERR_INVALID_ARG; }
+    if (Hin < ksize - 2 * pad || Win < ksize - 2 * pad) { set_error("secc_conv: empty output (Hin or Win + 2 pad < ksize)"); return R3D_ERR_INVALID_ARG; }
+    const long long Ho = ((long long)Hin + 2 * pad - ksize) / stride + 1, Wo = ((long long)Win + 2 * pad - ksize) / stride + 1;
+    if (!rows_ok("secc_conv", "B Ho Wo", (double)B * (double)Ho * (double)Wo)) return R3D_ERR_INVALID_ARG;
+    const int M = B * (int)Ho * (int)Wo, K = ksize * ksize * Cin;          // K <= 8 . 8 . 1024 by the bounds above
+    const Span spans[] = {writes(y, (size_t)M * Cout), reads(x, (size_t)B * Hin * Win * Cin)};
+    if (clash(spans)) { set_error("secc_conv: x and y overlap"); return R3D_ERR_INVALID_ARG; }
     hipStream_t st = (hipStream_t)stream;
     GemmArgs g = {};
-    g.a = x; g.Hin = Hin; g.Win = Win; g.Cin = Cin; g.Ho = Ho; g.Wo = Wo; g.ks = ksize; g.stride = stride; g.pad = pad;
-    g.M = B * Ho * Wo; g.K = ksize * ksize * Cin; g.w = w; g.N = Cout; g.bias = bias; g.y = y; g.ldy = Cout;
+    g.a = x; g.Hin = Hin; g.Win = Win; g.Cin = Cin; g.Ho = (int)Ho; g.Wo = (int)Wo; g.ks = ksize; g.stride = stride; g.pad = pad;
+    g.M = M; g.K = K; g.w = w; g.N = Cout; g.bias = bias; g.y = y; g.ldy = Cout;
     int rc = launch_gemm(A_CONV, false, g, st, "secc_conv");
     if (rc || !ln_g) return rc;
     return launch_layernorm(y, g.M, Cout, ln_g, ln_b, ln_eps, y, st);
@@ -370,9 +385,13 @@ extern "C" int r3d_secc_linear(const float* x, int M, int K, const float* ln_g, 
                                const float* bias, int N, int gelu, const float* residual, float* y, r3d_stream_t stream)
 {
     if (!x || !w || !y || (!ln_g) != (!ln_b)) { set_error("secc_linear: NULL pointer"); return R3D_ERR_INVALID_ARG; }
-    if (M <= 0 || K <= 0 || N <= 0 || K > 4096 || N > 4096 || (residual && residual != y && overlap(residual, (size_t)M * N, y, (size_t)M * N)))
-        { set_error("secc_linear: bad argument"); return R3D_ERR_INVALID_ARG; }
-    if (overlap(x, (size_t)M * K, y, (size_t)M * N)) { set_error("secc_linear: x and y overlap"); return R3D_ERR_INVALID_ARG; }
+    if (M <= 0 || K <= 0 || N <= 0 || K > 4096 || N > 4096)
+        { set_error("secc_linear: bad argument: M = %d, K = %d, N = %d (M > 0; K, N in 1 .. 4096)", M, K, N); return R3D_ERR_INVALID_ARG; }
+    if (!rows_ok("secc_linear", "M", (double)M)) return R3D_ERR_INVALID_ARG;
+    // the residual may be y itself: each element is read, then written, by one lane
+    const size_t ny = (size_t)M * N;
+    const Span spans[] = {writes(y, ny), reads(x, (size_t)M * K), reads(residual == y ? nullptr : residual, ny)};
+    if (clash(spans)) { set_error("secc_linear: y overlaps x, or residual without being residual"); return R3D_ERR_INVALID_ARG; }
     GemmArgs g = {};
     g.a = x; g.M = M; g.K = K; g.lda = K; g.ln_g = ln_g; g.ln_b = ln_b; g.ln_eps = ln_eps;
     g.w = w; g.N = N; g.bias = bias; g.gelu = gelu ? 1 : 0; g.res = residual; g.y = y; g.ldy = N;
@@ -382,8 +401,10 @@ extern "C" int r3d_secc_linear(const float* x, int M, int K, const float* ln_g, 
 extern "C" int r3d_secc_layernorm(const float* x, int M, int C, const float* ln_g, const float* ln_b, float eps, float* y, r3d_stream_t stream)
 {
     if (!x || !ln_g || !ln_b || !y) { set_error("secc_layernorm: NULL pointer"); return R3D_ERR_INVALID_ARG; }
-    if (M <= 0 || C <= 0 || !(eps > 0.0f)) { set_error("secc_layernorm: bad argument"); return R3D_ERR_INVALID_ARG; }
-    if (x != y && overlap(x, (size_t)M * C, y, (size_t)M * C)) { set_error("secc_layernorm: x and y overlap (y may be x itself)"); return R3D_ERR_INVALID_ARG; }
+    if (M <= 0 || C <= 0 || !(eps > 0.0f))
+        { set_error("secc_layernorm: bad argument: M = %d, C = %d, eps = %g must be positive", M, C, (double)eps); return R3D_ERR_INVALID_ARG; }
+    const Span spans[] = {writes(y, (size_t)M * C), reads(x == y ? nullptr : x, (size_t)M * C)};
+    if (clash(spans)) { set_error("secc_layernorm: x and y overlap (y may be x itself)"); return R3D_ERR_INVALID_ARG; }
     return launch_layernorm(x, M, C, ln_g, ln_b, eps, y, (hipStream_t)stream);
 }
 
@@ -391,21 +412,27 @@ extern "C" int r3d_secc_attention(const float* q, const float* kv, int B, int N,
                                   r3d_stream_t stream)
 {
     if (!q || !kv || !out) { set_error("secc_attention: NULL pointer"); return R3D_ERR_INVALID_ARG; }
-    if (B <= 0 || N <= 0 || heads <= 0 || C != 32 * heads) { set_error("secc_attention: bad argument (C = 32 heads)"); return R3D_ERR_INVALID_ARG; }
+    if (B <= 0 || N <= 0 || heads <= 0 || C != 32 * heads)
+        { set_error("secc_attention: bad argument: B = %d, N = %d, C = %d, heads = %d (B, N, heads > 0; C = 32 heads)", B, N, C, heads); return R3D_ERR_INVALID_ARG; }
     if (L <= 0 || L > 1024) { set_error("secc_attention: L = %d keys outside 1 .. 1024", L); return R3D_ERR_INVALID_ARG; }
+    if (!rows_ok("secc_attention", "N", (double)N)) return R3D_ERR_INVALID_ARG;
     const size_t nout = (size_t)B * N * C;
-    if (overlap(out, nout, kv, (size_t)B * L * 2 * C) || (out != q && overlap(out, nout, q, nout)))
-        { set_error("secc_attention: out overlaps kv, or q without being q"); return R3D_ERR_INVALID_ARG; }
-    hipLaunchKernelGGL(seg_attention, dim3((N + AQ - 1) / AQ, heads, B), dim3(256), 0, (hipStream_t)stream, q, kv, N, L, C, scale, out);
+    const Span spans[] = {writes(out, nout), reads(kv, (size_t)B * L * 2 * C), reads(out == q ? nullptr : q, nout)};
+    if (clash(spans)) { set_error("secc_attention: out overlaps kv, or q without being q"); return R3D_ERR_INVALID_ARG; }
+    hipLaunchKernelGGL(seg_attention, dim3((N - 1) / AQ + 1, heads, B), dim3(256), 0, (hipStream_t)stream, q, kv, N, L, C, scale, out);
     return check_launch("secc_attention");
 }
 
 extern "C" int r3d_secc_dwconv_gelu(const float* x, int B, int H, int W, int C, const float* w, const float* bias, float* y, r3d_stream_t stream)
 {
     if (!x || !w || !bias || !y) { set_error("secc_dwconv_gelu: NULL pointer"); return R3D_ERR_INVALID_ARG; }
-    if (B <= 0 || H <= 0 || W <= 0 || C <= 0) { set_error("secc_dwconv_gelu: bad argument"); return R3D_ERR_INVALID_ARG; }
+    if (B <= 0 || H <= 0 || W <= 0 || C <= 0)
+        { set_error("secc_dwconv_gelu: bad argument: B = %d, H = %d, W = %d, C = %d must be positive", B, H, W, C); return R3D_ERR_INVALID_ARG; }
+    // one thread an element, 256 a block: the block count is the grid's x, an unsigned below 2^31
+    if (!below_2_31("secc_dwconv_gelu", "ceil(B H W C / 256)", ceil((double)B * H * W * C / 256.0), "blocks")) return R3D_ERR_INVALID_ARG;
     const size_t total = (size_t)B * H * W * C;
-    if (overlap(x, total, y, total)) { set_error("secc_dwconv_gelu: bad argument (x and y overlap)"); return R3D_ERR_INVALID_ARG; }
+    const Span spans[] = {writes(y, total), reads(x, total)};
+    if (clash(spans)) { set_error("secc_dwconv_gelu: bad argument (x and y overlap)"); return R3D_ERR_INVALID_ARG; }
     hipLaunchKernelGGL(seg_dwconv_gelu, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, B, H, W, C, w, bias, y);
     return check_launch("secc_dwconv_gelu");
 }
@@ -415,6 +442,7 @@ extern "C" int r3d_secc_head(const float* c1, int B, int H1, int W1, const float
 {
     if (!c1 || !w1f || !f2 || !f3 || !f4 || !hconst || !bn_scale || !bn_shift || !out) { set_error("secc_head: NULL pointer"); return R3D_ERR_INVALID_ARG; }
     if (B <= 0 || H1 <= 0 || W1 <= 0 || H1 % 8 || W1 % 8) { set_error("secc_head: H1, W1 (= H/4, W/4) must be positive multiples of 8"); return R3D_ERR_INVALID_ARG; }
+    if (!rows_ok("secc_head", "B H1 W1", (double)B * H1 * W1)) return R3D_ERR_INVALID_ARG;
     const size_t hw = (size_t)H1 * W1, nout = (size_t)B * 256 * hw;
     const Span spans[] = {writes(out, nout), reads(c1, (size_t)B * hw * 32), reads(f2, (size_t)B * hw / 4 * 256), reads(f3, (size_t)B * hw / 16 * 256),
                           reads(f4, (size_t)B * hw / 64 * 256), reads(w1f, 256 * 32), reads(hconst, 256), reads(bn_scale, 256), reads(bn_shift, 256)};

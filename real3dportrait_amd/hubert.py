@@ -17,6 +17,7 @@ import torch.nn as nn
 from . import _lib
 from ._state import _FoldedModule
 from .synth import HUBERT_LARGE
+from .token_blocks import attention_half
 
 KERNEL, STRIDE = 400, 320          # the conv stack as one Conv1d (extract_hubert.py:48-49): 400 samples a frame, a frame every 320
 # the structure this module builds: field -> the value it must have (a config that lacks the field is taken to have it)
@@ -177,7 +178,7 @@ class HubertFeatureModel(_FoldedModule):
 
     # ---- the launches: B sequences of n samples at wave + offset + b stride ------------------------------------------------------------
     def _run(self, wave, stats, B, offset, stride, n, taps=None):
-        with torch.cuda.device(wave.device):
+        with self._device_of(wave):
             return self._launches(wave, stats, B, offset, stride, n, taps)
 
     def _launches(self, wave, stats, B, offset, stride, n, taps):
@@ -204,7 +205,7 @@ class HubertFeatureModel(_FoldedModule):
             cur, nxt = nxt, cur
         tap("extract_features", cur, (B, T, c["conv_dim"][-1]))
         M = B * T
-        X, P, Q, O, KV, Hb = w["x"], w["p"], w["q"], w["o"], w["kv"], w["h"]
+        X, P, Hb = w["x"], w["p"], w["h"]
         fp = self.feature_projection
         _lib.call("r3d_secc_linear", cur, M, c["conv_dim"][-1], fp.layer_norm.weight, fp.layer_norm.bias, fp.layer_norm.eps, fp.projection.weight,
                   fp.projection.bias, H, 0, None, P, st)
@@ -214,10 +215,7 @@ class HubertFeatureModel(_FoldedModule):
         tap("pos_conv", X, (B, T, H))
         for i, layer in enumerate(self.encoder.layers):
             a, ln, ff, fl = layer.attention, layer.layer_norm, layer.feed_forward, layer.final_layer_norm
-            _lib.call("r3d_secc_linear", X, M, H, ln.weight, ln.bias, ln.eps, a.q_proj.weight, a.q_proj.bias, H, 0, None, Q, st)
-            _lib.call("r3d_secc_linear", X, M, H, ln.weight, ln.bias, ln.eps, d["kv_w%d" % i], d["kv_b%d" % i], 2 * H, 0, None, KV, st)
-            _lib.call("r3d_i2p_attention", Q, KV, B, T, T, H, heads, (H // heads) ** -0.5, O, st)
-            _lib.call("r3d_secc_linear", O, M, H, None, None, 0.0, a.out_proj.weight, a.out_proj.bias, H, 0, X, X, st)
+            attention_half("r3d_i2p_attention", w, st, B, T, 1, H, heads, ln, a.q_proj, d["kv_w%d" % i], d["kv_b%d" % i], a.out_proj)
             _lib.call("r3d_secc_linear", X, M, H, fl.weight, fl.bias, fl.eps, ff.intermediate_dense.weight, ff.intermediate_dense.bias, I, 1, None, Hb,
                       st)
             _lib.call("r3d_secc_linear", Hb, M, I, None, None, 0.0, ff.output_dense.weight, ff.output_dense.bias, H, 0, X, X, st)
@@ -228,13 +226,6 @@ class HubertFeatureModel(_FoldedModule):
         _lib.call("r3d_secc_layernorm", X, M, H, en.weight, en.bias, en.eps, out, st)
         return out
 
-    def _check_device(self, t):
-        if not t.is_cuda:
-            raise ValueError("HubertFeatureModel: the waveform is not on a GPU: the library operates on device tensors only")
-        own = self.encoder.layer_norm.weight.device
-        if own != t.device:
-            raise ValueError("HubertFeatureModel: the waveform is on %s, the module's parameters on %s" % (t.device, own))
-
     @torch.no_grad()
     def forward(self, input_values, taps=None):
         """input_values [B, n], already normalised -> last_hidden_state [B, T, hidden]."""
@@ -244,7 +235,7 @@ class HubertFeatureModel(_FoldedModule):
         B, n = input_values.shape
         if self.frames(n)[0] is None:
             raise ValueError("HubertFeatureModel: %d samples are fewer than one frame needs" % n)
-        self._check_device(input_values)
+        self._check_device(input_values, "waveform")
         x = input_values.detach().float().contiguous()
         return self._run(x, None, B, 0, n, n, taps)
 
@@ -281,9 +272,9 @@ def hubert_features(model, speech, clip_frames=1000, chunk_batch=4, taps=None):
         raise ValueError("hubert_features: clip_frames and chunk_batch must be at least 1")
     dev = model.encoder.layer_norm.weight.device
     wave = wave.to(dev)
-    model._check_device(wave)
+    model._check_device(wave, "waveform")
     expected_T = (n - (KERNEL - STRIDE)) // STRIDE
-    with torch.cuda.device(dev):
+    with model._device_of(wave):
         stats = torch.empty(2, device=dev, dtype=torch.float64)
         _lib.call("r3d_hubert_wave_stats", wave, n, stats)
         plan = chunk_plan(n, clip_frames)

@@ -14,46 +14,12 @@ import torch.nn as nn
 
 from . import _lib
 from ._state import _FoldedModule
+from .token_blocks import Block, PatchEmbed, conv_weight_cl, mit_block          # conv_weight_cl: also this module's name for it
 
 DIM, HEADS, HIDDEN = 1024, 4, 2048          # Block(dim=1024, num_heads=4, mlp_ratio=2) of segformer/models.py:28,114
 INPUT_CHANNELS = {"rgb": 3, "rgb_alpha": 4, "rgb_camera": 6, "rgb_alpha_camera": 7}          # img2plane_model.py:19-29, before the 2 grid channels
 BLOCKS = {"small": (2, 1), "standard": (5, 1), "large": (10, 3)}          # (LowResolutionViT, TriplanePredictorViT), models.py:21-26,105-110
 LN_EPS = 1e-5
-
-
-class _PatchEmbed(nn.Module):
-    def __init__(self, cin):
-        super().__init__()
-        self.proj = nn.Conv2d(cin, DIM, 3, 2, 1)
-        self.norm = nn.LayerNorm(DIM)
-
-
-class _Attention(nn.Module):
-    def __init__(self, sr):
-        super().__init__()
-        self.q, self.kv, self.proj = nn.Linear(DIM, DIM), nn.Linear(DIM, 2 * DIM), nn.Linear(DIM, DIM)
-        self.sr_ratio = sr
-        if sr > 1:
-            self.sr = nn.Conv2d(DIM, DIM, sr, sr)
-            self.norm = nn.LayerNorm(DIM)
-
-
-class _DWConv(nn.Module):
-    def __init__(self):
-        super().__init__()
-        self.dwconv = nn.Conv2d(HIDDEN, HIDDEN, 3, 1, 1, groups=HIDDEN)
-
-
-class _Mlp(nn.Module):
-    def __init__(self):
-        super().__init__()
-        self.fc1, self.dwconv, self.fc2 = nn.Linear(DIM, HIDDEN), _DWConv(), nn.Linear(HIDDEN, DIM)
-
-
-class _Block(nn.Module):
-    def __init__(self, sr):
-        super().__init__()
-        self.norm1, self.attn, self.norm2, self.mlp = nn.LayerNorm(DIM), _Attention(sr), nn.LayerNorm(DIM), _Mlp()
 
 
 class _HighResoEncoder(nn.Module):
@@ -70,10 +36,10 @@ class _HighResoEncoder(nn.Module):
 class _LowResolutionViT(nn.Module):
     def __init__(self, num_blocks):
         super().__init__()
-        self.patch_embed = _PatchEmbed(256)
+        self.patch_embed = PatchEmbed(256, DIM, 3, 2)
         self.num_blocks = num_blocks
         for i in range(1, num_blocks + 1):
-            setattr(self, "block%d" % i, _Block(1))
+            setattr(self, "block%d" % i, Block(DIM, HIDDEN, 1))
         self.conv_after_upsample1 = nn.Conv2d(256, 128, 3, 1, 1)
         self.conv_after_upsample2 = nn.Conv2d(128, 128, 3, 1, 1)
         self.final_conv = nn.Conv2d(128, 96, 3, 1, 1)
@@ -84,10 +50,10 @@ class _TriplanePredictorViT(nn.Module):
         super().__init__()
         self.first_conv = nn.Conv2d(192, 256, 3, 1, 1)
         self.second_conv = nn.Conv2d(256, 128, 3, 1, 1)
-        self.patch_embed = _PatchEmbed(128)
+        self.patch_embed = PatchEmbed(128, DIM, 3, 2)
         self.num_blocks = num_blocks
         for i in range(1, num_blocks + 1):
-            setattr(self, "block%d" % i, _Block(2))
+            setattr(self, "block%d" % i, Block(DIM, HIDDEN, 2))
         self.first_conv_after_cat = nn.Conv2d(352, 256, 3, 1, 1)
         self.second_conv_after_cat = nn.Conv2d(256, 128, 3, 1, 1)
         self.third_conv_after_cat = nn.Conv2d(128, 128, 3, 1, 1)
@@ -97,11 +63,6 @@ class _TriplanePredictorViT(nn.Module):
 def pixel_shuffle_source(c, i, j):
     """nn.PixelShuffle(2): out[b, c, 2y + i, 2x + j] = in[b, 4c + 2i + j, y, x] -- the input channel r3d_i2p_pixel_shuffle reads."""
     return 4 * c + 2 * i + j
-
-
-def conv_weight_cl(w):
-    """[Cout, Cin, k, k] -> [Cout, k, k, Cin], what r3d_secc_conv and r3d_torso_conv read."""
-    return w.detach().permute(0, 2, 3, 1).contiguous().float()
 
 
 def is_reference_img2plane(m):
@@ -169,11 +130,7 @@ class Img2PlaneModel(_FoldedModule):
         if "alpha" in self.input_mode and isinstance(cond, dict) and cond.get("ref_alphas") is not None:
             if tuple(cond["ref_alphas"].shape) != (B, 1, H, W):
                 raise ValueError("Img2PlaneModel: cond['ref_alphas'] must be [B, 1, S, S], got %s" % (tuple(cond["ref_alphas"].shape),))
-        if not x.is_cuda:
-            raise ValueError("Img2PlaneModel: the image is not on a GPU: the library operates on device tensors only")
-        own = next(self.high_reso_encoder.parameters()).device
-        if own != x.device:
-            raise ValueError("Img2PlaneModel: the image is on %s, the module's parameters on %s" % (x.device, own))
+        self._check_device(x, "image", next(self.high_reso_encoder.parameters()))
         if self.low_reso_encoder is None:
             raise ValueError("Img2PlaneModel: no low_reso_encoder was given (this package constructs no DeepLabV3)")
         return B, H
@@ -203,29 +160,11 @@ class Img2PlaneModel(_FoldedModule):
         _lib.call("r3d_torso_conv", x, B, h, h, cin, 0, 0, None, None, 0.0, d[key], m.bias, m.out_channels, 3, act, slope, None, y, None, st)
 
     def _block(self, d, key, w, B, h, st):
-        blk = self.get_submodule(key)
-        a, n1, n2, mlp = blk.attn, blk.norm1, blk.norm2, blk.mlp
-        X, T, Q, O, H1, H2, SR, KV = w["x"], w["t"], w["q"], w["o"], w["h1"], w["h2"], w["sr"], w["kv"]
-        sr = a.sr_ratio
-        M, L = B * h * h, (h // sr) * (h // sr)
-        if sr > 1:
-            _lib.call("r3d_secc_layernorm", X, M, DIM, n1.weight, n1.bias, n1.eps, T, st)
-            _lib.call("r3d_secc_linear", T, M, DIM, None, None, 0.0, a.q.weight, a.q.bias, DIM, 0, None, Q, st)
-            _lib.call("r3d_secc_conv", T, B, h, h, DIM, d[key + ".attn.sr"], a.sr.bias, DIM, sr, sr, 0, None, None, 0.0, SR, st)
-            _lib.call("r3d_secc_linear", SR, B * L, DIM, a.norm.weight, a.norm.bias, a.norm.eps, a.kv.weight, a.kv.bias, 2 * DIM, 0, None, KV, st)
-        else:
-            _lib.call("r3d_secc_linear", X, M, DIM, n1.weight, n1.bias, n1.eps, a.q.weight, a.q.bias, DIM, 0, None, Q, st)
-            _lib.call("r3d_secc_linear", X, M, DIM, n1.weight, n1.bias, n1.eps, a.kv.weight, a.kv.bias, 2 * DIM, 0, None, KV, st)
-        _lib.call("r3d_i2p_attention", Q, KV, B, h * h, L, DIM, HEADS, (DIM // HEADS) ** -0.5, O, st)
-        _lib.call("r3d_secc_linear", O, M, DIM, None, None, 0.0, a.proj.weight, a.proj.bias, DIM, 0, X, X, st)
-        _lib.call("r3d_secc_linear", X, M, DIM, n2.weight, n2.bias, n2.eps, mlp.fc1.weight, mlp.fc1.bias, HIDDEN, 0, None, H1, st)
-        dw = mlp.dwconv.dwconv
-        _lib.call("r3d_secc_dwconv_gelu", H1, B, h, h, HIDDEN, dw.weight, dw.bias, H2, st)
-        _lib.call("r3d_secc_linear", H2, M, HIDDEN, None, None, 0.0, mlp.fc2.weight, mlp.fc2.bias, DIM, 0, X, X, st)
+        mit_block("r3d_i2p_attention", self.get_submodule(key), d.get(key + ".attn.sr"), w, st, B, h, h, DIM, HIDDEN, HEADS)
 
     def _run(self, x_in, feat_low, taps=None):
         """The library launches, on x_in's device and that device's current stream (which need not be the process's current device)."""
-        with torch.cuda.device(x_in.device):
+        with self._device_of(x_in):
             return self._launches(x_in, feat_low, taps)
 
     def _launches(self, x_in, feat_low, taps):

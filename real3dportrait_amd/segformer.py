@@ -16,6 +16,7 @@ from . import _lib
 from ._state import _FoldedModule
 from .superresolution import Conv2d, ConvStack
 from .synth import SECC_DIMS, SECC_HEADS, SECC_SR
+from .token_blocks import Block, PatchEmbed, conv_weight_cl, mit_block
 
 MAX_KEYS = 1024          # r3d_secc_attention's limit on L = (H/32)(W/32): inputs up to 1024^2
 
@@ -31,40 +32,6 @@ class _Prenet(nn.Module):
         self.register_buffer("resample_filter", torch.outer(f, f) / 64.0)
 
 
-class _PatchEmbed(nn.Module):
-    def __init__(self, cin, cout, k, stride):
-        super().__init__()
-        self.proj = nn.Conv2d(cin, cout, k, stride, k // 2)
-        self.norm = nn.LayerNorm(cout)
-
-
-class _Attention(nn.Module):
-    def __init__(self, C, sr):
-        super().__init__()
-        self.q, self.kv, self.proj = nn.Linear(C, C), nn.Linear(C, 2 * C), nn.Linear(C, C)
-        if sr > 1:
-            self.sr = nn.Conv2d(C, C, sr, sr)
-            self.norm = nn.LayerNorm(C)
-
-
-class _DWConv(nn.Module):
-    def __init__(self, C):
-        super().__init__()
-        self.dwconv = nn.Conv2d(C, C, 3, 1, 1, groups=C)
-
-
-class _Mlp(nn.Module):
-    def __init__(self, C):
-        super().__init__()
-        self.fc1, self.dwconv, self.fc2 = nn.Linear(C, 4 * C), _DWConv(4 * C), nn.Linear(4 * C, C)
-
-
-class _Block(nn.Module):
-    def __init__(self, C, sr):
-        super().__init__()
-        self.norm1, self.attn, self.norm2, self.mlp = nn.LayerNorm(C), _Attention(C, sr), nn.LayerNorm(C), _Mlp(C)
-
-
 class _MixVisionTransformer(nn.Module):
     """mit_b0's parameters (segformer.py:244-310, 407-413)."""
 
@@ -72,8 +39,8 @@ class _MixVisionTransformer(nn.Module):
         super().__init__()
         cin = 3
         for s, (C, sr) in enumerate(zip(SECC_DIMS, SECC_SR), 1):
-            setattr(self, "patch_embed%d" % s, _PatchEmbed(cin, C, 7 if s == 1 else 3, 4 if s == 1 else 2))
-            setattr(self, "block%d" % s, nn.ModuleList([_Block(C, sr) for _ in range(2)]))
+            setattr(self, "patch_embed%d" % s, PatchEmbed(cin, C, 7 if s == 1 else 3, 4 if s == 1 else 2))
+            setattr(self, "block%d" % s, nn.ModuleList([Block(C, 4 * C, sr) for _ in range(2)]))
             setattr(self, "norm%d" % s, nn.LayerNorm(C))
             cin = C
 
@@ -121,10 +88,10 @@ class SegFormerSECC2PlaneBackbone(_FoldedModule):
         d = {"conv": {}}
         for s in range(1, 5):
             pe = getattr(mv, "patch_embed%d" % s)
-            d["conv"]["pe%d" % s] = pe.proj.weight.detach().permute(0, 2, 3, 1).contiguous().float()
+            d["conv"]["pe%d" % s] = conv_weight_cl(pe.proj.weight)
             for j, blk in enumerate(getattr(mv, "block%d" % s)):
                 if hasattr(blk.attn, "sr"):
-                    d["conv"]["sr%d.%d" % (s, j)] = blk.attn.sr.weight.detach().permute(0, 2, 3, 1).contiguous().float()
+                    d["conv"]["sr%d.%d" % (s, j)] = conv_weight_cl(blk.attn.sr.weight)
         # the head fold, in fp64: W'_i = W_fuse[:, block(i)] W_ci, const = sum_i W_fuse[:, block(i)] b_ci, BN -> scale, shift
         wf = fh.linear_fuse.conv.weight.detach().double()[:, :, 0, 0]
         const = torch.zeros(256, dtype=torch.float64, device=wf.device)
@@ -160,52 +127,50 @@ class SegFormerSECC2PlaneBackbone(_FoldedModule):
             raise NotImplementedError("SegFormerSECC2PlaneBackbone: (H/32)(W/32) = %d keys > %d" % ((H // 32) * (W // 32), MAX_KEYS))
         return B, H, W
 
-    def _encode(self, x):
-        """Runs prenet + mix_vit; returns (buffers, B, H, W, params).  Stage outputs c1..c4 stay in the stream's buffers [B, h, w, C]."""
+    def _encode(self, x, head=False):
+        """Runs prenet + mix_vit on x's device and that device's current stream (the device rule of _FoldedModule); returns the stream's
+        buffers, where the stage outputs c1..c4 stay as [B, h, w, C], or with `head` the fuse_head output."""
         B, H, W = self._check_input(x)
+        self._check_device(x, "input")
         x = x.detach().float().contiguous()
-        st = torch.cuda.current_stream().cuda_stream
-        d = self._prepare()
-        w = self._buffers_for(x.device, B, H, W)
-        mv = self.mix_vit
-        X, T, Q, O, H1, H2, SR, KV = w["x"], w["t"], w["q"], w["o"], w["h1"], w["h2"], w["sr"], w["kv"]
+        with self._device_of(x):
+            st = torch.cuda.current_stream().cuda_stream
+            d = self._prepare()
+            w = self._buffers_for(x.device, B, H, W)
+            self._stages(x, w, d, B, H, W, st)
+            return self._head(w, d, B, H, W, st) if head else w
+
+    def _stages(self, x, w, d, B, H, W, st):
+        mv, X = self.mix_vit, w["x"]
         h, wd = H // 4, W // 4
         pe = mv.patch_embed1
         _lib.call("r3d_secc_embed1", x, B, self.in_dim, H, W, self.prenet.weight, self.prenet.bias, d["conv"]["pe1"], pe.proj.bias, pe.norm.weight,
                   pe.norm.bias, X, st)
-        for s, (C, heads, sr) in enumerate(zip(SECC_DIMS, SECC_HEADS, SECC_SR), 1):
+        for s, (C, heads) in enumerate(zip(SECC_DIMS, SECC_HEADS), 1):
             if s > 1:
                 pe, prev = getattr(mv, "patch_embed%d" % s), w["c"][s - 2]
                 _lib.call("r3d_secc_conv", prev, B, h, wd, SECC_DIMS[s - 2], d["conv"]["pe%d" % s], pe.proj.bias, C, 3, 2, 1, pe.norm.weight,
                           pe.norm.bias, pe.norm.eps, X, st)
                 h, wd = h // 2, wd // 2
-            M, L = B * h * wd, (h // sr) * (wd // sr)
             for j, blk in enumerate(getattr(mv, "block%d" % s)):
-                a, n1 = blk.attn, blk.norm1
-                if sr > 1:
-                    _lib.call("r3d_secc_layernorm", X, M, C, n1.weight, n1.bias, n1.eps, T, st)
-                    _lib.call("r3d_secc_linear", T, M, C, None, None, 0.0, a.q.weight, a.q.bias, C, 0, None, Q, st)
-                    _lib.call("r3d_secc_conv", T, B, h, wd, C, d["conv"]["sr%d.%d" % (s, j)], a.sr.bias, C, sr, sr, 0, None, None, 0.0, SR, st)
-                    _lib.call("r3d_secc_linear", SR, B * L, C, a.norm.weight, a.norm.bias, a.norm.eps, a.kv.weight, a.kv.bias, 2 * C, 0, None, KV, st)
-                else:
-                    _lib.call("r3d_secc_linear", X, M, C, n1.weight, n1.bias, n1.eps, a.q.weight, a.q.bias, C, 0, None, Q, st)
-                    _lib.call("r3d_secc_linear", X, M, C, n1.weight, n1.bias, n1.eps, a.kv.weight, a.kv.bias, 2 * C, 0, None, KV, st)
-                _lib.call("r3d_secc_attention", Q, KV, B, h * wd, L, C, heads, (C // heads) ** -0.5, O, st)
-                _lib.call("r3d_secc_linear", O, M, C, None, None, 0.0, a.proj.weight, a.proj.bias, C, 0, X, X, st)
-                mlp, n2 = blk.mlp, blk.norm2
-                _lib.call("r3d_secc_linear", X, M, C, n2.weight, n2.bias, n2.eps, mlp.fc1.weight, mlp.fc1.bias, 4 * C, 0, None, H1, st)
-                dw = mlp.dwconv.dwconv
-                _lib.call("r3d_secc_dwconv_gelu", H1, B, h, wd, 4 * C, dw.weight, dw.bias, H2, st)
-                _lib.call("r3d_secc_linear", H2, M, 4 * C, None, None, 0.0, mlp.fc2.weight, mlp.fc2.bias, C, 0, X, X, st)
+                mit_block("r3d_secc_attention", blk, d["conv"].get("sr%d.%d" % (s, j)), w, st, B, h, wd, C, 4 * C, heads)
             nrm = getattr(mv, "norm%d" % s)
-            _lib.call("r3d_secc_layernorm", X, M, C, nrm.weight, nrm.bias, nrm.eps, w["c"][s - 1], st)
-        return w, B, H, W, d
+            _lib.call("r3d_secc_layernorm", X, B * h * wd, C, nrm.weight, nrm.bias, nrm.eps, w["c"][s - 1], st)
+
+    def _head(self, w, d, B, H, W, st):
+        for s in (2, 3, 4):
+            n = B * (H // 2 ** (s + 1)) * (W // 2 ** (s + 1))
+            _lib.call("r3d_secc_linear", w["c"][s - 1], n, SECC_DIMS[s - 1], None, None, 0.0, d["wfold%d" % s], None, 256, 0, None, w["f"][s - 1], st)
+        out = torch.empty(B, 256, H // 4, W // 4, device=w["x"].device, dtype=torch.float32)
+        _lib.call("r3d_secc_head", w["c"][0], B, H // 4, W // 4, d["wfold1"], w["f"][1], w["f"][2], w["f"][3], d["hconst"], d["bn_scale"],
+                  d["bn_shift"], out, st)
+        return out
 
     @torch.no_grad()
     def forward_stages(self, x):
         """[c1, c2, c3, c4] NCHW (MixVisionTransformer.forward_features, segformer.py:377-410), as new tensors."""
-        w, B, H, W, _ = self._encode(x)
-        out = []
+        w = self._encode(x)
+        (B, _, H, W), out = x.shape, []
         for s, C in enumerate(SECC_DIMS, 1):
             h, wd = H // (2 ** (s + 1)), W // (2 ** (s + 1))
             out.append(w["c"][s - 1][:B * h * wd * C].view(B, h, wd, C).permute(0, 3, 1, 2).contiguous())
@@ -214,15 +179,7 @@ class SegFormerSECC2PlaneBackbone(_FoldedModule):
     @torch.no_grad()
     def forward_features(self, x):
         """fuse_head(mix_vit(prenet(x))): [B, 256, H/4, W/4] NCHW fp32."""
-        w, B, H, W, d = self._encode(x)
-        st = torch.cuda.current_stream().cuda_stream
-        for s in (2, 3, 4):
-            n = B * (H // 2 ** (s + 1)) * (W // 2 ** (s + 1))
-            _lib.call("r3d_secc_linear", w["c"][s - 1], n, SECC_DIMS[s - 1], None, None, 0.0, d["wfold%d" % s], None, 256, 0, None, w["f"][s - 1], st)
-        out = torch.empty(B, 256, H // 4, W // 4, device=x.device, dtype=torch.float32)
-        _lib.call("r3d_secc_head", w["c"][0], B, H // 4, W // 4, d["wfold1"], w["f"][1], w["f"][2], w["f"][3], d["hconst"], d["bn_scale"],
-                  d["bn_shift"], out, st)
-        return out
+        return self._encode(x, head=True)
 
     @torch.no_grad()
     def forward_raw(self, x):

@@ -1,4 +1,5 @@
-"""What one build of the library computes -- the head frame (both SR precisions), ray-kernel shapes, the torso frame -- saved so that
+"""What one build of the library computes -- the head frame (both SR precisions), ray-kernel shapes, the torso frame, the three
+token-transformer models with their launch traces -- saved so that
 `scripts/ab.py outputs A B` can compare two builds (the tolerances and their reasons are in `_ab.compare_outputs`).  `R3D_LIB` selects the
 build (default: the tree's own library).  Prints a `digest` line per group of arrays and `time` lines: the head frame on one stream by the
 host clock, the ray kernel per shape from the library's own events (`r3d_profile_read`, 20 calls).
@@ -46,4 +47,46 @@ fr = [frame(t).clone() for t in range(2)]
 torch.cuda.synchronize()
 print("digest torso_frame f16mx %s" % dig(*fr))
 SAVE["torso_frame_f16mx"] = torch.stack(fr).cpu().numpy()
+# 4. the token-transformer models, seeded synth weights at the goldens' smallest shapes: the output, and the launch
+# trace -- the _lib.counting() list with every address (device pointers, the stream) replaced by the index of its first appearance in the
+# trace, scalars kept: equal digests mean the same entry points in the same order with the same scalars and the same buffer wiring
+from real3dportrait_amd import synth
+from real3dportrait_amd.hubert import HubertFeatureModel, hubert_features
+from real3dportrait_amd.img2plane import Img2PlaneModel
+from real3dportrait_amd.segformer import SegFormerSECC2PlaneBackbone
+def trace(calls):
+    first, out = {}, []
+    for name, args in calls:
+        n, stream, devptrs, _ = _lib._plans[name]
+        where = {i for i, _, _ in devptrs} | ({n - 1} if stream else set())
+        out.append((name,) + tuple(first.setdefault(a, len(first)) if i in where and a is not None else a for i, a in enumerate(args)))
+    return out
+def token_model(name, model, sd, run):
+    own = {k: v for k, v in model.state_dict().items() if k.startswith("low_reso_encoder.")}          # the stand-in's, not synth's
+    model.load_state_dict(dict(own, **{k: torch.from_numpy(np.ascontiguousarray(v)) for k, v in sd.items()}), strict=True)
+    model.to(dev).eval()
+    with torch.no_grad(), _lib.counting() as calls:
+        out = run(model)
+    torch.cuda.synchronize()
+    tr = trace(calls)
+    print("digest %s output %s" % (name, dig(out)))
+    print("digest %s trace %s (%d calls)" % (name, hashlib.sha1(repr(tr).encode()).hexdigest()[:16], len(tr)))
+    SAVE["token_" + name] = out.cpu().numpy()
+class StandInEncoder(torch.nn.Module):
+    """In the place of DeepLabV3: [B, C, S, S] -> [B, 256, S/8, S/8], the 8 x 8 average pool with channel j % C scaled and shifted by seeded
+    constants -- element-wise, so that no library picks an algorithm for it."""
+    def __init__(self, seed=70):
+        super().__init__()
+        self.register_buffer("a", torch.from_numpy(synth.hash_unitvar(seed, (1, 256, 1, 1), stream=4900) * np.float32(2.0)))
+        self.register_buffer("b", torch.from_numpy(synth.hash_unitvar(seed, (1, 256, 1, 1), stream=4901) * np.float32(0.5)))
+    def forward(self, x):
+        p = torch.nn.functional.avg_pool2d(x, 8)
+        return p[:, torch.arange(256, device=x.device) % p.shape[1]] * self.a + self.b
+uniform = lambda seed, *shape: torch.from_numpy(synth.hash_uniform(seed, int(np.prod(shape)), stream=5).reshape(shape) * np.float32(2.0) - np.float32(1.0)).to(dev)
+token_model("secc_1x9x64x64", SegFormerSECC2PlaneBackbone(), synth.synth_secc_backbone(91), lambda m: m.forward_features(uniform(92, 1, 9, 64, 64)))
+token_model("img2plane_small_s64", Img2PlaneModel(96, hp={"img2plane_backbone_scale": "small"}, low_reso_encoder=StandInEncoder()),
+            synth.synth_img2plane(93, "small", 5, qk_gain=1.5), lambda m: m(uniform(94, 1, 3, 64, 64)))
+one_layer = {"hidden_size": 128, "num_hidden_layers": 1, "num_attention_heads": 2, "intermediate_size": 256, "conv_dim": (32,) * 7,
+             "num_conv_pos_embeddings": 16, "num_conv_pos_embedding_groups": 4}
+token_model("hubert_1layer_n4077", HubertFeatureModel(one_layer), synth.synth_hubert(95, one_layer), lambda m: hubert_features(m, uniform(96, 4077).cpu().numpy() * 0.3))
 if len(sys.argv) > 1: np.savez(sys.argv[1], **SAVE)

@@ -115,6 +115,47 @@ def test_batch_repeat_and_side_stream_are_bit_identical():
     assert torch.equal(both, s_out)
 
 
+def test_on_a_device_that_is_not_the_current_one():
+    """Module and input on the last visible GPU while the process's current device stays 0 (with one GPU they are the same device): the
+    launches go to the input's device and its current stream.  An input on another device than the parameters, or on none, is refused
+    before the library is entered."""
+    from real3dportrait_amd import _lib
+    g, sd, x = golden_case("secc_a_r64")
+    last = "cuda:%d" % (torch.cuda.device_count() - 1)
+    m = hip_backbone(sd, str(g["mode"])).to(last)
+    assert torch.cuda.current_device() == 0
+    head = m.forward_features(torch.from_numpy(x).to(last))
+    assert str(head.device) == last and torch.cuda.current_device() == 0
+    assert rel(head.cpu().numpy(), g["head"]) <= TOL
+    with _lib.counting() as calls:
+        if last != DEV:
+            with pytest.raises(ValueError, match="the module's parameters on"):
+                m.forward_features(torch.from_numpy(x).to(DEV))
+        for fn in (m.forward_features, m.forward_stages, m):
+            with pytest.raises(ValueError, match="not on a GPU"):
+                fn(torch.from_numpy(x))
+    assert calls == []
+
+
+def test_launch_list_of_forward_features():
+    """embed1; per stage the embedding conv (stages 2-4), two blocks and the stage's LayerNorm, a block being nine launches with
+    spatial reduction (stages 1-3) and seven without (stage 4); then the three folded linears and the head: 80."""
+    from real3dportrait_amd import _lib
+    g, sd, x = golden_case("secc_a_r64")
+    m = hip_backbone(sd, str(g["mode"]))
+    with _lib.counting() as calls:
+        m.forward_features(torch.from_numpy(x).to(DEV))
+    tail = ["r3d_secc_attention", "r3d_secc_linear", "r3d_secc_linear", "r3d_secc_dwconv_gelu", "r3d_secc_linear"]
+    reduced = ["r3d_secc_layernorm", "r3d_secc_linear", "r3d_secc_conv", "r3d_secc_linear"] + tail
+    plain = ["r3d_secc_linear", "r3d_secc_linear"] + tail
+    stage = lambda block: block * 2 + ["r3d_secc_layernorm"]
+    want = ["r3d_secc_embed1"] + stage(reduced) + (["r3d_secc_conv"] + stage(reduced)) * 2 + ["r3d_secc_conv"] + stage(plain) \
+        + ["r3d_secc_linear"] * 3 + ["r3d_secc_head"]
+    names = [n for n, _ in calls]
+    assert names == want
+    assert len(names) == 80 and names.count("r3d_secc_attention") == 8 and "r3d_i2p_attention" not in names
+
+
 def test_peaked_softmax_has_no_overflow():
     """q weights x 4 on top of synth's gain: the attention logits reach about +-80.  The max-subtracted softmax stays finite; c1 matches
     fp64 within the tolerance, and every later output as closely as an eager fp32 evaluation of the same math does (the cascade of

@@ -170,6 +170,39 @@ def test_c_entry_points_reject_bad_arguments_without_a_gpu():
     assert rc == -1 and b"bad argument" in lib.r3d_last_error()
     rc = lib.r3d_secc_conv(one, 1, 1, 1, 3, one, one, 17, 4, 2, 1, None, None, 0.0, ctypes.c_void_p(1 << 30), None)
     assert rc == -1 and b"empty output" in lib.r3d_last_error()      # 1 + 2 - 4 < 0: nn.Conv2d has no output either
+    # a "bad argument" names the values it is about
+    far = ctypes.c_void_p(1 << 30)
+    rc = lib.r3d_secc_embed1(one, 1, 7, 64, 64, one, one, one, one, one, one, one, None)
+    assert rc == -1 and b"bad argument" in lib.r3d_last_error() and b"in_dim = 7" in lib.r3d_last_error()
+    rc = lib.r3d_secc_conv(one, 1, 16, 16, 32, one, one, 64, 3, 0, 1, None, None, 0.0, far, None)
+    assert rc == -1 and b"bad argument" in lib.r3d_last_error() and b"stride = 0" in lib.r3d_last_error()
+    rc = lib.r3d_secc_conv(one, 1, 16, 16, 1025, one, one, 64, 3, 2, 1, None, None, 0.0, far, None)
+    assert rc == -1 and b"bad argument" in lib.r3d_last_error() and b"Cin = 1025" in lib.r3d_last_error()
+    rc = lib.r3d_secc_conv(one, 1, 16, 16, 32, one, one, 64, 3, 2, 3, None, None, 0.0, far, None)
+    assert rc == -1 and b"bad argument" in lib.r3d_last_error() and b"pad = 3" in lib.r3d_last_error()
+    rc = lib.r3d_secc_conv(one, 1, 16, 16, 32, one, one, 64, 9, 2, 1, None, None, 0.0, far, None)
+    assert rc == -1 and b"bad argument" in lib.r3d_last_error() and b"ksize = 9" in lib.r3d_last_error()
+    rc = lib.r3d_secc_linear(one, 64, 4097, None, None, 0.0, one, None, 32, 0, None, far, None)
+    assert rc == -1 and b"bad argument" in lib.r3d_last_error() and b"K = 4097" in lib.r3d_last_error()
+    rc = lib.r3d_secc_layernorm(one, 16, 32, one, one, 0.0, far, None)
+    assert rc == -1 and b"bad argument" in lib.r3d_last_error() and b"eps = 0" in lib.r3d_last_error()
+    rc = lib.r3d_secc_attention(one, far, 1, 256, 256, 64, 1, 0.17, ctypes.c_void_p(1 << 31), None)
+    assert rc == -1 and b"bad argument" in lib.r3d_last_error() and b"C = 64, heads = 1" in lib.r3d_last_error()
+    rc = lib.r3d_secc_dwconv_gelu(one, 1, 16, 0, 128, one, one, far, None)
+    assert rc == -1 and b"bad argument" in lib.r3d_last_error() and b"W = 0" in lib.r3d_last_error()
+    # products of sizes that the entry point or its kernel forms in int or unsigned are refused at 2^31, before any is formed
+    rc = lib.r3d_secc_conv(one, 65536, 512, 512, 32, one, one, 64, 3, 1, 1, None, None, 0.0, one, None)          # B Ho Wo = 2^34
+    assert rc == -1 and b"2^31" in lib.r3d_last_error() and b"B Ho Wo" in lib.r3d_last_error()
+    rc = lib.r3d_secc_conv(one, 1 << 15, 256, 256, 32, one, one, 64, 3, 1, 1, None, None, 0.0, one, None)        # = 2^31 exactly
+    assert rc == -1 and b"2^31" in lib.r3d_last_error()
+    rc = lib.r3d_secc_embed1(one, 1 << 21, 9, 128, 128, one, one, one, one, one, one, one, None)                  # B (H/4)(W/4) = 2^31
+    assert rc == -1 and b"2^31" in lib.r3d_last_error() and b"B (H/4)(W/4)" in lib.r3d_last_error()
+    rc = lib.r3d_secc_dwconv_gelu(one, 65536, 2048, 2048, 128, one, one, one, None)                               # 2^45 elements, 2^37 blocks
+    assert rc == -1 and b"2^31" in lib.r3d_last_error() and b"blocks" in lib.r3d_last_error()
+    rc = lib.r3d_secc_linear(one, (1 << 31) - 63, 32, None, None, 0.0, one, None, 32, 0, None, one, None)         # the last 64-row tile ends at 2^31
+    assert rc == -1 and b"2^31" in lib.r3d_last_error()
+    rc = lib.r3d_secc_head(one, 1 << 17, 128, 128, one, one, one, one, one, one, one, one, None)                  # B H1 W1 = 2^31
+    assert rc == -1 and b"2^31" in lib.r3d_last_error()
 
 
 def test_c_entry_points_reject_racing_overlaps_without_a_gpu():
@@ -202,6 +235,11 @@ def test_c_entry_points_reject_racing_overlaps_without_a_gpu():
     assert rc == -1 and b"overlap" in lib.r3d_last_error()
     # layernorm: partial overlap (y == x is in place and allowed)
     rc = lib.r3d_secc_layernorm(at(0), 16, 32, w, w, 1e-5, at(32), None)
+    assert rc == -1 and b"overlap" in lib.r3d_last_error()
+    # linear: x [64, 32] = 2048 floats, y and the residual [64, 64] = 4096; a residual that is not y itself may not share a float with it
+    rc = lib.r3d_secc_linear(at(0), 64, 32, None, None, 0.0, w, None, 64, 0, at(10000 + 4095), at(10000), None)
+    assert rc == -1 and b"overlap" in lib.r3d_last_error() and b"residual" in lib.r3d_last_error()
+    rc = lib.r3d_secc_linear(at(0), 64, 32, None, None, 0.0, w, None, 64, 0, at(10000), at(2047), None)
     assert rc == -1 and b"overlap" in lib.r3d_last_error()
     # head: out [1, 256, 8, 8] = 16384 floats; c1 2048, f2 4096, f3 1024, f4 256
     ins = [at(100000), at(200000), at(300000), at(400000), at(500000)]      # c1, f2, f3, f4, w1f
