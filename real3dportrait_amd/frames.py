@@ -155,13 +155,12 @@ class ClipRenderer:
         """precision: SR precision to set on the generator's blocks -- None = leave them as they are (library default 'f16mx'),
         'throughput' = superresolution.THROUGHPUT_SR_PRECISION (the default 'f16mx', unless R3D_SR_PRECISION names another),
         or a precision name ('f16x3' = the fp32-class tier, 'f32')."""
-        import os
         from . import _lib
-        from .superresolution import THROUGHPUT_SR_PRECISION, set_sr_precision
+        from .superresolution import THROUGHPUT_SR_PRECISION, process_sr_precision, set_sr_precision
         self._lib = _lib
         self.G = generator
         if precision == "throughput":
-            precision = os.environ.get("R3D_SR_PRECISION", THROUGHPUT_SR_PRECISION)
+            precision = process_sr_precision(THROUGHPUT_SR_PRECISION)
         set_sr_precision(generator.superresolution, precision)
         self.cano = cano_planes            # [1,3,32,H,W]
         self.residuals = residuals         # list of [1,3,32,H,W] (cycled) or None

@@ -11,8 +11,9 @@ they are).  Compared with running the reference forward over patched sub-modules
     r3d_person_occlusion) instead of ~25 ATen launches;
   * clip constants are computed once: the 512 -> 256 resizes of ref_torso_rgb / ref_bg_rgb and bg_encoder(ref_bg_rgb_256) are cached on
     the identity + version of the input tensors (the reference recomputes them every frame, :79-81,91);
-  * fp16 range folding: five r3d_chain_fold launches, each re-started from a MEASURED max|x| (taken in a conv epilogue, no extra pass)
-    so that no stored operand is more than three layers away from a measurement.
+  * fp16 range folding: four r3d_chain_fold launches per frame (block0's; torso_encoder + fuse_head_torso_convs + head_torso_block;
+    fuse_fg_bg_convs + block1; block1's conv1 operand), each started from a MEASURED max|x| (taken in a conv epilogue, no extra pass)
+    so that no stored operand is more than three layers away from a measurement; a fifth, bg_encoder's, runs once per background image.
 The face-vid2vid warp network `torso_model` is a cold-ish PyTorch encoder and is called as is (out of scope).
 """
 import torch
@@ -20,17 +21,12 @@ import torch
 from . import _lib
 from .sr_activation import _tag, as_input, bound_of, empty, fmt_of, logical_shape, tag_split
 from ._state import Derived
-from .superresolution import _BoundMeter, _f32c, blend_cat, chain_fold, const_bound, resize_bilinear
+from .superresolution import _BoundMeter, _RangeRows, _f32c, blend_cat, chain_fold, const_bound, resize_bilinear
 
-
-import os
-
-# A/B switch: 1 = head_torso_block's conv1 operand is re-folded from the measured max of fuse_head_torso_convs' output (rounds 3-4)
-_HB_TAIL_FOLD = os.environ.get("R3D_HB_TAIL_FOLD", "0") == "1"
-# A/B switch: 0 = person / background blend written as a SPLIT tensor (r3d_blend_cat_to_split) and read back by fuse_fg_bg_convs' 1x1 conv (rounds 2-5)
-_FUSE_BLEND = os.environ.get("R3D_FUSE_BLEND", "1") != "0"
-# A/B switch: 0 = torso_encoder writes the fp32 x_torso and r3d_blend_cat_to_split reads it back (rounds 2-5)
-_FUSE_TORSO_CAT = os.environ.get("R3D_FUSE_TORSO_CAT", "1") != "0"
+# The two fusions of the v2 forward.  Each has a general form for the shapes it refuses (Conv2d.can_blend, `fuse_cat` below), and
+# tests/test_gpu_warp_sr.py::test_warp_sr_forward_v2_round6_fusions_are_bit_identical sets these to False to run that form on the shipped shapes.
+_FUSE_BLEND = True           # the person / background blend inside fuse_fg_bg_convs' 1x1 conv (r3d_conv_forward_blend)
+_FUSE_TORSO_CAT = True       # torso_encoder writes its half of fuse_head_torso_convs' operand itself (r3d_conv_forward_cat)
 
 
 def blend(a, b, mask):
@@ -52,40 +48,34 @@ def person_occlusion(alpha, torso_occlusion, head_threshold):
     return out
 
 
-def _measured(t, S):
-    """Tag a (clip-constant) fp32 activation with its MEASURED max|x| (its own tensor, not a meter slot that later calls reuse)."""
+def _measured(t):
+    """Tag a (clip-constant) fp32 activation with its MEASURED max|x| (its own tensor, not a meter row that later calls reuse)."""
     return _tag(t, _BoundMeter()(t).clone(), 0)
 
 
 class WarpSRState:
-    """Per-module scratch of the fused forward (absmax slots, meters, clip-constant caches)."""
+    """Per-module scratch of the fused forward (range rows, meters, clip-constant caches)."""
 
     def __init__(self, hparams):
         self.hparams = dict(hparams)
-        self.slots = None
+        self.rows = _RangeRows(3)           # max|x0| (block0), max|x2| (head_torso_block), max|z| (fuse_fg_bg_convs): measured in the epilogues
         self.split_fold_pending = False     # split_input_spec() folded block0 for a SPLIT input that forward() has not consumed yet
         self.meter_x, self.meter_hid = _BoundMeter(), _BoundMeter()
         self.c_torso256, self.c_bg256, self.c_xbg, self.c_ws3 = Derived(), Derived(), Derived(), Derived()
 
-    def slot(self, k, N, dev):
-        if self.slots is None or self.slots.shape[1] != N or self.slots.device != dev:
-            self.slots = torch.zeros(4, N, device=dev, dtype=torch.float32)
-        return self.slots[k]
-
 
 def warp_split_input_spec(self, ws, N, dev):
     """As SuperresolutionHybrid8XDC.split_input_spec, for the fused Warp forward: block0's styles and range fold for the renderer's
-    feature image (|x| <= 1.01) are put in place NOW (the fold also clears the max|x0| slot block0's epilogue measures into), and
+    feature image (|x| <= 1.01) are put in place NOW (the fold also clears the max|x0| row block0's epilogue measures into), and
     (folded input multiplier, per-sample stride in floats, consuming block) is returned for r3d_render_forward's split_out.  The
     caller hands the SPLIT tensor to the next forward() as `x`; None when the precision has no SPLIT operand."""
-    from .superresolution import const_bound
     S = self._r3d_state
     b0 = self.block0
     if b0.precision not in ("f16x3", "f16mx") or self.input_resolution != 128:
         return None
     ws3 = S.c_ws3.get([ws], lambda: ws[:, -1:, :].expand(N, 3, -1).contiguous())
     b0.prepare(ws3, dev, ws_key=ws)
-    chain_fold([b0.chain_op(-1)], N, [const_bound(1.01, N, dev)], zero=[S.slot(0, N, dev)])
+    chain_fold([b0.chain_op(-1)], N, [const_bound(1.01, N, dev)], zero=[S.rows.at(N, dev)[0]])
     S.split_fold_pending = True
     scale, stride = b0.in_scale()
     return scale, stride, b0
@@ -116,29 +106,40 @@ def forward_v2(self, rgb, x, ws, ref_torso_rgb, ref_bg_rgb, weights_img, segmap,
     return _forward_v2(self, S, rgb, x, ws, ref_torso_rgb, ref_bg_rgb, weights_img, segmap, kp_s, kp_d, target_torso_mask, block_kwargs)
 
 
-def _forward_v1(self, rgb, x, ws, ref_torso_rgb, ref_bg_rgb, weights_img, segmap, kp_s, kp_d, target_torso_mask, block_kwargs):
-    hp = self._r3d_state.hparams
-    aa = self.sr_antialias
-    weights_img = weights_img.detach()
-    N = rgb.shape[0]
-    ws3 = ws[:, -1:, :].expand(N, 3, -1).contiguous()                                                   # :69
-    if x.shape[-1] != self.input_resolution:
+def _prologue(self, rgb, x, ws, ref_torso_rgb, ref_bg_rgb, weights_img, block_kwargs, cache=None):
+    """What every entry point does before block0 (sr_with_ref.py:69-82, :167-178): ws3, the resize to input_resolution where x has another,
+    the four 256^2 resizes, noise_mode 'none' unless the caller names one.  cache: the WarpSRState whose entries keep what is constant over
+    a clip (ws3, the two reference resizes) -- the fused forward's; None: computed on every call.
+    Returns (x, rgb, ws3, rgb_256, weights_256, ref_torso_rgb_256, ref_bg_rgb_256, block keywords)."""
+    aa, N = self.sr_antialias, rgb.shape[0]
+    once = lambda name, src, fn: fn() if cache is None else getattr(cache, name).get([src], fn)
+    to256 = lambda t: resize_bilinear(t, (256, 256), aa)
+    ws3 = once("c_ws3", ws, lambda: ws[:, -1:, :].expand(N, 3, -1).contiguous())                        # :69
+    if fmt_of(x) != "split" and x.shape[-1] != self.input_resolution:                                   # :71-75, cold
         sz = (self.input_resolution, self.input_resolution)
         x, rgb = resize_bilinear(x, sz, aa), resize_bilinear(rgb, sz, aa)
-    rgb_256 = resize_bilinear(rgb, (256, 256), aa)
-    weights_256 = resize_bilinear(weights_img, (256, 256), aa)
-    ref_torso_rgb_256 = resize_bilinear(ref_torso_rgb, (256, 256), aa)
-    ref_bg_rgb_256 = resize_bilinear(ref_bg_rgb, (256, 256), aa)
+    rgb_256 = to256(rgb)                                                                                # :77
+    weights_256 = to256(weights_img.detach())                                                           # :78
+    ref_torso_rgb_256 = once("c_torso256", ref_torso_rgb, lambda: to256(ref_torso_rgb))                 # :80 (clip constant)
+    ref_bg_rgb_256 = once("c_bg256", ref_bg_rgb, lambda: to256(ref_bg_rgb))                             # :82 (clip constant)
     kw = dict(block_kwargs)
     kw.setdefault("noise_mode", "none")
+    return x, rgb, ws3, rgb_256, weights_256, ref_torso_rgb_256, ref_bg_rgb_256, kw
+
+
+def _torso_forward(self, ref_torso_rgb_256, segmap, kp_s, kp_d, rgb_256, weights_256, target_torso_mask):
+    """The warp-based torso branch (PyTorch, untouched) (:84-87): a v2 torso model also takes the head weights."""
+    v1 = self._r3d_state.hparams.get("torso_model_version", "v1") == "v1"
+    return self.torso_model.forward(ref_torso_rgb_256, segmap, kp_s, kp_d, rgb_256.detach(), *(() if v1 else (weights_256.detach(),)),
+                                    cal_loss=True, target_torso_mask=target_torso_mask)
+
+
+def _forward_v1(self, rgb, x, ws, ref_torso_rgb, ref_bg_rgb, weights_img, segmap, kp_s, kp_d, target_torso_mask, block_kwargs):
+    hp, aa = self._r3d_state.hparams, self.sr_antialias
+    x, rgb, ws3, rgb_256, weights_256, ref_torso_rgb_256, ref_bg_rgb_256, kw = _prologue(self, rgb, x, ws, ref_torso_rgb, ref_bg_rgb, weights_img, block_kwargs)
     kw.update(_out_format="nchw", _return_x=True)         # the blocks are shared with the fused forward: the reference layout for these calls only
     x, rgb = self.block0(x, rgb, ws3, **kw)                                                             # :83
-    if hp.get("torso_model_version", "v1") == "v1":
-        rgb_torso, ret = self.torso_model.forward(ref_torso_rgb_256, segmap, kp_s, kp_d, rgb_256.detach(), cal_loss=True,
-                                                  target_torso_mask=target_torso_mask)
-    else:
-        rgb_torso, ret = self.torso_model.forward(ref_torso_rgb_256, segmap, kp_s, kp_d, rgb_256.detach(), weights_256.detach(),
-                                                  cal_loss=True, target_torso_mask=target_torso_mask)
+    rgb_torso, ret = _torso_forward(self, ref_torso_rgb_256, segmap, kp_s, kp_d, rgb_256, weights_256, target_torso_mask)
     x_torso = self.torso_encoder(ret["deformed_torso_hid"])                                             # :88
     x_bg = self.bg_encoder(ref_bg_rgb_256)                                                              # :90
     rgb = blend(rgb, rgb_torso, weights_256)                                                            # :94
@@ -152,24 +153,12 @@ def _forward_v1(self, rgb, x, ws, ref_torso_rgb, ref_bg_rgb, weights_img, segmap
 
 
 def _forward_v2(self, S, rgb, x, ws, ref_torso_rgb, ref_bg_rgb, weights_img, segmap, kp_s, kp_d, target_torso_mask, block_kwargs):
-    hp = S.hparams
-    aa = self.sr_antialias
-    weights_img = weights_img.detach()
+    hp, aa = S.hparams, self.sr_antialias
     N, dev = rgb.shape[0], rgb.device
-    ws3 = S.c_ws3.get([ws], lambda: ws[:, -1:, :].expand(N, 3, -1).contiguous())                   # :69
-    if fmt_of(x) != "split" and x.shape[-1] != self.input_resolution:                                   # :71-75, cold
-        sz = (self.input_resolution, self.input_resolution)
-        x, rgb = resize_bilinear(x, sz, aa), resize_bilinear(rgb, sz, aa)
-    rgb_256 = resize_bilinear(rgb, (256, 256), aa)                                                      # :77
-    weights_256 = resize_bilinear(weights_img, (256, 256), aa)                                          # :78
-    ref_torso_rgb_256 = S.c_torso256.get([ref_torso_rgb], lambda: resize_bilinear(ref_torso_rgb, (256, 256), aa))  # :80 (clip constant)
-    ref_bg_rgb_256 = S.c_bg256.get([ref_bg_rgb], lambda: resize_bilinear(ref_bg_rgb, (256, 256), aa))  # :82 (clip constant)
-
+    x, rgb, ws3, rgb_256, weights_256, ref_torso_rgb_256, ref_bg_rgb_256, kw = _prologue(self, rgb, x, ws, ref_torso_rgb, ref_bg_rgb, weights_img, block_kwargs, cache=S)
     b0, b1, hb = self.block0, self.block1, self.head_torso_block
     fuse_ht, fuse_fg = self.fuse_head_torso_convs, self.fuse_fg_bg_convs
-    m_x0, m_y, m_x2, m_z = (S.slot(k, N, dev) for k in range(4))
-    kw = dict(block_kwargs)
-    kw.setdefault("noise_mode", "none")
+    m_x0, m_x2, m_z = S.rows.at(N, dev)
 
     # ---- block0: 128^2 head features -> 256^2 (:83); its conv1 epilogue measures max|x0| ------------------------------------------
     prep0 = b0.prepare(ws3, dev, ws_key=ws)
@@ -185,13 +174,7 @@ def _forward_v2(self, S, rgb, x, ws, ref_torso_rgb, ref_bg_rgb, weights_img, seg
     # self.block0(x, rgb, ws) and expect NCHW x): the hand-off formats are per call
     x0, rgb0 = b0(x, rgb, ws3, _prepared=prep0, _folded=True, _x_absmax=m_x0, _out_format="cb8", _return_x=True, **kw)
 
-    # ---- warp-based torso branch (PyTorch, untouched) (:84-87) ---------------------------------------------------------------------
-    if hp.get("torso_model_version", "v1") == "v1":
-        rgb_torso, ret = self.torso_model.forward(ref_torso_rgb_256, segmap, kp_s, kp_d, rgb_256.detach(), cal_loss=True,
-                                                  target_torso_mask=target_torso_mask)
-    else:
-        rgb_torso, ret = self.torso_model.forward(ref_torso_rgb_256, segmap, kp_s, kp_d, rgb_256.detach(), weights_256.detach(),
-                                                  cal_loss=True, target_torso_mask=target_torso_mask)
+    rgb_torso, ret = _torso_forward(self, ref_torso_rgb_256, segmap, kp_s, kp_d, rgb_256, weights_256, target_torso_mask)          # :84-87
     hid = ret["deformed_torso_hid"]
     te = self.torso_encoder._plan() if _FUSE_TORSO_CAT else ()
     _, Ca, H0, W0 = logical_shape(x0)
@@ -199,7 +182,7 @@ def _forward_v2(self, S, rgb, x, ws, ref_torso_rgb, ref_bg_rgb, weights_img, seg
         and Ca % 16 == 0 and fmt_of(hid) == "nchw"
     if not fuse_cat:
         x_torso = self.torso_encoder(hid, out_format="cb8")                                            # :88 (1x1 conv, measured input)
-    x_bg = S.c_xbg.get([ref_bg_rgb], lambda: _measured(self.bg_encoder(ref_bg_rgb_256, out_format="cb8"), S))   # :90 (clip constant)
+    x_bg = S.c_xbg.get([ref_bg_rgb], lambda: _measured(self.bg_encoder(ref_bg_rgb_256, out_format="cb8")))   # :90 (clip constant)
 
     # ---- head / torso fusion (:99-105) -----------------------------------------------------------------------------------------------
     alpha = weights_256                                   # `head_torso_alpha[head_torso_alpha > weights_256] = ...` (:101-102) is a no-op
@@ -215,7 +198,7 @@ def _forward_v2(self, S, rgb, x, ws, ref_torso_rgb, ref_bg_rgb, weights_img, seg
         bh, dh = bound_of(hid, S.meter_hid, 1)
         tconv._depth_in = dh
         ops, head, last = fuse_ht.chain_ops(N, dev, -2, 0, base=1)
-        chain_fold([tconv.chain_op(-1, negative_slope=tslope)] + ops + [hb.chain_op(last)], N, [bh, m_x0], zero=[m_y] if _HB_TAIL_FOLD else [m_x2])
+        chain_fold([tconv.chain_op(-1, negative_slope=tslope)] + ops + [hb.chain_op(last)], N, [bh, m_x0], zero=[m_x2])
         fmt = "split_mx" if head.wants_mx() else "split"
         Cb = tconv.out_channels
         xs = tag_split(empty(fmt, N, Ca + Cb, H0, W0, dev), fmt, head)
@@ -223,12 +206,11 @@ def _forward_v2(self, S, rgb, x, ws, ref_torso_rgb, ref_bg_rgb, weights_img, seg
         blend_cat(x0, None, alpha, fuse_ht, _folded_head=head, _b_channels=Cb, _dst=xs)
     else:
         ops, head, last = fuse_ht.chain_ops(N, dev, -1, -2, base=0)
-        # round 5: head_torso_block's conv1 operand is three layers from the measured max|x0| (= MAX_DEPTH): no tail fold, no max|y| measurement (zero = the next slot)
-        chain_fold(ops + [hb.chain_op(last)], N, [m_x0, bound_of(x_torso, S.meter_hid, 3)[0]], zero=[m_y] if _HB_TAIL_FOLD else [m_x2])
+        chain_fold(ops + [hb.chain_op(last)], N, [m_x0, bound_of(x_torso, S.meter_hid, 3)[0]], zero=[m_x2])
         xs = blend_cat(x0, x_torso, alpha, fuse_ht, _folded_head=head)                                  # :104
-    y = fuse_ht(xs, out_format="split_mx" if hb.wants_mx() else "split", _next=hb, _y_absmax=m_y if _HB_TAIL_FOLD else None)       # :105
-    if _HB_TAIL_FOLD:
-        chain_fold([hb.chain_op(-1, tail=True)], N, [m_y], zero=[m_x2])
+    # head_torso_block's conv1 operand is three layers from the measured max|x0| (= MAX_DEPTH): the fold above covers it, and cleared the
+    # row the block measures max|x2| into
+    y = fuse_ht(xs, out_format="split_mx" if hb.wants_mx() else "split", _next=hb)                     # :105
     x2, rgb2 = hb(y, rgb1, ws3, _prepared=preph, _folded=True, _x_absmax=m_x2, _out_format="cb8", _return_x=True, **kw)      # :106
 
     # ---- person / background fusion (:107-115) ----------------------------------------------------------------------------------------
@@ -256,18 +238,7 @@ def infer_forward_stage1(self, rgb, x, ws, ref_torso_rgb, ref_bg_rgb, weights_im
     """sr_with_ref.py:164-188 (the reference's two-stage entry, unused by real3d_infer.py): block0 + the warp network's first stage; returns
     the dict the second stage continues from (keys as the reference: the torso model's own + 'ref_bg_rgb_256', 'weights_256', 'x', 'ws',
     'rgb').  Runs the HIP operators one by one (each folds its own range): the fused per-frame path is `forward`."""
-    aa = self.sr_antialias
-    weights_img = weights_img.detach()
-    ws3 = ws[:, -1:, :].repeat(1, 3, 1)                                                                  # :167
-    if x.shape[-1] != self.input_resolution:                                                            # :169-173
-        sz = (self.input_resolution, self.input_resolution)
-        x, rgb = resize_bilinear(x, sz, aa), resize_bilinear(rgb, sz, aa)
-    rgb_256 = resize_bilinear(rgb, (256, 256), aa)                                                      # :175-178
-    weights_256 = resize_bilinear(weights_img, (256, 256), aa)
-    ref_torso_rgb_256 = resize_bilinear(ref_torso_rgb, (256, 256), aa)
-    ref_bg_rgb_256 = resize_bilinear(ref_bg_rgb, (256, 256), aa)
-    kw = dict(block_kwargs)
-    kw.setdefault("noise_mode", "none")
+    x, rgb, ws3, rgb_256, weights_256, ref_torso_rgb_256, ref_bg_rgb_256, kw = _prologue(self, rgb, x, ws, ref_torso_rgb, ref_bg_rgb, weights_img, block_kwargs)  # :167-178
     x, rgb = self.block0(x, rgb, ws3, _out_format="nchw", _return_x=True, **kw)                         # :180
     ret = self.torso_model.infer_forward_stage1(ref_torso_rgb_256, segmap, kp_s, kp_d, rgb_256.detach(), cal_loss=True)      # :182
     ret["ref_bg_rgb_256"], ret["weights_256"], ret["x"], ret["ws"], ret["rgb"] = ref_bg_rgb_256, weights_256, x, ws3, rgb

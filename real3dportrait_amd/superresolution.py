@@ -45,20 +45,33 @@ def _setup_filter():
 # ---------------------------------------------------------------------------------------------------------------------
 # bounds
 # ---------------------------------------------------------------------------------------------------------------------
+class _RangeRows:
+    """The range state of an SR object: `rows` x N float32 on the device, zero-filled, rebuilt when N or the device changes.  A row is
+    what a fold zeroes and an epilogue (or r3d_absmax) then measures max|x| per sample into.  One object, one stream
+    (frames.clone_generator_shell)."""
+
+    def __init__(self, rows):
+        self._n, self._t = rows, None
+
+    def at(self, N, dev):
+        t = self._t
+        if t is None or t.shape[1] != N or t.device != dev:
+            t = self._t = torch.zeros(self._n, N, device=dev, dtype=torch.float32)
+        return t
+
+
 class _BoundMeter:
-    """max|x| per sample of an fp32 device tensor (r3d_absmax), two alternating result slots so that no memset launch is
-    needed (each call clears the slot of the next one)."""
+    """max|x| per sample of an fp32 device tensor (r3d_absmax), two alternating result rows so that no memset launch is
+    needed (each call clears the row of the next one)."""
 
     def __init__(self):
-        self._slots = None
+        self._rows = _RangeRows(2)
         self._k = 0
 
     def __call__(self, x):
         N = x.shape[0]
-        if self._slots is None or self._slots.shape[1] != N or self._slots.device != x.device:
-            self._slots = torch.zeros(2, N, device=x.device, dtype=torch.float32)
-            self._k = 0
-        cur, nxt = self._slots[self._k & 1], self._slots[(self._k + 1) & 1]
+        rows = self._rows.at(N, x.device)
+        cur, nxt = rows[self._k & 1], rows[(self._k + 1) & 1]
         self._k += 1
         _lib.call("r3d_absmax", x, x.numel() // N, N, cur, nxt)
         return cur
@@ -82,21 +95,21 @@ def const_bound(value, N, device):
     return t
 
 
-# Precision policy (round 5).  A module built by anybody -- a user, patch_model() on a reference model, frames.ClipRenderer,
-# bench.py -- computes in 'f16mx': fp32 operands as fp16 hi + lo, hi*hi on the f16 MFMA, the two cross products on the block-scaled 8-bit
-# MFMA, fp32 accumulate.  It earned the default when its activation records became OCP e5m2 (r3d_sr_f16x3.hip "f16mx"): every reference
-# golden, the benchmarked frame and the heavy-tail sweeps (spikes of 2^6 .. 2^14 sigma, near and far field) sit at 1.3e-5 .. 6.3e-5 of max|ref|
-# against the 2e-4 SURVEY 8(d) states; until round 4 (e4m3 records with one exponent per tensor) the far field left the tolerance at 2^14 sigma.
+# Precision policy.  A module built by anybody -- a user, patch_model() on a reference model, frames.ClipRenderer, bench.py -- computes in
+# 'f16mx': fp32 operands as fp16 hi + lo, hi*hi on the f16 MFMA, the two cross products on the block-scaled 8-bit MFMA, fp32 accumulate.
+# Its activation records are OCP e5m2 (r3d_sr_f16x3.hip "f16mx"): every reference golden, the benchmarked frame and the heavy-tail sweeps
+# (spikes of 2^6 .. 2^14 sigma, near and far field) sit at 1.3e-5 .. 6.3e-5 of max|ref| against the 2e-4 SURVEY 8(d) states.
 # 'f16x3' (every product as 3 fp16 MFMA terms: <= 1.3e-6, the fp32-class tier) and 'f32' (exact fp32 MFMA) are selected by name;
 # R3D_SR_PRECISION overrides the default for a process.  DESIGN 4.2c states the tiers.
 DEFAULT_SR_PRECISION = "f16mx"
-THROUGHPUT_SR_PRECISION = "f16mx"          # what ClipRenderer(precision='throughput') asks for: the default since round 5
+THROUGHPUT_SR_PRECISION = "f16mx"          # what ClipRenderer(precision='throughput') asks for
 FP32_CLASS_SR_PRECISION = "f16x3"
-# A/B switch: 1 = the head network re-folds block1's conv1 operand every frame from max|block0 output| measured in block0's epilogue (rounds 3-4: the
-# e4m3 records needed the operand within one layer of a measurement).  Round 5: the e5m2 records have the fp16 hi plane's exponent range, the
-# propagated bound of the main fold serves f16mx as it always served f16x3 -- one launch (~10 us on one stream) and one atomic per frame less.
-_MX_TAIL_FOLD = os.environ.get("R3D_MX_TAIL_FOLD", "0") == "1"
-_MX_UPCONV = os.environ.get("R3D_MX_UPCONV", "1") != "0"      # A/B switch: 0 = f16mx keeps block1's up-sampling conv on the 3-term fp16 split
+_MX_TAIL_FOLD = False          # read by bench.py's config-5 stress: the head network folds block1's conv1 operand once, in the main fold
+
+
+def process_sr_precision(default=DEFAULT_SR_PRECISION):
+    """The precision a module is constructed with: R3D_SR_PRECISION where the process sets it, else `default`."""
+    return os.environ.get("R3D_SR_PRECISION", default)
 
 
 def set_sr_precision(module, precision):
@@ -110,12 +123,6 @@ def set_sr_precision(module, precision):
             if isinstance(m, (SynthesisBlock, Conv2d)):
                 m.precision = precision
     return module
-
-# f16mx main loops only within this many layers of a measured bound (ConvStack.forward).  Round 4: 2 -- the e4m3 records carried one exponent
-# per tensor and went subnormal three propagated bounds (~15 binades) from a measurement.  Round 5: the e5m2 records have the fp16 hi plane's own
-# exponent range, so an MX operand is usable wherever a SPLIT operand is (MAX_DEPTH), including the hand-offs between a stack and a block
-# (fuse_fg_bg_convs -> block1: depth 3); measured at depth 3: to_plane_cnn 2.9e-5 (2.2e-5 at depth 2), torso frame 4.0e-5 of max|ref|.
-MX_MAX_DEPTH = int(os.environ.get("R3D_MX_MAX_DEPTH", str(MAX_DEPTH)))
 
 
 def chain_fold(ops, N, ext, zero=()):
@@ -203,13 +210,14 @@ class SynthesisBlock(_DeviceBuffers, nn.Module):
         # 'f16x3': fp32-accurate 3-term split on the f16 matrix pipe (<= 1.3e-6 over the operand sweeps);
         # 'f32': exact fp32 MFMA.
         # Override per module (`.precision`, set_sr_precision()) or for the process with R3D_SR_PRECISION.
-        self.precision = os.environ.get("R3D_SR_PRECISION", DEFAULT_SR_PRECISION)
+        self.precision = process_sr_precision()
         self._prepacked = None
         self._prepack_state = Derived()         # is _prepacked that of the two conv weights?
         self._styles = None
         self._styles_state = Derived()          # is _styles that of ws and the parameters?
         self._workspace = None
         self._meter = _BoundMeter()
+        self._blend_meters = (_BoundMeter(), _BoundMeter())      # blend_cat: the two sources of a blended input
         self._depth_in = 0             # layers between the last measurement and this block's input (set by whoever folds it)
         self._fold_epoch = 0           # bumped by every chain_op(): lets a caller see that nobody re-folded the block since its own fold
 
@@ -222,7 +230,7 @@ class SynthesisBlock(_DeviceBuffers, nn.Module):
     def wants_mx(self):
         """True when a producer of this block's SPLIT input should leave fp8 records in the lo plane (out_format 'split_mx'): the block's
         conv0 then runs the f16mx main loop (the up-sampling conv of SynthesisBlock, the plain 3x3 conv0 of SynthesisBlockNoUp)."""
-        return self._prec() == 2 and self.in_channels % 16 == 0 and (_MX_UPCONV or not self._UP)
+        return self._prec() == 2 and self.in_channels % 16 == 0
 
     def _clamp(self):
         return -1.0 if self.conv_clamp is None else float(self.conv_clamp)
@@ -354,11 +362,12 @@ class Conv2d(_DeviceBuffers, nn.Module):
         self._scales = None
         self._bias32 = None
         self._meter = _BoundMeter()
+        self._blend_meters = (_BoundMeter(), _BoundMeter())      # blend_cat: the two sources of a blended input
         self._depth_in = 0
         # 'f16mx' (library default): a 3x3 conv whose SPLIT input carries 8-bit records (R3D_FMT_SPLIT_MX) runs its cross products on the
         # block-scaled 8-bit MFMA; the PRODUCER of the input asks `wants_mx()` and writes the records | 'f16x3' (fp32-class).  'f32' = 'f16x3'
         # here (the plain convs have no exact-f32 kernel).  R3D_SR_PRECISION / set_sr_precision() as for the SR blocks.
-        self.precision = os.environ.get("R3D_SR_PRECISION", DEFAULT_SR_PRECISION)
+        self.precision = process_sr_precision()
 
     def wants_mx(self):
         return self.precision == "f16mx" and self.kernel_size[0] == 3 and self.in_channels % 16 == 0
@@ -512,8 +521,6 @@ def blend_cat(a, b, mask, consumer, ws=None, _folded_head=None, _b_channels=None
     if _folded_head is not None:
         head = _folded_head
     else:
-        if not hasattr(consumer, "_blend_meters"):
-            object.__setattr__(consumer, "_blend_meters", (_BoundMeter(), _BoundMeter()))
         meters = consumer._blend_meters
         L = consumer.num_layers()
         (ba, da), (bb, db) = bound_of(a, meters[0], L), bound_of(b, meters[1], L)
@@ -547,6 +554,11 @@ class ConvStack(nn.Sequential):
     state_dict keys are the reference's ('0.weight', '0.bias', '2.weight', ...).
 
     ConvStack.from_torch(seq) converts a torch nn.Sequential with loaded weights."""
+
+    def __init__(self, *args):
+        super().__init__(*args)
+        self._meter = _BoundMeter()                               # an fp32 input without a usable bound tag
+        self._blend_meters = (_BoundMeter(), _BoundMeter())      # blend_cat: the two sources of a blended input
 
     @classmethod
     def from_torch(cls, seq):
@@ -617,17 +629,15 @@ class ConvStack(nn.Sequential):
         else:
             x, _, presplit = as_input(x, plan[0][0])
             if not presplit:
-                if not hasattr(self, "_meter_obj"):
-                    object.__setattr__(self, "_meter_obj", _BoundMeter())
-                bx, dx = bound_of(x, self._meter_obj, len(plan))
+                bx, dx = bound_of(x, self._meter, len(plan))
                 self.fold_for_input(x.shape[0], x.device, [bx], depth=dx)
         for k, (m, slope, up) in enumerate(plan):
             nxt = plan[k + 1][0] if k + 1 < len(plan) else None
-            # The fp8 records carry ONE exponent per tensor (the fold's bound), and a bound propagated through the layers' L1 norms loosens by
-            # ~5 binades per layer: three layers from a measurement the typical operand sits 2^15 under its bound, xh8 = e4m3(hi * 2^-7) is a
-            # subnormal and the layer's cross products are noise (to_plane_cnn's last conv at full size: 3.4e-4 of max|ref| instead of 2.8e-5,
-            # tests/test_gpu_mx.py) -- so a layer whose operand is more than MX_MAX_DEPTH layers from a measured bound runs f16x3.
-            mx_next = nxt is not None and nxt.wants_mx() and m.out_channels % 16 == 0 and dx + k + 1 <= MX_MAX_DEPTH
+            # The e5m2 activation records carry an exponent per ELEMENT, with the fp16 hi plane's own range: a bound that loosened ~5 binades
+            # per propagated layer costs a record nothing a SPLIT operand does not pay too.  So an MX operand may sit as deep as a SPLIT one,
+            # MAX_DEPTH layers from a measured bound (to_plane_cnn with its last conv at depth 3: 2.9e-5 of max|ref|); a stack
+            # longer than that runs its deeper layers on f16x3.
+            mx_next = nxt is not None and nxt.wants_mx() and m.out_channels % 16 == 0 and dx + k + 1 <= MAX_DEPTH
             bl = _blend if k == 0 else None
             if up:
                 x = upsample2x_bilinear(m(x, negative_slope=slope, out_format="cb8", _folded=True, _blend=bl), "split_mx" if mx_next else "split", _next=nxt)
@@ -660,37 +670,29 @@ class SuperresolutionHybrid8XDC(nn.Module):
         self.block1.return_x = False           # forward() only returns rgb (:359)
         self._meter = _BoundMeter()
         self._ws3 = Derived()                  # ws[:, -1:].repeat(1, 3, 1): a clip renders every frame with one ws
-        self._mx_slot = None                   # f16mx: max|block0 output| measured in its conv1 epilogue
         self._fold = Derived()                 # is the main fold in place?  Source: the bound tensor; extra: _sig
 
     FEATURE_BOUND = 1.01      # |renderer feature image| <= 1.002 by construction (sigmoid * 1.002 - 0.001 composited with weights summing to <= 1)
 
     def _prepare_and_fold(self, ws, N, dev, bx, dx):
         """Style vectors of both blocks (cached per ws) + the range fold for an input bounded by bx (skipped while nothing it depends on
-        changed).  Returns (ws3, prep0, prep1, x_absmax slot or None)."""
+        changed).  Returns (ws3, prep0, prep1)."""
         ws3 = self._ws3.get([ws], lambda: ws[:, -1:, :].repeat(1, 3, 1))          # :349
         b0, b1 = self.block0, self.block1
         b1.precision = b0.precision
         prep0 = b0.prepare(ws3, dev, ws_key=ws)
         prep1 = b1.prepare(ws3, dev, ws_key=ws)
-        mx = b0.precision == "f16mx" and _MX_TAIL_FOLD
-        x_absmax = None
         if b0.precision in ("f16x3", "f16mx"):
             # one fold launch for both blocks; block0's conv1 epilogue then emits its output already multiplied by block1.conv0's
             # folded styles and split into fp16 hi/lo planes, so block1 stages its input with plain copies
             b0._depth_in, b1._depth_in = dx, dx + 2
-            if mx:      # R3D_MX_TAIL_FOLD=1: block1's conv1 operand within one layer of a measurement: block0 measures max|x0| in its epilogue
-                if self._mx_slot is None or self._mx_slot.shape[0] != N or self._mx_slot.device != dev:
-                    self._mx_slot = torch.zeros(N, device=dev, dtype=torch.float32)
-                x_absmax = self._mx_slot
             # The fold is a function of (bx, both blocks' style vectors).  With a constant bound (the renderer's feature image,
             # const_bound) and the per-clip style cache unchanged, the folded vectors of the previous frame are still in place:
-            # skip the launch (13 us per frame).  f16mx: the per-frame tail fold (forward) re-arms the max|x0| slot and only rewrites
-            # block1's conv1 operand vectors, which it rewrites again next frame before they are read: the main fold can be skipped too.
+            # skip the launch (13 us per frame).
             if not getattr(bx, "_r3d_const", False) or not self._fold.valid([bx], self._sig(dx)):
-                chain_fold([b0.chain_op(-1), b1.chain_op(0)], N, [bx], zero=[x_absmax] if mx else ())
+                chain_fold([b0.chain_op(-1), b1.chain_op(0)], N, [bx])
                 self._fold.put([bx], None, self._sig(dx))
-        return ws3, prep0, prep1, x_absmax
+        return ws3, prep0, prep1
 
     def _sig(self, dx):
         """What the main fold depends on besides the bound tensor: both blocks' style vectors, and that nobody folded a block since."""
@@ -726,20 +728,12 @@ class SuperresolutionHybrid8XDC(nn.Module):
             if b0.precision in ("f16x3", "f16mx"):
                 x = _keep_tags(x)
                 bx, dx = bound_of(x, self._meter, layers=4)
-        ws3, prep0, prep1, x_absmax = self._prepare_and_fold(ws, N, dev, bx, dx)
-        mx = x_absmax is not None              # (f16mx with R3D_MX_TAIL_FOLD=1)
+        ws3, prep0, prep1 = self._prepare_and_fold(ws, N, dev, bx, dx)
         if b0.precision in ("f16x3", "f16mx"):
             # f16mx: block0's conv1 epilogue leaves fp8 records in the lo plane and block1's up-sampling conv runs its cross products on them
             fmt0, nxt = ("split_mx" if b1.wants_mx() else "split"), b1
         else:
             fmt0, nxt = "cb8", None
-        x, rgb = b0(x, rgb, ws3, _prepared=prep0, _next=nxt, _folded=True, _x_absmax=x_absmax, _out_format=fmt0, **block_kwargs)
-        if mx:
-            # tail fold: block1's conv1 operand from the MEASURED max|x0|; clears the slot for the next frame (the kernel reads its
-            # bounds before it zeroes) -- our own fold, so the main fold's signature stays valid
-            fresh = self._fold.valid([bx], self._sig(dx))
-            chain_fold([b1.chain_op(-1, tail=True)], x.shape[0], [x_absmax], zero=[x_absmax])
-            if fresh:
-                self._fold.put([bx], None, self._sig(dx))
+        x, rgb = b0(x, rgb, ws3, _prepared=prep0, _next=nxt, _folded=True, _out_format=fmt0, **block_kwargs)
         x, rgb = b1(x, rgb, ws3, _prepared=prep1, _folded=True, _u8_out=_u8_out, _need_img=_need_img, **block_kwargs)
         return rgb

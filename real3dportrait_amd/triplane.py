@@ -162,11 +162,6 @@ class TriPlaneGenerator(nn.Module):
                               use_cached_backbone=use_cached_backbone, **synthesis_kwargs)
 
 
-def _copy_sr_block(dst, src):
-    missing = dst.load_state_dict(src.state_dict(), strict=True)
-    return missing
-
-
 def _reference_hparams(model):
     """The reference keeps its configuration in one global dict (utils/commons/hparams.py) that its modules read at call time;
     some shells also keep a copy as `self.hparams`."""

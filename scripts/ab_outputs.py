@@ -1,5 +1,5 @@
 """What one build of the library computes -- the head frame (both SR precisions), ray-kernel shapes, the torso frame, the three
-token-transformer models with their launch traces -- saved so that
+token-transformer models, and the launch traces of the frames and the models -- saved so that
 `scripts/ab.py outputs A B` can compare two builds (the tolerances and their reasons are in `_ab.compare_outputs`).  `R3D_LIB` selects the
 build (default: the tree's own library).  Prints a `digest` line per group of arrays and `time` lines: the head frame on one stream by the
 host clock, the ray kernel per shape from the library's own events (`r3d_profile_read`, 20 calls).
@@ -16,6 +16,43 @@ dev = torch.device("cuda:0")
 dig = lambda *ts: hashlib.sha1(b"".join(t.contiguous().cpu().numpy().tobytes() for t in ts)).hexdigest()[:16]
 print("lib", _lib.LIB_PATH)
 SAVE = {}
+# A launch trace: the _lib.counting() list with every address (device pointers, the stream) replaced by the index of its first appearance in the
+# trace, a host pointer (a ctypes object) by "host", scalars kept: equal digests mean the same entry points in the same order with the same scalars and the same buffer wiring
+def trace(calls):
+    first, out = {}, []
+    for name, args in calls:
+        n, stream, devptrs, _ = _lib._plans[name]
+        where = {i for i, _, _ in devptrs} | ({n - 1} if stream else set())
+        out.append((name,) + tuple(first.setdefault(a, len(first)) if i in where and a is not None else a if isinstance(a, (int, float, str, bytes, type(None))) else "host"
+                                   for i, a in enumerate(args)))
+    return out
+def fold_trace(frame):
+    """r3d_chain_fold takes HOST arrays, which the trace above cannot see into: every fold of one frame as (its ops' scalars and sources, N, the
+    bounds it reads, the rows it clears), the device addresses by first appearance over the frame's folds."""
+    from real3dportrait_amd import sr_with_ref, superresolution
+    first, out, real = {}, [], superresolution.chain_fold
+    ix = lambda a: None if a is None else first.setdefault(a, len(first))
+    def chain_fold(ops, N, ext, zero=()):
+        out.append(([(o.kind, o.Cin, o.Cout, o.ksize, o.act, o.gain, o.clamp, o.src_a, o.src_b, ix(o.scales), ix(o.prepacked), ix(o.bias)) for o in ops], N,
+                    [ix(t.data_ptr()) for t in ext], [ix(t.data_ptr()) for t in zero]))
+        return real(ops, N, ext, zero=zero)
+    superresolution.chain_fold = sr_with_ref.chain_fold = chain_fold
+    try:
+        frame()
+    finally:
+        superresolution.chain_fold = sr_with_ref.chain_fold = real
+    torch.cuda.synchronize()
+    return out
+def frame_trace(name, frame):
+    """The launch trace of one frame, taken after the frames above warmed every cache."""
+    with torch.no_grad(), _lib.counting() as calls:
+        frame()
+    torch.cuda.synchronize()
+    tr = trace(calls)
+    print("digest %s trace %s (%d calls)" % (name, hashlib.sha1(repr(tr).encode()).hexdigest()[:16], len(tr)))
+    with torch.no_grad():
+        folds = fold_trace(frame)
+    print("digest %s folds %s (%d folds)" % (name, hashlib.sha1(repr(folds).encode()).hexdigest()[:16], len(folds)))
 # 1. the head frame, 4 frames of the clip, both SR precisions
 for prec in ("f16mx", "f16x3"):
     G, clip, dec, scene = bench.build_scene(torch, dev, n_frames=8, precision=prec)
@@ -26,6 +63,7 @@ for prec in ("f16mx", "f16x3"):
     print("digest head_frame %s %s" % (prec, dig(*fr)))
     SAVE["head_frame_" + prec] = torch.stack(fr).cpu().numpy()
     print("time head_frame %s one stream %.4f ms" % (prec, (time.perf_counter() - t0) / 40 * 1e3))
+    frame_trace("head_frame " + prec, lambda: clip.render_u8(0))
 # 2. ray-kernel shapes (fp32 outputs), then the kernel's own time for the shape
 lib = _lib.load()
 for (R, Nc, Nf, N) in ((128, 48, 48, 1), (128, 48, 0, 1), (64, 96, 96, 2), (96, 32, 16, 1)):
@@ -47,20 +85,12 @@ fr = [frame(t).clone() for t in range(2)]
 torch.cuda.synchronize()
 print("digest torso_frame f16mx %s" % dig(*fr))
 SAVE["torso_frame_f16mx"] = torch.stack(fr).cpu().numpy()
-# 4. the token-transformer models, seeded synth weights at the goldens' smallest shapes: the output, and the launch
-# trace -- the _lib.counting() list with every address (device pointers, the stream) replaced by the index of its first appearance in the
-# trace, scalars kept: equal digests mean the same entry points in the same order with the same scalars and the same buffer wiring
+frame_trace("torso_frame f16mx", lambda: frame(2))
+# 4. the token-transformer models, seeded synth weights at the goldens' smallest shapes: the output, and the launch trace
 from real3dportrait_amd import synth
 from real3dportrait_amd.hubert import HubertFeatureModel, hubert_features
 from real3dportrait_amd.img2plane import Img2PlaneModel
 from real3dportrait_amd.segformer import SegFormerSECC2PlaneBackbone
-def trace(calls):
-    first, out = {}, []
-    for name, args in calls:
-        n, stream, devptrs, _ = _lib._plans[name]
-        where = {i for i, _, _ in devptrs} | ({n - 1} if stream else set())
-        out.append((name,) + tuple(first.setdefault(a, len(first)) if i in where and a is not None else a for i, a in enumerate(args)))
-    return out
 def token_model(name, model, sd, run):
     own = {k: v for k, v in model.state_dict().items() if k.startswith("low_reso_encoder.")}          # the stand-in's, not synth's
     model.load_state_dict(dict(own, **{k: torch.from_numpy(np.ascontiguousarray(v)) for k, v in sd.items()}), strict=True)

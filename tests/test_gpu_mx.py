@@ -144,8 +144,7 @@ def test_to_plane_stack_f16mx_full_size_batch_equals_singles_and_fp64():
         yr = ref(x[:1].double().cpu())
     e = float((yb[:1].double().cpu() - yr).abs().max() / yr.abs().max())
     print("to_plane_cnn f16mx at 128^2 -> 256^2 vs fp64: %.2e of max|ref|" % e)
-    # 2.8e-5 measured.  (With the LAST conv on MX as well -- three layers from the measured input bound -- it was 3.4e-4: the records' single exponent
-    # sits 2^15 above the typical operand there, superresolution.MX_MAX_DEPTH.)
+    # 2.8e-5 measured.
     assert e <= MX_TOL, e
     convs = [m for m in cnn.modules() if isinstance(m, Conv2d)]
     assert len(convs) == 4

@@ -41,9 +41,11 @@ def test_warp_sr_forward_v2_golden():
 
 @pytest.mark.parametrize("prec", ["f16mx", "f16x3"])
 def test_warp_sr_forward_v2_round6_fusions_are_bit_identical(prec):
-    """Round 6 moved two blend + concatenation steps into the convs next to them: torso_encoder writes its half of :104's operand itself
-    (r3d_conv_forward_cat, R3D_FUSE_TORSO_CAT) and fuse_fg_bg_convs' 1x1 conv computes :113's operand while it stages it (r3d_conv_forward_blend,
-    R3D_FUSE_BLEND).  Same arithmetic in the same order: the fused forward's image equals the round-5 sequence bit for bit, at both precisions."""
+    """Two blend + concatenation steps sit inside the convs next to them: torso_encoder writes its half of :104's operand itself
+    (r3d_conv_forward_cat, sr_with_ref._FUSE_TORSO_CAT) and fuse_fg_bg_convs' 1x1 conv computes :113's operand while it stages it
+    (r3d_conv_forward_blend, sr_with_ref._FUSE_BLEND).  Same arithmetic in the same order: the fused forward's image equals the unfused sequence --
+    the general path for shapes the fusions refuse, run here on the shipped shapes by setting the two module constants -- bit for bit, at both
+    precisions and in all four combinations."""
     import torch
     import warp_mock
     from real3dportrait_amd import sr_with_ref

@@ -343,3 +343,26 @@ def _check_bench_line(d):
         assert k in c, k
     assert c["kind"] in ("reference", "port")
     assert abs(d["value"] - d["steps"] * d["n_gpus"] / (d["ms_per_step"] * d["steps"] * 1e-3)) / d["value"] < 1e-3
+
+
+def test_package_reads_two_environment_variables():
+    """The package's Python reads R3D_LIB (which library, _lib.py) and R3D_SR_PRECISION (the SR precision of a process) and
+    nothing else: a text scan of real3dportrait_amd/*.py, as tests/test_abi.py scans csrc/ for getenv.  Every use of the environment must be
+    a read of a literal name, and the settled A/B switches of the SR host code stay retired: bench.py still reads
+    superresolution._MX_TAIL_FOLD, which is the constant False."""
+    import glob
+    import os
+    import re
+    pkg = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "real3dportrait_amd")
+    files = sorted(glob.glob(os.path.join(pkg, "*.py")))
+    assert len(files) >= 10
+    seen = set()
+    for f in files:
+        src = open(f).read()
+        for m in re.finditer(r"\b(?:environ|getenv|putenv|unsetenv)\b", src):
+            use = re.match(r"(?:environ\.get\(|environ\[|getenv\()\s*\"(\w+)\"", src[m.start():])
+            assert use and src[:m.start()].endswith("os."), "%s: %r" % (os.path.basename(f), src[max(0, m.start() - 20):m.end() + 40])
+            seen.add(use.group(1))
+    assert seen == {"R3D_LIB", "R3D_SR_PRECISION"}, seen
+    from real3dportrait_amd import superresolution
+    assert superresolution._MX_TAIL_FOLD is False
