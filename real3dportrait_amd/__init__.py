@@ -8,6 +8,8 @@ Operators keep the reference's names and signatures (see each module's docstring
     SegFormerSECC2PlaneBackbone                          (segformer.py: the per-frame SECC encoder, mode b0)
     Img2PlaneModel                                       (img2plane.py: the canonical image-to-plane backbone without its DeepLabV3;
                                                          patch_model(cano_backbone=True) installs it)
+    DeepLabV3                                            (deeplabv3.py: the backbone's low-resolution encoder, a dilated ResNet + ASPP;
+                                                         patch_model(cano_backbone=True, cano_low_reso_encoder=True) installs it)
     TorsoGenerator, Occlusion2Predictor                  (torso_generator.py: the torso network's warp + decoder, its Generator)
     TorsoMotionFieldEstimator                            (torso_motion.py: the torso network's per-frame MotionFieldEstimator)
     TorsoAppearanceFeatureExtractor                      (torso_appearance.py: the torso network's AppearanceFeatureExtractor)
@@ -27,7 +29,8 @@ Operators keep the reference's names and signatures (see each module's docstring
     HubertFeatureModel, hubert_features, chunk_plan, get_hubert, patch_hubert (hubert.py: the HuBERT audio features behind get_hubert)
     landmark_weights, fit_landmarks, fit_3dmm_for_landmarks, patch_fit_3dmm (fit_3dmm.py: the landmark-driven 3DMM fit, 400 Adam steps)
     render_clip_sharded                                  (frames.py: frame sharding + RCCL gather)
-All compute goes through libr3d_hip.so (include/r3d_hip.h, include/r3d_hip_img2plane.h, include/r3d_hip_hubert.h); there is no eager/CPU fallback.
+All compute goes through libr3d_hip.so (include/r3d_hip.h, include/r3d_hip_img2plane.h, include/r3d_hip_hubert.h,
+include/r3d_hip_deeplab.h); there is no eager/CPU fallback.
 """
 __version__ = "0.1.0"
 
@@ -48,6 +51,9 @@ def __getattr__(name):      # lazy: importing the package (e.g. for synth) must 
     if name == "Img2PlaneModel":
         from . import img2plane as m
         return getattr(m, name)
+    if name == "DeepLabV3":
+        from . import deeplabv3 as m
+        return m.DeepLabV3
     if name in ("TorsoGenerator", "Occlusion2Predictor"):
         from . import torso_generator as m
         return getattr(m, "Generator" if name == "TorsoGenerator" else name)

@@ -179,6 +179,12 @@ FEATURE_SIGNATURES = {
         "r3d_hubert_conv_ln_gelu": (c_int, [F, F, F, F, F, c_float, c_int, c_int, c_int, c_int, c_int, c_int, F, S]),
         "r3d_hubert_pos_conv": (c_int, [F, F, F, c_int, c_int, c_int, c_int, c_int, F, S]),
     },
+    "r3d_hip_deeplab.h": {
+        "r3d_dl_conv": (c_int, [F, c_int, c_int, c_int, c_int, F, F, c_int, c_int, c_int, c_int, c_int, c_int, F, c_int, F, c_int, c_int, S]),
+        "r3d_dl_maxpool": (c_int, [F, c_int, c_int, c_int, c_int, F, S]),
+        "r3d_dl_global_mean": (c_int, [F, c_int, c_int, c_int, F, S]),
+        "r3d_dl_assemble_input": (c_int, [F, F, F, c_int, c_int, c_int, F, S]),
+    },
 }
 
 # The headers' constants the package uses: _lib.X mirrors R3D_X of the header named (tests/test_abi.py compares every one).

@@ -23,6 +23,13 @@
 //     [B, split, H, W, C] -- a Conv2d followed by x.view(N, C, D, H, W) whose weight rows the caller ordered depth-major.
 // EXT = false compiles neither: the kernels of r3d_torso_conv3d are the code they were.
 //
+// DL = true (2-D, F32; the DeepLabV3 kernels of r3d_deeplab.hip) is nn.Conv2d with a stride, a dilation and an explicit padding:
+//   * tap (ky, kx) of output (oy, ox) is input (oy cstride - cpad + ky cdil, ox cstride - cpad + kx cdil), tested against the stored Hs x Ws
+//     (H x W is the OUTPUT grid; no up-sampling, no prologue, channel-last input only);
+//   * the epilogue is BasicBlock's: sum + bias[b bias_bs + n], + residual [M, Cout] (may alias y), THEN ReLU (act 1), written to channels
+//     [yco, yco + Cout) of rows of ycs floats.
+// DL = false compiles none of it, and the four fields it reads travel in the depth words of ConvArgs, which a 2-D kernel does not read (ConvArgs::set_dl).
+//
 // PREC selects the arithmetic of the products; loaders, tile order and epilogues are the same code for both.
 //   F32     the fp32 operands as they are, 8 v_mfma_f32_16x16x4_f32 per 16 x 16 tile and k step.
 //   BF16X3  store() splits every staged value into three bf16 pieces h + m + l == x (split_bf16x3) and compute() sums six of the nine
@@ -100,6 +107,13 @@ struct ConvArgs {
     int pool;                                    // average each 2 x 2 (H, W) window: M counts the un-pooled positions, quad-major
     int ycs, yco;                                // y's row length and this conv's first channel in it
     int ntm, mfast;                              // tiles along M; mfast: consecutive tiles share their channels, not their positions
+    // DL only (2-D, never with D3): its four values travel in the four depth words above, which no 2-D kernel reads, so the struct -- every
+    // kernel's argument segment -- keeps its size and layout.  H, W are then the OUTPUT grid.
+    __host__ __device__ void set_dl(int stride, int dilation, int pad, int bias_bs) { D = stride; Do = dilation; kd = pad; padz = bias_bs; }
+    __device__ __forceinline__ int cstride() const { return D; }          // the conv's stride
+    __device__ __forceinline__ int cdil() const { return Do; }            // its dilation
+    __device__ __forceinline__ int cpad() const { return kd; }            // its zero padding
+    __device__ __forceinline__ int bias_bs() const { return padz; }       // sample b adds bias[b bias_bs + n] (0: one bias for all)
 };
 
 __device__ __forceinline__ float leaky(float v, float slope) { return v < 0.0f ? slope * v : v; }
@@ -129,10 +143,11 @@ struct KPos {
     }
 };
 
-template <int PREC, bool VEC, bool D3, int WM, int WN, int TM, int TN, bool EXT = false>
+template <int PREC, bool VEC, bool D3, int WM, int WN, int TM, int TN, bool EXT = false, bool DL = false>
 __device__ __forceinline__ void conv_tile(const ConvArgs& g)
 {
     static_assert(WM * WN == 4, "four waves");
+    static_assert(!DL || (!D3 && PREC == F32), "the strided, dilated form is 2-D and fp32");
     static_assert(D3 || !EXT, "the extended epilogue belongs to the 3-D body");
     static_assert(PREC == F32 || PREC == BF16X3, "precision");
     constexpr int BM = WM * TM * 16, BN = WN * TN * 16;
@@ -149,7 +164,7 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& g)
     const int tile = nblk % 8 == 0 ? (bid % 8) * (nblk / 8) + bid / 8 : bid;
     int m0 = (tile / g.ntn) * BM, n0 = (tile % g.ntn) * BN;
     if constexpr (D3) { if (g.mfast) { m0 = (tile % g.ntm) * BM; n0 = (tile / g.ntm) * BN; } }
-    const int pad = g.ks >> 1, hw = g.H * g.W;
+    const int pad = DL ? g.cpad() : g.ks >> 1, hw = g.H * g.W;
     const int nsteps = (g.K + BK - 1) / BK;
 
     // ---- loader state ---------------------------------------------------------------------------------------------------------------
@@ -204,6 +219,12 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& g)
 
     // the offset of tap (kz, ky, kx) of row slot j inside its sample, in pixels; false outside the (padded) volume
     auto tap = [&](int j, size_t& pix) -> bool {
+        if constexpr (DL) {
+            const int iy = roy[j] * g.cstride() - pad + kp.ky * g.cdil(), ix = rox[j] * g.cstride() - pad + kp.kx * g.cdil();
+            if (!(iy >= 0 && iy < g.Hs && ix >= 0 && ix < g.Ws)) return false;
+            pix = (size_t)iy * g.Ws + ix;
+            return true;
+        }
         const int iy = roy[j] - pad + kp.ky, ix = rox[j] - pad + kp.kx;
         if (!(iy >= 0 && iy < g.H && ix >= 0 && ix < g.W)) return false;
         pix = (size_t)(iy >> g.up) * g.Ws + (ix >> g.up);
@@ -374,6 +395,34 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& g)
     }
 
     // D layout of 16x16x4: column lane & 15, rows 4 (lane >> 4) + r.  The bias and the residuals are fetched before they are needed.
+    if constexpr (DL) {
+        // every row's sample has a bias of its own, and the residual goes in before the ReLU
+#pragma unroll
+        for (int i = 0; i < TM; ++i)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int m = m0 + wm + i * 16 + (lane >> 4) * 4 + r;
+                if (m >= g.M) continue;
+                const size_t brow = (size_t)(m / hw) * g.bias_bs();
+                float bias[TN], res[TN];          // fetched before they are needed (res may alias y: read, then written, by this lane)
+#pragma unroll
+                for (int j = 0; j < TN; ++j) {
+                    const int n = n0 + wn + j * 16 + (lane & 15);
+                    bias[j] = (g.bias && n < g.Cout) ? g.bias[brow + n] : 0.0f;
+                    res[j] = (g.res && n < g.Cout) ? g.res[(size_t)m * g.Cout + n] : 0.0f;
+                }
+#pragma unroll
+                for (int j = 0; j < TN; ++j) {
+                    const int n = n0 + wn + j * 16 + (lane & 15);
+                    if (n >= g.Cout) continue;
+                    float v = acc[i][j][r] + bias[j];
+                    if (g.res) v += res[j];
+                    if (g.act && v < 0.0f) v = 0.0f;
+                    g.y[(size_t)m * g.ycs + g.yco + n] = v;
+                }
+            }
+        return;
+    }
     float bias[TN];
 #pragma unroll
     for (int j = 0; j < TN; ++j) {

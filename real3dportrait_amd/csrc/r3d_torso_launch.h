@@ -1,6 +1,7 @@
 // Host side of the torso convolutions: the one argument check, the one ConvArgs fill, the one tile table and the one launcher behind the
 // seven entry points r3d_torso_conv / _prec (r3d_torso.hip), r3d_torso_conv3d / _prec (r3d_torso_motion.hip) and r3d_torso_conv_pool,
-// r3d_torso_conv_split, r3d_torso_conv3d_res (r3d_torso_appearance.hip).  An entry point describes its call as a ConvCall and hands it,
+// r3d_torso_conv_split, r3d_torso_conv3d_res (r3d_torso_appearance.hip), and behind r3d_dl_conv (r3d_deeplab.hip: ConvCall::dl, the strided,
+// dilated form, which calls check_conv, fill and dispatch itself since it has one tier).  An entry point describes its call as a ConvCall and hands it,
 // with its unit's kernel family, to run<Family>().  A family is a tag struct with
 //   static constexpr bool tile64x16                                  it has the 64 x 16 tile (the two 3-D families)
 //   template <int PREC, bool VEC, int WM, int WN, int TM, int TN>
@@ -28,9 +29,12 @@ struct ConvCall {
     float* y = nullptr; int ycs = 0, yco = 0;    // channel-last output, its row length and this conv's first channel in it
     float* yn = nullptr;                         // NCHW / NCDHW output
     int precision = R3D_TORSO_F32;
+    // the strided, dilated form (r3d_dl_conv; conv_tile's DL): H x W is then the output grid, act 1 is ReLU and res goes in before it
+    bool dl = false; int stride = 1, dilation = 1, pad = 0, bias_bstride = 0;
 
-    int H() const { return Hs << upsample; }
-    int W() const { return Ws << upsample; }
+    int out_size(int n) const { const long long v = (long long)n + 2LL * pad - (long long)dilation * (ksize - 1) - 1; return v < 0 ? 0 : (int)(v / stride) + 1; }
+    int H() const { return dl ? out_size(Hs) : Hs << upsample; }
+    int W() const { return dl ? out_size(Ws) : Ws << upsample; }
     int Do() const { return full_depth ? 1 : D; }
     int kd() const { return full_depth ? D : volume ? ksize : 1; }
 
@@ -44,6 +48,7 @@ struct ConvCall {
         // a volume with fewer positions than output channels (down.4, up.0: 256 voxels under 57 MB of weights): the tiles that share a slab
         // of weights run next to each other on one XCD, so the slab comes from HBM once
         g.mfast = volume && g.M < Cout;
+        if (dl) g.set_dl(stride, dilation, pad, bias_bstride);          // after M and K: in the depth words
     }
 };
 
@@ -70,6 +75,21 @@ inline int check_conv(const char* what, const ConvCall& c)
     if (c.act < 0 || c.act > 2) { set_error("%s: act %d is not 0 (none), 1 (leaky) or 2 (sigmoid)", what, c.act); return R3D_ERR_INVALID_ARG; }
     if ((c.pool != 0 && c.pool != 1) || (c.full_depth != 0 && c.full_depth != 1))
         { set_error("%s: pool %d / full_depth %d is not 0 or 1", what, c.pool, c.full_depth); return R3D_ERR_INVALID_ARG; }
+    if (c.dl) {
+        if (c.stride != 1 && c.stride != 2) { set_error("%s: stride %d is not 1 or 2", what, c.stride); return R3D_ERR_INVALID_ARG; }
+        if (c.dilation < 1 || c.dilation > 64) { set_error("%s: dilation %d is not in 1 .. 64", what, c.dilation); return R3D_ERR_INVALID_ARG; }
+        if (c.pad < 0 || c.pad > 65536 || c.Hs > (1 << 24) || c.Ws > (1 << 24))
+            { set_error("%s: pad %d is not in 0 .. 65536, or a side of %d x %d is above 2^24", what, c.pad, c.Hs, c.Ws); return R3D_ERR_INVALID_ARG; }
+        if (c.act > 1) { set_error("%s: act %d is not 0 (none) or 1 (ReLU)", what, c.act); return R3D_ERR_INVALID_ARG; }
+        if (c.H() <= 0 || c.W() <= 0)
+            { set_error("%s: no output: %d x %d with ksize %d, dilation %d, pad %d is smaller than one window", what, c.Hs, c.Ws, c.ksize, c.dilation, c.pad);
+              return R3D_ERR_INVALID_ARG; }
+        if (c.bias_bstride != 0 && c.bias_bstride < c.Cout)
+            { set_error("%s: bias_bstride %d is not 0 or at least Cout = %d", what, c.bias_bstride, c.Cout); return R3D_ERR_INVALID_ARG; }
+        if (c.res && c.res == c.y && (c.ycs != c.Cout || c.yco != 0))
+            { set_error("%s: the residual [M, %d] cannot be y with rows of %d floats at channel %d", what, c.Cout, c.ycs, c.yco); return R3D_ERR_INVALID_ARG; }
+        if ((double)c.B * c.Hs * c.Ws * c.Cin > 9.0e18) { set_error("%s: more than 2^63 input elements", what); return R3D_ERR_INVALID_ARG; }
+    }
     const int H = c.H(), W = c.W(), Do = c.Do();
     if (c.pool && (H % 2 || W % 2)) { set_error("%s: pooling an odd size (%d x %d)", what, H, W); return R3D_ERR_INVALID_ARG; }
     if (c.pool && (c.yn || !c.y)) { set_error("%s: the pooled output is channel-last only (y, not y_ncdhw)", what); return R3D_ERR_INVALID_ARG; }
@@ -84,7 +104,8 @@ inline int check_conv(const char* what, const ConvCall& c)
     for (int o = 0; o < 2; ++o) {          // (an output, a bias or a prologue that is absent takes no part)
         const float* p = o ? c.yn : c.y;
         const size_t np = o ? nyn : ny;
-        const Span spans[] = {writes(p, np), reads(c.x, nin), reads(c.w, nw), reads(c.bias, c.Cout), reads(c.ps, c.Cin), reads(c.pt, c.Cin)};
+        const size_t nbias = (size_t)(c.B - 1) * c.bias_bstride + c.Cout;          // bias_bstride is 0 outside dl
+        const Span spans[] = {writes(p, np), reads(c.x, nin), reads(c.w, nw), reads(c.bias, nbias), reads(c.ps, c.Cin), reads(c.pt, c.Cin)};
         if (clash(spans)) { set_error("%s: an output overlaps x, w, bias or the prologue", what); return R3D_ERR_INVALID_ARG; }
         if (c.res != c.y && overlap(p, np, c.res, nyn))
             { set_error("%s: an output overlaps the residual without y being the residual", what); return R3D_ERR_INVALID_ARG; }

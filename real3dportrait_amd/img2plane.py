@@ -1,7 +1,9 @@
 """Img2PlaneModel (modules/img2plane/img2plane_model.py:12-82), the canonical image-to-plane backbone, on the HIP library: HighResoEncoder
 (simple_encoders/high_resolution_encoder.py), LowResolutionViT and TriplanePredictorViT (segformer/models.py, base.py) in exact fp32
-(include/r3d_hip_img2plane.h).  DeepLabV3 (low_reso_encoder) is whatever module the caller hands over and runs in torch, as
-does the input assembly of img2plane_model.py:45-64 that it shares; nothing in this package constructs a DeepLabV3.
+(include/r3d_hip_img2plane.h).  DeepLabV3 (low_reso_encoder) is whatever module the caller hands over.  When it is this package's
+DeepLabV3 (deeplabv3.py) the forward takes a fast path: r3d_dl_assemble_input writes the channel-last input, the encoder's
+forward_cl writes feat_low channel-last, and no layout conversion runs.  Any other encoder runs as it is, in torch, on the input that
+assemble_input (img2plane_model.py:45-64, verbatim) builds; nothing in this module constructs a DeepLabV3.
 
 The module keeps the reference's attribute names and state_dict keys, so a reference checkpoint loads with strict=True.  INFERENCE ONLY
 (Dropout / DropPath are identity); inputs are detached and no autograd graph is built.
@@ -165,14 +167,15 @@ class Img2PlaneModel(_FoldedModule):
     def _run(self, x_in, feat_low, taps=None):
         """The library launches, on x_in's device and that device's current stream (which need not be the process's current device)."""
         with self._device_of(x_in):
-            return self._launches(x_in, feat_low, taps)
+            B, cin, S, _ = x_in.shape
+            return self._launches(x_in.device, B, cin, S, x_in, feat_low, taps)
 
-    def _launches(self, x_in, feat_low, taps):
-        B, cin, S, _ = x_in.shape
+    def _launches(self, dev, B, cin, S, x_in, feat_low, taps):
+        """x_in / feat_low None: the stream's "xcl" / "fl" buffers hold them channel-last already (the fast path)."""
         s2, s4, s8, s16 = S // 2, S // 4, S // 8, S // 16
         st = torch.cuda.current_stream().cuda_stream
         d = self._prepare()
-        w = self._buffers_for(x_in.device, B, S, cin)
+        w = self._buffers_for(dev, B, S, cin)
         A, Bf, X, LV, C192, C352, OUT = w["a"], w["b"], w["x"], w["lv"], w["cat192"], w["cat352"], w["out"]
         img = B * s2 * s2
         lv, hv, pv = self.low_reso_vit, self.high_reso_encoder, self.triplane_predictor_vit
@@ -180,7 +183,8 @@ class Img2PlaneModel(_FoldedModule):
             if taps is not None else (lambda *a: None)
 
         # LowResolutionViT (models.py:65-88)
-        _lib.call("r3d_i2p_nchw_to_cl", feat_low, B, 256, s8, s8, w["fl"], st)
+        if feat_low is not None:
+            _lib.call("r3d_i2p_nchw_to_cl", feat_low, B, 256, s8, s8, w["fl"], st)
         pe = lv.patch_embed
         _lib.call("r3d_secc_conv", w["fl"], B, s8, s8, 256, d["low_reso_vit.patch_embed.proj"], pe.proj.bias, DIM, 3, 2, 1, pe.norm.weight, pe.norm.bias,
                   pe.norm.eps, X, st)
@@ -197,7 +201,8 @@ class Img2PlaneModel(_FoldedModule):
         _lib.call("r3d_i2p_copy_channels", LV, img, 96, C352, 352, 256, st)
 
         # HighResoEncoder (high_resolution_encoder.py:28-36)
-        _lib.call("r3d_i2p_nchw_to_cl", x_in, B, cin, S, S, w["xcl"], st)
+        if x_in is not None:
+            _lib.call("r3d_i2p_nchw_to_cl", x_in, B, cin, S, S, w["xcl"], st)
         _lib.call("r3d_secc_conv", w["xcl"], B, S, S, cin, d["high_reso_encoder.first"], hv.first.bias, 64, 7, 2, 3, None, None, 0.0, A, st)
         self._conv3(d, "high_reso_encoder.conv_layers.0", A, B, s2, 64, 1, 0.01, Bf, st)
         self._conv3(d, "high_reso_encoder.conv_layers.2", Bf, B, s2, 96, 1, 0.01, A, st)
@@ -221,12 +226,46 @@ class Img2PlaneModel(_FoldedModule):
         self._conv3(d, "triplane_predictor_vit.second_conv_after_cat", A, B, s2, 256, 1, 0.01, Bf, st)
         self._conv3(d, "triplane_predictor_vit.third_conv_after_cat", Bf, B, s2, 128, 1, 0.01, A, st)
         self._conv3(d, "triplane_predictor_vit.final_conv", A, B, s2, 128, 0, 0.0, OUT, st)
-        planes = torch.empty(B, 3, self.out_channels // 3, s2, s2, device=x_in.device, dtype=torch.float32)
+        planes = torch.empty(B, 3, self.out_channels // 3, s2, s2, device=dev, dtype=torch.float32)
         _lib.call("r3d_i2p_planes_out", OUT, B, s2, s2, self.out_channels // 3, planes, st)
         return planes
 
+    def _fast_encoder(self):
+        """This package's DeepLabV3 as low_reso_encoder, of this model's input width and 256 output channels (and _r3d_fast_path not
+        switched off, which tests do to compare the two routes): the encoder the fast path drives channel-last."""
+        from .deeplabv3 import DeepLabV3
+        enc = self.low_reso_encoder
+        if (isinstance(enc, DeepLabV3) and enc.in_channels == self.in_channels and enc.out_channels == 256
+                and getattr(self, "_r3d_fast_path", True)):
+            return enc
+        return None
+
+    def _forward_fast(self, enc, x, cond, B, S, taps):
+        """r3d_dl_assemble_input -> "xcl", enc.forward_cl -> "fl", then the launches without their two layout conversions.  The alpha
+        threshold and the camera Linear stay torch (a re-ordered mean could flip a borderline pixel; the Linear is 75 products)."""
+        x = x.detach().float().contiguous()
+        alpha = cam = None
+        if "alpha" in self.input_mode:
+            if cond is None or cond.get("ref_alphas") is None:
+                alpha = (x.mean(dim=1, keepdim=True) >= -0.999).float()
+            else:
+                alpha = cond["ref_alphas"].detach().float().contiguous()
+        if "camera" in self.input_mode:
+            cam = self.camera_to_channel(cond["ref_cameras"].detach().float()).reshape(B, 3).contiguous()
+        cin = self.in_channels
+        with self._device_of(x):
+            w = self._buffers_for(x.device, B, S, cin)
+            _lib.call("r3d_dl_assemble_input", x, alpha, cam, B, S, S, w["xcl"], torch.cuda.current_stream().cuda_stream)
+            fl = enc.forward_cl(w["xcl"][:B * S * S * cin].view(B, S, S, cin), out=w["fl"])
+            if taps is not None:
+                taps["feat_low"] = fl.permute(0, 3, 1, 2).contiguous()
+            return self._launches(x.device, B, cin, S, None, None, taps)
+
     def _forward(self, x, cond, taps):
         B, S = self._check(x, cond)
+        enc = self._fast_encoder()
+        if enc is not None:
+            return self._forward_fast(enc, x, cond, B, S, taps)
         x_in = self.assemble_input(x.detach().float(), cond).contiguous()
         feat_low = self.low_reso_encoder(x_in)
         if not torch.is_tensor(feat_low) or tuple(feat_low.shape) != (B, 256, S // 8, S // 8):

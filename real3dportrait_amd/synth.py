@@ -344,6 +344,57 @@ def synth_img2plane(seed, scale="standard", in_channels=5, qk_gain=1.5, out_chan
     return sd
 
 
+DEEPLAB_LAYERS = {"resnet18": (2, 2, 2, 2), "resnet34": (3, 4, 6, 3)}
+
+
+def deeplabv3_shapes(in_channels=5, encoder_name="resnet34", decoder_channels=256):
+    """[(state_dict key, shape)] of DeepLabV3 (modules/img2plane/deeplabv3/decoders/my_model.py) over a BasicBlock ResNet, in the order
+    of its state_dict; BatchNorm's num_batches_tracked (shape ()) included."""
+    conv = lambda p, co, ci, k: [(p + ".weight", (co, ci, k, k))]
+    bn = lambda p, c: [(p + ".weight", (c,)), (p + ".bias", (c,)), (p + ".running_mean", (c,)), (p + ".running_var", (c,)),
+                       (p + ".num_batches_tracked", ())]
+    out = conv("encoder.conv1", 64, in_channels, 7) + bn("encoder.bn1", 64)
+    inplanes = 64
+    for i, (planes, n) in enumerate(zip((64, 128, 256, 512), DEEPLAB_LAYERS[encoder_name])):
+        for j in range(n):
+            p = "encoder.layer%d.%d." % (i + 1, j)
+            cin = inplanes if j == 0 else planes
+            out += conv(p + "conv1", planes, cin, 3) + bn(p + "bn1", planes) + conv(p + "conv2", planes, planes, 3) + bn(p + "bn2", planes)
+            if j == 0 and i > 0:
+                out += conv(p + "downsample.0", planes, cin, 1) + bn(p + "downsample.1", planes)
+        inplanes = planes
+    C = decoder_channels
+    out += conv("decoder.0.convs.0.0", C, 512, 1)
+    for i in (1, 2, 3):
+        out += conv("decoder.0.convs.%d.0" % i, C, 512, 3)
+    out += conv("decoder.0.convs.4.1", C, 512, 1) + conv("decoder.0.project.0", C, 5 * C, 1) + conv("decoder.1", C, C, 3)
+    return out
+
+
+def synth_deeplabv3(seed, in_channels=5, encoder_name="resnet34"):
+    """A state_dict (numpy) of DeepLabV3 from hash streams, as the other synth_* functions make theirs: conv weights ~ N(0, gain / fan_in)
+    with gain 2 (He) and 0.5 on each block's second conv, on the downsample convs and on the last conv; BatchNorm weight 1 + 0.1 n, bias
+    and running mean 0.1 n, running variance 1 .. 1.2, num_batches_tracked 0.  With these every ReLU of the network passes a middling
+    share of its elements and no stage's magnitude runs away (the golden maker asserts both)."""
+    sd = {}
+    for i, (key, shape) in enumerate(deeplabv3_shapes(in_channels, encoder_name)):
+        st = 5600 + i
+        last = key.rsplit(".", 1)[-1]
+        if last == "num_batches_tracked":
+            v = np.zeros((), np.int64)
+        elif last == "running_var":
+            v = np.float32(1.0) + hash_uniform(seed, int(np.prod(shape)), st).reshape(shape) * np.float32(0.2)
+        elif last in ("bias", "running_mean"):
+            v = hash_unitvar(seed, shape, st) * np.float32(0.1)
+        elif len(shape) == 1:
+            v = np.float32(1.0) + hash_unitvar(seed, shape, st) * np.float32(0.1)
+        else:
+            small = ".conv2." in key or "downsample" in key or key.startswith("decoder.1.")
+            v = hash_unitvar(seed, shape, st) * np.float32(math.sqrt((0.5 if small else 2.0) / int(np.prod(shape[1:]))))
+        sd[key] = np.asarray(v, dtype=np.int64 if last == "num_batches_tracked" else np.float32)
+    return sd
+
+
 TORSO_C, TORSO_D = 32, 16          # the appearance volume [N, 32, 16, H, W] (facev2v_warp/network2.py:248-256)
 
 

@@ -176,7 +176,7 @@ def _reference_hparams(model):
 
 
 def patch_model(model, fuse_warp_sr=True, precision=None, secc_encoder=False, torso_generator=False, torso_motion=False, torso_precision=None,
-                torso_appearance=False, torso_forward=False, cano_backbone=False):
+                torso_appearance=False, torso_forward=False, cano_backbone=False, cano_low_reso_encoder=False):
     """Swap the hot-path operators of a constructed reference model for the HIP ones (in place).  INFERENCE ONLY: the HIP modules
     detach their inputs and build no autograd graph (the reference runs this path under torch.no_grad(), real3d_infer.py:435,479).
     precision: SR precision of the installed blocks (None = the library default 'f16mx': inside the 2e-4 of SURVEY 8(d) on every golden and heavy-tail sweep,
@@ -225,8 +225,14 @@ def patch_model(model, fuse_warp_sr=True, precision=None, secc_encoder=False, to
       model.img2plane_backbone on OSAvatar_Img2plane, when -- and only when -- it is the reference's Img2PlaneModel
       (modules/img2plane/img2plane_model.py:12-82), -> the HIP Img2PlaneModel (img2plane.py of this package: HighResoEncoder,
       LowResolutionViT and TriplanePredictorViT in exact fp32).  Its low_reso_encoder (DeepLabV3) is the reference's own object and stays
-      torch, as does the input assembly.  The replaced module stays reachable as model._r3d_reference_cano_backbone.  Anything else is
-      left as it is.
+      torch, as does the input assembly, unless cano_low_reso_encoder is given.  The replaced module stays reachable as
+      model._r3d_reference_cano_backbone.  Anything else is left as it is.
+    * cano_low_reso_encoder=True (opt-in; needs cano_backbone=True, anything else is a ValueError): the installed backbone's
+      low_reso_encoder, when it is the reference's DeepLabV3 over a BasicBlock ResNet at output stride 8 (deeplabv3.py's from_reference
+      reads stride, dilation and padding from each of its Conv2d objects), -> the HIP DeepLabV3, and the backbone's forward then assembles
+      its input with r3d_dl_assemble_input and runs channel-last throughout: no torch.nn.Conv2d runs inside the backbone.  The alpha
+      threshold and the camera Linear stay torch.  The old encoder stays reachable as <backbone>._r3d_reference_low_reso_encoder.  Any
+      other encoder is left as it is.
     Parameters are copied with strict key matching; the decoder module is left untouched (the renderer reads
     decoder.net[0|2].{weight,bias} directly)."""
     import types
@@ -237,6 +243,8 @@ def patch_model(model, fuse_warp_sr=True, precision=None, secc_encoder=False, to
     if torso_forward and not (torso_appearance and torso_motion and torso_generator):
         raise ValueError("patch_model: torso_forward=True needs torso_appearance=True, torso_motion=True and torso_generator=True (got %r, %r, %r): "
                          "it drives the three HIP modules" % (torso_appearance, torso_motion, torso_generator))
+    if cano_low_reso_encoder and not cano_backbone:
+        raise ValueError("patch_model: cano_low_reso_encoder=True needs cano_backbone=True: it swaps the encoder of the backbone that switch installs")
     dev = next(model.parameters()).device
     hp = _reference_hparams(model)
     old_r = model.renderer
@@ -310,7 +318,15 @@ def patch_model(model, fuse_warp_sr=True, precision=None, secc_encoder=False, to
             bb = getattr(model, name, None)
             if i2p.is_reference_img2plane(bb):
                 object.__setattr__(model, "_r3d_reference_cano_backbone", bb)        # reachable, not registered as a second sub-module
-                setattr(model, name, i2p.Img2PlaneModel.from_reference(bb))
+                new = i2p.Img2PlaneModel.from_reference(bb)
+                setattr(model, name, new)
+                if cano_low_reso_encoder:
+                    from . import deeplabv3 as dl
+                    old = new.low_reso_encoder
+                    enc = dl.DeepLabV3.from_reference(old) if dl.is_reference_deeplabv3(old) else None
+                    if enc is not None and enc.in_channels == new.in_channels and enc.out_channels == 256:
+                        object.__setattr__(new, "_r3d_reference_low_reso_encoder", old)        # reachable, not a second sub-module
+                        new.low_reso_encoder = enc
                 break
     for owner in (getattr(model, "secc_img2plane_backbone", None), getattr(model, "img2plane_backbone", None)):
         _patch_sequential(owner, "to_plane_cnn", dev)       # per-frame plane producer tail (segformer.py:691-700)
