@@ -10,6 +10,8 @@ Operators keep the reference's names and signatures (see each module's docstring
                                                          patch_model(cano_backbone=True) installs it)
     DeepLabV3                                            (deeplabv3.py: the backbone's low-resolution encoder, a dilated ResNet + ASPP;
                                                          patch_model(cano_backbone=True, cano_low_reso_encoder=True) installs it)
+    Plane2GridModule                                     (plane2grid.py: the Conv3d residual blocks that make tri-grids of the planes;
+                                                         patch_model(plane2grid=True) installs it)
     TorsoGenerator, Occlusion2Predictor                  (torso_generator.py: the torso network's warp + decoder, its Generator)
     TorsoMotionFieldEstimator                            (torso_motion.py: the torso network's per-frame MotionFieldEstimator)
     TorsoAppearanceFeatureExtractor                      (torso_appearance.py: the torso network's AppearanceFeatureExtractor)
@@ -30,7 +32,7 @@ Operators keep the reference's names and signatures (see each module's docstring
     landmark_weights, fit_landmarks, fit_3dmm_for_landmarks, patch_fit_3dmm (fit_3dmm.py: the landmark-driven 3DMM fit, 400 Adam steps)
     render_clip_sharded                                  (frames.py: frame sharding + RCCL gather)
 All compute goes through libr3d_hip.so (include/r3d_hip.h, include/r3d_hip_img2plane.h, include/r3d_hip_hubert.h,
-include/r3d_hip_deeplab.h); there is no eager/CPU fallback.
+include/r3d_hip_deeplab.h, include/r3d_hip_plane2grid.h); there is no eager/CPU fallback.
 """
 __version__ = "0.1.0"
 
@@ -54,6 +56,9 @@ def __getattr__(name):      # lazy: importing the package (e.g. for synth) must 
     if name == "DeepLabV3":
         from . import deeplabv3 as m
         return m.DeepLabV3
+    if name == "Plane2GridModule":
+        from . import plane2grid as m
+        return m.Plane2GridModule
     if name in ("TorsoGenerator", "Occlusion2Predictor"):
         from . import torso_generator as m
         return getattr(m, "Generator" if name == "TorsoGenerator" else name)

@@ -1,5 +1,6 @@
 """ctypes binding of libr3d_hip.so (the C ABI declared in include/r3d_hip.h and the five companion headers it includes, and in the
-extension headers of EXTENSION_SIGNATURES and the feature headers of FEATURE_SIGNATURES, which include r3d_hip.h).
+extension headers of EXTENSION_SIGNATURES, the feature headers of FEATURE_SIGNATURES and the module headers of MODULE_SIGNATURES, which
+include r3d_hip.h).
 
 The product path has NO fallback: if the HIP library is missing or fails to load, importing an
 operator raises.  Build it with `python -c "import __graft_entry__ as g; g.build()"` or
@@ -187,6 +188,16 @@ FEATURE_SIGNATURES = {
     },
 }
 
+# Module headers, each one torch module of a model restated (it includes r3d_hip.h): header -> its table, bound and found exactly as the
+# extension and feature tables are (required; same _bind).
+MODULE_SIGNATURES = {
+    "r3d_hip_plane2grid.h": {
+        "r3d_p2g_groupnorm_stats_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),
+        "r3d_p2g_groupnorm_stats": (c_int, [F, c_int, c_int, c_int, c_int, c_int, c_int, F, F, c_float, F, F, V, c_size_t, S]),
+        "r3d_p2g_conv3d": (c_int, [F, c_int, c_int, c_int, c_int, c_int, F, F, F, F, c_int, F, F, F, S]),
+    },
+}
+
 # The headers' constants the package uses: _lib.X mirrors R3D_X of the header named (tests/test_abi.py compares every one).
 CHAIN_SR_BLOCK, CHAIN_CONV, CHAIN_SR_BLOCK_TAIL, CHAIN_SRC_NONE, CHAIN_MAX_OPS, CHAIN_MAX_EXT, CHAIN_MAX_ZERO = 0, 1, 2, -1000, 12, 4, 4      # r3d_hip.h
 VIDEO_STATE_WORDS, VIDEO_PANELS_ALL, VIDEO_PANEL_DEPTH = 8, 31, 8                                           # r3d_hip_video.h
@@ -260,7 +271,7 @@ def load():
     except OSError as e:
         raise RuntimeError("real3dportrait_amd: cannot load %s: %s" % (LIB_PATH, e))
     required = dict(SIGNATURES)
-    for table in list(EXTENSION_SIGNATURES.values()) + list(FEATURE_SIGNATURES.values()):
+    for table in list(EXTENSION_SIGNATURES.values()) + list(FEATURE_SIGNATURES.values()) + list(MODULE_SIGNATURES.values()):
         required.update(table)
     for name, (res, params) in required.items():
         try:

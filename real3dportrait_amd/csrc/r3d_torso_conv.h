@@ -30,6 +30,13 @@
 //     [yco, yco + Cout) of rows of ycs floats.
 // DL = false compiles none of it, and the four fields it reads travel in the depth words of ConvArgs, which a 2-D kernel does not read (ConvArgs::set_dl).
 //
+// RP = true (3-D with EXT, F32, VEC; the Plane2GridModule kernels of r3d_plane2grid.hip) is nn.Conv3d(padding_mode='replicate')
+// behind a per-SAMPLE prologue, GroupNorm + ReLU as scale . x + shift:
+//   * a tap's coordinates are clamped into the volume in depth, height and width, so every tap of a row that exists is inside;
+//   * ps, pt are [B, Cin], and a tap is max(ps[b, c] x + pt[b, c], 0) with b the sample of ITS row (a tile's rows may belong to several
+//     samples), a NaN stays a NaN; pslope is not read.  The pair travels with the row's slot in the stage.
+// RP = false compiles none of it; ConvArgs is not touched.
+//
 // PREC selects the arithmetic of the products; loaders, tile order and epilogues are the same code for both.
 //   F32     the fp32 operands as they are, 8 v_mfma_f32_16x16x4_f32 per 16 x 16 tile and k step.
 //   BF16X3  store() splits every staged value into three bf16 pieces h + m + l == x (split_bf16x3) and compute() sums six of the nine
@@ -117,6 +124,7 @@ struct ConvArgs {
 };
 
 __device__ __forceinline__ float leaky(float v, float slope) { return v < 0.0f ? slope * v : v; }
+__device__ __forceinline__ float relu(float v) { return v < 0.0f ? 0.0f : v; }          // a NaN stays a NaN
 
 // the position of a running k = ((kz ks + ky) ks + kx) Cin + ci
 template <bool D3>
@@ -143,10 +151,15 @@ struct KPos {
     }
 };
 
-template <int PREC, bool VEC, bool D3, int WM, int WN, int TM, int TN, bool EXT = false, bool DL = false>
+// RP's part of a stage: slot j's prologue pair (its row's sample).  An empty base otherwise: the stage of every other kernel is the struct it was.
+template <bool RP, int AV> struct StagePro { float4 rps4[AV], rpt4[AV]; };
+template <int AV> struct StagePro<false, AV> {};
+
+template <int PREC, bool VEC, bool D3, int WM, int WN, int TM, int TN, bool EXT = false, bool DL = false, bool RP = false>
 __device__ __forceinline__ void conv_tile(const ConvArgs& g)
 {
     static_assert(WM * WN == 4, "four waves");
+    static_assert(!RP || (D3 && EXT && VEC && PREC == F32), "replicate padding with the per-sample prologue is the 3-D fp32 body, 16-byte loads");
     static_assert(!DL || (!D3 && PREC == F32), "the strided, dilated form is 2-D and fp32");
     static_assert(D3 || !EXT, "the extended epilogue belongs to the 3-D body");
     static_assert(PREC == F32 || PREC == BF16X3, "precision");
@@ -172,6 +185,7 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& g)
     // scalar: row t % BM, k entries t / BM + KSTEP j (consecutive lanes read consecutive pixels: coalesced for an NCHW input)
     constexpr int NR = VEC ? AV : 1;
     int roy[NR], rox[NR], roz[D3 ? NR : 1]; size_t rbase[NR];   // a row's position (oy < 0: no such row) and its sample's offset
+    int rpro[RP ? NR : 1];                                      // RP: the offset of the row's sample in ps and pt
 #pragma unroll
     for (int j = 0; j < NR; ++j) {
         const int m = m0 + (VEC ? (t >> 3) + 32 * j : t % BM);
@@ -191,12 +205,13 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& g)
                 const int b = plane / g.Do;
                 roz[j] = plane - b * g.Do;
                 rbase[j] = (size_t)b * g.D * g.Hs * g.Ws * g.Cin;
+                if constexpr (RP) rpro[j] = b * g.Cin;
             } else {
                 const int b = m / hw, r = m - b * hw;
                 roy[j] = r / g.W; rox[j] = r - roy[j] * g.W;
                 rbase[j] = (size_t)b * g.Hs * g.Ws * g.Cin;
             }
-        } else { roy[j] = -1000000; rox[j] = 0; rbase[j] = 0; }
+        } else { roy[j] = -1000000; rox[j] = 0; rbase[j] = 0; if constexpr (RP) rpro[j] = 0; }
     }
     KPos<D3> kp;
     kp.init(VEC ? 4 * (t & 7) : t / BM, g.Cin, g.ks);
@@ -210,7 +225,7 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& g)
         for (int j = 0; j < TN; ++j) acc[i][j] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
 
     // the registers of one k step in flight between its global loads and its LDS stores
-    struct Stage {
+    struct Stage : StagePro<RP, VEC ? AV : 1> {
         float4 av4[VEC ? AV : 1], wv4[VEC ? WV : 1], ps4, pt4;
         float avs[VEC ? 1 : AS], wvs[VEC ? 1 : WS], pss[VEC ? 1 : AS], pts[VEC ? 1 : AS];
         unsigned inside;                                        // bit j: slot / element j came from inside the image
@@ -223,6 +238,13 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& g)
             const int iy = roy[j] * g.cstride() - pad + kp.ky * g.cdil(), ix = rox[j] * g.cstride() - pad + kp.kx * g.cdil();
             if (!(iy >= 0 && iy < g.Hs && ix >= 0 && ix < g.Ws)) return false;
             pix = (size_t)iy * g.Ws + ix;
+            return true;
+        }
+        if constexpr (RP) {
+            if (roy[j] < 0) return false;                       // no such row; every tap of a row that exists is clamped into the volume
+            const int iy = min(max(roy[j] - pad + kp.ky, 0), g.H - 1), ix = min(max(rox[j] - pad + kp.kx, 0), g.W - 1);
+            const int iz = min(max(roz[j] - g.padz + kp.kz, 0), g.D - 1);
+            pix = ((size_t)iz * g.Hs + iy) * g.Ws + ix;
             return true;
         }
         const int iy = roy[j] - pad + kp.ky, ix = rox[j] - pad + kp.kx;
@@ -250,11 +272,19 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& g)
                 if (kin && tap(j, pix)) {
                     r.av4[j] = *reinterpret_cast<const float4*>(g.x + rbase[j] + pix * g.Cin + kp.ci);
                     r.inside |= 1u << j;
+                    if constexpr (RP) {
+                        if (g.ps) {
+                            r.rps4[j] = *reinterpret_cast<const float4*>(g.ps + rpro[j] + kp.ci);
+                            r.rpt4[j] = *reinterpret_cast<const float4*>(g.pt + rpro[j] + kp.ci);
+                        }
+                    }
                 }
             }
-            if (g.ps && kin) {
-                r.ps4 = *reinterpret_cast<const float4*>(g.ps + kp.ci);
-                r.pt4 = *reinterpret_cast<const float4*>(g.pt + kp.ci);
+            if constexpr (!RP) {
+                if (g.ps && kin) {
+                    r.ps4 = *reinterpret_cast<const float4*>(g.ps + kp.ci);
+                    r.pt4 = *reinterpret_cast<const float4*>(g.pt + kp.ci);
+                }
             }
 #pragma unroll
             for (int j = 0; j < WV; ++j) {
@@ -306,7 +336,13 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& g)
 #pragma unroll
             for (int j = 0; j < AV; ++j) {
                 float4 v = r.av4[j];
-                if (g.ps && (r.inside >> j & 1)) {
+                if constexpr (RP) {
+                    if (g.ps && (r.inside >> j & 1)) {
+                        const float4 s4 = r.rps4[j], t4 = r.rpt4[j];
+                        v.x = relu(fmaf(s4.x, v.x, t4.x)); v.y = relu(fmaf(s4.y, v.y, t4.y));
+                        v.z = relu(fmaf(s4.z, v.z, t4.z)); v.w = relu(fmaf(s4.w, v.w, t4.w));
+                    }
+                } else if (g.ps && (r.inside >> j & 1)) {
                     v.x = leaky(fmaf(r.ps4.x, v.x, r.pt4.x), g.pslope); v.y = leaky(fmaf(r.ps4.y, v.y, r.pt4.y), g.pslope);
                     v.z = leaky(fmaf(r.ps4.z, v.z, r.pt4.z), g.pslope); v.w = leaky(fmaf(r.ps4.w, v.w, r.pt4.w), g.pslope);
                 }

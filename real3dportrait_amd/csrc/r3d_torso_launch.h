@@ -1,7 +1,7 @@
 // Host side of the torso convolutions: the one argument check, the one ConvArgs fill, the one tile table and the one launcher behind the
 // seven entry points r3d_torso_conv / _prec (r3d_torso.hip), r3d_torso_conv3d / _prec (r3d_torso_motion.hip) and r3d_torso_conv_pool,
 // r3d_torso_conv_split, r3d_torso_conv3d_res (r3d_torso_appearance.hip), and behind r3d_dl_conv (r3d_deeplab.hip: ConvCall::dl, the strided,
-// dilated form, which calls check_conv, fill and dispatch itself since it has one tier).  An entry point describes its call as a ConvCall and hands it,
+// dilated form, which calls check_conv, fill and dispatch itself since it has one tier; r3d_p2g_conv3d of r3d_plane2grid.hip, ConvCall::rp, does the same).  An entry point describes its call as a ConvCall and hands it,
 // with its unit's kernel family, to run<Family>().  A family is a tag struct with
 //   static constexpr bool tile64x16                                  it has the 64 x 16 tile (the two 3-D families)
 //   template <int PREC, bool VEC, int WM, int WN, int TM, int TN>
@@ -31,6 +31,8 @@ struct ConvCall {
     int precision = R3D_TORSO_F32;
     // the strided, dilated form (r3d_dl_conv; conv_tile's DL): H x W is then the output grid, act 1 is ReLU and res goes in before it
     bool dl = false; int stride = 1, dilation = 1, pad = 0, bias_bstride = 0;
+    // replicate padding behind a per-sample prologue (r3d_p2g_conv3d; conv_tile's RP): ps, pt are then [B, Cin]
+    bool rp = false;
 
     int out_size(int n) const { const long long v = (long long)n + 2LL * pad - (long long)dilation * (ksize - 1) - 1; return v < 0 ? 0 : (int)(v / stride) + 1; }
     int H() const { return dl ? out_size(Hs) : Hs << upsample; }
@@ -105,7 +107,8 @@ inline int check_conv(const char* what, const ConvCall& c)
         const float* p = o ? c.yn : c.y;
         const size_t np = o ? nyn : ny;
         const size_t nbias = (size_t)(c.B - 1) * c.bias_bstride + c.Cout;          // bias_bstride is 0 outside dl
-        const Span spans[] = {writes(p, np), reads(c.x, nin), reads(c.w, nw), reads(c.bias, nbias), reads(c.ps, c.Cin), reads(c.pt, c.Cin)};
+        const size_t npro = (size_t)(c.rp ? c.B : 1) * c.Cin;
+        const Span spans[] = {writes(p, np), reads(c.x, nin), reads(c.w, nw), reads(c.bias, nbias), reads(c.ps, npro), reads(c.pt, npro)};
         if (clash(spans)) { set_error("%s: an output overlaps x, w, bias or the prologue", what); return R3D_ERR_INVALID_ARG; }
         if (c.res != c.y && overlap(p, np, c.res, nyn))
             { set_error("%s: an output overlaps the residual without y being the residual", what); return R3D_ERR_INVALID_ARG; }

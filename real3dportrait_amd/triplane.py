@@ -176,7 +176,7 @@ def _reference_hparams(model):
 
 
 def patch_model(model, fuse_warp_sr=True, precision=None, secc_encoder=False, torso_generator=False, torso_motion=False, torso_precision=None,
-                torso_appearance=False, torso_forward=False, cano_backbone=False, cano_low_reso_encoder=False):
+                torso_appearance=False, torso_forward=False, cano_backbone=False, cano_low_reso_encoder=False, plane2grid=False):
     """Swap the hot-path operators of a constructed reference model for the HIP ones (in place).  INFERENCE ONLY: the HIP modules
     detach their inputs and build no autograd graph (the reference runs this path under torch.no_grad(), real3d_infer.py:435,479).
     precision: SR precision of the installed blocks (None = the library default 'f16mx': inside the 2e-4 of SURVEY 8(d) on every golden and heavy-tail sweep,
@@ -233,6 +233,11 @@ def patch_model(model, fuse_warp_sr=True, precision=None, secc_encoder=False, to
       its input with r3d_dl_assemble_input and runs channel-last throughout: no torch.nn.Conv2d runs inside the backbone.  The alpha
       threshold and the camera Linear stay torch.  The old encoder stays reachable as <backbone>._r3d_reference_low_reso_encoder.  Any
       other encoder is left as it is.
+    * plane2grid=True (opt-in; independent of cano_backbone): model.plane2grid_module (img2plane_baseline.py:96-97, the trigrid_v2 models),
+      when it is the reference's Plane2GridModule at the renderer's width (in_out_dim 96, 32 channels per plane), -> the HIP
+      Plane2GridModule (plane2grid.py of this package: GroupNorm statistics and the replicate-padded Conv3d in exact fp32).  cal_plane /
+      cal_cano_plane reach it unchanged.  The old module stays reachable as model._r3d_reference_plane2grid_module.  Anything else, and a
+      model without the attribute, is left as it is.
     Parameters are copied with strict key matching; the decoder module is left untouched (the renderer reads
     decoder.net[0|2].{weight,bias} directly)."""
     import types
@@ -328,6 +333,13 @@ def patch_model(model, fuse_warp_sr=True, precision=None, secc_encoder=False, to
                         object.__setattr__(new, "_r3d_reference_low_reso_encoder", old)        # reachable, not a second sub-module
                         new.low_reso_encoder = enc
                 break
+    if plane2grid:
+        from . import plane2grid as p2g
+        old = getattr(model, "plane2grid_module", None)
+        new = p2g.Plane2GridModule.from_reference(old) if p2g.is_reference_plane2grid(old) else None
+        if new is not None:
+            object.__setattr__(model, "_r3d_reference_plane2grid_module", old)        # reachable, not registered as a second sub-module
+            model.plane2grid_module = new
     for owner in (getattr(model, "secc_img2plane_backbone", None), getattr(model, "img2plane_backbone", None)):
         _patch_sequential(owner, "to_plane_cnn", dev)       # per-frame plane producer tail (segformer.py:691-700)
     from .superresolution import set_sr_precision
